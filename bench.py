@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the PaSST training hot path on MI355X.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5                 (the headline line only; --full adds the figures below)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR  (and writes what the last timed step computed to DIR)
     python bench.py --gpus N --steps K --warmup W            (self-launching: forks one rank per GPU, like the reference's
                                                               DDP=N python ex_audioset.py, ex_audioset.py:499-524)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -17,7 +18,8 @@ mode: random fmin/fmax, SpecAugment masks) -> mixup -> PaSST forward (bf16 MFMA,
 -> BCE loss -> full backward -> [N>1: per-block RCCL all-reduce overlapped with backward] -> AdamW on
 all 86 M parameters.  Nothing is skipped or cached inside the timed region.
 
-Besides the contract line it reports
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, loss and the FLOP fractions that follow
+from them).  With --full it also reports
   roofline     : the dominant kernel (the MFMA GEMM family), timed per launch with HIP events on the
                  launch stream inside the timed region; achieved = algorithmic FLOPs / measured time,
                  against the 2.5 PFLOP/s dense bf16 MFMA peak (MI355X_MICROARCH.md).
@@ -25,10 +27,13 @@ Besides the contract line it reports
   frontend     : the mel front-end kernel: algorithmic GB/s against the 8 TB/s HBM peak.
   scaling_model: a MODELLED 2/4/8-GPU curve from this run's step time and the reducer's bucket sizes
                  (the measured curve is the driver's SCALE_rNN.json when it has an 8-GPU node).
+  parity_mode_clips_s, and for N > 1 the MEASURED all-reduce diagnostics (allreduce_measured, rccl).
 --config c4 | c4_ref | c5 runs the other BASELINE.json configurations (ViT-L geometry, the reference's passt_l,
 ESC-50 fine-tune); their lines are committed under profiles/.
   cpu_baseline : the oracle (CPU restatement of the reference, oracle/passt_oracle.py) timed on this
-                 host on a bounded sample of the same workload (train-mode fwd+bwd, B=2 per iteration).
+                 host on a bounded sample of the same workload (train-mode fwd+bwd, B=2 per iteration); --full only.
+--dump-outputs DIR writes loss.npy, params.npy and grads.npy (float32; see dump_outputs) after the timed steps: with the same
+arguments the inputs are the same in every run, so two builds can be compared output for output.
 """
 import argparse
 import contextlib
@@ -128,13 +133,17 @@ def modelled_scaling(ms_step_1gpu, bucket_bytes, link_gbps=153.0, links=7, bus_e
     return out
 
 
+def cpu_threads():
+    return min(32, os.cpu_count() or 1, int(os.environ.get("OMP_NUM_THREADS") or 32))
+
+
 def cpu_baseline(budget_s=12.0, threads=None):
     """Oracle (port of the reference) fwd+bwd in train mode on this host's cores.  Bounded: at most
     ~budget_s of CPU work; the thread count is capped (torch's CPU GEMMs stop scaling -- and collapse from
-    oversubscription -- long before the 100+ hardware threads of a GPU host)."""
+    oversubscription -- long before the 100+ hardware threads of a GPU host; and never above the OMP_NUM_THREADS allotment)."""
     from oracle import detgen
     from oracle import passt_oracle as O
-    threads = threads or min(32, os.cpu_count() or 1)
+    threads = threads or cpu_threads()
     torch.set_num_threads(threads)
     cfg = O.make_cfg(s_patchout_t=40, s_patchout_f=4)
     sd = O.to_torch(detgen.passt_state_dict(cfg, 1), requires_grad=True)
@@ -160,10 +169,10 @@ def cpu_baseline(budget_s=12.0, threads=None):
 def cpu_baseline_forward(budget_s=10.0, threads=None):
     """north_star: "the reference CPU forward timed on the same host (core count stated)" = BASELINE config #1 exactly:
     passt_s_swa_p16_128_ap476, eval-mode forward of batch 2 synthetic 10 s @ 32 kHz waveforms, mel front end + network,
-    no patchout (1190 tokens), fp32, on the oracle (the port of the reference; /root/reference is not on the GPU box)."""
+    no patchout (1190 tokens), fp32, on the oracle (the port of the reference, which the GPU box does not have)."""
     from oracle import detgen
     from oracle import passt_oracle as O
-    threads = threads or min(32, os.cpu_count() or 1)
+    threads = threads or cpu_threads()
     torch.set_num_threads(threads)
     cfg = O.make_cfg()
     sd = O.to_torch(detgen.passt_state_dict(cfg, 1))
@@ -185,6 +194,28 @@ def cpu_baseline_forward(budget_s=10.0, threads=None):
             "sample": f"BASELINE config #1: {len(used)} eval-mode forwards of batch {B} x 10 s @ 32 kHz waveforms (mel front end + "
                       f"network, no patchout, 1190 tokens, fp32 torch CPU restatement of the reference, {threads} threads of "
                       f"{os.cpu_count()} hw threads), {dt:.1f} s"}
+
+
+DUMP_SAMPLE = 4 << 20     # elements per dumped array at most: params + grads + loss stay under 33 MB of float32
+
+
+def dump_outputs(out_dir, net, loss):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the step's loss (loss.npy), the updated
+    parameters (params.npy) and the step's gradients (grads.npy; zeros for a parameter without one), flattened in
+    net.named_parameters() order, float32.  Longer than DUMP_SAMPLE elements (passt_s: 86 M), both arrays hold the same fixed
+    sample: DUMP_SAMPLE distinct indices drawn with numpy's default_rng(0), ascending -- the same in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for _, p in net.named_parameters()]
+    with torch.no_grad():
+        flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+        flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])
+        if flat_p.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(flat_p.numel(), DUMP_SAMPLE, replace=False))
+            idx = torch.from_numpy(idx).to(flat_p.device)
+            flat_p, flat_g = flat_p[idx], flat_g[idx]
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(-1).cpu().numpy())
+    np.save(os.path.join(out_dir, "params.npy"), flat_p.cpu().numpy())
+    np.save(os.path.join(out_dir, "grads.npy"), flat_g.cpu().numpy())
 
 
 def _sha16(path):
@@ -536,13 +567,25 @@ def main():
                     help="the reference's model_speed_test flow (ex_audioset.py:364-426) around passt_amd's module: torch.compile + "
                          "fp16 autocast + GradScaler + SGD on x = ones(B,1,128,998); one line per batch (64 and 12, or --batch)")
     ap.add_argument("--no-compile", action="store_true", help="--speedtest without torch.compile(net) (A/B)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-launch roofline / attention / front-end figures from instrumented timed steps, "
+                         "the modelled scaling curve, the fp32 parity-mode rate, the CPU baselines and the N > 1 all-reduce "
+                         "diagnostics (a plain run only sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss, parameters, gradients) to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        error_line(args, f"--steps must be >= 1 and --warmup >= 0, got {args.steps} / {args.warmup}")
+        sys.exit(2)
 
     if args.sweep_gpus:
         sys.exit(sweep(args))
     if args.speedtest:
         if not torch.cuda.is_available():
             error_line(args, "no HIP device visible (passt_amd has no CPU path)", devices_visible=0)
+            sys.exit(2)
+        if args.dump_outputs:
+            error_line(args, "--dump-outputs writes the training step's outputs: not available with --speedtest")
             sys.exit(2)
         if args.steps == 20 and args.warmup == 5:
             args.steps, args.warmup = 100, 10                 # the reference's test_length / warm-up (:381, :397)
@@ -687,7 +730,7 @@ def run(args):
             ts.phases.clear()                   # phase diagnostics: timed steps only (warm-up carries one-time module loads)
         # per-launch HIP events on the GEMM family (roofline): two event records per launch cost several % of the step
         # when every step is instrumented, so one timed step in PROFILE_EVERY carries them (profiled_steps)
-        prof = {} if (rank == 0 and not args.no_roofline and not args.graph) else None
+        prof = {} if (args.full and rank == 0 and not args.no_roofline and not args.graph) else None
         prof_at = set(profiled_steps(args.steps))
         t0 = time.perf_counter()
         for i in range(args.steps):
@@ -702,6 +745,8 @@ def run(args):
     elapsed = float(elapsed.item())
     loss_v = float(loss.item())
     assert np.isfinite(loss_v), "non-finite loss"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, net, loss)
 
     # ---- outside the timed region -------------------------------------------------------------------------------
     # (a) N > 1: MEASURED per-bucket all-reduce (HIP events: launch -> released, and how long the compute stream was
@@ -715,7 +760,7 @@ def run(args):
 
     # (b) the parity mode (exact-f32 MFMA, <= 3e-6 of the fp32 reference: the bound north_star states) trains this fast
     parity_clips = None
-    if world == 1 and args.config == "c2" and args.precision == "bf16" and not args.no_cpu_baseline and args.path == "trainstep":
+    if args.full and world == 1 and args.config == "c2" and args.precision == "bf16" and not args.no_cpu_baseline and args.path == "trainstep":
         net.precision = "fp32"
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
@@ -826,23 +871,24 @@ def run(args):
                                    "sampling": f"HIP events around every GEMM launch of 1 timed step in {PROFILE_EVERY} (steps {', '.join(map(str, list(profiled_steps(args.steps))[:3]))}{', ...' if len(profiled_steps(args.steps)) > 3 else ''})",
                                    "gemm_time_share_of_step": round(tot_ms / n_prof_steps / ms_step, 4),
                                    "per_epilogue": per_kind}
-            # multi-GPU: SCALE is measured by the driver when it has an 8-GPU node; what can be said from ONE GPU is a model
-            bus_eff, bus_src = 0.35, "35 % (an ASSUMED RCCL bus efficiency: no N > 1 measurement in this run)"
-            idle_bus = (allreduce or {}).get("idle", {}).get("bus_GBps_total") if not dry else None
-            if idle_bus:
-                bus_eff = idle_bus / (min(world - 1, 7) * 153.0)
-                bus_src = (f"{100 * bus_eff:.1f} % = this run's own idle all-reduce of the same buckets ({idle_bus} GB/s bus bandwidth at "
-                           f"N = {world}, allreduce_measured.idle) over the link peak")
-            out["scaling_model"] = {"kind": "MODELLED, not measured" + (" (wire term from this run's measured bus bandwidth)" if idle_bus else ""),
-                                    "inputs": "this run's ms_per_step, the reducer's bucket bytes (one bucket per block, launched from the "
-                                    f"backward), min(N-1, 7) xGMI links x 153 GB/s at {bus_src}, GEMM slow-down next to a co-running "
-                                    "whole-CU kernel from profiles/r04_copersist_probe.txt (worst case: +28 %)",
-                                    "bus_efficiency": round(bus_eff, 4),
-                                    "bucket_MB": {str(k): round(v / 1e6, 2) for k, v in ts.reducer.bucket_bytes().items()},
-                                    "n_gpus": modelled_scaling(1e3 * elapsed / args.steps, ts.reducer.bucket_bytes(), bus_eff=bus_eff)}
-            if world == 1 and not args.no_cpu_baseline and args.config == "c2":
-                out["cpu_baseline"] = cpu_baseline()
-                out["cpu_baseline_forward"] = cpu_baseline_forward()
+            if args.full:
+                # multi-GPU: SCALE is measured by the driver when it has an 8-GPU node; what can be said from ONE GPU is a model
+                bus_eff, bus_src = 0.35, "35 % (an ASSUMED RCCL bus efficiency: no N > 1 measurement in this run)"
+                idle_bus = (allreduce or {}).get("idle", {}).get("bus_GBps_total") if not dry else None
+                if idle_bus:
+                    bus_eff = idle_bus / (min(world - 1, 7) * 153.0)
+                    bus_src = (f"{100 * bus_eff:.1f} % = this run's own idle all-reduce of the same buckets ({idle_bus} GB/s bus bandwidth at "
+                               f"N = {world}, allreduce_measured.idle) over the link peak")
+                out["scaling_model"] = {"kind": "MODELLED, not measured" + (" (wire term from this run's measured bus bandwidth)" if idle_bus else ""),
+                                        "inputs": "this run's ms_per_step, the reducer's bucket bytes (one bucket per block, launched from the "
+                                        f"backward), min(N-1, 7) xGMI links x 153 GB/s at {bus_src}, GEMM slow-down next to a co-running "
+                                        "whole-CU kernel from profiles/r04_copersist_probe.txt (worst case: +28 %)",
+                                        "bus_efficiency": round(bus_eff, 4),
+                                        "bucket_MB": {str(k): round(v / 1e6, 2) for k, v in ts.reducer.bucket_bytes().items()},
+                                        "n_gpus": modelled_scaling(1e3 * elapsed / args.steps, ts.reducer.bucket_bytes(), bus_eff=bus_eff)}
+                if world == 1 and not args.no_cpu_baseline and args.config == "c2":
+                    out["cpu_baseline"] = cpu_baseline()
+                    out["cpu_baseline_forward"] = cpu_baseline_forward()
             if parity_clips is not None:
                 out["parity_mode_clips_s"] = parity_clips     # same step, precision="fp32": what meets the <= 1e-3 parity bound
             if allreduce is not None:
@@ -866,7 +912,7 @@ def run(args):
         os._exit(0)
 
     watchdog = None
-    if world > 1:
+    if world > 1 and args.full:
         watchdog = threading.Timer(DIAG_TIMEOUT_S if rank == 0 else DIAG_TIMEOUT_S + 20, watchdog_fire)
         watchdog.daemon = True
         watchdog.start()

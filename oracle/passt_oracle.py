@@ -7,9 +7,9 @@ autograd over this restatement.
 
 Pinning status
 --------------
-* Model path (patch-embed .. head, fwd+bwd): PINNED -- checked against the real reference
-  classes imported from /root/reference (tests/test_oracle_pinned.py) and against the
-  committed fixtures ``tests/golden/*.npz`` produced by ``tests/golden/make_golden.py``.
+* Model path (patch-embed .. head, fwd+bwd): PINNED -- checked (tests/test_oracle_pinned.py) against the
+  committed fixtures ``tests/golden/*.npz``, outputs of the real reference classes written by
+  ``tests/golden/make_golden.py``.
 * Front end: the STFT/power/log/affine chain is PINNED the same way (the reference's own
   ``AugmentMelSTFT.forward`` runs with ``torch.stft``).  Two pieces live in the un-vendored
   dependency torchaudio 0.13.1 (environment.yml:99): ``compliance.kaldi.get_mel_banks`` and

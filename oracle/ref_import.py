@@ -1,8 +1,7 @@
 """Import the *real* reference (kkoutini/PaSST at /root/reference) on CPU (TEST INFRASTRUCTURE).
 
-Only usable in the build container: /root/reference does not exist on the GPU box, so this
-module is imported solely by ``tests/golden/make_golden.py`` (fixture generation) and by the
-``-m "not gpu"`` pinning tests, which skip when the tree is absent.
+Only usable where the reference tree is present.  Imported solely by ``tests/golden/make_golden.py`` (fixture
+generation) and ``tools/time_reference_cpu.py``: the test suite reads the fixtures, never the reference itself.
 
 The reference needs third-party packages that are not installed here (timm, ba3l/sacred,
 torchaudio).  We stub exactly the symbols it touches:

@@ -2,6 +2,7 @@
 (kkoutini/PaSST, imported read-only from /root/reference through oracle/ref_import.py).
 
     python tests/golden/make_golden.py          # rewrites tests/golden/*.npz
+    python tests/golden/make_golden.py live     # only the live_*.npz the CPU pinning tests compare with
 
 Only outputs are stored; inputs/weights are regenerated bit-exactly by oracle/detgen.py.
 The GPU box has no /root/reference -- the `-m gpu` parity tests compare the HIP path with
@@ -304,6 +305,163 @@ def gen_swa_case(out_dir=HERE):
     np.savez_compressed(os.path.join(out_dir, "swa_callback.npz"), **out)
 
 
+# ---- outputs of the reference's own code for the pinning tests that used to import it live (CPU suite) ----------------
+# Arrays longer than 4096 entries are stored the way subsample() stores the model gradients above (every 7th entry), those of
+# live_geometries.npz as at most GEOMETRY_SAMPLE evenly spaced entries; next to each: the whole array's L2 norm and largest
+# magnitude (pin_sample / _pinned_into).
+# live_train_step.npz  : the reference PaSST, train mode, one BCE step on model_small_train's geometry (seed 991): logits, features,
+#                        every gradient
+# live_geometries.npz  : the same for GEOMETRY_CASES (other strides, u_patchout, the 2000-frame model), 4 torch seeds each; a seed
+#                        on which the reference raises IndexError (it indexes past its own time cut) is stored as failed
+# live_frontend.npz    : the reference AugmentMelSTFT, eval and train mode, on the default STFT and on STFT_CASES
+# live_helpers.npz     : helpers/mixup.py's my_mixup draws, helpers/ramp.py's exp_warmup_linear_down values, what
+#                        helpers/models_size.py's count_non_zero_params reports for a passt_amd.PaSST, the reference's parameter
+#                        names / shapes of a small PaSST
+LIVE_TRAIN_STEP = dict(cfg=CASES["model_small_train"]["cfg"], seed=991, torch_seed=5)
+GEOMETRY_CASES = [(dict(stride=(12, 12), s_patchout_t=30, s_patchout_f=3), 998),
+                  (dict(stride=(20, 20), s_patchout_t=10, s_patchout_f=1), 990),
+                  (dict(stride=(10, 16), u_patchout=100), 998),
+                  (dict(img_size=(128, 2000), s_patchout_t=80, s_patchout_f=4), 2000),
+                  (dict(stride=(20, 20), s_patchout_t=10, s_patchout_f=1), 998)]
+GEOMETRY_SEEDS = range(4)
+FRONTEND_LIVE = dict(B=2, L=40000, seed=31, torch_seed=3, kw=dict(fmin_aug_range=10, fmax_aug_range=2000))
+STFT_CASES = [dict(hopsize=160), dict(hopsize=100), dict(hopsize=500, win_length=1024), dict(win_length=400, n_mels=64),
+              dict(hopsize=333, fmin=50.0, fmax=14000)]
+STFT_LIVE = dict(B=2, L=24000, seed=32, torch_seed=4, kw=dict(fmin_aug_range=10, fmax_aug_range=2000))
+MIXUP_CASES = [(64, 0.3), (12, 0.3), (1, 0.3), (7, 2.0)]
+MIXUP_SEEDS = (0, 1, 1234)
+RAMP_EPOCHS = list(range(0, 131)) + [0.25, 4.5, 50.5, 99.9]
+MODELS_SIZE_SEED = 0
+NAMES_CFG = dict(embed_dim=128, depth=2, num_heads=2, num_classes=9, img_size=(128, 100))
+
+
+def geometry_cfg(kw):
+    return O.make_cfg(embed_dim=48, depth=1, num_heads=3, num_classes=11, **kw)
+
+
+GEOMETRY_SAMPLE = 256
+
+
+def pin_sample(a, limit=None):
+    """The entries of ``a`` a live_*.npz fixture keeps: subsample()'s, or at most ``limit`` evenly spaced ones."""
+    flat = np.ascontiguousarray(a).reshape(-1)
+    if limit is None or flat.size <= limit:
+        return subsample(flat)[0]
+    return flat[np.linspace(0, flat.size - 1, limit).astype(np.int64)].copy()
+
+
+def _pinned_into(out, key, a, limit=None):
+    a = np.ascontiguousarray(a, np.float32)
+    out[key] = pin_sample(a, limit)
+    out[key + ".stats"] = np.array([np.linalg.norm(a.astype(np.float64)), np.abs(a).max() if a.size else 0.0])
+
+
+def _grads_into(out, prefix, named_params, limit=None):
+    """every parameter's gradient, packed: names, has_grad, stats (L2 norm, largest magnitude), and the pin_sample() entries of
+    all of them concatenated (samples[offsets[i]:offsets[i + 1]] belongs to names[i])"""
+    names, has, stats, samples, offsets = [], [], [], [], [0]
+    for k, p in named_params:
+        g = None if p.grad is None else p.grad.detach().numpy().astype(np.float32)
+        names.append(k)
+        has.append(g is not None)
+        stats.append([np.linalg.norm(g.astype(np.float64)), np.abs(g).max()] if g is not None else [0.0, 0.0])
+        samples.append(pin_sample(g, limit) if g is not None else np.zeros(0, np.float32))
+        offsets.append(offsets[-1] + samples[-1].size)
+    out[prefix + "names"], out[prefix + "has_grad"] = np.array(names), np.array(has)
+    out[prefix + "stats"], out[prefix + "offsets"] = np.array(stats, np.float64), np.array(offsets, np.int64)
+    out[prefix + "samples"] = np.concatenate(samples).astype(np.float32)
+
+
+def gen_live_cases(out_dir=HERE):
+    import warnings
+    # the reference's train step on the oracle's small geometry
+    c = LIVE_TRAIN_STEP
+    sd_np = detgen.passt_state_dict(c["cfg"], c["seed"])
+    x, y = model_inputs(dict(CASES["model_small_train"], seed=c["seed"]))
+    m = ref_import.build_reference_passt(c["cfg"], sd_np)
+    m.train()
+    torch.manual_seed(c["torch_seed"])
+    lr, fr = ref_import.run_silently(m, torch.from_numpy(x))
+    O.bce_loss(lr, torch.from_numpy(y)).backward()
+    out = {"logits": lr.detach().numpy(), "features": fr.detach().numpy()}
+    _grads_into(out, "", m.named_parameters())
+    np.savez_compressed(os.path.join(out_dir, "live_train_step.npz"), **out)
+
+    # other geometries, four torch seeds each
+    out = {}
+    for ci, (kw, T) in enumerate(GEOMETRY_CASES):
+        cfg = geometry_cfg(kw)
+        sd_np = detgen.passt_state_dict(cfg, 993)
+        x, y = model_inputs(dict(cfg=cfg, B=2, T=T, seed=993))
+        m = ref_import.build_reference_passt(cfg, sd_np)
+        m.train()
+        for seed in GEOMETRY_SEEDS:
+            m.zero_grad()
+            pre = f"c{ci}.s{seed}."
+            torch.manual_seed(seed)
+            try:
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    lo, fo = ref_import.run_silently(m, torch.from_numpy(x))
+                O.bce_loss(lo, torch.from_numpy(y)).backward()
+            except IndexError:
+                out[pre + "failed"] = np.bool_(True)
+                continue
+            out[pre + "failed"] = np.bool_(False)
+            out[pre + "logits"], out[pre + "features"] = lo.detach().numpy(), fo.detach().numpy()
+            _grads_into(out, pre, m.named_parameters(), GEOMETRY_SAMPLE)
+        print("geometry", ci, kw, T, "failed seeds", [s for s in GEOMETRY_SEEDS if out[f"c{ci}.s{s}.failed"]])
+    np.savez_compressed(os.path.join(out_dir, "live_geometries.npz"), **out)
+
+    # the front end: default STFT and other STFT geometries, eval and train mode
+    _, ref_pre = ref_import.load_reference()
+    out = {}
+    for tag, case, kws in [("base", FRONTEND_LIVE, [{}])] + [("stft", STFT_LIVE, STFT_CASES)]:
+        wave = torch.from_numpy(frontend_inputs(case))
+        for i, kw in enumerate(kws):
+            mel = ref_import.run_silently(ref_pre.AugmentMelSTFT, **dict(case["kw"], **kw))
+            for training in (False, True):
+                mel.train(training)
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    torch.manual_seed(case["torch_seed"])
+                    with torch.no_grad():
+                        mel_out = mel(wave).numpy()
+                    _pinned_into(out, f"{tag}{i}.train{int(training)}", mel_out)
+                    out[f"{tag}{i}.train{int(training)}.shape"] = np.array(mel_out.shape, np.int64)
+    np.savez_compressed(os.path.join(out_dir, "live_frontend.npz"), **out)
+
+    # small helpers of the caller
+    out = {}
+    my_mixup = ref_import.import_reference_file("helpers/mixup.py").my_mixup
+    for size, alpha in MIXUP_CASES:
+        for seed in MIXUP_SEEDS:
+            torch.manual_seed(seed)
+            np.random.seed(seed)
+            idx, lam = my_mixup(size, alpha)
+            after = (torch.randint(1 << 30, (1,)).item(), np.random.randint(1 << 30))
+            pre = f"mixup.{size}_{alpha}.s{seed}."
+            out[pre + "idx"], out[pre + "lam"], out[pre + "after"] = idx.numpy(), lam.numpy(), np.array(after, np.int64)
+    ramp = ref_import.import_reference_file("helpers/ramp.py").exp_warmup_linear_down(5, 50, 50, 0.01)
+    out["ramp"] = np.array([ramp(e) for e in RAMP_EPOCHS], np.float64)
+    import passt_amd
+    count = ref_import.import_reference_file("helpers/models_size.py").count_non_zero_params
+    torch.manual_seed(MODELS_SIZE_SEED)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        net = passt_amd.get_model(arch="passt_s_swa_p16_128_ap476", pretrained=False, s_patchout_t=40, s_patchout_f=4)
+    desc, total, nonzero = count(net)
+    out["models_size.desc"] = np.array([l for l in desc.split("\n") if l.strip()])
+    out["models_size.total"], out["models_size.nonzero"] = np.int64(total), np.int64(nonzero)
+    cfg = O.make_cfg(**NAMES_CFG)
+    ref = ref_import.build_reference_passt(cfg, detgen.passt_state_dict(cfg, 1))
+    out["names.params"] = np.array([n for n, _ in ref.named_parameters()])
+    out["names.state"] = np.array(list(ref.state_dict()))
+    out["names.shapes"] = np.array([",".join(map(str, v.shape)) for v in ref.state_dict().values()])
+    np.savez_compressed(os.path.join(out_dir, "live_helpers.npz"), **out)
+    print("live fixtures written")
+
+
 def gen_rng_kat():
     """SURVEY.md App. C KAT: the index path on torch CPU."""
     torch.manual_seed(123)
@@ -319,7 +477,10 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "swa":       # the SWA callback run live (r06)
         gen_swa_case()
         sys.exit(0)
-    if len(sys.argv) > 1 and sys.argv[1] == "big":       # only the full-size cases (minutes of CPU time); big <name>: one of them
+    if len(sys.argv) > 1 and sys.argv[1] == "live":      # what the CPU pinning tests compare with (live_*.npz)
+        gen_live_cases()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "big":      # only the full-size cases (minutes of CPU time); big <name>: one of them
         for n, c in BIG_CASES.items():
             if len(sys.argv) < 3 or n in sys.argv[2:]:
                 gen_model_case(n, c)
@@ -341,3 +502,4 @@ if __name__ == "__main__":
     gen_rng_kat()
     gen_wave_case()
     gen_swa_case()
+    gen_live_cases()

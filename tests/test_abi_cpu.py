@@ -119,7 +119,7 @@ def test_product_path_has_no_cpu_fallback():
                 assert "oracle" not in open(os.path.join(root, f)).read().replace("# oracle", ""), f
 
 
-def test_state_dict_schema_and_parameter_order():
+def test_state_dict_schema_and_parameter_order(golden_dir):
     import passt_amd
     from oracle import detgen
     from oracle import passt_oracle as O
@@ -135,18 +135,16 @@ def test_state_dict_schema_and_parameter_order():
     names = [n for n, _ in m.named_parameters()]
     assert names[:5] == ["cls_token", "dist_token", "new_pos_embed", "freq_new_pos_embed", "time_new_pos_embed"]
     assert names[-2:] == ["head_dist.weight", "head_dist.bias"]
-    from oracle import ref_import
-    if ref_import.reference_available():
-        ref = ref_import.build_reference_passt(O.make_cfg(embed_dim=128, depth=2, num_heads=2, num_classes=9,
-                                                          img_size=(128, 100)),
-                                               detgen.passt_state_dict(O.make_cfg(embed_dim=128, depth=2, num_heads=2,
-                                                                                  num_classes=9, img_size=(128, 100)), 1))
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            mine = passt_amd.PaSST(img_size=(128, 100), stride=10, embed_dim=128, depth=2, num_heads=2, num_classes=9,
-                                   distilled=True)
-        assert [n for n, _ in ref.named_parameters()] == [n for n, _ in mine.named_parameters()]
-        mine.load_state_dict(ref.state_dict(), strict=True)
+    # the reference PaSST of the same small geometry: its parameter names and state_dict (names, shapes), stored by
+    # tests/golden/make_golden.py live
+    gold = dict(np.load(os.path.join(golden_dir, "live_helpers.npz")))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        mine = passt_amd.PaSST(img_size=(128, 100), stride=10, embed_dim=128, depth=2, num_heads=2, num_classes=9,
+                               distilled=True)
+    assert list(gold["names.params"]) == [n for n, _ in mine.named_parameters()]
+    ref_sd = {k: torch.zeros([int(d) for d in shp.split(",") if d]) for k, shp in zip(gold["names.state"], gold["names.shapes"])}
+    mine.load_state_dict(ref_sd, strict=True)
 
 
 def test_host_index_logic_matches_reference_order():

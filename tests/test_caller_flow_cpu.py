@@ -1,7 +1,9 @@
 """The reference's own caller flow around the two modules, on CPU (behaviours ex_audioset.py relies on).
 
-* ``passt_amd.mixup.my_mixup`` == the live ``helpers/mixup.py`` function, bit for bit, on the same RNG state;
-* ``count_non_zero_params(net)`` (ex_audioset.py:121), imported live from the reference, walks a passt_amd.PaSST;
+* ``passt_amd.mixup.my_mixup`` == the ``helpers/mixup.py`` function, bit for bit, on the same RNG state (its draws stored in
+  tests/golden/live_helpers.npz by make_golden.py live);
+* ``count_non_zero_params(net)`` (ex_audioset.py:121): what the reference's function reported walking a passt_amd.PaSST (stored
+  the same way) is what the module's parameters are, module by module;
 * ``torch.compile(net)`` (ex_audioset.py:135, model_speed_test :391): the compiled module runs the forward as ONE opaque
   eager call -- no graph is captured, nothing is recompiled on later calls (the GPU half of this is
   tests/test_gpu_model.py::test_model_speed_test_flow).
@@ -14,21 +16,21 @@ import pytest
 import torch
 
 import passt_amd
-from oracle import ref_import
 from passt_amd.mixup import my_mixup
+from tests.golden import make_golden as G
 
-needs_ref = pytest.mark.skipif(not ref_import.reference_available(), reason="needs /root/reference (build container only)")
+
+def _live_helpers(golden_dir):
+    return dict(np.load(os.path.join(golden_dir, "live_helpers.npz")))
 
 
-@needs_ref
-@pytest.mark.parametrize("size,alpha", [(64, 0.3), (12, 0.3), (1, 0.3), (7, 2.0)])
-def test_my_mixup_is_the_reference_function(size, alpha):
-    ref = ref_import.import_reference_file("helpers/mixup.py").my_mixup
-    for seed in (0, 1, 1234):
-        torch.manual_seed(seed)
-        np.random.seed(seed)
-        r_idx, r_lam = ref(size, alpha)
-        after_ref = (torch.randint(1 << 30, (1,)).item(), np.random.randint(1 << 30))
+@pytest.mark.parametrize("size,alpha", G.MIXUP_CASES)
+def test_my_mixup_is_the_reference_function(golden_dir, size, alpha):
+    gold = _live_helpers(golden_dir)
+    for seed in G.MIXUP_SEEDS:
+        pre = f"mixup.{size}_{alpha}.s{seed}."
+        r_idx, r_lam = torch.from_numpy(gold[pre + "idx"]), torch.from_numpy(gold[pre + "lam"])
+        after_ref = tuple(int(v) for v in gold[pre + "after"])
         torch.manual_seed(seed)
         np.random.seed(seed)
         idx, lam = my_mixup(size, alpha, device="cpu")
@@ -52,13 +54,22 @@ def _passt_s():
         return passt_amd.get_model(arch="passt_s_swa_p16_128_ap476", pretrained=False, s_patchout_t=40, s_patchout_f=4)
 
 
-@needs_ref
-def test_count_non_zero_params_walks_the_module():
-    count = ref_import.import_reference_file("helpers/models_size.py").count_non_zero_params
+def test_count_non_zero_params_walks_the_module(golden_dir):
+    gold = _live_helpers(golden_dir)
+    desc, total, nonzero = list(gold["models_size.desc"]), int(gold["models_size.total"]), int(gold["models_size.nonzero"])
+    torch.manual_seed(G.MODELS_SIZE_SEED)
     net = _passt_s()
-    desc, total, nonzero = count(net)
     assert total == sum(p.numel() for p in net.parameters()) == 86_153_758          # passt_s / 527 classes
-    assert 0 < nonzero <= total and "type Linear, weight" in desc and "type PaSST, cls_token" in desc
+    assert 0 < nonzero <= total and any(l.startswith("type Linear, weight,") for l in desc) \
+        and any(l.startswith("type PaSST, cls_token,") for l in desc)
+    # the function visits every module through Module.apply (children before their parent) and lists the module's own
+    # parameters: "type <class>, <name>,  <numel>, <non-zero>, <dtype>, "
+    mine = []
+    net.apply(lambda m: mine.extend((type(m).__name__, k, p.numel(), int((p != 0).sum()), str(p.dtype))
+                                    for k, p in m.named_parameters(recurse=False)))
+    theirs = [tuple(f.strip() for f in l.split(",")[:5]) for l in desc]
+    assert [(t[len("type "):], k, int(n), int(nz), dt) for t, k, n, nz, dt in theirs] == mine
+    assert sum(nz for *_, nz, _ in mine) == nonzero
 
 
 def test_eager_import_does_not_load_dynamo():

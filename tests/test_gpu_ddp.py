@@ -105,7 +105,7 @@ def test_bench_self_launch_clean_env():
     env["PASST_AMD_BENCH_DRY_GLOO"] = "1"
     for path in ("trainstep", "autograd"):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4",
-                            "--path", path], env=env, capture_output=True, timeout=900)
+                            "--path", path, "--full"], env=env, capture_output=True, timeout=900)
         out = r.stdout.decode()
         assert r.returncode == 0, (out, r.stderr.decode()[-3000:])
         lines = [l for l in out.splitlines() if l.startswith("{")]
@@ -182,7 +182,7 @@ def test_bench_multi_rank_dry_run():
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    HSA_ENABLE_IPC_MODE_LEGACY="0", PASST_AMD_BENCH_DRY_GLOO="1")
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                                       "--batch", "4"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE))
+                                       "--batch", "4", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE))
     outs = []
     for p in procs:
         o, e = p.communicate(timeout=600)
@@ -210,7 +210,7 @@ def test_bench_multi_rank_line_survives_failing_diagnostics(fail_rank):
                    HSA_ENABLE_IPC_MODE_LEGACY="0", PASST_AMD_BENCH_DRY_GLOO="1", PASST_AMD_BENCH_DIAG_FAIL_RANK=str(fail_rank),
                    PASST_AMD_BENCH_DIAG_TIMEOUT_S="15")
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                                       "--batch", "4"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE))
+                                       "--batch", "4", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE))
     outs = []
     for p in procs:
         o, e = p.communicate(timeout=600)
@@ -232,7 +232,7 @@ def test_bench_sweep_dry_run():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", PASST_AMD_BENCH_DRY_GLOO="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--sweep-gpus", "1,2", "--steps", "2", "--warmup", "1", "--batch", "4",
-                        "--no-cpu-baseline"], env=env, capture_output=True, timeout=900)
+                        "--no-cpu-baseline", "--full"], env=env, capture_output=True, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [json.loads(l) for l in r.stdout.decode().splitlines() if l.startswith("{")]
     assert [d["n_gpus"] for d in lines] == [1, 2] and all(d["value"] > 0 for d in lines)

@@ -394,7 +394,7 @@ def test_train_step_two_steps_at_bench_shape_vs_oracle(precision, loss):
     init = {k: v.detach().clone() for k, v in sd.items()}
     opt = torch.optim.AdamW([v for k, v in sd.items() if not k.startswith("head_dist.")], lr=lr, weight_decay=wd)
     ref_losses = []
-    torch.set_num_threads(min(32, os.cpu_count() or 1))
+    torch.set_num_threads(min(16, os.cpu_count() or 1))             # a GPU host's job gets 16 of its CPUs
     for step in range(2):
         torch.manual_seed(4000 + step)
         np.random.seed(4000 + step)

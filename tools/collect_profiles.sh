@@ -2,7 +2,7 @@
 # The measurements behind bench.py's roofline object and DESIGN.md's tables, in one go (run on the GPU box):
 #   bash tools/collect_profiles.sh gpurun_out/rNN
 # Writes into the given directory:
-#   bench_c2.log        the default bench line (with cpu_baseline)
+#   bench_c2.log        the --full bench line (roofline, cpu_baseline, ...)
 #   kernel_stats.txt    per-kernel time of 6 steps (5 timed + 1 warm-up)  (rocprofv3 --kernel-trace, summarised by rocpd_stats.py)
 #   pmc_fetch.txt / pmc_write.txt / gemm_traffic.json / mel_traffic.json
 #                       HBM bytes per launch: FETCH_SIZE and WRITE_SIZE in separate passes (MI355X_MICROARCH.md:
@@ -14,7 +14,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/${1:-gpurun_out/prof}
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py"
+BENCH="python $R/bench.py --full"         # the per-launch figures of the profiled steps as before
 
 timeout 400 $BENCH > "$O/bench_c2.log" 2>&1
 

@@ -40,7 +40,7 @@ for transport in torch rccl_abi; do
       env_persist=""
       [ "$persist" = persistent ] && env_persist="PASST_AMD_DDP_PERSISTENT=1"
       echo "== $tag"
-      env $env_persist timeout 1500 python bench.py --sweep-gpus "$GPUS" --steps "$STEPS" --warmup 10 --no-cpu-baseline \
+      env $env_persist timeout 1500 python bench.py --full --sweep-gpus "$GPUS" --steps "$STEPS" --warmup 10 --no-cpu-baseline \
           --transport $transport --comm-dtype $wire > "$O/scale_$tag.jsonl" 2> "$O/scale_$tag.err"
       grep -c '"metric"' "$O/scale_$tag.jsonl" | sed "s/^/   lines: /"
     done
@@ -55,7 +55,7 @@ print(",".join(str(g) for g in (1, 2, 4) if g <= n))
 EOF
 )
 for transport in torch rccl_abi; do
-  timeout 900 python bench.py --config c5 --sweep-gpus "$C5" --steps $((2 * STEPS)) --warmup 10 --no-cpu-baseline --transport $transport \
+  timeout 900 python bench.py --full --config c5 --sweep-gpus "$C5" --steps $((2 * STEPS)) --warmup 10 --no-cpu-baseline --transport $transport \
       > "$O/scale_c5_$transport.jsonl" 2> "$O/scale_c5_$transport.err"
 done
 
