@@ -18,45 +18,18 @@
 
 namespace pa {
 
-// occupancy targets of the bf16 kernels (waves per SIMD); overridable for A/B builds
-#ifndef PA_ATTN_FWD_WAVES
-#define PA_ATTN_FWD_WAVES 3
-#endif
-#ifndef PA_ATTN_DQ_WAVES
-#define PA_ATTN_DQ_WAVES 3
-#endif
-#ifndef PA_ATTN_DKDV_WAVES
-#define PA_ATTN_DKDV_WAVES 2
-#endif
-// Wave priorities (A/B knob).  1: static, distinct priority per hardware wave slot (HW_ID.wave_id & 3), 2: per workgroup
-// id.  Tried in round 3 against the observation that the co-resident waves of a SIMD pass through the matrix phase and
-// the VALU phase of a tile together: no gain (fwd 71.4 -> 74.5 us, profiles/r03_attention_experiments.md), default off.
-#ifndef PA_ATTN_PRIO
-#define PA_ATTN_PRIO 0
-#endif
-// Packed f32 math on accumulator register pairs (A/B knob, round 4): the row sums of the forward as 16 v_pk_add_f32 instead of
-// 32 v_add_f32, the p * dP products of the backward as 8 v_pk_mul_f32 instead of 16 v_mul_f32 (pairs (r, r + 1), r even, are
-// 64-bit aligned in an MFMA accumulator block).
-#ifndef PA_ATTN_PK
-#define PA_ATTN_PK 0
-#endif
-// Cache policy of the result stores (A/B build knob, round 6 sweep profiles/r06_cache_policy.txt): 1 = non-temporal
-#ifndef PA_ATTN_FUSED_NT_LD
-#define PA_ATTN_FUSED_NT_LD 0      // 2: the single-pass backward stages K and the Q / dO tiles (each read by ONE workgroup) non-temporally
-#endif
-#ifndef PA_ATTN_NT_KV
-#define PA_ATTN_NT_KV 0            // 2: streamed tiles of the forward / two-kernel backward non-temporally
-#endif
-#ifndef PA_ATTN_NT_ST
-#define PA_ATTN_NT_ST 0
-#endif
-template <typename V> __device__ __forceinline__ void attn_store(V* p, const V& v) {
-#if PA_ATTN_NT_ST
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
+// occupancy targets of the bf16 kernels (waves per SIMD)
+static constexpr int FWD_WAVES = 3, DQ_WAVES = 3, DKDV_WAVES = 2;
+// Measured and not kept:
+//  * static wave priorities, distinct per hardware wave slot or per workgroup, against the observation that the co-resident
+//    waves of a SIMD pass through the matrix phase and the VALU phase of a tile together: no gain (fwd 71.4 -> 74.5 us,
+//    profiles/r03_attention_experiments.md);
+//  * packed f32 math on accumulator register pairs (round 4): the row sums of the forward as 16 v_pk_add_f32 instead of
+//    32 v_add_f32, the p * dP products of the backward as 8 v_pk_mul_f32 instead of 16 v_mul_f32 (profiles/r04_mfma_valu_arbitration.txt:
+//    packed f32 has no rate advantage per element next to MFMAs; the Makefile keeps the SLP vectoriser from re-introducing it);
+//  * non-temporal hints (profiles/r06_cache_policy.txt): on the result stores, 8- and 16-byte row pieces written through as partial
+//    lines (forward 57 -> 70 us, backward 177 -> 225); on the LDS-DMA of the streamed tiles or of the single-pass backward's
+//    K / Q / dO tiles, each read by one workgroup (+0.3 to +0.7 % on the step).
 static constexpr int HD = 64;       // head dim (all PaSST archs: 768/12, 1024/16, 384/6, 128/2)
 static constexpr int TROWS = 64;    // streamed rows per LDS tile
 static constexpr float LOG2E = 1.4426950408889634f;
@@ -167,7 +140,7 @@ __device__ __forceinline__ void stage_tile_off(char* lds, const char* tile_base,
 #pragma unroll
     for (int i = 0; i < LaneOff<T>::PER_WAVE; ++i)
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tile_base + voff[i]),
-                                         (__attribute__((address_space(3))) void*)(lds + (wave * LaneOff<T>::PER_WAVE + i) * 1024), 16, 0, PA_ATTN_NT_KV);
+                                         (__attribute__((address_space(3))) void*)(lds + (wave * LaneOff<T>::PER_WAVE + i) * 1024), 16, 0, 0);
 }
 template <typename T> __device__ __forceinline__ void lane_offsets(LaneOff<T>& lo, int lane) {
     const int row = lane & 31, h = lane >> 5;
@@ -208,16 +181,12 @@ __device__ __forceinline__ typename Frag<T>::type col_frag_off(const char* lds, 
 
 // Wait until at most PENDING younger LDS operations are outstanding and tie the fragments to the wait, so no use
 // of them can be scheduled above it.  f32 fragments come from plain loads the compiler tracks itself: no-op.
-#ifndef PA_ATTN_DEBUG_WAIT
-#define PA_ATTN_DEBUG_WAIT 0
-#endif
-
 template <int PENDING, typename F> __device__ __forceinline__ void col_settle(F& a, F& b) {
-    if constexpr (sizeof(F) == 16 && __is_same(F, bf16x8)) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(PA_ATTN_DEBUG_WAIT ? 0 : PENDING));
+    if constexpr (sizeof(F) == 16 && __is_same(F, bf16x8)) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(PENDING));
 }
 template <int PENDING, typename F> __device__ __forceinline__ void col_settle(F& a, F& b, F& c, F& d) {
     if constexpr (sizeof(F) == 16 && __is_same(F, bf16x8))
-        asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(PA_ATTN_DEBUG_WAIT ? 0 : PENDING));
+        asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(PENDING));
 }
 
 // Store two 32x32 accumulator tiles acc[db] (lane = owned row, register = d) as rows of 64 contiguous elements
@@ -236,7 +205,7 @@ __device__ __forceinline__ void store_rows_direct(const f32x16 (&acc)[2], float 
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const f32x4 v = {acc[db][4 * g] * mul, acc[db][4 * g + 1] * mul, acc[db][4 * g + 2] * mul, acc[db][4 * g + 3] * mul};
-                if (ok) attn_store((f32x4*)(rowp + db * 32 + 8 * g + 4 * h), v);
+                if (ok) *(f32x4*)(rowp + db * 32 + 8 * g + 4 * h) = v;
             }
         } else {
 #pragma unroll
@@ -252,7 +221,7 @@ __device__ __forceinline__ void store_rows_direct(const f32x16 (&acc)[2], float 
                 const auto r1 = __builtin_amdgcn_permlane32_swap(w[1], w[3], false, false);
                 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
                 const u32x4 v = {r0[0], r1[0], r0[1], r1[1]};
-                if (ok) attn_store((u32x4*)(rowp + db * 32 + 16 * gp + 8 * h), v);
+                if (ok) *(u32x4*)(rowp + db * 32 + 16 * gp + 8 * h) = v;
             }
         }
     }
@@ -313,19 +282,6 @@ template <typename F> __device__ __forceinline__ void frag_settle(F& a, F& b, in
 template <typename F> __device__ __forceinline__ void frag_settle1(F& a, int pending) {
     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "i"(pending));
 }
-__device__ __forceinline__ void wave_static_prio() {
-#if PA_ATTN_PRIO == 1
-    const uint32_t slot = __builtin_amdgcn_s_getreg((4 /*HW_REG_HW_ID*/) | (0 << 6) | ((4 - 1) << 11)) & 3;   // wave_id[1:0]
-    if (slot == 0) __builtin_amdgcn_s_setprio(3);
-    else if (slot == 1) __builtin_amdgcn_s_setprio(2);
-    else if (slot == 2) __builtin_amdgcn_s_setprio(1);
-#elif PA_ATTN_PRIO == 2
-    const uint32_t slot = (blockIdx.x >> 3) & 3;
-    if (slot == 0) __builtin_amdgcn_s_setprio(3);
-    else if (slot == 1) __builtin_amdgcn_s_setprio(2);
-    else if (slot == 2) __builtin_amdgcn_s_setprio(1);
-#endif
-}
 // max / sum of a per-lane value with the lane that holds the other half of the same owned row (lane ^ 32), on the
 // VALU (v_permlane32_swap; __shfl_xor goes through ds_bpermute and an lgkmcnt wait)
 __device__ __forceinline__ float other_half(float v) {
@@ -365,7 +321,7 @@ static inline unsigned attn_grid(int nblk, int BH) { return (unsigned)(nblk * 8 
 // 32 adds cost 32), tail masks only in the tail instance, addresses precomputed per lane (LaneOff), rows stored straight
 // from the registers, and waves without a query row skip the arithmetic.
 template <typename T, bool PRE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? PA_ATTN_FWD_WAVES : 2))) void attn_fwd_kernel(const T* __restrict__ qkv, int ldqkv, T* __restrict__ o,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? FWD_WAVES : 2))) void attn_fwd_kernel(const T* __restrict__ qkv, int ldqkv, T* __restrict__ o,
                                                        int ldo, float* __restrict__ lse, int H, int N, int nq, float scale, int nblk, int BH) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using F = typename Frag<T>::type;
@@ -374,7 +330,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int blk, bh;
     if (!attn_block(nblk, BH, blk, bh)) return;
-    wave_static_prio();
     const int b = bh / H, h = bh % H;
     const int D = H * HD;
     const T* base = qkv + (int64_t)b * N * ldqkv + h * HD;      // q of token 0 of this (b,h)
@@ -465,20 +420,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
             }
         }
         float psum = 0.f;
-#if PA_ATTN_PK
-        f32x2 ps2 = {0.f, 0.f};
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            if (kb == 1 && !both) break;
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                s[kb][r] = __builtin_amdgcn_exp2f(s[kb][r]);
-                s[kb][r + 1] = __builtin_amdgcn_exp2f(s[kb][r + 1]);
-                ps2 += f32x2{s[kb][r], s[kb][r + 1]};
-            }
-        }
-        psum = ps2[0] + ps2[1];
-#else
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
             if (kb == 1 && !both) break;
@@ -488,7 +429,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
                 psum += s[kb][r];
             }
         }
-#endif
         l_run += psum;
         // O^T[d][q] += V^T[d][key] P^T[key][q]; the V column fragments of step i+1 are in flight under the MFMAs of step i
         constexpr int ns = both ? 2 * NSB : NSB;
@@ -544,7 +484,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 // backward, part 1: dK, dV.  Workgroup owns 128 keys (lane = key); queries stream through LDS.
 // ------------------------------------------------------------------------------------------------
 template <typename T, bool PRE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? PA_ATTN_DKDV_WAVES : 1))) void attn_bwd_dkdv_kernel(const T* __restrict__ qkv, int ldqkv,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? DKDV_WAVES : 1))) void attn_bwd_dkdv_kernel(const T* __restrict__ qkv, int ldqkv,
                                                             const T* __restrict__ d_o, int ldo,
                                                             const float* __restrict__ ws, int64_t plane,
                                                             T* __restrict__ dqkv, int lddqkv, int H, int N, int nq, float scale, int nblk, int BH) {
@@ -555,7 +495,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int blk, bh;
     if (!attn_block(nblk, BH, blk, bh)) return;
-    wave_static_prio();
     const int b = bh / H, h = bh % H;
     const int D = H * HD;
     const T* base = qkv + (int64_t)b * N * ldqkv + h * HD;
@@ -632,22 +571,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 #pragma unroll
             for (int r = 0; r < 16; ++r) sa[r] = fmaf(sa[r], sl2, nl[r]);
         }
-#if PA_ATTN_PK
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-            const f32x2 pp = {__builtin_amdgcn_exp2f(sa[r]), __builtin_amdgcn_exp2f(sa[r + 1])};
-            const f32x2 d2 = f32x2{dpa[r], dpa[r + 1]} * pp;    // dS / scale
-            sa[r] = pp[0]; sa[r + 1] = pp[1];
-            dpa[r] = d2[0]; dpa[r + 1] = d2[1];
-        }
-#else
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const float p = __builtin_amdgcn_exp2f(sa[r]);
             sa[r] = p;
             dpa[r] *= p;                                        // dS / scale
         }
-#endif
         // queries beyond nq exist only in the last tile; lanes whose own key is beyond N only produce their own,
         // never stored, outputs and need no mask
         if (LAST && (nq & (TROWS - 1))) {
@@ -709,7 +638,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 // backward, part 2: dQ.  Workgroup owns 128 queries (lane = query); keys stream through LDS.
 // ------------------------------------------------------------------------------------------------
 template <typename T, bool PRE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? PA_ATTN_DQ_WAVES : 1))) void attn_bwd_dq_kernel(const T* __restrict__ qkv, int ldqkv,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? DQ_WAVES : 1))) void attn_bwd_dq_kernel(const T* __restrict__ qkv, int ldqkv,
                                                           const T* __restrict__ o, const T* __restrict__ d_o, int ldo,
                                                           const float* __restrict__ lse, float* __restrict__ delta, int64_t plane,
                                                           T* __restrict__ dqkv, int lddqkv, int H, int N, int nq, float scale, int nblk, int BH) {
@@ -720,7 +649,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int blk, bh;
     if (!attn_block(nblk, BH, blk, bh)) return;
-    wave_static_prio();
     const int b = bh / H, h = bh % H;
     const int D = H * HD;
     const T* base = qkv + (int64_t)b * N * ldqkv + h * HD;
@@ -800,17 +728,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
             mma32<T>(sa, row_frag_off<T>(sK, lo, kb * 32, st), qf[st]);
             mma32<T>(dpa, row_frag_off<T>(sV, lo, kb * 32, st), dof[st]);
         }
-#if PA_ATTN_PK
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-            const f32x2 pp = {__builtin_amdgcn_exp2f(PRE ? sa[r] : fmaf(sa[r], sl2, -lse2)), __builtin_amdgcn_exp2f(PRE ? sa[r + 1] : fmaf(sa[r + 1], sl2, -lse2))};
-            const f32x2 d2 = f32x2{dpa[r], dpa[r + 1]} * pp;    // dS^T / scale
-            dpa[r] = d2[0]; dpa[r + 1] = d2[1];
-        }
-#else
 #pragma unroll
         for (int r = 0; r < 16; ++r) dpa[r] *= __builtin_amdgcn_exp2f(PRE ? sa[r] : fmaf(sa[r], sl2, -lse2));      // dS^T / scale
-#endif
         if (LAST && (N & (TROWS - 1))) {                        // keys beyond N: last tile only
 #pragma unroll
             for (int r = 0; r < 16; ++r)
@@ -879,13 +798,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 // waves per SIMD, 256 registers each).  Index math of T and of the phase-2 operand fetches: tools/emulate_attn_bwd_fused.py
 // (values and bank conflicts under the MI355X lane-group rules, on the CPU).
 // ------------------------------------------------------------------------------------------------
-// timing ablations (A/B builds only, results are wrong): 1 = no phase 2, 2 = no exp / dS arithmetic, 4 = no dV / dK products (and no
-// column fragments, no T writes), 8 = no score products, 16 = no barrier per tile
-#ifndef PA_FUSED_ABL
-#define PA_FUSED_ABL 0
-#endif
-
-
+// (Where the time goes, phase by phase -- builds that drop phase 2, the exp / dS arithmetic, the dV / dK products, the score
+// products or the barrier per tile: profiles/r05_attention_single_pass.txt, profiles/r06_attention_w16.txt.)
 static constexpr int FK = 512;                                   // key rows of the resident K tile (N <= FK)
 static constexpr int FT_PLANE = FK * 32;                         // one 16-query plane of T: FK keys x 16 queries x 2 B
 static constexpr int F_OFF_T = FK * 128;
@@ -949,7 +863,7 @@ __global__ __launch_bounds__(W16 ? 1024 : 512) __attribute__((amdgpu_waves_per_e
             const int row = rq * 8 + (lane >> 3);
             const int c = (lane & 7) ^ swz_f128(row);
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gK + (int64_t)min(row, N - 1) * ldbq + c * 16),
-                                             (__attribute__((address_space(3))) void*)(sK + rq * 1024), 16, 0, PA_ATTN_FUSED_NT_LD);
+                                             (__attribute__((address_space(3))) void*)(sK + rq * 1024), 16, 0, 0);
         }
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #pragma unroll
@@ -965,7 +879,7 @@ __global__ __launch_bounds__(W16 ? 1024 : 512) __attribute__((amdgpu_waves_per_e
         if (W16 && wave >= 8) return;
         const int grow = min(t * 32 + st_row, N - 1);
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(st_src + (int64_t)grow * st_ldb + st_chunk),
-                                         (__attribute__((address_space(3))) void*)(sStage + (t & 1) * F_STAGE + st_tensor * 4096 + st_piece * 1024), 16, 0, PA_ATTN_FUSED_NT_LD);
+                                         (__attribute__((address_space(3))) void*)(sStage + (t & 1) * F_STAGE + st_tensor * 4096 + st_piece * 1024), 16, 0, 0);
     };
     stage(0);
     const int kbase0 = wave * (32 * NKB);
@@ -1069,7 +983,7 @@ __global__ __launch_bounds__(W16 ? 1024 : 512) __attribute__((amdgpu_waves_per_e
             // rounding of P than the eight-wave form); dO fragments two deep; column fragments requested after the arithmetic.
 #pragma unroll
             for (int st = 0; st < NF; ++st) vf[0][st] = *(const F*)(vrow + st * 16);
-            if (!(PA_FUSED_ABL & 8)) {
+            {
                 F qf[2], kf[2];
 #pragma unroll
                 for (int st = 0; st < 2; ++st) {
@@ -1086,10 +1000,8 @@ __global__ __launch_bounds__(W16 ? 1024 : 512) __attribute__((amdgpu_waves_per_e
                     }
                 }
             }
-            if (!(PA_FUSED_ABL & 2)) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) sa[r] = __builtin_amdgcn_exp2f(sa[r]);
-            }
+            for (int r = 0; r < 16; ++r) sa[r] = __builtin_amdgcn_exp2f(sa[r]);
 #pragma unroll
             for (int st = 0; st < NS; ++st) pfp[st] = acc_frag<T>(sa, st);
             // pin the order (volatile asm statements keep theirs, and the fragment loads of the dP chain are such): left alone the
@@ -1103,7 +1015,7 @@ __global__ __launch_bounds__(W16 ? 1024 : 512) __attribute__((amdgpu_waves_per_e
 #pragma unroll
                 for (int e = 0; e < 4; ++e) dpa[4 * g + e] = d[e];
             }
-            if (!(PA_FUSED_ABL & 8)) {
+            {
                 F df[2];
 #pragma unroll
                 for (int st = 0; st < 2; ++st) df[st] = lds_b128_imm<F>(aS[st], ODO);
@@ -1117,65 +1029,51 @@ __global__ __launch_bounds__(W16 ? 1024 : 512) __attribute__((amdgpu_waves_per_e
             // the next tile's Q / dO rows are requested HERE, behind the only vector-memory loads of the block (the V fragments above:
             // the compiler's wait for them is then exact, nothing younger is in flight) and in front of half a tile of work
             if (t + 1 < nt) stage(t + 1);
-            if (!(PA_FUSED_ABL & 2)) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) dpa[r] *= (float)pfp[r >> 3][r & 7];       // dS / scale
-            }
-            if (PA_FUSED_ABL & 4) {
-                asm volatile("" :: "v"(pfp[0]), "v"(pfp[1]), "v"(dpa));
-                return;
-            }
+            for (int r = 0; r < 16; ++r) dpa[r] *= (float)pfp[r >> 3][r & 7];       // dS / scale
             issue_cf(0);
         } else {
-        // the fragment reads are asm (issued where they are written, settled by counted waits): left to itself the compiler, at
-        // the register limit, either hoists all twelve loads and spills the V fragments or serialises load -> wait -> MFMA
-        if (!(PA_FUSED_ABL & 8)) {
-            F qf[NF], kf[NF];
+            // the fragment reads are asm (issued where they are written, settled by counted waits): left to itself the compiler, at
+            // the register limit, either hoists all twelve loads and spills the V fragments or serialises load -> wait -> MFMA
+            {
+                F qf[NF], kf[NF];
 #pragma unroll
-            for (int st = 0; st < NF; ++st) {
-                qf[st] = lds_b128_imm<F>(aS[st], OQ);
-                kf[st] = lds_b128_imm<F>(aS[st] + (uint32_t)kdelta, kb * 4096);
+                for (int st = 0; st < NF; ++st) {
+                    qf[st] = lds_b128_imm<F>(aS[st], OQ);
+                    kf[st] = lds_b128_imm<F>(aS[st] + (uint32_t)kdelta, kb * 4096);
+                }
+#pragma unroll
+                for (int st = 0; st < NF; ++st) {
+                    frag_settle(qf[st], kf[st], 2 * (NF - 1 - st));
+                    mma32<T>(sa, qf[st], kf[st]);
+                }
             }
+            // dP'[q][key] = dO V^T - delta: requested behind the score chain, whose MFMAs cover the latency
 #pragma unroll
-            for (int st = 0; st < NF; ++st) {
-                frag_settle(qf[st], kf[st], 2 * (NF - 1 - st));
-                mma32<T>(sa, qf[st], kf[st]);
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 d = ld4f(sc + FK * 4 + g * 32);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) dpa[4 * g + e] = d[e];
             }
-        }
-        // dP'[q][key] = dO V^T - delta: requested behind the score chain, whose MFMAs cover the latency
+            // (column fragments single-buffered: 16 registers, not 32 -- the kernel sits at the 256-register limit of two waves per
+            // SIMD, and a spilled accumulator inside the tile loop drains the Q / dO prefetch in front of its reload.  The first
+            // set is requested in front of the dP chain / the exponentials, which cover its latency)
+            {
+                F df[NF];
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 d = ld4f(sc + FK * 4 + g * 32);
+                for (int st = 0; st < NF; ++st) df[st] = lds_b128_imm<F>(aS[st], ODO);
+                issue_cf(0);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) dpa[4 * g + e] = d[e];
-        }
-        // (column fragments single-buffered: 16 registers, not 32 -- the kernel sits at the 256-register limit of two waves per
-        // SIMD, and a spilled accumulator inside the tile loop drains the Q / dO prefetch in front of its reload.  The first
-        // set is requested in front of the dP chain / the exponentials, which cover its latency)
-        if (!(PA_FUSED_ABL & 8)) {
-            F df[NF];
-#pragma unroll
-            for (int st = 0; st < NF; ++st) df[st] = lds_b128_imm<F>(aS[st], ODO);
-            if (!(PA_FUSED_ABL & 4)) issue_cf(0);
-#pragma unroll
-            for (int st = 0; st < NF; ++st) {
-                frag_settle1(df[st], NF - 1 - st + ((PA_FUSED_ABL & 4) ? 0 : 8));
-                mma32<T>(dpa, df[st], vf[kb][st]);
+                for (int st = 0; st < NF; ++st) {
+                    frag_settle1(df[st], NF - 1 - st + 8);
+                    mma32<T>(dpa, df[st], vf[kb][st]);
+                }
             }
-        } else if (!(PA_FUSED_ABL & 4)) {
-            issue_cf(0);
-        }
-        if (!(PA_FUSED_ABL & 2)) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 sa[r] = __builtin_amdgcn_exp2f(sa[r]);
                 dpa[r] *= sa[r];                                // dS / scale
             }
-        }
-        if (PA_FUSED_ABL & 4) {
-            asm volatile("" :: "v"(sa), "v"(dpa));
-            return;
-        }
         }
         // dV^T[d][key] += dO^T[d][q] P[q][key] ; dK^T[d][key] += Q^T[d][q] dS[q][key] ; T[key][q] = bf16(dS)
 #pragma unroll
@@ -1240,9 +1138,9 @@ __global__ __launch_bounds__(W16 ? 1024 : 512) __attribute__((amdgpu_waves_per_e
             if (k + AHEAD < NSTEP) issue(k + AHEAD);
             bf16x4 &k0 = ka[k & 3][0], &k1 = ka[k & 3][1], &t0 = ta[k & 3][0], &t1 = ta[k & 3][1];
             const int younger = (NSTEP - 1 - k) < AHEAD ? (NSTEP - 1 - k) : AHEAD;      // steps issued after this one
-            if (younger == 3) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(k0), "+v"(k1), "+v"(t0), "+v"(t1) : "n"(PA_ATTN_DEBUG_WAIT ? 0 : 12));
-            else if (younger == 2) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(k0), "+v"(k1), "+v"(t0), "+v"(t1) : "n"(PA_ATTN_DEBUG_WAIT ? 0 : 8));
-            else if (younger == 1) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(k0), "+v"(k1), "+v"(t0), "+v"(t1) : "n"(PA_ATTN_DEBUG_WAIT ? 0 : 4));
+            if (younger == 3) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(k0), "+v"(k1), "+v"(t0), "+v"(t1) : "n"(12));
+            else if (younger == 2) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(k0), "+v"(k1), "+v"(t0), "+v"(t1) : "n"(8));
+            else if (younger == 1) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(k0), "+v"(k1), "+v"(t0), "+v"(t1) : "n"(4));
             else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(k0), "+v"(k1), "+v"(t0), "+v"(t1));
             const F a = {k0[0], k0[1], k0[2], k0[3], k1[0], k1[1], k1[2], k1[3]};
             const F bq = {t0[0], t0[1], t0[2], t0[3], t1[0], t1[1], t1[2], t1[3]};
@@ -1252,8 +1150,8 @@ __global__ __launch_bounds__(W16 ? 1024 : 512) __attribute__((amdgpu_waves_per_e
         const int q = t * 32 + q16 * 16 + (lane & 15);
         if (q < N) {
             const bf16x2 lo2 = {(bf16)(acc[0] * scale), (bf16)(acc[1] * scale)}, hi2 = {(bf16)(acc[2] * scale), (bf16)(acc[3] * scale)};
-            attn_store((u32x2_t*)(dqkv + ((int64_t)b * N + q) * lddqkv + h * HD + d16 * 16 + 4 * (lane >> 4)),
-                       u32x2_t{__builtin_bit_cast(uint32_t, lo2), __builtin_bit_cast(uint32_t, hi2)});
+            *(u32x2_t*)(dqkv + ((int64_t)b * N + q) * lddqkv + h * HD + d16 * 16 + 4 * (lane >> 4)) =
+                u32x2_t{__builtin_bit_cast(uint32_t, lo2), __builtin_bit_cast(uint32_t, hi2)};
         }
     };
 
@@ -1278,7 +1176,7 @@ __global__ __launch_bounds__(W16 ? 1024 : 512) __attribute__((amdgpu_waves_per_e
     };
     auto sync = [&]() __attribute__((always_inline)) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (!(PA_FUSED_ABL & 16)) __syncthreads();
+        __syncthreads();
     };
     // (Measured and dropped, profiles/r05_attention_single_pass.txt: the two waves of a SIMD running phase 2 / phase 1 of an
     // inter-barrier interval in OPPOSITE orders -- two loop nests chosen once per wave.  The second nest costs the allocator four
@@ -1287,7 +1185,7 @@ __global__ __launch_bounds__(W16 ? 1024 : 512) __attribute__((amdgpu_waves_per_e
         if (!W16 && t + 1 < nt) stage(t + 1);
         phase1(buf_tag, t);
         sync();
-        if (!(PA_FUSED_ABL & 1) && (!W16 || wave < 8)) phase2(buf_tag, NCH{}, t);
+        if (!W16 || wave < 8) phase2(buf_tag, NCH{}, t);
     };
     int t = 0;
     for (; t + 1 < nt; t += 2) {

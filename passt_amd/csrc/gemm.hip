@@ -18,12 +18,9 @@
 
 namespace pa {
 
-#ifndef PA_NT_GROUP_M
-#define PA_NT_GROUP_M 4      // row-tiles walked per column-tile by consecutive work items (L2 patch shape)
-#endif
-#ifndef PA_NT_SUBSTEPS
-#define PA_NT_SUBSTEPS 1
-#endif
+// row-tiles walked per column-tile by consecutive work items (L2 patch shape).  2 and 8 measure the same as 4 in the step, 16 is
+// 0.8 % slower (profiles/r03_gemm_variants_ab.txt, profiles/r06_tiles_under_policy.txt).
+static constexpr int NT_GROUP_M = 4;
 static constexpr int BM = 128, BN = 128, KB = 128;  // KB: K bytes per step
 static constexpr int TILE_BYTES = BM * KB;            // 16 KiB per operand tile
 static constexpr int GEMM_LDS = 2 * 2 * TILE_BYTES;   // 64 KiB (TN kernel)
@@ -54,86 +51,7 @@ static constexpr int PROBE_SLOTS = 512;
 #define PA_PROBE_FLAG(a, bit) 0
 #endif
 
-// ---- Cache policy of the step's GEMM memory instructions, per role (round 6, profiles/r06_cache_policy.txt) ----------------
-// The `aux` immediate of the buffer / LDS-DMA instructions: 1 = sc0, 2 = nt (non-temporal), 16 = sc1.  Every output line and
-// every epilogue operand row of a GEMM is touched exactly once by that GEMM; weights are re-read by every row band, activation
-// tiles by N / 256 column tiles, and the NEXT kernel wants this kernel's outputs.  With the default policy the single-use
-// lines compete for the caches with the re-used ones; marked non-temporal they do not: 1.5 - 2.4 % of the whole training step
-// (config #2, same box, ABBA: 22.39 -> 21.98, 21.78 -> 21.46, 21.98 -> 21.48 ms; ESC-50 - 2.9 %, config #4 - 1.6 %), e.g.
-// fc2 / proj + residual 104.5 -> 95.0 us, fc1 + GELU 170 -> 157 us.  The bytes crossing the L2's fabric side do NOT change
-// (FETCH_SIZE / WRITE_SIZE: 439 against 440 MB per launch): the effect is behind them, in the 256 MiB Infinity Cache / HBM.
-// What the sweep settled, role by role:
-//   nt  fc1's blocked pre-activation (written in the forward, next read in the backward)                      PA_AUX_ST_PRE
-//   nt  the bf16 outputs of the STORE / GELU / GELU' epilogues (full 128-byte lines per 8 lanes)               PA_AUX_ST_OUT
-//   nt  the epilogue operand rows read once (residual rows, pre-activation blocks)                            PA_AUX_LD_AUX
-//   nt  the A operand of the residual GEMMs (N = D: a tile is read by D / 256 column tiles only)              PA_AUX_DMA_A_RESID
-//   nt  the split-K slabs when the finishing reduction reads them (each once)                                 PA_NT_LD_SLAB
-//   default: the f32 residual-stream output (nt: the LayerNorm behind it slows down, +0.5 %), the A operand of every other GEMM
-//       (nt: fc1 + GELU 170 -> 188 us), the weights (nt: +4 % on the step), the weight-gradient operands and slab stores
-//       (+- 0), sc1 instead of nt on the outputs (half the gain), nt on the A operand of plain-store GEMMs with N = D (+0.5 %).
-// -DPA_NO_CACHE_POLICY builds the library with the default policy everywhere (A/B: tools/build_variant.sh).
-#ifdef PA_NO_CACHE_POLICY
-#define PA_CP(x) 0
-#else
-#define PA_CP(x) x
-#endif
-#ifndef PA_AUX_ST_PRE
-#define PA_AUX_ST_PRE PA_CP(2)
-#endif
-#ifndef PA_AUX_ST_OUT
-#define PA_AUX_ST_OUT PA_CP(2)
-#endif
-#ifndef PA_AUX_ST_ACT
-#define PA_AUX_ST_ACT PA_AUX_ST_OUT      // ... fc1's activation only (the fc2 GEMM behind it reads it non-temporally)
-#endif
-#ifndef PA_AUX_ST_DPRE
-#define PA_AUX_ST_DPRE PA_AUX_ST_OUT     // ... the GELU' epilogue's output only
-#endif
-#ifndef PA_AUX_ST_STORE
-#define PA_AUX_ST_STORE PA_AUX_ST_OUT    // ... the plain-store epilogue only
-#endif
-#ifndef PA_AUX_ST_RES
-#define PA_AUX_ST_RES 0
-#endif
-#ifndef PA_AUX_LD_AUX
-#define PA_AUX_LD_AUX PA_CP(2)
-#endif
-#ifndef PA_AUX_LD_PRE
-#define PA_AUX_LD_PRE PA_AUX_LD_AUX      // ... the GELU' epilogue's pre-activation only
-#endif
-#ifndef PA_AUX_LD_RES
-#define PA_AUX_LD_RES PA_AUX_LD_AUX      // ... the residual rows only
-#endif
-#ifndef PA_AUX_DMA_A
-#define PA_AUX_DMA_A 0         // LDS-DMA of the A operand (activations) of the role-split NT kernel
-#endif
-#ifndef PA_AUX_DMA_A_RESID
-#define PA_AUX_DMA_A_RESID PA_CP(2)      // ... in the residual GEMMs
-#endif
-#ifndef PA_NT_A_STORE_MAXN
-#define PA_NT_A_STORE_MAXN 0   // plain-store GEMMs with N <= this read their A operand non-temporally too (input gradients: N = D)
-#endif
-#ifndef PA_NT_LD_SLAB
-#define PA_NT_LD_SLAB PA_CP(1) // the finishing reduction reads the slabs (each once) non-temporally
-#endif
-#ifndef PA_NT_STORE_MAXN
-#define PA_NT_STORE_MAXN 0     // > 0: the plain-store epilogue uses PA_AUX_ST_OUT only when N <= this, the default policy above
-#endif
-#ifndef PA_NT_ST_SLAB
-#define PA_NT_ST_SLAB 0        // 1: split-K partial slabs (weight gradients, small-M NT GEMMs) leave as non-temporal stores
-#endif
-#ifndef PA_AUX_DMA_B
-#define PA_AUX_DMA_B 0         // LDS-DMA of the B operand (weights)
-#endif
-#ifndef PA_AUX_DMA_TN
-#define PA_AUX_DMA_TN 0        // LDS-DMA of both operands of the weight-gradient kernel
-#endif
-#ifndef PA_AUX_DMA_TN_A
-#define PA_AUX_DMA_TN_A PA_AUX_DMA_TN      // ... of dY only
-#endif
-#ifndef PA_AUX_DMA_TN_B
-#define PA_AUX_DMA_TN_B PA_AUX_DMA_TN      // ... of X only
-#endif
+// (The cache policy of the memory instructions -- the CP_* constants used below -- is named per role in pa_common.h.)
 
 // Shared epilogue: the TM x 2 MFMA accumulators of this wave (TM*32 x 64 outputs at rows m0 + wr*TM*32,
 // columns n0 + wc*64) -> per-wave LDS slab [32][68] -> 8-wide row vectors with the fused epilogue math.
@@ -351,8 +269,7 @@ __device__ __forceinline__ void gemm_epilogue_f32_direct(const pa_gemm_args& a, 
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 float* dstp = (float*)(obase + (vo + (uint32_t)(i * 32 + (r & 3) + 8 * (r >> 2)) * ldo4 + j * 128));
-                if (PA_NT_ST_SLAB && !RES) __builtin_nontemporal_store(v[r], dstp);
-                else *dstp = v[r];
+                *dstp = v[r];
             }
         }
     } else {   // edge tiles and the row-remapped (patch embedding) form: per-element checks
@@ -404,15 +321,6 @@ __device__ __forceinline__ void gemm_epilogue_f32_direct(const pa_gemm_args& a, 
 //    columns of a row; reads: one 16-byte slot per lane, 16 lanes = one row, 4 rows per instruction); the residual rows
 //    and the outputs move as 16-byte vectors, 4x fewer vector-memory instructions than the dword-per-lane form.
 // ------------------------------------------------------------------------------------------------
-#ifndef PA_EPILOGUE_V2
-#define PA_EPILOGUE_V2 1
-#endif
-#ifndef PA_V2_DEPTH_X
-#define PA_V2_DEPTH_X 2        // DGELU: 32-row passes of pre-activation rows requested ahead of their use (16 registers each)
-#endif
-#ifndef PA_V2_DEPTH_R
-#define PA_V2_DEPTH_R 1        // RESID: 32-row passes of residual rows requested ahead (32 registers each; 2 spills at TM = 4)
-#endif
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((__vector_size__(4 * sizeof(int)))) int rsrc_bits_t;
 __device__ __forceinline__ uint32_t perm_lo16(uint32_t hi_src, uint32_t lo_src) { return __builtin_amdgcn_perm(hi_src, lo_src, 0x05040100u); }
@@ -425,6 +333,9 @@ __device__ __forceinline__ auto tile_rsrc(const void* origin, int64_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(origin), 0, n, 0x00020000);
 }
 static constexpr uint32_t V2_OOB = 0x80000000u;     // a lane offset no descriptor of < 2 GiB contains
+// how far ahead of their use the auxiliary rows are requested (V2Aux / V3Aux)
+static constexpr int AUX_DEPTH_X = 2;               // DGELU: 32-row passes of pre-activation rows (16 registers each)
+static constexpr int AUX_DEPTH_R = 1;               // RESID: 32-row passes of residual rows (32 registers each; 2 spills at TM = 4)
 
 // rows of the blocked pre-activation buffer: whole multiples of 768 = lcm(256, 192, 128), so every 32-row pass of every
 // tile height (TM = 4 / 3 / 2) has its block inside the buffer -- rounding to 256 left the last passes of a 192-row tile
@@ -446,8 +357,8 @@ __host__ __device__ __forceinline__ int64_t blocked_pre_rows(int M) { return ((i
 template <int EPI, int TM, bool BLK = false> struct V2Aux {
     static constexpr bool X = EPI == PA_EPI_DGELU, R = EPI == PA_EPI_RESID;
     uint32_t blk_base = 0, blk_pitch = 0;                 // BLK: byte offset of pass 0's block, bytes between passes
-    static constexpr int PASSES = X ? (PA_V2_DEPTH_X < TM ? PA_V2_DEPTH_X : TM) : 0;                    // DGELU: 32-row passes in flight
-    static constexpr int HALVES = R ? (PA_V2_DEPTH_R < TM ? 2 * PA_V2_DEPTH_R : 2 * TM) : 0;        // RESID: 16-row half passes
+    static constexpr int PASSES = X ? (AUX_DEPTH_X < TM ? AUX_DEPTH_X : TM) : 0;                    // DGELU: 32-row passes in flight
+    static constexpr int HALVES = R ? (AUX_DEPTH_R < TM ? 2 * AUX_DEPTH_R : 2 * TM) : 0;        // RESID: 16-row half passes
     static constexpr int N = X ? PASSES * 4 : HALVES * 4;                                           // loads per wave in issue()
     u32x4 v[N > 0 ? N : 1];
     decltype(tile_rsrc(nullptr, 0)) rs;
@@ -488,19 +399,19 @@ template <int EPI, int TM, bool BLK = false> struct V2Aux {
         if constexpr (BLK) {       // blocked layout: the four 1 KiB quarters of pass i's block -> v[slot*4 + q]
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                v[slot * 4 + q] = __builtin_amdgcn_raw_buffer_load_b128(rs, vofs + (uint32_t)q * 1024u, blk_base + (uint32_t)i * blk_pitch, PA_AUX_LD_PRE);
+                v[slot * 4 + q] = __builtin_amdgcn_raw_buffer_load_b128(rs, vofs + (uint32_t)q * 1024u, blk_base + (uint32_t)i * blk_pitch, CP_LD_EPI);
         } else {
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int q = 0; q < 2; ++q)
-                    v[slot * 4 + t * 2 + q] = __builtin_amdgcn_raw_buffer_load_b128(rs, vofs + (uint32_t)(i * 32 + 16 * t + q) * ld, 0, PA_AUX_LD_PRE);
+                    v[slot * 4 + t * 2 + q] = __builtin_amdgcn_raw_buffer_load_b128(rs, vofs + (uint32_t)(i * 32 + 16 * t + q) * ld, 0, CP_LD_EPI);
         }
     }
     // RESID: rows it*4 + (lane>>4) of half pass hp  ->  v[slot*4 + it]
     __device__ __forceinline__ void load_half(int slot, int hp) {
 #pragma unroll
-        for (int it = 0; it < 4; ++it) v[slot * 4 + it] = __builtin_amdgcn_raw_buffer_load_b128(rs, vofs + (uint32_t)(hp * 16 + it * 4) * ld, 0, PA_AUX_LD_RES);
+        for (int it = 0; it < 4; ++it) v[slot * 4 + it] = __builtin_amdgcn_raw_buffer_load_b128(rs, vofs + (uint32_t)(hp * 16 + it * 4) * ld, 0, CP_LD_EPI);
     }
 };
 
@@ -616,7 +527,7 @@ __device__ __forceinline__ void gemm_epilogue_v2_bf16(const pa_gemm_args& a, f32
             for (int q = 0; q < 4; ++q) {
                 const u32x4 d = {pk[q >> 1][4 * (q & 1)], pk[q >> 1][4 * (q & 1) + 1], pk[q >> 1][4 * (q & 1) + 2], pk[q >> 1][4 * (q & 1) + 3]};
                 __builtin_amdgcn_raw_buffer_store_b128(d, brs, (PA_PROBE_FLAG(a, 0) ? V2_OOB : (uint32_t)lane * 16u) + (uint32_t)q * 1024u,
-                                                       bbase + (uint32_t)i * bpitch, PA_AUX_ST_PRE);
+                                                       bbase + (uint32_t)i * bpitch, CP_ST_PRE);
             }
         }
 #pragma unroll
@@ -636,14 +547,8 @@ __device__ __forceinline__ void gemm_epilogue_v2_bf16(const pa_gemm_args& a, f32
                 const u32x4 hi = {perm_hi16(d0[1], d0[0]), perm_hi16(d0[3], d0[2]), perm_hi16(d1[1], d1[0]), perm_hi16(d1[3], d1[2])};
                 const uint32_t ldb = o ? ld2b : ld2;
                 const uint32_t off = (PA_PROBE_FLAG(a, 0) ? V2_OOB : (o ? vo2 : vo)) + (uint32_t)(i * 32 + 16 * t) * ldb;
-                if (EPI == PA_EPI_STORE && PA_NT_STORE_MAXN > 0 && a.N > PA_NT_STORE_MAXN) {       // uniform
-                    __builtin_amdgcn_raw_buffer_store_b128(lo, ors, off, 0, 0);
-                    __builtin_amdgcn_raw_buffer_store_b128(hi, ors, off + ldb, 0, 0);
-                } else {
-                    constexpr int AUX_ST = EPI == PA_EPI_GELU ? PA_AUX_ST_ACT : (EPI == PA_EPI_DGELU ? PA_AUX_ST_DPRE : PA_AUX_ST_STORE);
-                    __builtin_amdgcn_raw_buffer_store_b128(lo, o ? ors2 : ors, off, 0, AUX_ST);
-                    __builtin_amdgcn_raw_buffer_store_b128(hi, o ? ors2 : ors, off + ldb, 0, AUX_ST);
-                }
+                __builtin_amdgcn_raw_buffer_store_b128(lo, o ? ors2 : ors, off, 0, CP_ST_OUT);
+                __builtin_amdgcn_raw_buffer_store_b128(hi, o ? ors2 : ors, off + ldb, 0, CP_ST_OUT);
             }
     }
     if constexpr (EPI == PA_EPI_DGELU) {
@@ -696,7 +601,7 @@ __device__ __forceinline__ void gemm_epilogue_v2_resid(const pa_gemm_args& a, f3
             if (hp + DEPTH < NH) aux.load_half(hp % DEPTH, hp + DEPTH);
 #pragma unroll
             for (int it = 0; it < 4; ++it)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[it]), ors, vo + (uint32_t)(hp * 16 + it * 4) * ldo4, 0, PA_AUX_ST_RES);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[it]), ors, vo + (uint32_t)(hp * 16 + it * 4) * ldo4, 0, 0);
         }
     }
 }
@@ -724,8 +629,8 @@ __device__ __forceinline__ void gemm_epilogue_v2_resid(const pa_gemm_args& a, f3
 // ------------------------------------------------------------------------------------------------
 template <int EPI, int TM> struct V3Aux {
     static constexpr bool X = EPI == PA_EPI_DGELU, R = EPI == PA_EPI_RESID;
-    static constexpr int PASSES = X ? (PA_V2_DEPTH_X < TM ? PA_V2_DEPTH_X : TM) : 0;              // DGELU: 32-row passes in flight
-    static constexpr int HALVES = R ? (PA_V2_DEPTH_R < TM ? 2 * PA_V2_DEPTH_R : 2 * TM) : 0;  // RESID: 32-row x 32-column blocks in flight
+    static constexpr int PASSES = X ? (AUX_DEPTH_X < TM ? AUX_DEPTH_X : TM) : 0;              // DGELU: 32-row passes in flight
+    static constexpr int HALVES = R ? (AUX_DEPTH_R < TM ? 2 * AUX_DEPTH_R : 2 * TM) : 0;  // RESID: 32-row x 32-column blocks in flight
     static constexpr int N = X ? PASSES * 4 : HALVES * 4;        // loads per wave in issue(): the K loop's counted vmcnt wait relies on it
     u32x4 v[N > 0 ? N : 1];
     decltype(tile_rsrc(nullptr, 0)) rs;
@@ -1163,12 +1068,12 @@ template <typename T, int EPI, int TM, bool A3 = false, bool BLK = false, bool T
 __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const pa_gemm_args a, const int tiles_m, const int tiles_n,
                                                               const int nwg, const int ksteps_per_split, const int total) {
     using G = StaggerGeom<TM, A3>;
-    static_assert(!TR || (PA_EPILOGUE_V2 && sizeof(T) == 2 && EPI != PA_EPI_PARTIAL && !BLK), "v3: bf16 operands, fused epilogues, row-major pre-activation");
+    static_assert(!TR || (sizeof(T) == 2 && EPI != PA_EPI_PARTIAL && !BLK), "v3: bf16 operands, fused epilogues, row-major pre-activation");
     constexpr int WN = 4;
     constexpr int TBM = G::TBM, TBN = G::TBN;         // TM = 2/3/4 -> 128/192/256-row tiles (tile quantisation)
     constexpr int A_PER = TM;                         // A copies per wave per stage: TBM*128/1024/8
     constexpr int NA = G::NA, PDA = NA - 1;           // A ring slots; K-tiles of lead of the A requests (B: always 1)
-    constexpr bool USE_V2 = PA_EPILOGUE_V2 && sizeof(T) == 2 && EPI != PA_EPI_PARTIAL;
+    constexpr bool USE_V2 = sizeof(T) == 2 && EPI != PA_EPI_PARTIAL;
     static_assert(!A3 || (TM <= 3 && (USE_V2 || EPI == PA_EPI_PARTIAL)), "A3: LDS budget / 8 KiB slabs");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -1190,7 +1095,7 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const pa_gemm_args
         const int item = r * nres + xcd_swizzle(bid, n);
         int tm, tn;
         const int sp = item / nwg;
-        tile_coords(item - sp * nwg, tiles_m, tiles_n, PA_NT_GROUP_M, tm, tn);
+        tile_coords(item - sp * nwg, tiles_m, tiles_n, NT_GROUP_M, tm, tn);
         tab[r] = make_int4(tm * TBM, tn * TBN, sp, 0);
     }
 #ifdef PA_PROBE
@@ -1238,17 +1143,12 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const pa_gemm_args
     auto dmaA = [&](int slot, int step) {
         char* sA = smem + G::a_off(slot) + wave * (A_PER * 1024);
         const char* sb = baseA + (int64_t)step * KB;
-        if (EPI == PA_EPI_STORE && PA_NT_A_STORE_MAXN > 0 && a.N <= PA_NT_A_STORE_MAXN) {       // uniform
-#pragma unroll
-            for (int i = 0; i < A_PER; ++i)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sb + voffA[i]),
-                                                 (__attribute__((address_space(3))) void*)(sA + i * 1024), 16, 0, 2);
-            return;
-        }
+        (void)a;      // captured and unused: without it ten kernels come out with two address registers renamed (no other change).
+                      // Kept so that the commit that folded the build-time variants left every kernel body as it was; drop it freely.
 #pragma unroll
         for (int i = 0; i < A_PER; ++i)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sb + voffA[i]),
-                                             (__attribute__((address_space(3))) void*)(sA + i * 1024), 16, 0, EPI == PA_EPI_RESID ? PA_AUX_DMA_A_RESID : PA_AUX_DMA_A);
+                                             (__attribute__((address_space(3))) void*)(sA + i * 1024), 16, 0, EPI == PA_EPI_RESID ? CP_DMA_A_RESID : 0);
     };
     auto dmaB = [&](int slot, int step) {
         char* sB = smem + G::b_off(slot) + wave * 4096;
@@ -1256,7 +1156,7 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const pa_gemm_args
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sb + voffB[i]),
-                                             (__attribute__((address_space(3))) void*)(sB + i * 1024), 16, 0, PA_AUX_DMA_B);
+                                             (__attribute__((address_space(3))) void*)(sB + i * 1024), 16, 0, 0);
     };
 
     const int rsw = swz_f128(lane);
@@ -1321,27 +1221,25 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const pa_gemm_args
                 else if (tail == AUXN) wait_vmcnt<(AUXN > 0 ? AUXN : 1)>();
                 else wait_vmcnt<A_PER + AUXN>();
             };
-            // PA_NT_SUBSTEPS 16-wide k-substeps per L / M segment pair (1: 8 barriers per K-tile, 2: 4)
-            constexpr int SUB = PA_NT_SUBSTEPS, NPH = 4 / SUB;
+            // one 16-wide k-substep per L / M segment pair: 8 barriers per K-tile (two substeps and 4 barriers: +2.7 % on the step,
+            // profiles/r03_gemm_variants_ab.txt)
+            constexpr int NPH = 4;
 #pragma unroll
             for (int ph = 0; ph < NPH; ++ph) {
                 // ---------------- L segment ----------------
-                typename Frag<T>::type fa[SUB][TM], fb[SUB][2];
+                typename Frag<T>::type fa[TM], fb[2];
+                const int coff = ((ph * 2 + half) ^ rsw) << 4;
 #pragma unroll
-                for (int u = 0; u < SUB; ++u) {
-                    const int coff = (((ph * SUB + u) * 2 + half) ^ rsw) << 4;
+                for (int i = 0; i < TM; ++i) fa[i] = *(const typename Frag<T>::type*)(sA + offA + i * 32 * 128 + coff);
 #pragma unroll
-                    for (int i = 0; i < TM; ++i) fa[u][i] = *(const typename Frag<T>::type*)(sA + offA + i * 32 * 128 + coff);
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) fb[u][j] = *(const typename Frag<T>::type*)(sB + offB + j * 32 * 128 + coff);
-                }
+                for (int j = 0; j < 2; ++j) fb[j] = *(const typename Frag<T>::type*)(sB + offB + j * 32 * 128 + coff);
                 // the next K-tile(s) are requested at least one full segment pair before they are waited for
                 if constexpr (A3) {
                     if (ph == 0 && fetchB) dmaB(ib ^ 1, stepB);
-                    if (ph == (NPH == 4 ? 1 : 0) && fetchA) dmaA(slotA, stepA);
+                    if (ph == 1 && fetchA) dmaA(slotA, stepA);
                 } else {
                     if (ph == 0 && fetchA) dmaA(slotA, stepA);
-                    if (ph == (NPH == 4 ? 1 : 0) && fetchB) dmaB(ib ^ 1, stepB);
+                    if (ph == 1 && fetchB) dmaB(ib ^ 1, stepB);
                 }
                 // last K-tile of the item: request the first auxiliary rows of its epilogue now, AFTER this tile's LDS-DMA:
                 // they land under the remaining MFMAs
@@ -1362,20 +1260,12 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const pa_gemm_args
 #pragma unroll
                     for (int i = 0; i < TM; ++i)
 #pragma unroll
-                        for (int j = 0; j < 2; ++j) mma32_first<T>(acc[i][j], TR ? fb[0][j] : fa[0][i], TR ? fa[0][i] : fb[0][j]);
-#pragma unroll
-                    for (int u = 1; u < SUB; ++u)
-#pragma unroll
-                        for (int i = 0; i < TM; ++i)
-#pragma unroll
-                            for (int j = 0; j < 2; ++j) mma32<T>(acc[i][j], TR ? fb[u][j] : fa[u][i], TR ? fa[u][i] : fb[u][j]);
+                        for (int j = 0; j < 2; ++j) mma32_first<T>(acc[i][j], TR ? fb[j] : fa[i], TR ? fa[i] : fb[j]);
                 } else {
 #pragma unroll
-                    for (int u = 0; u < SUB; ++u)
+                    for (int i = 0; i < TM; ++i)
 #pragma unroll
-                        for (int i = 0; i < TM; ++i)
-#pragma unroll
-                            for (int j = 0; j < 2; ++j) mma32<T>(acc[i][j], TR ? fb[u][j] : fa[u][i], TR ? fa[u][i] : fb[u][j]);
+                        for (int j = 0; j < 2; ++j) mma32<T>(acc[i][j], TR ? fb[j] : fa[i], TR ? fa[i] : fb[j]);
                 }
                 __builtin_amdgcn_s_setprio(0);
                 if (ph == NPH - 1 && wr == 0) wait_tile();
@@ -1469,7 +1359,7 @@ static int launch_gemm_stagger(const pa_gemm_args& a, hipStream_t st) {
     // the LDS-free epilogue (transposed accumulators) wherever it applies: bf16 operands, a fused epilogue, row-major
     // pre-activation, no column sums asked of the DGELU epilogue (they are lane-local only in the v2 orientation)
     // (the 256-row RESID tile keeps v2: 128 accumulators + 32 residual registers in flight spill in the v3 form)
-    if constexpr (!TR && !BLK && PA_EPILOGUE_V2 && sizeof(T) == 2 && EPI != PA_EPI_PARTIAL && !(EPI == PA_EPI_RESID && TM == 4)) {
+    if constexpr (!TR && !BLK && sizeof(T) == 2 && EPI != PA_EPI_PARTIAL && !(EPI == PA_EPI_RESID && TM == 4)) {
         if ((epilogue_v3_enabled() || (a.reserved & PA_GEMM_EPILOGUE_V3)) && !(EPI == PA_EPI_DGELU && a.colsum_out) &&
             !(EPI == PA_EPI_RESID && a.row_mod > 0))
             return launch_gemm_stagger<T, EPI, TM, A3, false, true>(a, st);
@@ -1488,7 +1378,7 @@ static int launch_gemm_stagger(const pa_gemm_args& a, hipStream_t st) {
     const bool big = (int64_t)a.M * a.ldolp * 2 >= lim || (int64_t)a.M * a.ldolp2 * 2 >= lim || (int64_t)a.M * a.ldaux * 2 >= lim ||
                      (int64_t)a.M * a.ldr * 4 >= lim || (int64_t)a.M * a.ldo32 * 4 >= lim;
     if (ksteps < 1 || (int64_t)(splits - 1) * per >= ksteps ||
-        (PA_EPILOGUE_V2 && sizeof(T) == 2 && EPI != PA_EPI_PARTIAL && (big || (EPI == PA_EPI_RESID && a.row_mod > 0))))
+        (sizeof(T) == 2 && EPI != PA_EPI_PARTIAL && (big || (EPI == PA_EPI_RESID && a.row_mod > 0))))
         return BLK ? PA_EUNSUPPORTED : launch_gemm_v<T, EPI, 2, 2, 2, 2>(a, st);     // (the generic kernel has no blocked form)
     if constexpr (A3) {      // two K-tiles of lead need two K-tiles in every item; the short item table bounds the rounds
         if (ksteps - (splits - 1) * per < 2 || per < 2 || cdiv(total, 256) > G::MAX_ROUNDS) return launch_gemm_stagger<T, EPI, TM, false, BLK, TR>(a, st);
@@ -1781,25 +1671,16 @@ __device__ __forceinline__ bf16x8 tn2_frag(const char* tile, int ms, int cbase, 
 // are activations that come from HBM in the training step, and one stage of lead (~1.4 us) is less than a loaded HBM
 // round trip (the same effect cost the K = 2304 / 3072 NT GEMMs 15 %: profiles/r02_instep_vs_isolated.json).
 static constexpr int TN_ROWS = PA_TN_STEP_ROWS;          // tokens per stage (host code sizes the K slices in these units)
-#ifndef PA_TN_FRAG_PIPE
-// Three schedules of the same work were measured in the step, same box, same call (profiles/r02_tn_loop_variants.json):
-//   0: role split, fragment reads in the L segment                                   355.9 us per block launch, 763 k cycles
-//   1: role split, fragment reads issued inside the previous M segment               360.9 us, 771 k
-//   2: lockstep, software pipelined, counted lgkmcnt waits, 2 barriers per stage     368.0 us, 801 k   (all at 2.03 GHz)
-// although the probe timeline (tools/probe_tn.py) shows variant 0 spending as long in L as in M.  What fills L is apparently not the
-// twelve LDS reads (~300 cycles of loaded latency, hidden in 1 and 2) but the ISSUE of the LDS-DMA pieces (100-185 cycles
-// each inside a busy phase, MI355X_MICROARCH.md; two per wave and phase): the role split keeps it out of the instruction
-// stream of the wave that is issuing MFMAs, a lockstep loop puts it back in.
-#define PA_TN_FRAG_PIPE 0
-#endif
-#ifndef PA_TN_LOCKSTEP_OFFSET
-#define PA_TN_LOCKSTEP_OFFSET 0   // variant 2 only: s_sleep units (64 cycles) group 1 waits after every stage barrier (A/B:
-                                  // 0 / 2 / 4 -> 359.8 / 371.6 / 376.6 us against 353.2 for the role split, run r10)
-#endif
-#ifndef PA_TN_STAGES
-#define PA_TN_STAGES 3         // (A/B: -DPA_TN_STEP_ROWS=64 -DPA_TN_STAGES=2 is the r01 pipeline)
-#endif
-static constexpr int TN_STAGES = PA_TN_STAGES;
+// Three schedules of the K loop were measured in the step, same box, same call (profiles/r02_tn_loop_variants.json):
+//   role split, fragment reads in the L segment (this one)                          355.9 us per block launch, 763 k cycles
+//   role split, fragment reads issued inside the previous M segment                 360.9 us, 771 k
+//   lockstep, software pipelined, counted lgkmcnt waits, 2 barriers per stage       368.0 us, 801 k   (all at 2.03 GHz)
+// although the probe timeline (tools/probe_tn.py) shows the first spending as long in L as in M.  What fills L is apparently not
+// the twelve LDS reads (~300 cycles of loaded latency, hidden in the other two) but the ISSUE of the LDS-DMA pieces (100-185
+// cycles each inside a busy phase, MI355X_MICROARCH.md; two per wave and phase): the role split keeps it out of the instruction
+// stream of the wave that is issuing MFMAs, a lockstep loop puts it back in.  (Holding the two waves of a SIMD half a phase
+// apart in the lockstep loop with a sleep after every stage barrier made it slower still: 359.8 -> 371.6 / 376.6 us.)
+static constexpr int TN_STAGES = 3;
 static constexpr int TN_OP_BYTES = TN_ROWS * 512, TN_STAGE_BYTES = 2 * TN_OP_BYTES;     // 24 KiB per operand, 48 KiB per stage
 static constexpr int TN_LDS = TN_STAGES * TN_STAGE_BYTES;                               // 144 KiB
 static_assert(TN_ROWS % 16 == 0 && TN_ROWS * 512 % (8 * 1024) == 0, "whole 16-token phases, whole 1 KiB pieces per wave");
@@ -1849,16 +1730,18 @@ __device__ __forceinline__ void gemm_tn_stagger_range(const pa_gemm_args& a, con
         const char* sb = base + (int64_t)step * MROWS * ld * 2;              // uniform
         const int valid = Mtok - (st_begin + step) * MROWS;                  // token rows that exist in this stage
         if (valid >= MROWS) {
+            // (one arm per operand, the same instruction in both: the per-operand cache-policy trial ended at the default for both,
+            // profiles/r06_cache_policy.txt.  Merging the arms moves instructions in the compiled loop: a change of its own.)
             if (opB) {         // (a constant at both call sites: folded after inlining)
 #pragma unroll
                 for (int i = 0; i < PER; ++i)
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sb + voff[i]),
-                                                     (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, PA_AUX_DMA_TN_B);
+                                                     (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
             } else {
 #pragma unroll
                 for (int i = 0; i < PER; ++i)
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sb + voff[i]),
-                                                     (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, PA_AUX_DMA_TN_A);
+                                                     (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
             }
         } else {   // last stage of the last split: rows past the end re-read the last token (zeroed by zero_tail)
 #pragma unroll
@@ -1905,14 +1788,12 @@ __device__ __forceinline__ void gemm_tn_stagger_range(const pa_gemm_args& a, con
     for (int e = 0; e < 8; ++e) ones[e] = (bf16)1.0f;
 
     if (nsteps > 0) { dmaA(0, 0); dmaB(0, 0); }
-    if (TN_STAGES > 2 && nsteps > 1) { dmaA(1, 1); dmaB(1, 1); }
+    if (nsteps > 1) { dmaA(1, 1); dmaB(1, 1); }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (nsteps > 0) zero_tail(0, 0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-#if PA_TN_FRAG_PIPE != 2
     if (wr == 1) __builtin_amdgcn_s_barrier();             // group 1 runs one barrier behind
-#endif
 
     // per-lane fragment addresses inside a stage (see tn2_frag: the +4-row partner is +2048 bytes, a 16-token
     // phase +8192, and the swizzle term only depends on the lane)
@@ -1943,194 +1824,17 @@ __device__ __forceinline__ void gemm_tn_stagger_range(const pa_gemm_args& a, con
         return f;
     };
 
-#if PA_TN_FRAG_PIPE == 2
-    // Software-pipelined lockstep loop (r02).  The probe timeline of the role-split loop (tools/probe_tn.py) showed the L
-    // segment as long as the M segment: a loaded ds_read_b64_tr_b16 takes ~300 cycles to return and L ended with a wait for
-    // all twelve, so every barrier interval carried that latency; issuing the reads inside the previous M segment only
-    // moved the wait.  Here all eight waves run the same schedule:
-    //   * the fragments of phase p+1 are requested inside phase p, each one right after the last MFMA that reads its old
-    //     value has been issued (operands are read at issue, LDS data returns >= 64 cycles later): no second register set;
-    //   * MFMAs go column-major -- (0,0) (1,0) (2,0) (3,0) | fb0' | (0,1) fa0' (1,1) fa1' (2,1) fa2' (3,1) fa3' fb1' -- and
-    //     every MFMA waits only for ITS operands with a counted s_waitcnt lgkmcnt (LDS returns in issue order; the twelve
-    //     reads outstanding at a phase start are fb0 fa0 fa1 fa2 fa3 fb1): lgkmcnt(8) (6) (4) (2) | (2);
-    //   * no barrier per phase: B1 at the end of the second-to-last phase publishes stage t+1 (every wave waited for its
-    //     own DMA pieces first) because the last phase requests fragments of stage t+1; B2 at the end of the stage: every
-    //     wave has consumed all its reads of stage t's slot, so the DMA of stage t+3, requested in phases 0 / 1 of stage
-    //     t+1, may overwrite it.
-    // Two barriers per stage instead of six, no LDS drain anywhere, the two waves of a SIMD share the matrix pipe freely.
-    static_assert(TN_STAGES == 3, "two stages of DMA lead");
-    constexpr int LEAD = TN_STAGES - 1;
-    int slot = 0;
-    bf16x8 fa[TM], fb[2];
-    auto wait_lgkm = [](auto nc) { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(decltype(nc)::value) : "memory"); };
-    fb[0] = join(lds_tr16_asm<0>(offB[0]), lds_tr16_asm<2048>(offB[0]));
-#pragma unroll
-    for (int i = 0; i < TM; ++i) fa[i] = join(lds_tr16_asm<0>(offA[i]), lds_tr16_asm<2048>(offA[i]));
-    fb[1] = join(lds_tr16_asm<0>(offB[1]), lds_tr16_asm<2048>(offB[1]));
-    for (int t = 0; t < nsteps; ++t) {
-        const uint32_t sb = slot * STAGE_BYTES;
-        const bool more = t + 1 < nsteps, more2 = t + LEAD < nsteps;
-        const int slot1 = slot == TN_STAGES - 1 ? 0 : slot + 1;
-        const int slot2 = slot1 == TN_STAGES - 1 ? 0 : slot1 + 1;
-        auto wait_stage = [&]() {      // stage t+1 landed; the 2*PER pieces of stage t+2 (younger) may stay in flight
-            if (more2) wait_vmcnt<2 * PER>(); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (more) zero_tail(slot1, t + 1);
-        };
-        auto phase = [&](auto phc) {
-            constexpr int ph = decltype(phc)::value;
-            constexpr int NOFF = ph == NPH - 1 ? 0 : (ph + 1) * 8192;       // next phase: same stage, or phase 0 of stage t+1
-            const uint32_t nsb = ph == NPH - 1 ? (uint32_t)slot1 * STAGE_BYTES : sb;
-            if (more2) {
-                if (ph == 0) dmaA(slot2, t + LEAD);
-                if (ph == 1) dmaB(slot2, t + LEAD);
-            }
-            bf16x8 fcs = ones;       // CSUM items (1 in 12): own fragment of dY row-block wc, and a full LDS drain (simple)
-            if (CSUM) {
-                fcs = join(lds_tr16_asm<ph * 8192>(offCS + sb), lds_tr16_asm<ph * 8192 + 2048>(offCS + sb));
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            auto msteps = [&](auto firstc) {
-                constexpr bool FIRST = decltype(firstc)::value;
-                auto mm = [&](int i, int j) {
-                    if constexpr (FIRST) mma32_first<bf16>(acc[i][j], fa[i], fb[j]); else mma32<bf16>(acc[i][j], fa[i], fb[j]);
-                };
-                wait_lgkm(std::integral_constant<int, 8>{}); __builtin_amdgcn_sched_barrier(0);
-                mm(0, 0); __builtin_amdgcn_sched_barrier(0);
-                wait_lgkm(std::integral_constant<int, 6>{}); __builtin_amdgcn_sched_barrier(0);
-                mm(1, 0); __builtin_amdgcn_sched_barrier(0);
-                wait_lgkm(std::integral_constant<int, 4>{}); __builtin_amdgcn_sched_barrier(0);
-                mm(2, 0); __builtin_amdgcn_sched_barrier(0);
-                wait_lgkm(std::integral_constant<int, 2>{}); __builtin_amdgcn_sched_barrier(0);
-                mm(3, 0); __builtin_amdgcn_sched_barrier(0);
-                fb[0] = join(lds_tr16_asm<NOFF>(offB[0] + nsb), lds_tr16_asm<NOFF + 2048>(offB[0] + nsb));
-                wait_lgkm(std::integral_constant<int, 2>{}); __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    mm(i, 1); __builtin_amdgcn_sched_barrier(0);
-                    fa[i] = join(lds_tr16_asm<NOFF>(offA[i] + nsb), lds_tr16_asm<NOFF + 2048>(offA[i] + nsb));
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                fb[1] = join(lds_tr16_asm<NOFF>(offB[1] + nsb), lds_tr16_asm<NOFF + 2048>(offB[1] + nsb));
-            };
-            if (ph == 0 && t == 0) msteps(std::true_type{}); else msteps(std::false_type{});
-            if (CSUM) asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(accb) : "v"(fcs), "v"(ones));
-            if (ph == NPH - 2) {           // B1: publish stage t+1 before anyone requests its fragments
-                wait_stage();
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-            }
-            if (ph == NPH - 1) {           // B2: every wave is through with its reads of stage t's slot
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-#if PA_TN_LOCKSTEP_OFFSET
-                if (wr == 1) __builtin_amdgcn_s_sleep(PA_TN_LOCKSTEP_OFFSET);     // A/B: keep the two waves of a SIMD half a phase apart
-#endif
-            }
-            PA_PROBE_STAMP_TN(t >= 4 && t < 12, ((t - 4) * NPH + ph) * 4 + 3);
-        };
-        phase(std::integral_constant<int, 0>{});
-        phase(std::integral_constant<int, 1>{});
-        phase(std::integral_constant<int, 2>{});
-        if constexpr (NPH == 4) phase(std::integral_constant<int, 3>{});
-        static_assert(NPH == 3 || NPH == 4, "three or four 16-token phases per stage");
-        slot = slot1;
-    }
-#elif PA_TN_FRAG_PIPE == 1
-    // Fragment pipeline (r02): the 12 transpose reads of a phase are issued INSIDE the previous M segment, each fragment
-    // right after the last MFMA that reads its old value has been issued (operands are read at issue; the LDS data
-    // returns >= 64 cycles later), so they cost no registers and the L segment shrinks to DMA requests + the wait.
-    // ds_read_b64_tr_b16 only reaches its rate with several waves issuing (MI355X_MICROARCH.md, LDS): with the reads in
-    // the L segment only one wave per SIMD was issuing them and L (~12 reads) was longer than M (8 MFMAs).
-    // Consequence: the last phase of a stage reads the NEXT stage, so that stage is waited for / published one barrier
-    // earlier than before (group 0: in its last L segment; group 1, one barrier behind: after its second-to-last M).
-    static_assert(TN_STAGES == 3, "the fragment pipeline assumes two stages of lead");
-    constexpr int LEAD = TN_STAGES - 1;
-    int slot = 0;
-    bf16x8 fa[TM], fb[2];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) fa[i] = join(lds_tr16_asm<0>(offA[i]), lds_tr16_asm<2048>(offA[i]));
-#pragma unroll
-    for (int j = 0; j < 2; ++j) fb[j] = join(lds_tr16_asm<0>(offB[j]), lds_tr16_asm<2048>(offB[j]));
-    for (int t = 0; t < nsteps; ++t) {
-        const uint32_t sb = slot * STAGE_BYTES;
-        const bool more = t + 1 < nsteps, more2 = t + LEAD < nsteps;
-        const int slot1 = slot == TN_STAGES - 1 ? 0 : slot + 1;
-        const int slot2 = slot1 == TN_STAGES - 1 ? 0 : slot1 + 1;
-        // stage t+1 (requested during stage t-1) must have landed; the 2*PER pieces of stage t+2, the youngest in this
-        // wave's queue, may stay in flight (vmcnt retires in issue order)
-        auto wait_stage = [&]() {
-            if (more2) wait_vmcnt<2 * PER>(); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (more) zero_tail(slot1, t + 1);
-        };
-        auto phase = [&](auto phc) {
-            constexpr int ph = decltype(phc)::value;
-            constexpr int NOFF = ph == NPH - 1 ? 0 : (ph + 1) * 8192;       // next phase: same stage, or phase 0 of stage t+1
-            const uint32_t nsb = ph == NPH - 1 ? (uint32_t)slot1 * STAGE_BYTES : sb;
-            // ---------------- L segment: DMA requests, (CSUM: own fragment), wait for the fragments ----------------
-            bf16x8 fcs = ones;       // CSUM: this wave's own copy of dY row-block wc (fa[wc] would be a run-time register index)
-            if (CSUM) fcs = join(lds_tr16_asm<ph * 8192>(offCS + sb), lds_tr16_asm<ph * 8192 + 2048>(offCS + sb));
-            if (more2) {
-                if (ph == 0) dmaA(slot2, t + LEAD);
-                if (ph == 1) dmaB(slot2, t + LEAD);
-            }
-            if (ph == NPH - 1 && wr == 0) wait_stage();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            PA_PROBE_STAMP_TN(t >= 4 && t < 12, ((t - 4) * NPH + ph) * 4 + 0);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            PA_PROBE_STAMP_TN(t >= 4 && t < 12, ((t - 4) * NPH + ph) * 4 + 1);
-            // ---------------- M segment: MFMAs, each fragment reloaded as soon as it is free ----------------
-            __builtin_amdgcn_s_setprio(1);
-            auto msteps = [&](auto firstc) {
-                constexpr bool FIRST = decltype(firstc)::value;
-                auto mm = [&](int i, int j) {
-                    if constexpr (FIRST) mma32_first<bf16>(acc[i][j], fa[i], fb[j]); else mma32<bf16>(acc[i][j], fa[i], fb[j]);
-                };
-#pragma unroll
-                for (int i = 0; i < TM - 1; ++i) {
-                    mm(i, 0);
-                    mm(i, 1);
-                    __builtin_amdgcn_sched_barrier(0);
-                    fa[i] = join(lds_tr16_asm<NOFF>(offA[i] + nsb), lds_tr16_asm<NOFF + 2048>(offA[i] + nsb));
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                mm(TM - 1, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                fb[0] = join(lds_tr16_asm<NOFF>(offB[0] + nsb), lds_tr16_asm<NOFF + 2048>(offB[0] + nsb));
-                __builtin_amdgcn_sched_barrier(0);
-                mm(TM - 1, 1);
-                __builtin_amdgcn_sched_barrier(0);
-                fa[TM - 1] = join(lds_tr16_asm<NOFF>(offA[TM - 1] + nsb), lds_tr16_asm<NOFF + 2048>(offA[TM - 1] + nsb));
-                fb[1] = join(lds_tr16_asm<NOFF>(offB[1] + nsb), lds_tr16_asm<NOFF + 2048>(offB[1] + nsb));
-            };
-            if (ph == 0 && t == 0) msteps(std::true_type{}); else msteps(std::false_type{});
-            if (CSUM) asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(accb) : "v"(fcs), "v"(ones));
-            __builtin_amdgcn_s_setprio(0);
-            if (ph == NPH - 2 && wr == 1) wait_stage();
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            PA_PROBE_STAMP_TN(t >= 4 && t < 12, ((t - 4) * NPH + ph) * 4 + 3);
-        };
-        phase(std::integral_constant<int, 0>{});
-        phase(std::integral_constant<int, 1>{});
-        phase(std::integral_constant<int, 2>{});
-        if constexpr (NPH == 4) phase(std::integral_constant<int, 3>{});
-        static_assert(NPH == 3 || NPH == 4, "three or four 16-token phases per stage");
-        slot = slot1;
-    }
-#else
-    constexpr int LEAD = TN_STAGES - 1; // stages of lead of the requests (2; 1 in the two-stage A/B build)
+    constexpr int LEAD = TN_STAGES - 1; // stages of lead of the requests
     int slot = 0;                       // ring slot of stage t;  stage t+LEAD goes into the slot stage t-1 just left
     for (int t = 0; t < nsteps; ++t) {
         const uint32_t sb = slot * STAGE_BYTES;
         const bool more = t + 1 < nsteps, more2 = t + LEAD < nsteps;
         const int slot1 = slot == TN_STAGES - 1 ? 0 : slot + 1;
-        const int slot2 = LEAD == 1 ? slot1 : (slot1 == TN_STAGES - 1 ? 0 : slot1 + 1);
+        const int slot2 = slot1 == TN_STAGES - 1 ? 0 : slot1 + 1;
         // end of the stage: stage t+1 (requested during stage t-1) must have landed; the 2*PER pieces of stage t+2, the
         // youngest in this wave's queue, may stay in flight (vmcnt retires in issue order)
         auto wait_stage = [&]() {
-            if (LEAD > 1 && more2) wait_vmcnt<2 * PER>(); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (more2) wait_vmcnt<2 * PER>(); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (more) zero_tail(slot1, t + 1);
         };
         auto phase = [&](auto phc) {
@@ -2191,10 +1895,7 @@ __device__ __forceinline__ void gemm_tn_stagger_range(const pa_gemm_args& a, con
         static_assert(NPH == 3 || NPH == 4, "three or four 16-token phases per stage");
         slot = slot1;
     }
-#endif
-#if PA_TN_FRAG_PIPE != 2
     if (wr == 0) __builtin_amdgcn_s_barrier();
-#endif
 #ifdef PA_PROBE
     __syncthreads();
     if (g_probe_buf && blockIdx.x < 8)
@@ -2831,11 +2532,8 @@ __global__ __launch_bounds__(256) void reduce_partials_batched_kernel(const Redu
     for (int64_t i = t0; i < n4; i += stride) {
         f32x4 s = d.accumulate ? ((const f32x4*)d.out)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
         for (int z = 0; z < d.splits; ++z) {
-#if PA_NT_LD_SLAB
-            s += __builtin_nontemporal_load((const f32x4*)(d.partial + (int64_t)z * n + i * 4));
-#else
-            s += *(const f32x4*)(d.partial + (int64_t)z * n + i * 4);
-#endif
+            if constexpr (CP_NT_SLAB_LOADS) s += __builtin_nontemporal_load((const f32x4*)(d.partial + (int64_t)z * n + i * 4));
+            else s += *(const f32x4*)(d.partial + (int64_t)z * n + i * 4);
         }
         ((f32x4*)d.out)[i] = s;
     }

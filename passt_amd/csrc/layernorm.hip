@@ -12,49 +12,24 @@ namespace pa {
 static constexpr int LN_MAXV = 8;       // float4 per lane -> D <= 2048 (kernels are instantiated for 1,2,3,4,8)
 static constexpr int LN_BWD_BLOCKS = 1024;
 
-// Cache policy (A/B build knobs, round 6 sweep profiles/r06_cache_policy.txt): PA_LN_NT_LD = the row operands that are read for
-// the last time here (x in the forward; dy, x, dres in the backward) as non-temporal loads, PA_LN_NT_ST bit 0 = the f32 outputs
-// (dx), bit 1 = the low-precision outputs (y, dx_lp: the next GEMM's A operand) as non-temporal stores
-#ifndef PA_LN_NT_LD
-#define PA_LN_NT_LD 0
-#endif
-#ifndef PA_LN_NT_ST
-#define PA_LN_NT_ST 0
-#endif
+// Default cache policy on every access (round 6 sweep, profiles/r06_cache_policy.txt): non-temporal loads of the row operands read
+// for the last time here (x in the forward; dy, x, dres in the backward) and non-temporal stores of dx are +- 0 on the step; with
+// the low-precision outputs (y, dx_lp: the next GEMM's A operand) non-temporal too, fc1 + GELU goes back from 157 to 167 us.
 __device__ __forceinline__ float4 ldrow4(const float* p) {
-#if PA_LN_NT_LD
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const f4 v = __builtin_nontemporal_load((const f4*)p);
-    return make_float4(v[0], v[1], v[2], v[3]);
-#else
     return *(const float4*)p;
-#endif
 }
 template <typename T> __device__ __forceinline__ void store4(T* p, const float4& v);
 template <> __device__ __forceinline__ void store4<float>(float* p, const float4& v) {
-#if PA_LN_NT_ST & 2
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, (f4*)p);
-#else
     *(float4*)p = v;
-#endif
 }
 template <> __device__ __forceinline__ void store4<bf16>(bf16* p, const float4& v) {
     bf16x4 o; o[0] = (bf16)v.x; o[1] = (bf16)v.y; o[2] = (bf16)v.z; o[3] = (bf16)v.w;
-#if PA_LN_NT_ST & 2
-    __builtin_nontemporal_store(o, (bf16x4*)p);
-#else
     *(bf16x4*)p = o;
-#endif
 }
 template <typename T> __device__ __forceinline__ float4 load4(const T* p);
 template <> __device__ __forceinline__ float4 load4<float>(const float* p) { return ldrow4(p); }
 template <> __device__ __forceinline__ float4 load4<bf16>(const bf16* p) {
-#if PA_LN_NT_LD
-    const bf16x4 v = __builtin_nontemporal_load((const bf16x4*)p);
-#else
     const bf16x4 v = *(const bf16x4*)p;
-#endif
     return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
 }
 
@@ -158,12 +133,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
                     o.x += dr.x; o.y += dr.y; o.z += dr.z; o.w += dr.w;
                 }
                 {
-#if PA_LN_NT_ST & 1
-                    typedef float f4 __attribute__((ext_vector_type(4)));
-                    __builtin_nontemporal_store(f4{o.x, o.y, o.z, o.w}, (f4*)(dx + base + 4 * c));
-#else
                     *(float4*)(dx + base + 4 * c) = o;
-#endif
                 }
                 if (dx_lp) store4<T>(dx_lp + base + 4 * c, o);
                 ac[i].x += o.x; ac[i].y += o.y; ac[i].z += o.z; ac[i].w += o.w;

@@ -39,23 +39,15 @@ namespace pa {
 
 static constexpr int NFFT = 1024;
 static constexpr int NC = 512;            // complex points
-#ifndef PA_MEL_FRAMES
-#define PA_MEL_FRAMES 16
-#endif
-static constexpr int FR_DEFAULT = PA_MEL_FRAMES;  // frames per workgroup (template parameter FR_PER_WG of the kernel)
+static constexpr int FR_DEFAULT = 16;     // frames per workgroup (template parameter FR_PER_WG of the kernel)
+static constexpr int FR_PERSIST = 8;      // frames per tile of the persistent form (two per wave; 32-byte output rows; 49 KiB: three workgroups per CU)
 static constexpr int MEL_WAVES = 4;
-#ifndef PA_MEL_ABL
-#define PA_MEL_ABL 0
-#endif
-#ifndef PA_MEL_LEAN_PERSIST
-#define PA_MEL_LEAN_PERSIST 8             // the persistent form carries the tile bookkeeping too: every untangle twiddle from one copy (no scratch:
-#endif                                    // a scratch reload in the frame loop would wait for the span DMA in flight -- vmcnt retires in order)
-#ifndef PA_MEL_PERSIST_FRAMES
-#define PA_MEL_PERSIST_FRAMES 8           // frames per tile of the persistent form (two per wave; 32-byte output rows; 49 KiB: three workgroups per CU)
-#endif
-#ifndef PA_MEL_LEAN
-#define PA_MEL_LEAN 3                     // how many of the untangle twiddles use the one-copy product (register budget: 168)
-#endif
+// how many of the eight untangle twiddles use the one-copy product: 3 (register budget: 168); the persistent form carries the
+// tile bookkeeping too and takes every one from one copy (no scratch: a scratch reload in the frame loop would wait for the
+// span DMA in flight -- vmcnt retires in order)
+static constexpr int LEAN = 3, LEAN_PERSIST = 8;
+// (What a frame's stages cost -- builds without the band stage, without the untangle, without the span requests or the output
+// stores: profiles/r05_mel_probe.txt, profiles/r06_mel_persistent.txt.)
 static constexpr int XROW1 = 68;          // exchange-1 row stride (complex) : conflict-free reads
 static constexpr int XROW2 = 72;          // exchange-2 row stride (complex)
 static constexpr int WAVE_SCRATCH = 8 * XROW2 * 8;   // 4608 bytes
@@ -324,10 +316,8 @@ __global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
         const int nt_ = tile + (int)gridDim.x;
         if (nt_ < n_tiles) {
             const int nb = nt_ / tiles_per_clip, nf0 = (nt_ - nb * tiles_per_clip) * FR_PER_WG;
-#ifndef PA_MEL_NODMA         // timing ablation: the next tile's span is not requested (stale samples)
             if (interior(nf0)) stage_dma((it + 1) & 1, nb, nf0);
             else stage_slow((float*)(smem + ((it + 1) & 1) * span_bytes), nb, nf0);
-#endif
         }
     }
     for (int fi = 0; fi < FR_PER_WG / MEL_WAVES; ++fi) {
@@ -376,15 +366,6 @@ __global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
             for (int c = 0; c < 8; ++c) v[c] = scr[r * XROW2 + c * 8 + pp];
         }
         dft8(v);                              // over c -> s ; lane' holds Z[lane' + 64 s]
-#if PA_MEL_ABL >= 2      // ablation builds (probe only): 2 = no untangle, no band stage; 1 = no band stage
-        {
-            cf a = v[0];
-#pragma unroll
-            for (int s = 1; s < 8; ++s) a += v[s];
-            sOut[lane * (FR_PER_WG + 1) + fl] = a.x;
-            sOut[(lane + 64) * (FR_PER_WG + 1) + fl] = a.y;
-        }
-#else
         // untangle the packed real FFT: needs Z[k] and Z[512-k]
 #pragma unroll
         for (int s = 0; s < 8; ++s) scr[lane + 64 * s] = v[s];
@@ -398,19 +379,10 @@ __global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
             // and that factor lives in the band weights (un = u / 4: exact)
             const cf e2 = addcj(zk, zc);                       // 2 e
             const cf o2 = cmul_negi(subcj(zk, zc));            // 2 o = (Z[k] - conj Z[N-k]) / i
-            const cf X2 = e2 + (s < (PERSIST ? PA_MEL_LEAN_PERSIST : PA_MEL_LEAN) ? cmul_lean(o2, tw3[s]) : cmul(o2, tw3[s]));               // 2 X
+            const cf X2 = e2 + (s < (PERSIST ? LEAN_PERSIST : LEAN) ? cmul_lean(o2, tw3[s]) : cmul(o2, tw3[s]));               // 2 X
             const cf sq = X2 * X2;
             pk[s] = sq.x + sq.y;                               // 4 |X|^2
         }
-#if PA_MEL_ABL == 1
-        {
-            float a = pk[0];
-#pragma unroll
-            for (int s = 1; s < 8; ++s) a += pk[s];
-            sOut[lane * (FR_PER_WG + 1) + fl] = a;
-            sOut[(lane + 64) * (FR_PER_WG + 1) + fl] = a * un[0] * keep[0].x * (float)sa[0];
-        }
-#else
         // ---- sparse mel bands.  Every bin feeds at most two triangles: P u to triangle j_k, P (1 - u) to triangle j_k - 1.
         // The power spectrum changes owner (lane + 64 s -> 8 consecutive bins per lane), every lane runs the segment
         // recurrence acc = (keep ? acc : 0) + {P u, P - P u} over its bins -- once from zero (its open tail), then, after ONE
@@ -453,8 +425,6 @@ __global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
             const int band = lane + 64 * h;
             if (band < p.n_mels) sOut[band * (FR_PER_WG + 1) + fl] = slot[band].x + slot[band + 1].y;
         }
-#endif
-#endif
 #ifdef PA_MEL_PROBE
         if (fi == 3) MEL_STAMP(3);
 #endif
@@ -470,9 +440,6 @@ __global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
         float v = __logf(sOut[mel * (FR_PER_WG + 1) + fl] + p.log_eps);
         const bool masked = (mel >= p.fmask_start && mel < p.fmask_end) || (t >= p.tmask_start && t < p.tmask_end);
         if (masked) v = 0.f;
-#ifdef PA_MEL_NOSTORE        // timing ablation (A/B builds only): no output stores
-        if (v != 12345.678f) continue;
-#endif
         out[((int64_t)b * p.n_mels + mel) * T + t] = (v + p.out_add) * p.out_scale;
     }
 #ifdef PA_MEL_PROBE
@@ -518,7 +485,7 @@ extern "C" int pa_mel_frontend_fwd(const float* wave, int B, int L, const float*
     // selects it (A/B, parity-tested).
     static const int persist_env = [] { const char* e = getenv("PA_MEL_PERSIST"); return e ? atoi(e) : 0; }();
     if (persist_env && p->hop % 2 == 0) {
-        constexpr int FRP = PA_MEL_PERSIST_FRAMES;
+        constexpr int FRP = FR_PERSIST;
         const int spanp = (FRP - 1) * p->hop + NFFT;
         const size_t span_bytes = ((size_t)(spanp + 4) * 4 + 1023) & ~(size_t)1023;
         const size_t ldsp = 2 * span_bytes + MEL_WAVES * WAVE_SCRATCH + std::max<size_t>((size_t)p->n_mels * (FRP + 1) * 4, 2 * NC * 4);

@@ -92,35 +92,18 @@ __global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, c
 // transposed cast), everything else in runs of 4096 elements.  Same adamw_one() as adamw_kernel: parameters, moments and both
 // copies are bit-identical to adamw_kernel + stage_weights_kernel (tests/test_gpu_model.py).
 struct AdamwHyper { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; };
-// Cache policy of the matrix path (A/B build knob, round 6 sweep profiles/r06_cache_policy.txt): bit 0 = parameters, moments and
-// gradients (each touched once per step) as non-temporal loads / stores, bit 1 = the GEMM-ready copies as non-temporal stores
-#ifndef PA_OPT_NT
-#ifdef PA_NO_CACHE_POLICY
-#define PA_OPT_NT 0
-#else
-#define PA_OPT_NT 1        // (with the slab loads of the finishing reduction: -0.2 % of the step; the copies: +- 0)
-#endif
-#endif
+// Parameters, moments and gradients of the matrix path are touched once per step: non-temporal (CP_NT_ADAMW, pa_common.h).  The
+// GEMM-ready copies leave as plain stores (non-temporal: +- 0, profiles/r06_cache_policy.txt).
 template <typename V> __device__ __forceinline__ V opt_ld(const V* p) {
-#if PA_OPT_NT & 1
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
+    if constexpr (CP_NT_ADAMW) return __builtin_nontemporal_load(p);
+    else return *p;
 }
 template <typename V> __device__ __forceinline__ void opt_st(V* p, const V& v) {
-#if PA_OPT_NT & 1
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
+    if constexpr (CP_NT_ADAMW) __builtin_nontemporal_store(v, p);
+    else *p = v;
 }
-template <typename V> __device__ __forceinline__ void opt_st_copy(V* p, const V& v) {
-#if PA_OPT_NT & 2
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
+template <typename TO> __device__ __forceinline__ void st_bf16x4(TO* p, const f32x4& w) {
+    *(bf16x4*)p = bf16x4{(bf16)w[0], (bf16)w[1], (bf16)w[2], (bf16)w[3]};
 }
 
 template <typename TO>
@@ -203,7 +186,7 @@ __global__ __launch_bounds__(256) void adamw_stage_kernel(float* __restrict__ p,
                 }
                 opt_st((f32x4*)(pp + at), pv[i]); opt_st((f32x4*)(mp + at), mv[i]); opt_st((f32x4*)(vp + at), vv[i]);
                 if (dst) {
-                    if constexpr (sizeof(TO) == 2) opt_st_copy((bf16x4*)(dst + at), bf16x4{(bf16)pv[i][0], (bf16)pv[i][1], (bf16)pv[i][2], (bf16)pv[i][3]});
+                    if constexpr (sizeof(TO) == 2) st_bf16x4(dst + at, pv[i]);
                     else *(f32x4*)(dst + at) = pv[i];
                 }
             } else {
@@ -219,7 +202,7 @@ __global__ __launch_bounds__(256) void adamw_stage_kernel(float* __restrict__ p,
             const int c = c0 + lr + 16 * i, r = r0 + l4;
             if (c < d.cols && r < d.rows) {
                 const f32x4 w = {tile[l4][lr + 16 * i], tile[l4 + 1][lr + 16 * i], tile[l4 + 2][lr + 16 * i], tile[l4 + 3][lr + 16 * i]};
-                if constexpr (sizeof(TO) == 2) opt_st_copy((bf16x4*)(dst_t + (int64_t)c * d.rows + r), bf16x4{(bf16)w[0], (bf16)w[1], (bf16)w[2], (bf16)w[3]});
+                if constexpr (sizeof(TO) == 2) st_bf16x4(dst_t + (int64_t)c * d.rows + r, w);
                 else *(f32x4*)(dst_t + (int64_t)c * d.rows + r) = w;
             }
         }

@@ -17,6 +17,38 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 namespace pa {
 
+// ---- Cache policy of the step's memory instructions, per role (round 6, profiles/r06_cache_policy.txt) --------------------
+// The `aux` immediate of the buffer / LDS-DMA instructions: 1 = sc0, 2 = nt (non-temporal), 16 = sc1.  Every output line and
+// every epilogue operand row of a GEMM is touched exactly once by that GEMM; weights are re-read by every row band, activation
+// tiles by N / 256 column tiles, and the NEXT kernel wants this kernel's outputs.  With the default policy the single-use
+// lines compete for the caches with the re-used ones; marked non-temporal they do not: 1.5 - 2.4 % of the whole training step
+// (config #2, same box, ABBA: 22.39 -> 21.98, 21.78 -> 21.46, 21.98 -> 21.48 ms; ESC-50 - 2.9 %, config #4 - 1.6 %), e.g.
+// fc2 / proj + residual 104.5 -> 95.0 us, fc1 + GELU 170 -> 157 us.  The bytes crossing the L2's fabric side do NOT change
+// (FETCH_SIZE / WRITE_SIZE: 439 against 440 MB per launch): the effect is behind them, in the 256 MiB Infinity Cache / HBM.
+// What the sweep settled, role by role:
+//   nt  fc1's blocked pre-activation (written in the forward, next read in the backward)
+//   nt  the bf16 outputs of the STORE / GELU / GELU' epilogues (full 128-byte lines per 8 lanes)
+//   nt  the epilogue operand rows read once (residual rows, pre-activation blocks)
+//   nt  the A operand of the residual GEMMs (N = D: a tile is read by D / 256 column tiles only)
+//   nt  the split-K slabs when the finishing reduction reads them (each once)
+//   nt  AdamW's parameters, moments and gradients, each touched once per step (with the slab loads: -0.2 % of the step)
+//   default: the f32 residual-stream output (nt: the LayerNorm behind it slows down, +0.5 %), the A operand of every other GEMM
+//       (nt: fc1 + GELU 170 -> 188 us), the weights (nt: +4 % on the step), the weight-gradient operands and slab stores
+//       (+- 0), sc1 instead of nt on the outputs (half the gain), nt on the A operand of plain-store GEMMs with N = D (+0.5 %),
+//       AdamW's GEMM-ready copies (+- 0), every access of the attention and LayerNorm kernels (attention.hip, layernorm.hip).
+// -DPA_NO_CACHE_POLICY builds the library with the default policy everywhere (the one A/B worth repeating on a new ROCm).
+#ifdef PA_NO_CACHE_POLICY
+#define PA_CP(x) 0
+#else
+#define PA_CP(x) x
+#endif
+static constexpr int CP_ST_PRE = PA_CP(2);          // `aux` of the blocked pre-activation stores
+static constexpr int CP_ST_OUT = PA_CP(2);          // `aux` of the bf16 epilogue output stores
+static constexpr int CP_LD_EPI = PA_CP(2);          // `aux` of the epilogue operand loads
+static constexpr int CP_DMA_A_RESID = PA_CP(2);     // `aux` of the A operand's LDS-DMA in the residual GEMMs
+static constexpr bool CP_NT_SLAB_LOADS = PA_CP(1);  // the finishing reduction reads the slabs with non-temporal loads
+static constexpr bool CP_NT_ADAMW = PA_CP(1);       // AdamW reads and writes parameters, moments and gradients non-temporally
+
 int set_hip_error(hipError_t e);  // records the error text for pa_last_hip_error(); returns PA_ELAUNCH
 
 inline int check_launch() {
@@ -87,25 +119,17 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
     return fmaf(x * 0.39894228040143267794f, ex, cdf);
 }
 
-// ---- GELU for the bf16 epilogues: odd minimax polynomials on the clamped argument, two elements per
-// v_pk_fma_f32 and no transcendental (quarter-rate) instruction.  The fc1 / dgrad-fc2 GEMM epilogues are VALU
+// ---- GELU for the bf16 epilogues: odd minimax polynomials on the clamped argument, no transcendental (quarter-rate)
+// instruction.  The fc1 / dgrad-fc2 GEMM epilogues are VALU
 // bound (65536 outputs per CU per tile), so this is ~2.7x cheaper than the erf form above.  Coefficients and
 // error bounds from tools/gelu_fit.py: |Phi err| <= 1.3e-5, |gelu' err| <= 1.5e-4 in f32 evaluation -- 1/30 and
 // 1/10 of a bf16 half-ulp of the stored results.  The f32 parity path keeps gelu_erf / gelu_erf_grad.
 //   Phi(x)   = 1/2 + xc P(xc^2),   gelu'(x) = 1/2 + xc Q(xc^2),   xc = clamp(x, -4.25, 4.25)
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f32x2 pk_splat(float v) { return f32x2{v, v}; }
-__device__ __forceinline__ f32x2 gelu_clamp2(f32x2 x) {
-    return f32x2{__builtin_amdgcn_fmed3f(x[0], -4.25f, 4.25f), __builtin_amdgcn_fmed3f(x[1], -4.25f, 4.25f)};
-}
-// r02: evaluated with SCALAR f32 FMAs (PA_GELU_PACKED = 0).  On gfx950 a wave64 v_fma_f32 issues in 2 cycles (SIMD-32), so
+// r02: evaluated with SCALAR f32 FMAs, not two elements per v_pk_fma_f32.  On gfx950 a wave64 v_fma_f32 issues in 2 cycles (SIMD-32), so
 // packed f32 math has no throughput advantage per element, and v_pk_fma_f32 measured slower than two v_fma_f32 (the GELU
 // epilogue ran ~13.5k cycles per 256x256 tile against a ~6.6k VALU floor; MI355X_MICROARCH.md prices 1 v_pk_fma_f32 at
 // +22 cycles over 2 v_fma_f32 next to MFMAs).  gemm.hip is compiled with -fno-slp-vectorize so that the compiler does
 // not re-pack the scalar chains.
-#ifndef PA_GELU_PACKED
-#define PA_GELU_PACKED 0
-#endif
 __device__ __forceinline__ float gelu_phi_fast1(float x) {       // Phi(x)
     const float xc = __builtin_amdgcn_fmed3f(x, -4.25f, 4.25f), t = xc * xc;
     float p = fmaf(5.564853169e-11f, t, -5.327756179e-09f);
@@ -132,37 +156,10 @@ __device__ __forceinline__ float gelu_grad_fast1(float x) {
     return fmaf(xc, q, 0.5f);
 }
 __device__ __forceinline__ f32x2 gelu_fast2(f32x2 x) {
-#if PA_GELU_PACKED
-    const f32x2 xc = gelu_clamp2(x), t = xc * xc;
-    f32x2 p = pk_fma(pk_splat(5.564853169e-11f), t, pk_splat(-5.327756179e-09f));
-    p = pk_fma(p, t, pk_splat(2.255428225e-07f));
-    p = pk_fma(p, t, pk_splat(-5.626429780e-06f));
-    p = pk_fma(p, t, pk_splat(9.341873147e-05f));
-    p = pk_fma(p, t, pk_splat(-1.108561126e-03f));
-    p = pk_fma(p, t, pk_splat(9.815971666e-03f));
-    p = pk_fma(p, t, pk_splat(-6.634449192e-02f));
-    p = pk_fma(p, t, pk_splat(3.989023391e-01f));
-    return x * pk_fma(xc, p, pk_splat(0.5f));
-#else
     return f32x2{x[0] * gelu_phi_fast1(x[0]), x[1] * gelu_phi_fast1(x[1])};
-#endif
 }
 __device__ __forceinline__ f32x2 gelu_grad_fast2(f32x2 x) {
-#if PA_GELU_PACKED
-    const f32x2 xc = gelu_clamp2(x), t = xc * xc;
-    f32x2 q = pk_fma(pk_splat(-3.426787246e-11f), t, pk_splat(3.552477616e-09f));
-    q = pk_fma(q, t, pk_splat(-1.634916764e-07f));
-    q = pk_fma(q, t, pk_splat(4.432675237e-06f));
-    q = pk_fma(q, t, pk_splat(-7.936289004e-05f));
-    q = pk_fma(q, t, pk_splat(9.965486026e-04f));
-    q = pk_fma(q, t, pk_splat(-9.040460278e-03f));
-    q = pk_fma(q, t, pk_splat(5.909254817e-02f));
-    q = pk_fma(q, t, pk_splat(-2.653926090e-01f));
-    q = pk_fma(q, t, pk_splat(7.977564352e-01f));
-    return pk_fma(xc, q, pk_splat(0.5f));
-#else
     return f32x2{gelu_grad_fast1(x[0]), gelu_grad_fast1(x[1])};
-#endif
 }
 // 8-element forms used by the epilogues: T selects the exact (f32 parity) or the fast (bf16) evaluation
 template <typename T> __device__ __forceinline__ void gelu8(const float (&x)[8], float (&g)[8]) {

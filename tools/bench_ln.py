@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """LayerNorm forward / backward alone at the training shapes (HIP events), for A/B builds of layernorm.hip:
-    PASST_AMD_LIB=passt_amd/libpasst_amd_ln_<name>.so PA_LN_BWD_BLOCKS=768 python tools/bench_ln.py"""
+    PASST_AMD_LIB=<other .so> PA_LN_BWD_BLOCKS=768 python tools/bench_ln.py"""
 import json
 import os
 import sys

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Where a front-end workgroup spends its life: the probe build of mel.hip (make mel_variant NAME=probe MEL_DEFS=-DPA_MEL_PROBE)
+"""Where a front-end workgroup spends its life: the probe build of mel.hip (make -C passt_amd/csrc mel_probe)
 leaves s_memrealtime stamps (100 MHz) of every wave's phases in the output tile.
     PASST_AMD_LIB=passt_amd/libpasst_amd_mel_probe.so python tools/probe_mel.py"""
 import json
