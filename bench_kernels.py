@@ -107,6 +107,15 @@ def main():
     o, lse = ops.attention_fwd(qkv, B, H, N, 0.125, flags=ops.ATTN_Q_PRESCALED)
     sec = timeit(lambda: ops.attention_fwd(qkv, B, H, N, 0.125, flags=ops.ATTN_Q_PRESCALED), args.iters)
     add(f"attention fwd B{B} H{H} N{N}", sec, flops=4.0 * N * N * 64 * B * H)
+    # packed sequences of different lengths (eval on ragged batches): the token counts of clips of 998 / 437 / 1203 / 16 / 251 / 640 /
+    # 998 / 33 frames (stride 10, patch 16, 99 time positions), TF/s on the executed FLOPs sum_b 4 N_b^2 64 H
+    vl = [2 + 12 * t for t in (99, 43, 99, 1, 24, 63, 99, 2)]
+    cu = torch.tensor([0] + list(torch.tensor(vl).cumsum(0)), dtype=torch.int32, device=DEV)
+    qkv_vl = rnd(sum(vl), 3 * D)
+    sec = timeit(lambda: ops.attention_fwd_varlen(qkv_vl, cu, len(vl), H, max(vl), 0.125, flags=ops.ATTN_Q_PRESCALED), args.iters)
+    add(f"varlen_attention fwd B{len(vl)} H{H} N{min(vl)}..{max(vl)} ({sum(vl)} tokens)", sec, flops=sum(4.0 * n * n * 64 * H for n in vl))
+    sec = timeit(lambda: ops.attention_fwd(qkv, 8, H, N, 0.125, flags=ops.ATTN_Q_PRESCALED), args.iters)
+    add(f"attention fwd B8 H{H} N{N} (fixed length, for comparison)", sec, flops=4.0 * N * N * 64 * 8 * H)
     do = rnd(M, D)
     sec = timeit(lambda: ops.attention_bwd(qkv, o, do, lse, B, H, N, 0.125, flags=ops.ATTN_Q_PRESCALED), args.iters)
     add(f"attention bwd (library's choice: single pass for B*H >= 512, N <= 512) B{B} H{H} N{N}", sec, flops=10.0 * N * N * 64 * B * H)

@@ -78,6 +78,16 @@ int pa_mel_num_frames(int L, int hop);
  * twiddle[n_fft/2][2]: (cos, -sin)(2 pi k / n_fft), k = 0..n_fft/2-1 */
 int pa_mel_frontend_fwd(const float* wave, int B, int L, const float* window, const float* bin_mel,
                         const float* twiddle, float* out, const pa_mel_params* p, void* stream);
+/* The same for a batch of clips of different lengths (inference on ragged input; the reference runs such clips one at a time,
+ * ex_fsd50k.py:53-56).  wave[B][ldw] f32, clips left-aligned; lens[B] int32 IN DEVICE MEMORY: valid samples of every row
+ * (lens[b] <= ldw, lens[b] - 1 > n_fft/2; the caller checks both, the library cannot read them).  Row b of out[B][n_mels][T_max]
+ * holds, in its first pa_mel_num_frames(lens[b], hop) columns, exactly what pa_mel_frontend_fwd returns for that clip alone
+ * (pre-emphasis and the centred reflect padding end at the clip's own last sample; samples at or behind lens[b] are never read),
+ * and `fill` in every column behind them.  p->n_frames must equal T_max = pa_mel_num_frames(max lens, hop) <= pa_mel_num_frames(ldw,
+ * hop); the time mask of p applies to every row alike.  A row with lens[b] - 1 <= n_fft/2 is written as `fill` throughout.  One-tile
+ * kernel form only (PA_MEL_PERSIST is ignored).  wave, lens, the three tables and out are device memory. */
+int pa_mel_frontend_fwd_varlen(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
+                               const float* twiddle, float* out, int T_max, float fill, const pa_mel_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Parameter staging (no reference counterpart: AMP autocast casts weights per op)
@@ -320,6 +330,20 @@ int pa_colsum_f32(const float* in, int R, int C, int ld, float* out, int accumul
 #define PA_ATTN_BWD_SINGLE_PASS_W16 8
 int pa_attention_fwd(const void* qkv, int ldqkv, void* o, int ldo, float* lse, int B, int H, int N, int nq,
                      float scale, int dtype, int flags, void* stream);
+/* Forward over PACKED sequences of different lengths (eval on ragged batches; no backward exists).  The B sequences lie back to back
+ * in qkv: sequence b owns token rows cu_tok[b] .. cu_tok[b+1] - 1, N_b = cu_tok[b+1] - cu_tok[b] >= 1; cu_tok is B + 1 int32 IN
+ * DEVICE MEMORY with cu_tok[0] = 0, non-decreasing, and max_N >= every N_b (it only sizes the launch: cdiv(max_N, 128) query blocks
+ * per (sequence, head), the ones a short sequence does not have return at once).  Every sequence gets bit for bit what
+ * pa_attention_fwd(B = 1, N = N_b) computes for it alone: same tile loop, same tail instances; the K / V rows staged for a
+ * sequence's last tile are clamped to ITS last row, so no row of a neighbour and no row at or behind cu_tok[B] is ever read (qkv
+ * needs no slack after its last row).
+ *   nq >= max_N: every query.  o is packed like qkv's rows, o[cu_tok[b] + q][H*64]; lse is head-major over the packed rows,
+ *                lse[h * cu_tok[B] + cu_tok[b] + q]  (H * cu_tok[B] floats).
+ *   nq <  max_N: the first min(nq, N_b) queries of every sequence, COMPACT as in pa_attention_fwd: o[(b*nq + q)][H*64],
+ *                lse[(b*H + h)*nq + q]  (nq = 2: the last block's prefix rows); rows q >= N_b are not written.
+ * flags as pa_attention_fwd.  qkv, o, lse, cu_tok are device memory. */
+int pa_attention_fwd_varlen(const void* qkv, int ldqkv, void* o, int ldo, float* lse, const int32_t* cu_tok, int B, int H,
+                            int max_N, int nq, float scale, int dtype, int flags, void* stream);
 /* number of floats of pa_attention_bwd's `delta` workspace */
 int64_t pa_attention_bwd_ws_floats(int B, int H, int nq);
 /* dqkv[B*N][3*H*64] from d_o[B*nq][H*64]; lse from the forward; delta: f32 workspace of pa_attention_bwd_ws_floats()
@@ -354,6 +378,20 @@ int pa_patch_bwd(const float* dtok, int B, int Ntok, int D, const int32_t* patch
                  const int32_t* patch_t, int Np, int toff, int Tpe, int Fpe, float* gsum,
                  float* d_cls, float* d_dist, float* d_npe, float* d_bias, float* d_time_pos,
                  float* d_freq_pos, int accumulate, void* dpatch, int dtype, void* stream);
+/* Packed batch of clips of different lengths (eval forward of PaSST.forward(x, lengths), models/passt.py:513-526 per clip).  The token
+ * matrix has M = sum_b (2 + Np_b) rows, clip after clip, each clip's cls and dist rows first.  Per token row r three int32 arrays
+ * IN DEVICE MEMORY: row_clip[r] (row of x), row_f[r] / row_t[r] = grid coordinates of the patch, or row_f[r] = -1 for a prefix row with
+ * row_t[r] = 0 (cls) / 1 (dist).
+ * pa_patch_gather_varlen: x[B][1][F][T_max] f32 (clips left-aligned, anything behind a clip's own frames is never addressed by its
+ *   rows) -> cols[M][P*P] (dtype), im2col of the row's patch; a prefix row is all zeros.  Coordinates outside x read as 0.
+ * pa_patch_pos_table_varlen: table[M][D] f32 = bias + time_pos[:, row_t] + freq_pos[:, row_f] (time offset 0: eval, :519-521), and
+ *   on a prefix row cls + npe[0] / dist + npe[1] -- the rows cu_tok[b] + {0, 1} of the packed matrix.
+ * One pa_gemm_nt(cols, W, PA_EPI_RESID, resid = table, row_mod = 0) then writes all M token rows (a prefix row is 0 * W + table). */
+int pa_patch_gather_varlen(const float* x, int B, int F, int T_max, const int32_t* row_clip, const int32_t* row_f,
+                           const int32_t* row_t, int M, int P, int fstride, int tstride, void* cols, int dtype, void* stream);
+int pa_patch_pos_table_varlen(const float* bias, const float* time_pos, int Tpe, const float* freq_pos, int Fpe,
+                              const int32_t* row_f, const int32_t* row_t, int M, int D, float* table, const float* cls,
+                              const float* dist, const float* npe, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Head: final norm on the two prefix tokens, their mean, head LayerNorm + Linear

@@ -54,6 +54,7 @@ SIGNATURES = {
     "pa_last_hip_error": (C.c_char_p, []),
     "pa_mel_num_frames": (i32, [i32, i32]),
     "pa_mel_frontend_fwd": (i32, [vp, i32, i32, vp, vp, vp, vp, C.POINTER(MelParams), vp]),
+    "pa_mel_frontend_fwd_varlen": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i32, f32, C.POINTER(MelParams), vp]),
     "pa_convert_f32": (i32, [vp, vp, i64, i32, vp]),
     "pa_convert_to_f32": (i32, [vp, i32, vp, i64, vp]),
     "pa_transpose": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp]),
@@ -81,6 +82,7 @@ SIGNATURES = {
     "pa_rowsum": (i32, [vp, i32, i32, i32, i32, vp, i32, vp]),
     "pa_colsum_f32": (i32, [vp, i32, i32, i32, vp, i32, vp]),
     "pa_attention_fwd": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, f32, i32, i32, vp]),
+    "pa_attention_fwd_varlen": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp]),
     "pa_attention_bwd_ws_floats": (i64, [i32, i32, i32]),
     "pa_attention_bwd": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp]),
     "pa_gather_rows": (i32, [vp, vp, i32, i64, vp, vp]),
@@ -88,6 +90,8 @@ SIGNATURES = {
     "pa_zero2d": (i32, [vp, i64, i64, i64, vp]),
     "pa_patch_gather": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, i32, vp]),
     "pa_patch_pos_table": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "pa_patch_gather_varlen": (i32, [vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp]),
+    "pa_patch_pos_table_varlen": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "pa_patch_bwd": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp]),
     "pa_head_pre_fwd": (i32, [vp, i32, i32, i32, vp, vp, f32, vp, vp, f32, vp, vp, vp, vp]),
     "pa_linear_f32_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),

@@ -320,9 +320,20 @@ static inline unsigned attn_grid(int nblk, int BH) { return (unsigned)(nblk * 8 
 // (C operand), lazy reference moves, row sums as plain adds (a fifth product against ones costs 4 MFMAs = 76 ns per tile,
 // 32 adds cost 32), tail masks only in the tail instance, addresses precomputed per lane (LaneOff), rows stored straight
 // from the registers, and waves without a query row skip the arithmetic.
-template <typename T, bool PRE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? FWD_WAVES : 2))) void attn_fwd_kernel(const T* __restrict__ qkv, int ldqkv, T* __restrict__ o,
-                                                       int ldo, float* __restrict__ lse, int H, int N, int nq, float scale, int nblk, int BH) {
+//
+// attn_fwd_body is the kernel; attn_fwd_kernel (fixed length) and attn_fwd_varlen_kernel are its two entry points.
+// VL (pa_attention_fwd_varlen): the sequences are packed back to back and differ in length.  Sequence b owns token rows
+// cu_tok[b] .. cu_tok[b + 1] of qkv; its first row and its N come from two scalar loads, and everything behind them -- the tile
+// loop, the tail instances, the clamps -- is the code of the fixed-length kernel, run per sequence.  The launch carries
+// cdiv(max N, 128) query blocks per (sequence, head) through the SAME item map (a head's blocks stay on one XCD); the blocks a
+// short sequence does not have return before their first memory access.  The kernel arguments N / nq hold max N and the
+// caller's nq there: nq == max N means "every query" (o and lse packed like qkv's rows, lse[h][total tokens]), otherwise o and
+// lse are compact as in the fixed-length form.  K / V rows staged for the tail tile are clamped to the sequence's own last row
+// (stage_last), so no row of a neighbour -- nor one behind the end of qkv -- is ever read.
+template <typename T, bool PRE, bool VL>
+__device__ __forceinline__ void attn_fwd_body(const T* __restrict__ qkv, int ldqkv, T* __restrict__ o,
+                                              int ldo, float* __restrict__ lse, int H, int N, int nq, float scale, int nblk, int BH,
+                                              const int32_t* __restrict__ cu_tok) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using F = typename Frag<T>::type;
     constexpr int NF = Tile<T>::NFRAG, NSB = AccSteps<T>::N, TB = Tile<T>::BYTES;
@@ -332,7 +343,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
     if (!attn_block(nblk, BH, blk, bh)) return;
     const int b = bh / H, h = bh % H;
     const int D = H * HD;
-    const T* base = qkv + (int64_t)b * N * ldqkv + h * HD;      // q of token 0 of this (b,h)
+    int64_t tok0 = (int64_t)b * N;                              // first token row of this sequence in qkv
+    int64_t orow0 = (int64_t)b * nq;                            // first row of this sequence in o
+    float* lse_row = lse + (int64_t)bh * nq;
+    if constexpr (VL) {
+        const int t0 = cu_tok[b], t1 = cu_tok[b + 1];           // wave-uniform: scalar loads
+        const bool all_queries = nq == N;                       // N is max N here
+        N = t1 - t0;
+        tok0 = t0;
+        nq = min(nq, N);
+        if (all_queries) {
+            orow0 = t0;
+            lse_row = lse + (int64_t)h * cu_tok[BH / H] + t0;
+        }
+        if (blk * 128 >= nq) return;                            // (also N <= 0) a block this sequence does not have: whole workgroup
+    }
+    const T* base = qkv + tok0 * ldqkv + h * HD;                // q of token 0 of this (b,h)
     const int q0 = blk * 128 + wave * 32;
     const int qrow = min(q0 + (lane & 31), N - 1);
     const bool active = q0 < nq;                                // wave-uniform: this wave owns at least one stored query
@@ -475,9 +501,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
         else tile(std::true_type{}, std::false_type{}, ntiles - 1);
         // only the first nq queries of every sequence are produced; o / lse are compact (nq rows per sequence)
         l_run += other_half(l_run);
-        if (lane < 32 && q0 + lane < nq) lse[(int64_t)bh * nq + q0 + lane] = (m_run + __builtin_amdgcn_logf(l_run)) * LN2;   // natural log units
-        store_rows_direct<T>(oacc, __builtin_amdgcn_rcpf(l_run), o + (int64_t)b * nq * ldo + h * HD, ldo, q0, min(32, nq - q0), lane);
+        if (lane < 32 && q0 + lane < nq) lse_row[q0 + lane] = (m_run + __builtin_amdgcn_logf(l_run)) * LN2;   // natural log units
+        store_rows_direct<T>(oacc, __builtin_amdgcn_rcpf(l_run), o + orow0 * ldo + h * HD, ldo, q0, min(32, nq - q0), lane);
     }
+}
+
+template <typename T, bool PRE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? FWD_WAVES : 2))) void attn_fwd_kernel(const T* __restrict__ qkv, int ldqkv, T* __restrict__ o,
+                                                       int ldo, float* __restrict__ lse, int H, int N, int nq, float scale, int nblk, int BH) {
+    attn_fwd_body<T, PRE, false>(qkv, ldqkv, o, ldo, lse, H, N, nq, scale, nblk, BH, nullptr);
+}
+// the packed form (see the note in front of attn_fwd_body): N = max N, nq == N: every query
+template <typename T, bool PRE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? FWD_WAVES : 2))) void attn_fwd_varlen_kernel(const T* __restrict__ qkv, int ldqkv,
+                                                       T* __restrict__ o, int ldo, float* __restrict__ lse, int H, int N, int nq, float scale,
+                                                       int nblk, int BH, const int32_t* __restrict__ cu_tok) {
+    attn_fwd_body<T, PRE, true>(qkv, ldqkv, o, ldo, lse, H, N, nq, scale, nblk, BH, cu_tok);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1222,6 +1261,26 @@ static int attention_fwd_t(const void* qkv, int ldqkv, void* o, int ldo, float* 
     return check_launch();
 }
 
+// Work-item map of the packed form: cdiv(min(nq, max_N), 128) query blocks for EVERY (sequence, head), dealt by attn_item as in the
+// fixed-length launch, the surplus blocks of short sequences returning at once (an empty workgroup costs about a microsecond of one
+// CU slot; the AudioSet / FSD50K mix launches 960 workgroups of which 552 do work).  Chosen over a host-built (sequence, block)
+// list because it needs no upload beyond cu_tok, does not depend on the order of the clips, and keeps the XCD placement of a
+// head's blocks by construction.
+template <typename T>
+static int attention_fwd_varlen_t(const void* qkv, int ldqkv, void* o, int ldo, float* lse, const int32_t* cu_tok, int B, int H, int max_N,
+                                  int nq, float scale, int flags, hipStream_t st) {
+    const int nqk = nq >= max_N ? max_N : nq;                   // == max_N: every query (the kernel's convention)
+    const int nblk = (int)cdiv(nqk, 128);
+    const dim3 grid(attn_grid(nblk, B * H)), block(256);
+    if (flags & PA_ATTN_Q_PRESCALED)
+        hipLaunchKernelGGL((attn_fwd_varlen_kernel<T, true>), grid, block, fwd_lds<T>(), st, (const T*)qkv, ldqkv, (T*)o, ldo, lse, H, max_N, nqk, scale, nblk,
+                           B * H, cu_tok);
+    else
+        hipLaunchKernelGGL((attn_fwd_varlen_kernel<T, false>), grid, block, fwd_lds<T>(), st, (const T*)qkv, ldqkv, (T*)o, ldo, lse, H, max_N, nqk, scale, nblk,
+                           B * H, cu_tok);
+    return check_launch();
+}
+
 template <typename T, bool PRE>
 static int attention_bwd_t(const void* qkv, int ldqkv, const void* o, const void* d_o, int ldo, const float* lse,
                            float* delta, void* dqkv, int lddqkv, int B, int H, int N, int nq, float scale, hipStream_t st) {
@@ -1270,6 +1329,15 @@ extern "C" int pa_attention_fwd(const void* qkv, int ldqkv, void* o, int ldo, fl
     if (!attn_args_ok(ldqkv, dtype) || !attn_args_ok(ldo, dtype)) return PA_EUNSUPPORTED;
     if (dtype == PA_BF16) return attention_fwd_t<bf16>(qkv, ldqkv, o, ldo, lse, B, H, N, nq, scale, flags, (hipStream_t)stream);
     if (dtype == PA_F32) return attention_fwd_t<float>(qkv, ldqkv, o, ldo, lse, B, H, N, nq, scale, flags, (hipStream_t)stream);
+    return PA_EINVAL;
+}
+
+extern "C" int pa_attention_fwd_varlen(const void* qkv, int ldqkv, void* o, int ldo, float* lse, const int32_t* cu_tok, int B, int H,
+                                       int max_N, int nq, float scale, int dtype, int flags, void* stream) {
+    if (!qkv || !o || !lse || !cu_tok || B <= 0 || H <= 0 || max_N <= 0 || nq <= 0 || (flags & ~PA_ATTN_Q_PRESCALED)) return PA_EINVAL;
+    if (!attn_args_ok(ldqkv, dtype) || !attn_args_ok(ldo, dtype)) return PA_EUNSUPPORTED;
+    if (dtype == PA_BF16) return attention_fwd_varlen_t<bf16>(qkv, ldqkv, o, ldo, lse, cu_tok, B, H, max_N, nq, scale, flags, (hipStream_t)stream);
+    if (dtype == PA_F32) return attention_fwd_varlen_t<float>(qkv, ldqkv, o, ldo, lse, cu_tok, B, H, max_N, nq, scale, flags, (hipStream_t)stream);
     return PA_EINVAL;
 }
 

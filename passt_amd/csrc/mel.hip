@@ -126,13 +126,22 @@ __device__ __forceinline__ cf tw1024(const float2* __restrict__ tw, int j) {
 // table loads per lane sit in front of every 16 frames any more (they were 4.2 us of a 14 us workgroup life, profiles/r05_mel_probe.txt).
 // The pre-emphasis then happens where stage 1 reads the samples (the DMA cannot apply it); tiles that touch the reflect padding at the
 // clip edges are staged by the lanes themselves, pre-emphasised, as before (`raw` tells stage 1 which form the buffer holds).
-template <int FR_PER_WG, bool PERSIST>
-__global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void mel_frontend_kernel(const float* __restrict__ wave, int L,
+//
+// VL (pa_mel_frontend_fwd_varlen, one-tile form only): the rows of `wave` are clips of different lengths, left-aligned with pitch
+// `Lp`.  Clip b has lens[b] valid samples and 1 + (lens[b] - 1) / hop frames; the pre-emphasis, the reflect padding and the choice
+// between the 16-byte staging of an interior tile and the sample-by-sample staging are taken from the clip's OWN length, so the
+// frames equal those of the clip transformed alone and nothing at or behind lens[b] is read.  The output keeps p.n_frames (the
+// longest clip's) columns per row; a workgroup whose frames all lie behind its clip's end writes `fill` and leaves, and the frames
+// behind the end inside the clip's last tile get `fill` from the epilogue.
+template <int FR_PER_WG, bool PERSIST, bool VL>
+__global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void mel_frontend_kernel(const float* __restrict__ wave, const int Lp,
                                                             const float* __restrict__ window,
                                                             const float* __restrict__ bin_mel,
                                                             const float2* __restrict__ twiddle,
                                                             float* __restrict__ out, const pa_mel_params p,
-                                                            const int tiles_per_clip, const int n_tiles) {
+                                                            const int tiles_per_clip, const int n_tiles,
+                                                            const int32_t* __restrict__ lens, const float fill) {
+    static_assert(!(VL && PERSIST), "the packed form is the one-tile kernel");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int span = (FR_PER_WG - 1) * p.hop + NFFT;
     // one span buffer holds span (+ 4: the sample behind the last one, for the pre-emphasis) floats, rounded up to whole 1 KiB DMA pieces
@@ -154,22 +163,33 @@ __global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
 #define MEL_STAMP(i) do {} while (0)
 #endif
     MEL_STAMP(0);
-    const int T = p.n_frames;
-    const int Ly = L - 1;
     constexpr int NT = MEL_WAVES * 64;
     static_assert(NC == 2 * NT, "two bins per thread");
     // tile -> (clip, first frame); non-persistent: the grid is (tiles per clip, clips)
     int tile = PERSIST ? (int)blockIdx.x : (int)(blockIdx.y * gridDim.x + blockIdx.x);
     int b = PERSIST ? tile / tiles_per_clip : (int)blockIdx.y;
     int f0 = (PERSIST ? tile - b * tiles_per_clip : (int)blockIdx.x) * FR_PER_WG;
+    const int Tp = p.n_frames;                               // columns of an output row
+    const int L = VL ? lens[b] : Lp;                         // VL: this clip's own length (wave-uniform: a scalar load)
+    const int T = VL ? min(Tp, 1 + (L - 1) / p.hop) : Tp;    // frames this clip has
+    const int Ly = L - 1;
+    if constexpr (VL) {
+        if (f0 >= T || Ly <= NFFT / 2) {                     // every frame of the tile lies behind the clip's end (or the clip is too short to reflect)
+            for (int idx = tid; idx < p.n_mels * FR_PER_WG; idx += NT) {
+                const int mel = idx / FR_PER_WG, t = f0 + idx % FR_PER_WG;
+                if (t < Tp) out[((int64_t)b * p.n_mels + mel) * Tp + t] = fill;
+            }
+            return;
+        }
+    }
     // a tile whose span needs no reflection and can move as 16-byte pieces (i0: sample index of sSig[0])
     auto interior = [&](int f0_) {
         const int i0 = f0_ * p.hop - NFFT / 2;
-        return i0 >= 0 && i0 + span + 4 <= Ly && ((i0 | L) & 3) == 0;
+        return i0 >= 0 && i0 + span + 4 <= Ly && ((i0 | Lp) & 3) == 0;
     };
     // PERSIST: request the raw span of tile (b_, f0_) into buffer `buf` by LDS-DMA: 1 KiB pieces dealt round-robin to the waves
     auto stage_dma = [&](int buf, int b_, int f0_) {
-        const float* xs = wave + (int64_t)b_ * L + (f0_ * p.hop - NFFT / 2);
+        const float* xs = wave + (int64_t)b_ * Lp + (f0_ * p.hop - NFFT / 2);
         const int nchunk = (span + 4) >> 2;                           // 16-byte chunks covering x[0 .. span] (x[span] feeds y[span - 1])
         // Issued by INLINE ASM, not by __builtin_amdgcn_global_load_lds: with the builtin the compiler, which cannot tell the DMA's LDS
         // destination from the other span buffer, puts s_waitcnt vmcnt(0) in front of the next LDS read -- the first sample read of
@@ -187,7 +207,7 @@ __global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
     };
     // the lanes stage the span themselves: y[i] = x[i+1] - preemph * x[i], reflect-padded by n_fft/2 (clip edges, odd geometries)
     auto stage_slow = [&](float* sSig, int b_, int f0_) {
-        const float* x = wave + (int64_t)b_ * L;
+        const float* x = wave + (int64_t)b_ * Lp;
         const int i0 = f0_ * p.hop - NFFT / 2;
         for (int j = tid; j < span; j += NT) {
             int i = i0 + j;
@@ -222,7 +242,7 @@ __global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
         if (interior(f0)) stage_dma(0, b, f0);
         else stage_slow(sSig0, b, f0);
     } else {
-        const float* x = wave + (int64_t)b * L;
+        const float* x = wave + (int64_t)b * Lp;
         const int i0 = f0 * p.hop - NFFT / 2;                    // sample index of sSig[0]
         if (interior(f0) && (span & 3) == 0 && span <= 12 * 4 * NT) {
             // interior tile (no reflection, 16-byte aligned): one 16-byte load + the next sample per 4 outputs, every
@@ -436,17 +456,18 @@ __global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
     for (int idx = tid; idx < p.n_mels * FR_PER_WG; idx += NT) {
         const int mel = idx / FR_PER_WG, fl = idx % FR_PER_WG;
         const int t = f0 + fl;
+        if (VL && t >= T && t < Tp) out[((int64_t)b * p.n_mels + mel) * Tp + t] = fill;
         if (t >= T) continue;
         float v = __logf(sOut[mel * (FR_PER_WG + 1) + fl] + p.log_eps);
         const bool masked = (mel >= p.fmask_start && mel < p.fmask_end) || (t >= p.tmask_start && t < p.tmask_end);
         if (masked) v = 0.f;
-        out[((int64_t)b * p.n_mels + mel) * T + t] = (v + p.out_add) * p.out_scale;
+        out[((int64_t)b * p.n_mels + mel) * Tp + t] = (v + p.out_add) * p.out_scale;
     }
 #ifdef PA_MEL_PROBE
     MEL_STAMP(5);
     __syncthreads();
     if (lane == 0) {
-        float* o = out + ((int64_t)b * p.n_mels + wv * 16) * T + f0;
+        float* o = out + ((int64_t)b * p.n_mels + wv * 16) * Tp + f0;
         o[0] = (float)(stamp[0] & 0xFFFFFFu);                 // absolute start, 10 ns units, 24 bits
         for (int i = 1; i < 6; ++i) o[(int64_t)i * T] = (float)(stamp[i] - stamp[0]);
     }
@@ -493,7 +514,7 @@ extern "C" int pa_mel_frontend_fwd(const float* wave, int B, int L, const float*
             static signed char lds_attr_p[64] = {0};
             static int cus[64] = {0};
             int dev = 0;
-            if (lds_attr_on_this_device((const void*)mel_frontend_kernel<FRP, true>, 160 * 1024, lds_attr_p) && hipGetDevice(&dev) == hipSuccess &&
+            if (lds_attr_on_this_device((const void*)mel_frontend_kernel<FRP, true, false>, 160 * 1024, lds_attr_p) && hipGetDevice(&dev) == hipSuccess &&
                 dev >= 0 && dev < 64) {
                 if (cus[dev] == 0) {
                     int n = 0;
@@ -504,8 +525,8 @@ extern "C" int pa_mel_frontend_fwd(const float* wave, int B, int L, const float*
                 const int per_cu = (int)std::max<size_t>(1, (160 * 1024) / ldsp);
                 if (n_tiles < ((int64_t)1 << 31)) {
                     const int grid = (int)std::min<int64_t>(n_tiles, (int64_t)cus[dev] * per_cu);
-                    hipLaunchKernelGGL((mel_frontend_kernel<FRP, true>), dim3((unsigned)grid), dim3(MEL_WAVES * 64), ldsp, st, wave, L, window, bin_mel,
-                                       (const float2*)twiddle, out, *p, tiles_per_clip, (int)n_tiles);
+                    hipLaunchKernelGGL((mel_frontend_kernel<FRP, true, false>), dim3((unsigned)grid), dim3(MEL_WAVES * 64), ldsp, st, wave, L, window, bin_mel,
+                                       (const float2*)twiddle, out, *p, tiles_per_clip, (int)n_tiles, (const int32_t*)nullptr, 0.f);
                     return check_launch();
                 }
             }
@@ -517,9 +538,27 @@ extern "C" int pa_mel_frontend_fwd(const float* wave, int B, int L, const float*
                        std::max<size_t>((size_t)p->n_mels * (fr + 1) * 4, 2 * NC * 4);
     if (lds > 160 * 1024) return PA_EUNSUPPORTED;
     static signed char lds_attr[64] = {0};
-    (void)lds_attr_on_this_device((const void*)mel_frontend_kernel<FR_DEFAULT, false>, 160 * 1024, lds_attr);
+    (void)lds_attr_on_this_device((const void*)mel_frontend_kernel<FR_DEFAULT, false, false>, 160 * 1024, lds_attr);
     dim3 grid((unsigned)cdiv(p->n_frames, fr), (unsigned)B);
-    hipLaunchKernelGGL((mel_frontend_kernel<FR_DEFAULT, false>), grid, dim3(MEL_WAVES * 64), lds, st, wave, L, window, bin_mel,
-                       (const float2*)twiddle, out, *p, (int)cdiv(p->n_frames, fr), (int)(cdiv(p->n_frames, fr) * B));
+    hipLaunchKernelGGL((mel_frontend_kernel<FR_DEFAULT, false, false>), grid, dim3(MEL_WAVES * 64), lds, st, wave, L, window, bin_mel,
+                       (const float2*)twiddle, out, *p, (int)cdiv(p->n_frames, fr), (int)(cdiv(p->n_frames, fr) * B), (const int32_t*)nullptr, 0.f);
+    return check_launch();
+}
+
+extern "C" int pa_mel_frontend_fwd_varlen(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
+                                          const float* twiddle, float* out, int T_max, float fill, const pa_mel_params* p, void* stream) {
+    if (!wave || !lens || !window || !bin_mel || !twiddle || !out || !p || B <= 0 || T_max <= 0) return PA_EINVAL;
+    if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
+    if (ldw - 1 <= NFFT / 2) return PA_EUNSUPPORTED;        // no row can hold a clip long enough for the reflect padding
+    if (p->n_frames != T_max || T_max > pa_mel_num_frames(ldw, p->hop)) return PA_EINVAL;
+    const int fr = FR_DEFAULT;
+    const int span = (fr - 1) * p->hop + NFFT;
+    const size_t lds = ((span * 4 + 15) & ~15) + MEL_WAVES * WAVE_SCRATCH + std::max<size_t>((size_t)p->n_mels * (fr + 1) * 4, 2 * NC * 4);
+    if (lds > 160 * 1024) return PA_EUNSUPPORTED;
+    static signed char lds_attr[64] = {0};
+    (void)lds_attr_on_this_device((const void*)mel_frontend_kernel<FR_DEFAULT, false, true>, 160 * 1024, lds_attr);
+    dim3 grid((unsigned)cdiv(T_max, fr), (unsigned)B);
+    hipLaunchKernelGGL((mel_frontend_kernel<FR_DEFAULT, false, true>), grid, dim3(MEL_WAVES * 64), lds, (hipStream_t)stream, wave, ldw, window, bin_mel,
+                       (const float2*)twiddle, out, *p, (int)cdiv(T_max, fr), (int)(cdiv(T_max, fr) * B), lens, fill);
     return check_launch();
 }

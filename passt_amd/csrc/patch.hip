@@ -37,6 +37,41 @@ __global__ void patch_pos_table_kernel(const float* __restrict__ bias, const flo
     }
 }
 
+// ---- packed batch of clips of different lengths (eval forward) --------------------------------------------------------------
+// Token row r of the packed [M][.] matrices belongs to clip row_clip[r]; row_f[r] >= 0: the patch at grid position (row_f, row_t) of
+// that clip; row_f[r] < 0: a prefix token (row_t = 0: cls, 1: dist).  cols gets a zero row under every prefix token, the table the
+// token itself, so ONE patch GEMM with the residual epilogue (rrow = orow = m) writes the whole token matrix: 0 * W + table.
+// one workgroup (P*P threads) per token row: cols[r][i*P+j] = x[clip][f*fs+i][t*ts+j]
+template <typename T>
+__global__ void patch_gather_varlen_kernel(const float* __restrict__ x, int B, int F, int Tt, const int32_t* __restrict__ row_clip,
+                                           const int32_t* __restrict__ row_f, const int32_t* __restrict__ row_t, int P, int fs, int ts,
+                                           T* __restrict__ cols) {
+    const int r = blockIdx.x;
+    const int i = threadIdx.x / P, j = threadIdx.x % P;
+    const int c = row_clip[r], pf = row_f[r];
+    float v = 0.f;
+    if (pf >= 0) {
+        const int f = pf * fs + i, t = row_t[r] * ts + j;
+        if ((unsigned)c < (unsigned)B && f < F && (unsigned)t < (unsigned)Tt) v = x[((int64_t)c * F + f) * Tt + t];
+    }
+    cols[(int64_t)r * (P * P) + threadIdx.x] = from_f32<T>(v);
+}
+
+// table[r][d] = bias[d] + tpos[d][row_t] + fpos[d][row_f] (the time embedding is read from offset 0: eval mode), or the prefix
+// token + its position row
+__global__ void patch_pos_table_varlen_kernel(const float* __restrict__ bias, const float* __restrict__ tpos, int Tpe,
+                                              const float* __restrict__ fpos, int Fpe, const int32_t* __restrict__ row_f,
+                                              const int32_t* __restrict__ row_t, int M, int D, float* __restrict__ table,
+                                              const float* __restrict__ cls, const float* __restrict__ dist,
+                                              const float* __restrict__ npe) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)M * D) return;
+    const int r = (int)(i / D), d = (int)(i % D);
+    const int pf = row_f[r], pt = row_t[r];
+    if (pf < 0) table[i] = (pt == 0 ? cls[d] : dist[d]) + npe[(pt == 0 ? 0 : 1) * D + d];
+    else table[i] = bias[d] + tpos[(int64_t)d * Tpe + min(pt, Tpe - 1)] + fpos[(int64_t)d * Fpe + min(pf, Fpe - 1)];
+}
+
 // gsum[n][d] = sum_b dtok[b][n][d]: 16 bytes per thread, four clips in flight (round 5: the scalar one-clip-at-a-time loop ran
 // at 2.9 TB/s)
 __global__ __launch_bounds__(256) void batch_sum_kernel(const float* __restrict__ dtok, int B, int64_t per, float* __restrict__ gsum) {
@@ -160,6 +195,33 @@ extern "C" int pa_patch_pos_table(const float* bias, const float* time_pos, int 
     const int64_t n = (int64_t)Np * D + (int64_t)B * 2 * D;
     hipLaunchKernelGGL(patch_pos_table_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, bias,
                        time_pos, Tpe, freq_pos, Fpe, patch_f, patch_t, Np, toff, D, table, cls, dist, npe, tok, B, Ntok);
+    return check_launch();
+}
+
+extern "C" int pa_patch_gather_varlen(const float* x, int B, int F, int T_max, const int32_t* row_clip, const int32_t* row_f,
+                                      const int32_t* row_t, int M, int P, int fstride, int tstride, void* cols, int dtype, void* stream) {
+    if (!x || !row_clip || !row_f || !row_t || !cols || B <= 0 || F <= 0 || T_max <= 0 || M <= 0 || P <= 0 || fstride <= 0 || tstride <= 0)
+        return PA_EINVAL;
+    if (P * P > 1024) return PA_EUNSUPPORTED;
+    const dim3 grid((unsigned)M), block((unsigned)(P * P));
+    if (dtype == PA_BF16)
+        hipLaunchKernelGGL(patch_gather_varlen_kernel<bf16>, grid, block, 0, (hipStream_t)stream, x, B, F, T_max, row_clip, row_f, row_t, P, fstride,
+                           tstride, (bf16*)cols);
+    else if (dtype == PA_F32)
+        hipLaunchKernelGGL(patch_gather_varlen_kernel<float>, grid, block, 0, (hipStream_t)stream, x, B, F, T_max, row_clip, row_f, row_t, P, fstride,
+                           tstride, (float*)cols);
+    else return PA_EINVAL;
+    return check_launch();
+}
+
+extern "C" int pa_patch_pos_table_varlen(const float* bias, const float* time_pos, int Tpe, const float* freq_pos, int Fpe,
+                                         const int32_t* row_f, const int32_t* row_t, int M, int D, float* table, const float* cls,
+                                         const float* dist, const float* npe, void* stream) {
+    if (!bias || !time_pos || !freq_pos || !row_f || !row_t || !table || !cls || !dist || !npe || M <= 0 || D <= 0 || Tpe <= 0 || Fpe <= 0)
+        return PA_EINVAL;
+    const int64_t n = (int64_t)M * D;
+    hipLaunchKernelGGL(patch_pos_table_varlen_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, bias, time_pos, Tpe,
+                       freq_pos, Fpe, row_f, row_t, M, D, table, cls, dist, npe);
     return check_launch();
 }
 

@@ -172,6 +172,22 @@ def mel_frontend(wave, window, bin_mel, twiddle, params: MelParams):
     return out
 
 
+def mel_frontend_varlen(wave, lens_dev, window, bin_mel, twiddle, params: MelParams, fill=0.0):
+    """Ragged batch: wave (B, L_max) f32 with clips left-aligned, lens_dev (B,) int32 on the device (valid samples per row; the
+    caller has checked 1 + n_fft/2 < len <= L_max on the host).  Returns (B, n_mels, params.n_frames); the frames behind a clip's
+    own end hold ``fill``."""
+    if wave.dim() != 2 or lens_dev.dim() != 1 or lens_dev.numel() != wave.shape[0]:
+        raise _lib.PasstAmdError(f"mel_frontend_varlen: wave {tuple(wave.shape)} needs one length per row, got {tuple(lens_dev.shape)}")
+    B, L = wave.shape
+    out = torch.empty((B, params.n_mels, params.n_frames), device=wave.device, dtype=torch.float32)
+    _timed("mel", 4.0 * (B * L + out.numel()),
+           lambda: check(_lib.load().pa_mel_frontend_fwd_varlen(_p(wave, torch.float32), B, wave.stride(0), _p(lens_dev, torch.int32),
+                                                                _p(window, torch.float32), _p(bin_mel, torch.float32), _p(twiddle, torch.float32),
+                                                                _p(out), params.n_frames, float(fill), C.byref(params), _stream()),
+                         "pa_mel_frontend_fwd_varlen"))
+    return out
+
+
 # ---- staging ---------------------------------------------------------------------------------
 def convert(x_f32, dtype):
     if dtype == PA_F32:
@@ -680,6 +696,35 @@ def attention_fwd(qkv, B, H, N, scale, nq=None, flags=0):
     return o, lse
 
 
+def attention_fwd_varlen(qkv, cu_tok, B, H, max_N, scale, nq=None, flags=0):
+    """Packed sequences: sequence b owns rows cu_tok[b] .. cu_tok[b+1] of qkv [total][3*H*64] (cu_tok: B + 1 int32 on the device,
+    cu_tok[B] == qkv.shape[0]; max_N >= the longest sequence).  nq=None: every query -> o [total][H*64] packed like qkv,
+    lse [H][total].  nq < max_N (the model's nq=2): compact o [(b*nq+q)][H*64], lse [(b*H+h)*nq+q]; rows of a sequence shorter
+    than nq stay zero."""
+    dtype = PA_DTYPE[qkv.dtype]
+    total, D = qkv.shape[0], H * 64
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * D or cu_tok.dim() != 1 or cu_tok.numel() != B + 1 or not 1 <= max_N <= total:
+        raise _lib.PasstAmdError(f"attention_fwd_varlen: qkv {tuple(qkv.shape)}, cu_tok {tuple(cu_tok.shape)}, B={B}, H={H}, max_N={max_N}")
+    if nq is None or nq >= max_N:
+        nq = max_N
+        o = torch.empty((total, D), device=qkv.device, dtype=qkv.dtype)
+        lse = torch.empty((H, total), device=qkv.device, dtype=torch.float32)
+        work = None
+    else:
+        if nq < 1:
+            raise _lib.PasstAmdError("attention_fwd_varlen: nq must be >= 1")
+        o = torch.zeros((B * nq, D), device=qkv.device, dtype=qkv.dtype)
+        lse = torch.zeros((B * H * nq,), device=qkv.device, dtype=torch.float32)
+        work = 4.0 * nq * total * 64 * H
+    # executed FLOPs of the all-queries form depend on the lengths, which live on the device: the per-launch profile files the
+    # upper bound B * max_N^2 (bench_kernels.py reports the exact figure from its host copy of the lengths)
+    _timed("attn_fwd", work if work is not None else 4.0 * max_N * max_N * 64 * B * H,
+           lambda: check(_lib.load().pa_attention_fwd_varlen(_p(qkv, None, True), qkv.stride(0), _p(o), o.stride(0), _p(lse),
+                                                             _p(cu_tok, torch.int32), B, H, max_N, nq, scale, dtype, flags, _stream()),
+                         "pa_attention_fwd_varlen"))
+    return o, lse
+
+
 def attention_bwd(qkv, o, d_o, lse, B, H, N, scale, nq=None, flags=0):
     """dqkv [B*N][3D]; with nq < N (o, d_o, lse compact) the Q third is zero outside the first nq rows."""
     dtype = PA_DTYPE[qkv.dtype]
@@ -734,6 +779,32 @@ def patch_pos_table(bias, time_pos, freq_pos, patch_f, patch_t, toff, cls, dist,
     check(_lib.load().pa_patch_pos_table(_p(bias), _p(time_pos), Tpe, _p(freq_pos), Fpe, _p(patch_f), _p(patch_t),
                                          Np, toff, D, _p(table), _p(cls), _p(dist), _p(npe), _p(tok), B, Ntok,
                                          _stream()), "pa_patch_pos_table")
+    return table
+
+
+def patch_gather_varlen(x, row_clip, row_f, row_t, P, fstride, tstride, dtype):
+    """cols [M][P*P] for the packed token rows of a ragged batch (prefix rows zero); index arrays: (M,) int32 on the device."""
+    B, _, F, T = x.shape
+    M = row_f.numel()
+    if row_clip.numel() != M or row_t.numel() != M or M < 1:
+        raise _lib.PasstAmdError("patch_gather_varlen: row_clip / row_f / row_t must have one entry per token row")
+    cols = torch.empty((M, P * P), device=x.device, dtype=TORCH_DTYPE[dtype])
+    check(_lib.load().pa_patch_gather_varlen(_p(x, torch.float32), B, F, T, _p(row_clip, torch.int32), _p(row_f, torch.int32),
+                                             _p(row_t, torch.int32), M, P, fstride, tstride, _p(cols), dtype, _stream()),
+          "pa_patch_gather_varlen")
+    return cols
+
+
+def patch_pos_table_varlen(bias, time_pos, freq_pos, row_f, row_t, cls, dist, npe):
+    """table [M][D] f32: positional rows + conv bias under the patch rows, cls / dist + their position rows under the prefix rows."""
+    M, D = row_f.numel(), bias.numel()
+    Tpe, Fpe = time_pos.shape[-1], freq_pos.shape[-2]
+    if row_t.numel() != M or M < 1 or time_pos.numel() != D * Tpe or freq_pos.numel() != D * Fpe or npe.numel() != 2 * D:
+        raise _lib.PasstAmdError("patch_pos_table_varlen: inconsistent shapes")
+    table = torch.empty((M, D), device=bias.device, dtype=torch.float32)
+    check(_lib.load().pa_patch_pos_table_varlen(_p(bias, torch.float32), _p(time_pos, torch.float32), Tpe, _p(freq_pos, torch.float32), Fpe,
+                                                _p(row_f, torch.int32), _p(row_t, torch.int32), M, D, _p(table), _p(cls, torch.float32),
+                                                _p(dist, torch.float32), _p(npe, torch.float32), _stream()), "pa_patch_pos_table_varlen")
     return table
 
 

@@ -370,6 +370,119 @@ def _passt_forward(model, x, save, draws=None):
     return logits, feat, ctx
 
 
+# --------------------------------------------------------------------------------------------
+# packed eval forward for clips of different lengths
+# --------------------------------------------------------------------------------------------
+def varlen_geometry(lengths, P, tstride, F_dim, Tpe, T_max=None):
+    """Host geometry of a packed ragged batch (models/passt.py:513-526 per clip, eval mode).  ``lengths``: valid frames per clip.
+    Clip i has T_i = (len_i - P) // tstride + 1 patch columns, cut to the time embedding's ``Tpe``; its tokens are cls, dist and
+    the F_dim x T_i patches in frequency-major order (:546), and the clips lie back to back.  Returns a dict of int32 numpy arrays
+    -- per token row ``row_clip`` / ``row_f`` / ``row_t`` (row_f = -1 on the prefix rows, row_t = 0 cls / 1 dist there), ``cu_tok``
+    (B + 1 row offsets) -- plus ``T_eff`` (patch columns kept per clip), ``cut`` (clips whose columns reach or exceed Tpe: the
+    reference warns for them) and ``max_N``.  ValueError names the first clip shorter than one patch or longer than ``T_max``."""
+    lens = [int(v) for v in lengths]
+    if not lens:
+        raise ValueError("lengths is empty")
+    T_eff, cut = [], []
+    for i, n in enumerate(lens):
+        if n < P:
+            raise ValueError(f"clip {i}: {n} frames are shorter than one patch ({P} frames): no patch column")
+        if T_max is not None and n > T_max:
+            raise ValueError(f"clip {i}: length {n} exceeds the input's {T_max} frames")
+        T_dim = (n - P) // tstride + 1
+        if T_dim >= Tpe:
+            cut.append(i)
+        T_eff.append(min(T_dim, Tpe))
+    ntok = np.array([2 + F_dim * t for t in T_eff], dtype=np.int64)
+    cu = np.zeros(len(lens) + 1, dtype=np.int64)
+    np.cumsum(ntok, out=cu[1:])
+    M = int(cu[-1])
+    if M >= 2 ** 31:
+        raise ValueError("packed batch has too many tokens")
+    row_clip = np.repeat(np.arange(len(lens), dtype=np.int32), ntok)
+    row_f = np.empty(M, dtype=np.int32)
+    row_t = np.empty(M, dtype=np.int32)
+    for i, t in enumerate(T_eff):
+        o = int(cu[i])
+        row_f[o:o + 2], row_t[o:o + 2] = -1, (0, 1)
+        row_f[o + 2:o + 2 + F_dim * t] = np.repeat(np.arange(F_dim, dtype=np.int32), t)
+        row_t[o + 2:o + 2 + F_dim * t] = np.tile(np.arange(t, dtype=np.int32), F_dim)
+    return dict(row_clip=row_clip, row_f=row_f, row_t=row_t, cu_tok=cu.astype(np.int32), T_eff=T_eff, cut=cut, max_N=int(ntok.max()))
+
+
+def passt_forward_varlen(model, x, lengths):
+    """Kernel sequence of the packed eval forward: every clip gets what it would get alone at batch size 1.  Returns (logits, features)."""
+    with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
+        return _passt_forward_varlen(model, x, lengths)
+
+
+def _passt_forward_varlen(model, x, lengths):
+    if not x.is_cuda:
+        raise PasstAmdError("passt_amd.PaSST runs on a HIP device only (no CPU fallback); got a CPU tensor")
+    dt = _precision(model)
+    st = model._staged
+    x = x.contiguous().float()
+    if x.dim() != 4 or x.shape[1] != 1:
+        raise ValueError(f"PaSST expects a (B, 1, n_mels, frames) spectrogram, got {tuple(x.shape)} "
+                         "(in_chans = 1 in every reference arch, models/passt.py:961)")
+    if torch.is_tensor(lengths):
+        if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+            raise ValueError("lengths must be a sequence of ints or a 1-D integer tensor")
+        lengths = lengths.tolist()                   # a device tensor costs one host read here: the geometry is decided on the host
+    lengths = [int(v) for v in lengths]
+    B, Cin, F, T = x.shape
+    if len(lengths) != B:
+        raise ValueError(f"lengths has {len(lengths)} entries for a batch of {B} clips")
+    P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
+    F_dim = (F - P) // fs + 1
+    Tpe, Fpe = model.time_new_pos_embed.shape[-1], model.freq_new_pos_embed.shape[-2]
+    if F_dim != Fpe:
+        raise RuntimeError(f"patch grid has {F_dim} frequency rows but freq_new_pos_embed has {Fpe}")
+    g = varlen_geometry(lengths, P, ts, F_dim, Tpe, T_max=T)
+    if g["cut"]:
+        warnings.warn(f"the patches shape of clips {g['cut']} are larger than the expected time encodings "
+                      f"{tuple(model.time_new_pos_embed.shape)}, x will be cut")              # :524-526, once per call
+    D, H = model.embed_dim, model.num_heads
+    M, max_N = g["row_f"].size, g["max_N"]
+    scale = (D // H) ** -0.5
+    # one upload: [row_clip | row_f | row_t | cu_tok | prefix rows]
+    cu = g["cu_tok"]
+    pidx_np = (cu[:-1, None] + np.arange(2, dtype=np.int32)[None, :]).reshape(-1).astype(np.int32)
+    idx = ops.upload_small(np.concatenate([g["row_clip"], g["row_f"], g["row_t"], cu, pidx_np]), x.device)
+    row_clip, row_f, row_t = idx[:M], idx[M:2 * M], idx[2 * M:3 * M]
+    cu_tok, pidx = idx[3 * M:3 * M + B + 1], idx[3 * M + B + 1:]
+
+    # patch embedding: the packed im2col has a zero row under every prefix token and the table holds the token there, so the one
+    # GEMM with the residual epilogue writes the whole token matrix (no scatter pass)
+    cols = ops.patch_gather_varlen(x, row_clip, row_f, row_t, P, fs, ts, dt)
+    table = ops.patch_pos_table_varlen(model.patch_embed.proj.bias, model.time_new_pos_embed, model.freq_new_pos_embed, row_f, row_t,
+                                       model.cls_token, model.dist_token, model.new_pos_embed)
+    xs = torch.empty((M, D), device=x.device, dtype=torch.float32)
+    ops.gemm_nt(cols, st.get(model.patch_embed.proj.weight, dt, False), dt, EPI_RESID, resid=table, out_f32=xs)
+
+    nblk = len(model.blocks)
+    aflags = ops.ATTN_Q_PRESCALED
+    for bi, blk in enumerate(model.blocks):
+        last = bi == nblk - 1
+        ln1, _, _ = ops.layernorm_fwd(xs, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt, False)
+        qkv = ops.linear(ln1, st.get(blk.attn.qkv.weight, dt, False), blk.attn.qkv.bias, dt, colscale_n=D, colscale=scale * ops.LOG2E)
+        if not last:
+            att, _ = ops.attention_fwd_varlen(qkv, cu_tok, B, H, max_N, scale, flags=aflags)
+            x_res = xs
+        else:                                          # prefix-only tail, as in _passt_forward
+            att, _ = ops.attention_fwd_varlen(qkv, cu_tok, B, H, max_N, scale, nq=2, flags=aflags)
+            x_res = ops.gather_rows(xs, pidx)
+        x_mid = ops.linear_resid(att, st.get(blk.attn.proj.weight, dt, False), blk.attn.proj.bias, x_res, dt)
+        ln2, _, _ = ops.layernorm_fwd(x_mid, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, False)
+        _, h_act = ops.linear_gelu(ln2, st.get(blk.mlp.fc1.weight, dt, False), blk.mlp.fc1.bias, dt)
+        xs = ops.linear_resid(h_act, st.get(blk.mlp.fc2.weight, dt, False), blk.mlp.fc2.bias, x_mid, dt)
+    xl = xs.view(B, 2, D)
+    feat, hn, _ = ops.head_pre_fwd(xl, model.norm.weight, model.norm.bias, model.norm.eps, model.head[0].weight,
+                                   model.head[0].bias, model.head[0].eps)
+    logits = ops.linear_f32_fwd(hn, model.head[1].weight, model.head[1].bias)
+    return logits, feat
+
+
 def _wgrad_pair(dY, X, dW, db, dt, scratch, accumulate):
     """dW[N][K] = dY^T X, db[N] = colsum(dY) from row-major dY[M][N], X[M][K], both read in place
     (pa_gemm_tn: transpose-read MFMA operands, deterministic split-K over tokens)."""
@@ -799,8 +912,16 @@ class PaSST(nn.Module):
         self._staged.epoch += 1
 
     @compile_opaque
-    def forward(self, x):
+    def forward(self, x, lengths=None):
         """x: (B,1,F,T) -> (logits (B,C), features (B,D)); always a tuple (models/passt.py:588,595).
+
+        ``lengths`` (a sequence of ints or a 1-D integer tensor, one entry per clip): a batch of clips of DIFFERENT lengths, left-aligned
+        in ``x`` (B, 1, n_mels, T_max); clip i is valid in its first lengths[i] frames and whatever lies behind them has no influence
+        (it is never read).  Row i of both outputs is what ``forward(x[i:i+1, :, :, :lengths[i]])`` returns at batch size 1 -- the
+        reference's own way of evaluating clips of different lengths (ex_fsd50k.py:53-56) -- but the batch runs as ONE packed kernel
+        sequence over sum_i tokens.  Eval mode only, no gradients (outputs carry no grad_fn).  The token geometry is decided on the
+        host: ``lengths`` given as a device tensor costs one host read.  A clip shorter than one patch raises ValueError; clips whose
+        patch columns reach the time embedding's length are cut to it, with one warning per call.
 
         ``torch.compile(net)`` (ex_audioset.py:135, model_speed_test :391): the whole forward is ONE opaque call to the
         compiler (``_lib.compile_opaque``: torch.compiler.disable's mechanism without the torch._dynamo import, installed at class
@@ -810,6 +931,12 @@ class PaSST(nn.Module):
         flow).  Under ``torch.autocast`` of either 16-bit type (Lightning precision=16 / torch.cuda.amp.autocast() are fp16) the
         kernels run the bf16 MFMA path with f32 accumulation and return f32 logits / features: bf16 has f32's exponent range,
         so a GradScaler's loss scale flows through the backward without overflow and its inf checks never fire."""
+        if lengths is not None:
+            if self.training:
+                raise NotImplementedError("PaSST.forward(x, lengths=...): training on ragged batches is not supported (eval mode only; "
+                                          "no reference flow trains on clips of different lengths)")
+            with torch.no_grad():
+                return passt_forward_varlen(self, x, lengths)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             # head_dist.* is not part of the graph -- as in the reference, whose forward never touches it
             # (models/passt.py:583-595; hence find_unused_parameters=True under torch DDP there and here)
@@ -916,10 +1043,11 @@ class EnsembelerModel(nn.Module):
         super().__init__()
         self.models = nn.ModuleList(models)
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
+        """``lengths``: handed to every member (PaSST.forward's ragged-batch eval forward)."""
         all_out = None
         for m in self.models:
-            out, _ = m(x)
+            out, _ = m(x) if lengths is None else m(x, lengths=lengths)
             all_out = out if all_out is None else out + all_out
         all_out = all_out / len(self.models)
         return all_out, all_out

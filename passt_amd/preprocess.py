@@ -86,7 +86,16 @@ class AugmentMelSTFT(nn.Module):
         self.register_buffer("_twiddle", tw.float().contiguous(), persistent=False)
 
     @compile_opaque                 # ONE opaque eager call under torch.compile, like PaSST.forward
-    def forward(self, x):
+    def forward(self, x, lengths=None):
+        """x: (B, L) waveforms -> (B, n_mels, 1 + (L-1)//hop).
+
+        ``lengths`` (sequence of ints or 1-D integer tensor): valid samples per row of a zero-padded batch of clips of different
+        lengths (left-aligned).  Returns ``(spec, frames)``: spec (B, n_mels, T_max), T_max = frames of the longest clip, row i equal
+        to ``forward(x[i:i+1, :lengths[i]])`` in its first frames[i] columns (pre-emphasis and reflect padding at the clip's own
+        end; samples behind lengths[i] are never read) and exactly 0.0 behind them; ``frames``: int64 CPU tensor, ready for
+        ``PaSST.forward(spec[:, None], lengths=frames)``.  Eval mode only.  A device tensor of lengths costs one host read."""
+        if lengths is not None:
+            return self._forward_varlen(x, lengths)
         if not x.is_cuda:
             raise PasstAmdError("passt_amd.AugmentMelSTFT runs on a HIP device only (no CPU fallback)")
         if x.dim() != 2:
@@ -114,6 +123,47 @@ class AugmentMelSTFT(nn.Module):
             if isinstance(self.timem, _AxisMasking):
                 p.tmask_start, p.tmask_end = self.timem.draw(p.n_frames)                  # :82
         return ops.mel_frontend(x, self._window_padded, self._bin_mel, self._twiddle, p)
+
+    def _forward_varlen(self, x, lengths):
+        if self.training:
+            raise NotImplementedError("AugmentMelSTFT.forward(x, lengths=...): eval mode only (the frequency / time masks and the "
+                                      "fmin / fmax jitter are training-time augmentations; no reference flow trains on ragged batches)")
+        if not x.is_cuda:
+            raise PasstAmdError("passt_amd.AugmentMelSTFT runs on a HIP device only (no CPU fallback)")
+        if x.dim() != 2:
+            raise ValueError("expected (batch, samples)")
+        if torch.is_tensor(lengths):
+            if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+                raise ValueError("lengths must be a sequence of ints or a 1-D integer tensor")
+            lengths = lengths.tolist()
+        lengths = [int(v) for v in lengths]
+        x = x.contiguous().float()
+        B, L = x.shape
+        if len(lengths) != B:
+            raise ValueError(f"lengths has {len(lengths)} entries for a batch of {B} waveforms")
+        for i, n in enumerate(lengths):
+            if n > L:
+                raise ValueError(f"clip {i}: length {n} exceeds the batch's {L} samples")
+            if n - 1 <= self.n_fft // 2:
+                raise PasstAmdError(f"pa_mel_frontend_fwd_varlen failed: unsupported configuration: clip {i} has {n} samples; the "
+                                    f"centred reflect padding needs more than {self.n_fft // 2 + 1} (torch.stft rule)")
+        # RNG order of the reference: both randint calls always execute (:63-64), once per call here
+        torch.randint(self.fmin_aug_range, (1,))
+        torch.randint(self.fmax_aug_range, (1,))
+        frames = [1 + (n - 1) // self.hopsize for n in lengths]
+        p = MelParams()
+        p.n_fft, p.hop, p.n_mels = self.n_fft, self.hopsize, self.n_mels
+        p.n_frames = max(frames)
+        p.preemph = 0.97
+        mel_low = 1127.0 * math.log(1.0 + self.fmin / 700.0)
+        mel_high = 1127.0 * math.log(1.0 + self.fmax / 700.0)
+        p.mel_low = mel_low
+        p.inv_mel_delta = (self.n_mels + 1) / (mel_high - mel_low)
+        p.log_eps, p.out_add, p.out_scale = 0.00001, 4.5, 1.0 / 5.0
+        p.fmask_start = p.fmask_end = p.tmask_start = p.tmask_end = 0
+        lens_dev = ops.upload_small(torch.tensor(lengths, dtype=torch.int32), x.device)
+        spec = ops.mel_frontend_varlen(x, lens_dev, self._window_padded, self._bin_mel, self._twiddle, p, fill=0.0)
+        return spec, torch.tensor(frames, dtype=torch.int64)
 
     def extra_repr(self):
         return 'winsize={}, hopsize={}'.format(self.win_length, self.hopsize)
