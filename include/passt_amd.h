@@ -373,11 +373,24 @@ int pa_patch_pos_table(const float* bias, const float* time_pos, int Tpe, const 
 /* backward of the above given dtok[B][Ntok][D] f32: gsum[Ntok][D] = sum_b dtok (ws), then
  * d_cls, d_dist, d_npe[2][D], d_bias[D], d_time_pos[D][Tpe], d_freq_pos[D][Fpe] (all overwritten
  * or accumulated), and dcols_src: the patch rows of dtok compacted to [B*Np][D] (dtype) for the
- * weight-gradient GEMM. */
+ * weight-gradient GEMM.  gsum and the six parameter gradients all NULL: only dpatch is produced (frozen network, where dpatch
+ * feeds the input-gradient GEMM of pa_patch_input_bwd). */
 int pa_patch_bwd(const float* dtok, int B, int Ntok, int D, const int32_t* patch_f,
                  const int32_t* patch_t, int Np, int toff, int Tpe, int Fpe, float* gsum,
                  float* d_cls, float* d_dist, float* d_npe, float* d_bias, float* d_time_pos,
                  float* d_freq_pos, int accumulate, void* dpatch, int dtype, void* stream);
+/* gradient w.r.t. the input spectrogram: the fold (col2im) of the kept patches, mirror image of pa_patch_gather.
+ * dcols[B*Np][P*P] (dtype) = dpatch[B*Np][D] . W[D][P*P] (one pa_gemm_nt, PA_EPI_STORE, with the transposed conv weight) ->
+ * dx[B][1][F][T] f32 with dx[b][f][t] = sum over the kept patches p that cover the pixel of dcols[b*Np+p][(f - patch_f[p]*fstride)*P +
+ * (t - patch_t[p]*tstride)].  EVERY element of dx is written: a pixel no kept patch covers gets 0 (dropped Patchout patches, the
+ * strip behind the last patch row / column, the frames behind the time cut, the gaps of a stride larger than P).  Gather form: one
+ * output pixel adds its <= ceil(P/fstride) * ceil(P/tstride) patches in a fixed order (frequency row, then time column), no
+ * atomics -- the result does not depend on the launch geometry.  grid_ws: int32 workspace of pa_patch_input_bwd_ws_ints() entries;
+ * the call builds the grid -> slot table in it ([(F-P)/fstride+1][(T-P)/tstride+1], -1 = no kept patch there); (patch_f, patch_t)
+ * pairs must be distinct, pairs outside the grid are ignored.  Spectrogram only: there is no gradient w.r.t. a waveform. */
+int64_t pa_patch_input_bwd_ws_ints(int F, int T, int P, int fstride, int tstride);
+int pa_patch_input_bwd(const void* dcols, int dtype, int B, int Np, const int32_t* patch_f, const int32_t* patch_t, int P,
+                       int fstride, int tstride, int F, int T, int32_t* grid_ws, float* dx, void* stream);
 /* Packed batch of clips of different lengths (eval forward of PaSST.forward(x, lengths), models/passt.py:513-526 per clip).  The token
  * matrix has M = sum_b (2 + Np_b) rows, clip after clip, each clip's cls and dist rows first.  Per token row r three int32 arrays
  * IN DEVICE MEMORY: row_clip[r] (row of x), row_f[r] / row_t[r] = grid coordinates of the patch, or row_f[r] = -1 for a prefix row with
@@ -406,7 +419,7 @@ int pa_head_pre_fwd(const float* x, int B, int Ntok, int D, const float* norm_g,
 /* logits[B][C] = hn[B][D] W[C][D]^T + b  (small f32 GEMM, any C) */
 int pa_linear_f32_fwd(const float* x, const float* W, const float* b, float* y, int B, int C, int D,
                       void* stream);
-/* dx[B][D] = dy[B][C] W[C][D]; dW[C][D] (+)= dy^T x; db[C] (+)= colsum(dy) */
+/* dx[B][D] = dy[B][C] W[C][D]; dW[C][D] (+)= dy^T x; db[C] (+)= colsum(dy).  dW = db = NULL: dx only (frozen network). */
 int pa_linear_f32_bwd(const float* dy, const float* x, const float* W, float* dx, float* dW,
                       float* db, int accumulate, int B, int C, int D, void* stream);
 /* backward of pa_head_pre_fwd: dhn[B][D] (+ optional dfeat[B][D]) -> dx[B][Ntok][D] (rows 0,1

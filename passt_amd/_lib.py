@@ -93,6 +93,8 @@ SIGNATURES = {
     "pa_patch_gather_varlen": (i32, [vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp]),
     "pa_patch_pos_table_varlen": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "pa_patch_bwd": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp]),
+    "pa_patch_input_bwd_ws_ints": (i64, [i32, i32, i32, i32, i32]),
+    "pa_patch_input_bwd": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "pa_head_pre_fwd": (i32, [vp, i32, i32, i32, vp, vp, f32, vp, vp, f32, vp, vp, vp, vp]),
     "pa_linear_f32_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "pa_linear_f32_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),

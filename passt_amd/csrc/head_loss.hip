@@ -298,11 +298,11 @@ extern "C" int pa_linear_f32_fwd(const float* x, const float* W, const float* b,
 
 extern "C" int pa_linear_f32_bwd(const float* dy, const float* x, const float* W, float* dx, float* dW, float* db,
                                  int accumulate, int B, int C, int D, void* stream) {
-    if (!dy || !x || !W || !dx || !dW || !db || B <= 0 || C <= 0 || D <= 0) return PA_EINVAL;
+    if (!dy || !x || !W || !dx || !dW != !db || B <= 0 || C <= 0 || D <= 0) return PA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(linear_bwd_dx_kernel, dim3((unsigned)cdiv(D, 64), (unsigned)B), dim3(256), 0, st, dy, W, dx, B, C, D);
     int rc = check_launch();
-    if (rc) return rc;
+    if (rc || !dW) return rc;                        // dW = db = NULL: input gradient only (frozen network)
     hipLaunchKernelGGL(linear_bwd_dw_kernel, dim3((unsigned)cdiv((int64_t)C * D + C, 256)), dim3(256), 0, st, dy, x, dW, db, accumulate, B, C, D);
     return check_launch();
 }

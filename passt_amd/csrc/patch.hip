@@ -172,6 +172,86 @@ __global__ void patch_rows_kernel(const float* __restrict__ dtok, int Ntok, int 
     }
 }
 
+// ---- gradient w.r.t. the input spectrogram: fold (col2im) of the kept patches ------------------------------------------------
+// grid[gf][gt] = index of the kept patch at that position of the patch grid, -1 where there is none (Patchout, time cut)
+// (ONE workgroup: the table has a few thousand cells, and filling and scattering in one launch needs no second kernel boundary)
+__global__ __launch_bounds__(1024) void patch_grid_build_kernel(const int32_t* __restrict__ pf, const int32_t* __restrict__ pt, int Np, int Fg,
+                                                                int Tg, int32_t* __restrict__ grid) {
+    const int cells = Fg * Tg;
+    for (int i = threadIdx.x; i < cells; i += blockDim.x) grid[i] = -1;
+    __syncthreads();                                 // (workgroup-scope ordering of the global stores above and below)
+    for (int p = threadIdx.x; p < Np; p += blockDim.x) {
+        const int f = pf[p], t = pt[p];
+        if ((unsigned)f < (unsigned)Fg && (unsigned)t < (unsigned)Tg) grid[f * Tg + t] = p;
+    }
+}
+
+// first / last patch-grid coordinate whose patch [g * stride, g * stride + P) holds pixel coordinate c (hi < lo: none)
+__device__ __forceinline__ void cover_range(int c, int P, int stride, int G, int& lo, int& hi) {
+    lo = c >= P ? (c - P) / stride + 1 : 0;
+    hi = min(c / stride, G - 1);
+}
+
+// dx[b][f][t] = sum of dcols[b*Np + slot][(f - gf*fs)*P + (t - gt*ts)] over the kept patches (gf, gt) that hold (f, t), added in
+// (gf, gt) order.  One thread = four consecutive elements of the flat dx (one 16-byte store; the flat index keeps the store
+// aligned whatever T is).  Four pixels of one row share their patches: the slot is looked up once per patch, and where the four
+// columns lie inside the patch at an even offset (always, for even T and tstride) bf16 dcols are read as two 4-byte pairs.
+template <typename T>
+__global__ __launch_bounds__(256) void patch_fold_kernel(const T* __restrict__ dcols, const int32_t* __restrict__ grid, int Np, int P,
+                                                         int fs, int ts, int Fg, int Tg, int F, int Tt, int64_t n, float* __restrict__ dx) {
+    const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i0 >= n) return;
+    const int64_t row0 = i0 / Tt;
+    const int t0 = (int)(i0 - row0 * Tt);
+    const int PP = P * P;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (t0 + 4 <= Tt) {
+        const int f = (int)(row0 % F);
+        const int64_t b = row0 / F;
+        int flo, fhi, tlo, thi, unused;
+        cover_range(f, P, fs, Fg, flo, fhi);
+        cover_range(t0, P, ts, Tg, tlo, unused);
+        cover_range(t0 + 3, P, ts, Tg, unused, thi);
+        for (int gf = flo; gf <= fhi; ++gf) {
+            for (int gt = tlo; gt <= thi; ++gt) {
+                const int slot = grid[gf * Tg + gt];
+                if (slot < 0) continue;
+                const int j0 = t0 - gt * ts;
+                const T* src = dcols + (b * Np + slot) * PP + (f - gf * fs) * P;
+                if constexpr (sizeof(T) == 2) {
+                    if (j0 >= 0 && j0 + 4 <= P && !((j0 | P) & 1)) {
+                        const bf16x2 lo = *(const bf16x2*)(src + j0), hi = *(const bf16x2*)(src + j0 + 2);
+                        v[0] += (float)lo[0]; v[1] += (float)lo[1]; v[2] += (float)hi[0]; v[3] += (float)hi[1];
+                        continue;
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if ((unsigned)(j0 + e) < (unsigned)P) v[e] += to_f32<T>(src[j0 + e]);
+            }
+        }
+    } else {                                         // the four elements straddle a row end (T % 4 != 0) or the end of dx
+        for (int e = 0; e < 4 && i0 + e < n; ++e) {
+            const int64_t row = (i0 + e) / Tt;
+            const int t = (int)(i0 + e - row * Tt), f = (int)(row % F);
+            const int64_t b = row / F;
+            int flo, fhi, tlo, thi;
+            cover_range(f, P, fs, Fg, flo, fhi);
+            cover_range(t, P, ts, Tg, tlo, thi);
+            for (int gf = flo; gf <= fhi; ++gf)
+                for (int gt = tlo; gt <= thi; ++gt) {
+                    const int slot = grid[gf * Tg + gt];
+                    if (slot >= 0) v[e] += to_f32<T>(dcols[(b * Np + slot) * PP + (f - gf * fs) * P + (t - gt * ts)]);
+                }
+        }
+    }
+    if (i0 + 4 <= n) {
+        *(f32x4*)(dx + i0) = f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+        for (int e = 0; i0 + e < n; ++e) dx[i0 + e] = v[e];
+    }
+}
+
 }  // namespace pa
 
 using namespace pa;
@@ -229,21 +309,53 @@ extern "C" int pa_patch_bwd(const float* dtok, int B, int Ntok, int D, const int
                             int Np, int toff, int Tpe, int Fpe, float* gsum, float* d_cls, float* d_dist, float* d_npe,
                             float* d_bias, float* d_time_pos, float* d_freq_pos, int accumulate, void* dpatch, int dtype,
                             void* stream) {
-    if (!dtok || !patch_f || !patch_t || !gsum || !d_cls || !d_dist || !d_npe || !d_bias || !d_time_pos || !d_freq_pos || !dpatch)
-        return PA_EINVAL;
+    // gsum and the six parameter gradients all NULL: only the compaction (frozen network: dpatch feeds the input-gradient GEMM)
+    const bool rows_only = !gsum && !d_cls && !d_dist && !d_npe && !d_bias && !d_time_pos && !d_freq_pos;
+    if (!dtok || !patch_f || !patch_t || !dpatch || B <= 0 || Np <= 0 || D <= 0) return PA_EINVAL;
+    if (!rows_only && (!gsum || !d_cls || !d_dist || !d_npe || !d_bias || !d_time_pos || !d_freq_pos)) return PA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t per = (int64_t)Ntok * D;
-    hipLaunchKernelGGL(batch_sum_kernel, dim3((unsigned)cdiv(per, 1024)), dim3(256), 0, st, dtok, B, per, gsum);
-    int rc = check_launch();
-    if (rc) return rc;
-    hipLaunchKernelGGL(patch_param_grads_kernel, dim3((unsigned)cdiv(D, 16), (unsigned)(1 + Tpe + Fpe)), dim3(256), 0, st, gsum, D, patch_f,
-                       patch_t, Np, toff, Tpe, Fpe, d_cls, d_dist, d_npe, d_bias, d_time_pos, d_freq_pos, accumulate);
-    rc = check_launch();
-    if (rc) return rc;
+    int rc = PA_OK;
+    if (!rows_only) {
+        const int64_t per = (int64_t)Ntok * D;
+        hipLaunchKernelGGL(batch_sum_kernel, dim3((unsigned)cdiv(per, 1024)), dim3(256), 0, st, dtok, B, per, gsum);
+        rc = check_launch();
+        if (rc) return rc;
+        hipLaunchKernelGGL(patch_param_grads_kernel, dim3((unsigned)cdiv(D, 16), (unsigned)(1 + Tpe + Fpe)), dim3(256), 0, st, gsum, D, patch_f,
+                           patch_t, Np, toff, Tpe, Fpe, d_cls, d_dist, d_npe, d_bias, d_time_pos, d_freq_pos, accumulate);
+        rc = check_launch();
+        if (rc) return rc;
+    }
     const int64_t total = (int64_t)B * Np * D;
     const int blocks = (int)std::min<int64_t>(cdiv(total, 256), 8192);
     if (dtype == PA_BF16) hipLaunchKernelGGL(patch_rows_kernel<bf16>, dim3(blocks), dim3(256), 0, st, dtok, Ntok, D, Np, (bf16*)dpatch, total);
     else if (dtype == PA_F32) hipLaunchKernelGGL(patch_rows_kernel<float>, dim3(blocks), dim3(256), 0, st, dtok, Ntok, D, Np, (float*)dpatch, total);
     else return PA_EINVAL;
+    return check_launch();
+}
+
+extern "C" int64_t pa_patch_input_bwd_ws_ints(int F, int T, int P, int fstride, int tstride) {
+    if (P <= 0 || fstride <= 0 || tstride <= 0 || F < P || T < P) return 0;
+    return (int64_t)((F - P) / fstride + 1) * ((T - P) / tstride + 1);
+}
+
+extern "C" int pa_patch_input_bwd(const void* dcols, int dtype, int B, int Np, const int32_t* patch_f, const int32_t* patch_t, int P,
+                                  int fstride, int tstride, int F, int T, int32_t* grid_ws, float* dx, void* stream) {
+    if (!dcols || !patch_f || !patch_t || !grid_ws || !dx || B <= 0 || Np <= 0 || P <= 0 || fstride <= 0 || tstride <= 0 || F < P || T < P)
+        return PA_EINVAL;
+    if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
+    const int64_t cells = pa_patch_input_bwd_ws_ints(F, T, P, fstride, tstride);
+    const int Fg = (F - P) / fstride + 1, Tg = (T - P) / tstride + 1;
+    const int64_t n = (int64_t)B * F * T;
+    // distinct kept patches fit the grid; int32 indexing of the table and of the launch grid
+    if (Np > cells || cells >= ((int64_t)1 << 31) || cdiv(n, 1024) >= ((int64_t)1 << 31)) return PA_EUNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(patch_grid_build_kernel, dim3(1), dim3(1024), 0, st, patch_f, patch_t, Np, Fg, Tg, grid_ws);
+    int rc = check_launch();
+    if (rc) return rc;
+    const dim3 grid((unsigned)cdiv(n, 1024)), block(256);
+    if (dtype == PA_BF16)
+        hipLaunchKernelGGL(patch_fold_kernel<bf16>, grid, block, 0, st, (const bf16*)dcols, grid_ws, Np, P, fstride, tstride, Fg, Tg, F, T, n, dx);
+    else
+        hipLaunchKernelGGL(patch_fold_kernel<float>, grid, block, 0, st, (const float*)dcols, grid_ws, Np, P, fstride, tstride, Fg, Tg, F, T, n, dx);
     return check_launch();
 }

@@ -812,12 +812,29 @@ def patch_bwd(dtok, patch_f, patch_t, toff, Tpe, Fpe, d_cls, d_dist, d_npe, d_bi
               accumulate=False):
     B, Ntok, D = dtok.shape
     Np = patch_f.numel()
-    gsum = torch.empty((Ntok, D), device=dtok.device, dtype=torch.float32)
+    gsum = torch.empty((Ntok, D), device=dtok.device, dtype=torch.float32) if d_cls is not None else None   # all d_* None: dpatch only
     dpatch = torch.empty((B * Np, D), device=dtok.device, dtype=TORCH_DTYPE[dtype])
     check(_lib.load().pa_patch_bwd(_p(dtok), B, Ntok, D, _p(patch_f), _p(patch_t), Np, toff, Tpe, Fpe, _p(gsum),
                                    _p(d_cls), _p(d_dist), _p(d_npe), _p(d_bias), _p(d_tpos), _p(d_fpos),
                                    int(accumulate), _p(dpatch), dtype, _stream()), "pa_patch_bwd")
     return dpatch
+
+
+def patch_input_bwd(dcols, patch_f, patch_t, B, F, T, P, fstride, tstride, out=None):
+    """dx [B][1][F][T] f32 = fold (col2im) of dcols [B*Np][P*P] (f32 or bf16) over the kept patches: the gradient w.r.t. the input
+    spectrogram of patch_gather.  Every element is written (0 where no kept patch covers the pixel); deterministic (no atomics).
+    out: an existing (B, 1, F, T) f32 tensor to overwrite."""
+    Np = patch_f.numel()
+    if dcols.dim() != 2 or dcols.shape[0] != B * Np or dcols.shape[1] != P * P or patch_t.numel() != Np or F < P or T < P:
+        raise _lib.PasstAmdError(f"patch_input_bwd: dcols {tuple(dcols.shape)} for B={B}, Np={Np}, P={P}, F={F}, T={T}")
+    lib = _lib.load()
+    dx = torch.empty((B, 1, F, T), device=dcols.device, dtype=torch.float32) if out is None else out
+    if dx.shape != (B, 1, F, T):
+        raise _lib.PasstAmdError(f"patch_input_bwd: out is {tuple(dx.shape)}, expected {(B, 1, F, T)}")
+    grid = torch.empty(lib.pa_patch_input_bwd_ws_ints(F, T, P, fstride, tstride), device=dcols.device, dtype=torch.int32)
+    check(lib.pa_patch_input_bwd(_p(dcols), PA_DTYPE[dcols.dtype], B, Np, _p(patch_f, torch.int32), _p(patch_t, torch.int32), P, fstride, tstride,
+                                 F, T, _p(grid, torch.int32), _p(dx, torch.float32), _stream()), "pa_patch_input_bwd")
+    return dx
 
 
 # ---- head / loss -----------------------------------------------------------------------------

@@ -365,8 +365,9 @@ def _passt_forward(model, x, save, draws=None):
     logits = ops.linear_f32_fwd(hn, model.head[1].weight, model.head[1].bias)
     ctx = None
     if save:
-        ctx = dict(dt=dt, B=B, Ntok=Ntok, Np=Np, pf=pf, pt=pt_pos, toff=toff, cols=cols, saved=saved, xl=xl, feat=feat,
-                   hn=hn, stats=stats, scale=scale)
+        # pt_grid: the kept patches' own grid columns (pt may carry the time-positional offset); F, T: the input gradient's shape
+        ctx = dict(dt=dt, B=B, Ntok=Ntok, Np=Np, pf=pf, pt=pt_pos, pt_grid=pt, F=F, T=T, toff=toff, cols=cols, saved=saved, xl=xl,
+                   feat=feat, hn=hn, stats=stats, scale=scale)
     return logits, feat, ctx
 
 
@@ -492,6 +493,13 @@ def _wgrad_pair(dY, X, dW, db, dt, scratch, accumulate):
         ops.colsum(dY, db, accumulate=accumulate)
 
 
+class _NoRowJobs(list):
+    """``defer`` sink of the no-weight-gradients backward: deferred row reductions are dropped, nothing finishes them."""
+
+    def append(self, job):
+        pass
+
+
 class _SideStream:
     """Weight-gradient GEMMs and bias-gradient reductions are off the input-gradient critical path: they run
     on a second HIP stream so their workgroups interleave with the dgrad / LayerNorm / attention kernels
@@ -516,22 +524,39 @@ class _SideStream:
             torch.cuda.current_stream().wait_stream(self.stream)
 
 
-def passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done=None):
+class _NoGrads(dict):
+    """``grads`` of the no-weight-gradients backward: every parameter's output buffer is None."""
+
+    def __missing__(self, name):
+        return None
+
+
+def passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done=None, want_dx=False):
     """Backward of passt_forward.  ``grads``: dict param-name -> f32 tensor to OVERWRITE.
     ``on_block_done(i)`` is called after block i's parameter gradients are enqueued (i = depth for the
     head, then depth-1 .. 0, then -1 for the patch embedding) -- the hook the data-parallel reducer
-    uses to start all-reducing finished buckets while the rest of the backward runs."""
+    uses to start all-reducing finished buckets while the rest of the backward runs.
+
+    ``want_dx``: also return the gradient w.r.t. the input spectrogram, (B, 1, F, T) f32 -- one more N = P*P GEMM with the
+    transposed patch-embedding weight and the fold of the kept patches (pa_patch_input_bwd); otherwise returns None.
+    ``grads=None``: the no-weight-gradients mode of a fully frozen network (a loss network): no weight-gradient GEMM, no bias /
+    positional / head parameter reduction and no ``on_block_done``.  What the activation-gradient kernels produce anyway stays
+    where it falls and is never reduced: the LayerNorm backward's dgamma / dbeta partial rows (in that call's own workspace) and
+    the head's per-clip LayerNorm partials (pa_head_pre_bwd's ``part``)."""
     with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
-        return _passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done)
+        return _passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done, want_dx)
 
 
-def _passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done=None):
+def _passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done=None, want_dx=False):
     dt, B, Ntok, Np = ctx["dt"], ctx["B"], ctx["Ntok"], ctx["Np"]
     st = model._staged
     D, H = model.embed_dim, model.num_heads
     M = B * Ntok
     scratch = model._scratch
-    g = grads
+    frozen = grads is None
+    g = _NoGrads() if frozen else grads
+    if frozen:
+        on_block_done = None
     side = scratch.get("side")
     if side is not None and side.enabled != bool(getattr(model, "overlap_wgrad", False)):
         side = None
@@ -540,6 +565,8 @@ def _passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done=None):
 
     def wgrad_async(dY, X, dW, db, done=None):
         """dW, db on the side stream; optionally report block completion from there (DDP bucket launch)."""
+        if frozen:
+            return
         with side.fork(dY, X):
             _wgrad_pair(dY, X, dW, db, dt, scratch, False)
             if done is not None and on_block_done:
@@ -547,17 +574,21 @@ def _passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done=None):
 
     # bf16, single stream: the four weight gradients of a block wait until the block's last operand exists and go out as
     # ONE batched launch (+ one batched split-K reduction): no drain / prologue between them, equal-sized work items
-    pending = [] if (dt == PA_BF16 and not side.enabled and not os.environ.get("PASST_AMD_NO_BATCH_WGRAD")) else None
+    pending = [] if (dt == PA_BF16 and not side.enabled and not frozen and not os.environ.get("PASST_AMD_NO_BATCH_WGRAD")) else None
     # ... and so do the block's small finishing reductions: the two LayerNorms' dgamma | dbeta (+ the bias gradient each carries)
     # and the GELU' epilogue's fc1.bias rows stay as partial rows and are reduced by the SAME finishing launch as the split-K
     # slabs (three launches per block less; PASST_AMD_NO_DEFER_ROWS=1: A/B, every reduction right behind its producer)
     rowjobs = [] if (pending is not None and not os.environ.get("PASST_AMD_NO_DEFER_ROWS")) else None
+    if frozen:
+        rowjobs = _NoRowJobs()      # the LayerNorm backward leaves its parameter-gradient partial rows unreduced
     # PASST_AMD_BIAS_FROM_WGRAD=1 (A/B; required by PA_EPILOGUE_V3=1): fc1.bias out of the weight-gradient launch instead of the
     # GELU' epilogue's lane-local column sums
     bias_from_wgrad = (dt == PA_BF16 and ops.wgrad_tn_fuses_bias(dt) and not os.environ.get("PASST_AMD_NO_FUSED_BIAS")
                        and (os.environ.get("PASST_AMD_BIAS_FROM_WGRAD") == "1" or os.environ.get("PA_EPILOGUE_V3") == "1"))
 
     def wgrad(dY, X, dW, db, done=None, fuse=False):
+        if frozen:
+            return
         if pending is None:
             return wgrad_async(dY, X, dW, db, done)
         # the block's last problem (qkv) -- and fc1, `fuse` -- get their bias gradient out of the batched launch itself (a
@@ -582,7 +613,8 @@ def _passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done=None):
                                  ctx["stats"])
     part4 = part.view(B, 4, D)
     for j, name in enumerate(("head.0.weight", "head.0.bias", "norm.weight", "norm.bias")):
-        ops.colsum_f32(part4[:, j, :], g[name])
+        if not frozen:
+            ops.colsum_f32(part4[:, j, :], g[name])
     if on_block_done:
         on_block_done(len(model.blocks))
     nblk = len(model.blocks)
@@ -597,7 +629,7 @@ def _passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done=None):
         # fc2.bias gradient = column sums of dx: already produced by the LayerNorm backward that made dx (the next
         # block's norm1) -- except for the last block, whose dx comes from the head
         wgrad(dx_lp, h_act, g[pfx + "mlp.fc2.weight"], g[pfx + "mlp.fc2.bias"] if last else None)
-        if bias_from_wgrad:
+        if bias_from_wgrad or frozen:
             # the fc1.bias gradient (column sums of d_pre) rides in the weight-gradient launch, like qkv.bias (the LDS-free
             # GELU' epilogue -- transposed accumulators, lane = token -- has no lane-local column sums to offer)
             d_pre = ops.dgelu_gemm(dx_lp, st.get(blk.mlp.fc2.weight, dt, True), h_pre, dt)
@@ -638,7 +670,15 @@ def _passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done=None):
                            g["dist_token"], g["new_pos_embed"], g["patch_embed.proj.bias"],
                            g["time_new_pos_embed"], g["freq_new_pos_embed"], dt)
     wgrad_async(dpatch, ctx["cols"], g["patch_embed.proj.weight"], None, done=-1)
+    dx_in = None
+    if want_dx:
+        # ---- input spectrogram: dcols = dpatch W (the im2col GEMM mirrored), then the fold of the kept patches
+        P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
+        dcols = torch.empty((B * Np, P * P), device=dpatch.device, dtype=dpatch.dtype)
+        ops.gemm_nt(dpatch, st.get(model.patch_embed.proj.weight, dt, True), dt, EPI_STORE, out_lp=dcols)
+        dx_in = ops.patch_input_bwd(dcols, ctx["pf"], ctx["pt_grid"], B, ctx["F"], ctx["T"], P, fs, ts)
     side.join()
+    return dx_in
 
 
 class _PasstFunction(torch.autograd.Function):
@@ -647,11 +687,12 @@ class _PasstFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, x, *params):
-        if x.requires_grad:
-            raise NotImplementedError("passt_amd.PaSST does not produce a gradient w.r.t. its input spectrogram (the reference's "
-                                      "training never asks for one); detach() the input")
         logits, feat, c = passt_forward(model, x, save=True)
         ctx.model, ctx.c = model, c
+        # the input spectrogram's gradient is computed only when asked for; a graph none of whose parameters requires a gradient
+        # (a frozen loss network) runs the backward without any weight-gradient work
+        ctx.want_dx = bool(ctx.needs_input_grad[1])
+        ctx.frozen = not any(ctx.needs_input_grad[2:])
         ctx.named, ctx.total = model._graph_params(validate=False)     # the list forward() just handed to apply()
         # bound to a passt_amd.optim.AdamW (PaSST.bind_flat_grads): the only input is a token; the backward writes the gradients
         # straight into the optimizer's persistent flat buffer -- p.grad are views of it -- and hands autograd nothing
@@ -669,10 +710,19 @@ class _PasstFunction(torch.autograd.Function):
         # them all; parameters with requires_grad=False are simply not handed back to autograd (frozen backbone, ...)
         named, total = ctx.named, ctx.total
         fl = ctx.flat
+        if dlogits is not None:
+            dlogits = dlogits.contiguous()
+        if ctx.frozen:
+            # nothing but the input asked for a gradient: no flat buffer, no weight-gradient launch, no reducer (dx is a local quantity)
+            if dlogits is None:
+                dlogits = torch.zeros((c["B"], model.num_classes), device=dfeat.device, dtype=torch.float32)
+            dx = passt_backward(model, c, dlogits, None if dfeat is None else dfeat.contiguous(), None, want_dx=ctx.want_dx)
+            ctx.c = None
+            return (None, dx) + (None,) * (len(named) if fl is None else 1)
         if fl is not None and fl["fresh"]:
             flat, grads = fl["flat_g"], fl["grads"]     # overwritten in place: the caller zeroed (optimizer.zero_grad()) since the last backward
         else:
-            flat = torch.empty(total, device=dlogits.device, dtype=torch.float32)
+            flat = torch.empty(total, device=(dfeat if dlogits is None else dlogits).device, dtype=torch.float32)
             # one C++ call makes the 159 views (a Python loop of slice + view costs 1.3 ms of host time in front of the first
             # backward kernel: exposed whenever the caller synchronised in this step, and the reference's mixup does)
             views = torch._C._nn.unflatten_dense_tensors(flat, [p for _, p in named])
@@ -695,18 +745,20 @@ class _PasstFunction(torch.autograd.Function):
             dfeat = None if dfeat is None else dfeat * inv
             red.flat = flat
             try:
-                passt_backward(model, c, dlogits, dfeat, grads, on_block_done=red.on_block_done)
+                dx = passt_backward(model, c, dlogits, dfeat, grads, on_block_done=red.on_block_done, want_dx=ctx.want_dx)
             finally:
                 red.wait()              # also after an exception: no collective may stay in flight on a buffer we drop
+            if dx is not None:
+                dx.mul_(float(red.world))       # not reduced: the gradient of THIS rank's loss (dlogits went in divided by world)
         else:
-            passt_backward(model, c, dlogits, dfeat, grads)
+            dx = passt_backward(model, c, dlogits, dfeat, grads, want_dx=ctx.want_dx)
         ctx.c = None
         if fl is not None:
             if not fl["fresh"]:                 # a second backward without zero_grad (gradient accumulation): add, as AccumulateGrad would
                 fl["flat_g"].add_(flat)
             fl["fresh"] = False
-            return None, None, None
-        out = [None, None]
+            return None, dx, None
+        out = [None, dx]
         for n, p in named:                      # the same list, in the same order, as PaSST.forward handed to apply()
             out.append(grads[n] if p.requires_grad else None)
         return tuple(out)
@@ -769,6 +821,10 @@ class PaSST(nn.Module):
         # opt-in: run weight/bias-gradient kernels on a second stream (+2.4 % step throughput measured on MI355X);
         # off by default so that every kernel runs alone and per-kernel timings (bench.py roofline, rocprof) are exact
         self.overlap_wgrad = False
+        # opt-in: with TRAINABLE parameters, also hand back the gradient w.r.t. an input spectrogram that requires one (off: such a
+        # call raises NotImplementedError, as it always did).  A fully frozen network needs no switch: there the input is the only
+        # thing that can ask for a gradient
+        self.input_grad = False
         self.init_weights(weight_init)
         self._reset_runtime()
 
@@ -915,11 +971,16 @@ class PaSST(nn.Module):
     def forward(self, x, lengths=None):
         """x: (B,1,F,T) -> (logits (B,C), features (B,D)); always a tuple (models/passt.py:588,595).
 
+        An ``x`` that requires a gradient gets one (``x.grad`` / ``torch.autograd.grad``), as in the reference: PaSST as a
+        differentiable loss network.  With every parameter frozen (``net.requires_grad_(False)``) this needs no switch and the backward
+        runs no weight-gradient kernel at all; with trainable parameters it is opt-in (``net.input_grad = True``, otherwise
+        NotImplementedError as before) and everything is computed as in training, plus the input gradient.
+
         ``lengths`` (a sequence of ints or a 1-D integer tensor, one entry per clip): a batch of clips of DIFFERENT lengths, left-aligned
         in ``x`` (B, 1, n_mels, T_max); clip i is valid in its first lengths[i] frames and whatever lies behind them has no influence
         (it is never read).  Row i of both outputs is what ``forward(x[i:i+1, :, :, :lengths[i]])`` returns at batch size 1 -- the
         reference's own way of evaluating clips of different lengths (ex_fsd50k.py:53-56) -- but the batch runs as ONE packed kernel
-        sequence over sum_i tokens.  Eval mode only, no gradients (outputs carry no grad_fn).  The token geometry is decided on the
+        sequence over sum_i tokens.  Eval mode only, no gradients (outputs carry no grad_fn, also for an ``x`` that requires one).  The token geometry is decided on the
         host: ``lengths`` given as a device tensor costs one host read.  A clip shorter than one patch raises ValueError; clips whose
         patch columns reach the time embedding's length are cut to it, with one warning per call.
 
@@ -937,7 +998,16 @@ class PaSST(nn.Module):
                                           "no reference flow trains on clips of different lengths)")
             with torch.no_grad():
                 return passt_forward_varlen(self, x, lengths)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        want_dx = torch.is_grad_enabled() and torch.is_tensor(x) and x.requires_grad
+        if want_dx and not getattr(self, "input_grad", False) and any(p.requires_grad for _, p in self._graph_params()[0]):
+            raise NotImplementedError("passt_amd.PaSST with trainable parameters produces a gradient w.r.t. its input spectrogram only "
+                                      "when asked to: set net.input_grad = True (or freeze the network: net.requires_grad_(False); "
+                                      "or detach() the input)")
+        if want_dx:
+            # the kernels read a dense f32 spectrogram: the conversion happens where autograd sees it, so x.grad comes back in the
+            # caller's own shape, dtype and layout (a sliced / transposed / 16-bit x)
+            x = x.contiguous().float()
+        if torch.is_grad_enabled() and (want_dx or any(p.requires_grad for p in self.parameters())):
             # head_dist.* is not part of the graph -- as in the reference, whose forward never touches it
             # (models/passt.py:583-595; hence find_unused_parameters=True under torch DDP there and here)
             named = self._graph_params()[0]
