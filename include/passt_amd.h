@@ -330,7 +330,7 @@ int pa_colsum_f32(const float* in, int R, int C, int ld, float* out, int accumul
 #define PA_ATTN_BWD_SINGLE_PASS_W16 8
 int pa_attention_fwd(const void* qkv, int ldqkv, void* o, int ldo, float* lse, int B, int H, int N, int nq,
                      float scale, int dtype, int flags, void* stream);
-/* Forward over PACKED sequences of different lengths (eval on ragged batches; no backward exists).  The B sequences lie back to back
+/* Forward over PACKED sequences of different lengths (ragged batches; backward: pa_attention_bwd_varlen).  The B sequences lie back to back
  * in qkv: sequence b owns token rows cu_tok[b] .. cu_tok[b+1] - 1, N_b = cu_tok[b+1] - cu_tok[b] >= 1; cu_tok is B + 1 int32 IN
  * DEVICE MEMORY with cu_tok[0] = 0, non-decreasing, and max_N >= every N_b (it only sizes the launch: cdiv(max_N, 128) query blocks
  * per (sequence, head), the ones a short sequence does not have return at once).  Every sequence gets bit for bit what
@@ -352,6 +352,21 @@ int64_t pa_attention_bwd_ws_floats(int B, int H, int nq);
 int pa_attention_bwd(const void* qkv, int ldqkv, const void* o, const void* d_o, int ldo,
                      const float* lse, float* delta, void* dqkv, int lddqkv, int B, int H, int N, int nq,
                      float scale, int dtype, int flags, void* stream);
+/* Backward over PACKED sequences of different lengths: the backward of pa_attention_fwd_varlen, same cu_tok / max_N / nq meaning, same
+ * layouts.  nq >= max_N: o / d_o are packed like qkv's rows and lse is [H][cu_tok[B]]; nq < max_N (the last block's nq = 2): o / d_o /
+ * lse are compact as in pa_attention_bwd, o[(b*nq + q)][H*64], lse[(b*H + h)*nq + q].  ws: f32 workspace of
+ * pa_attention_bwd_varlen_ws_floats(cu_tok[B], B, H, nq) floats (enough for either layout); the dQ kernel leaves the two planes
+ * -rowsum(dO*O) and -lse*log2 e in it, in lse's layout (plane pitch H * cu_tok[B], resp. B * H * nq), for the dK/dV kernel.
+ * Every row [0, cu_tok[B]) of dqkv is written in all three thirds (with nq < max_N the Q third of the rows q >= nq is written as zero:
+ * no pa_zero2d by the caller) and nothing at or behind row cu_tok[B].  Always the dQ + dK/dV kernel pair -- the single pass needs one
+ * N <= 512 for the whole launch; the PA_ATTN_BWD_* flags are accepted and ignored.  cdiv(nq, 128) query blocks and cdiv(max_N, 128)
+ * key blocks are launched per (sequence, head); those a short sequence does not have return before their first memory access, and
+ * tail tiles (K / V as well as Q / dO) are clamped to the sequence's own last row: no row of a neighbour is read.  Equal lengths
+ * reproduce pa_attention_bwd(..., PA_ATTN_BWD_TWO_PASS) bit for bit. */
+int64_t pa_attention_bwd_varlen_ws_floats(int64_t total_tokens, int B, int H, int nq);
+int pa_attention_bwd_varlen(const void* qkv, int ldqkv, const void* o, const void* d_o, int ldo, const float* lse, float* ws,
+                            void* dqkv, int lddqkv, const int32_t* cu_tok, int B, int H, int max_N, int nq, float scale, int dtype,
+                            int flags, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Patch embedding + positional terms + Patchout: PatchEmbed.forward (models/passt.py:318-328) and
@@ -405,6 +420,22 @@ int pa_patch_gather_varlen(const float* x, int B, int F, int T_max, const int32_
 int pa_patch_pos_table_varlen(const float* bias, const float* time_pos, int Tpe, const float* freq_pos, int Fpe,
                               const int32_t* row_f, const int32_t* row_t, int M, int D, float* table, const float* cls,
                               const float* dist, const float* npe, void* stream);
+/* Backward of the packed patch stage (eval: no Patchout).  The packed token matrix is regular per clip -- cls, dist, then Fg x T_eff[b]
+ * patches in frequency-major order with T_eff[b] = (cu_tok[b+1] - cu_tok[b] - 2) / Fg -- so the row of patch (f, t) of clip b is
+ * cu_tok[b] + 2 + f * T_eff[b] + t and both entry points need cu_tok (B + 1 int32 in device memory) only.
+ * pa_patch_input_bwd_varlen: the fold.  dcols[M][P*P] (dtype) = dtok[M][D] . W[D][P*P] over ALL M rows (one pa_gemm_nt; the rows under
+ *   the prefix tokens are never read here) -> dx[B][1][F][T_max] f32, Fg = (F - P) / fstride + 1.  Gather form as pa_patch_input_bwd:
+ *   one thread per four consecutive elements, the covering patches added in (frequency row, time column) order, no atomics.  EVERY
+ *   element of dx is written; it is exactly 0 at and behind frame (T_eff[b] - 1) * tstride + P of clip b (the clip's own end, the
+ *   time cut) and behind the last patch row.
+ * pa_patch_bwd_varlen: d_cls, d_dist, d_npe[2][D], d_bias[D], d_time_pos[D][Tpe], d_freq_pos[D][Fpe] (overwritten or accumulated)
+ *   from dtok[M][D] f32, M = cu_tok[B], Fg = Fpe.  Deterministic: a slot's rows are enumerated clip after clip in a fixed order, no
+ *   atomics.  All six NULL (frozen network): nothing is launched.  (The patch weight gradient is one weight-gradient GEMM of dtok
+ *   against the packed cols: their prefix rows are zero.) */
+int pa_patch_input_bwd_varlen(const void* dcols, int dtype, const int32_t* cu_tok, int B, int P, int fstride, int tstride, int F,
+                              int T_max, float* dx, void* stream);
+int pa_patch_bwd_varlen(const float* dtok, int M, int D, const int32_t* cu_tok, int B, int Tpe, int Fpe, float* d_cls, float* d_dist,
+                        float* d_npe, float* d_bias, float* d_time_pos, float* d_freq_pos, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Head: final norm on the two prefix tokens, their mean, head LayerNorm + Linear

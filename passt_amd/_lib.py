@@ -85,6 +85,8 @@ SIGNATURES = {
     "pa_attention_fwd_varlen": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp]),
     "pa_attention_bwd_ws_floats": (i64, [i32, i32, i32]),
     "pa_attention_bwd": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp]),
+    "pa_attention_bwd_varlen_ws_floats": (i64, [i64, i32, i32, i32]),
+    "pa_attention_bwd_varlen": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, f32, i32, i32, vp]),
     "pa_gather_rows": (i32, [vp, vp, i32, i64, vp, vp]),
     "pa_scatter_rows": (i32, [vp, vp, i32, i64, vp, vp]),
     "pa_zero2d": (i32, [vp, i64, i64, i64, vp]),
@@ -92,6 +94,8 @@ SIGNATURES = {
     "pa_patch_pos_table": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp]),
     "pa_patch_gather_varlen": (i32, [vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp]),
     "pa_patch_pos_table_varlen": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "pa_patch_input_bwd_varlen": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "pa_patch_bwd_varlen": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]),
     "pa_patch_bwd": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp]),
     "pa_patch_input_bwd_ws_ints": (i64, [i32, i32, i32, i32, i32]),
     "pa_patch_input_bwd": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),

@@ -522,11 +522,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 // ------------------------------------------------------------------------------------------------
 // backward, part 1: dK, dV.  Workgroup owns 128 keys (lane = key); queries stream through LDS.
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool PRE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? DKDV_WAVES : 1))) void attn_bwd_dkdv_kernel(const T* __restrict__ qkv, int ldqkv,
-                                                            const T* __restrict__ d_o, int ldo,
-                                                            const float* __restrict__ ws, int64_t plane,
-                                                            T* __restrict__ dqkv, int lddqkv, int H, int N, int nq, float scale, int nblk, int BH) {
+// attn_bwd_dkdv_body is the kernel; attn_bwd_dkdv_kernel (fixed length) and attn_bwd_dkdv_varlen_kernel are its two entry points.
+// VL (pa_attention_bwd_varlen): packed sequences, as in attn_fwd_body.  Sequence b owns token rows cu_tok[b] .. cu_tok[b + 1] of qkv and
+// dqkv; its first row and its N come from two scalar loads and everything behind them is the fixed-length code, run per sequence.
+// The arguments N / nq hold max N and the caller's nq: nq == max N means "every query" (d_o packed like qkv's rows, the workspace
+// planes [H][total tokens] like the forward's lse), otherwise d_o and the workspace are compact (nq rows per sequence) and this
+// kernel also zeroes the Q third of the rows it owns at or behind nq (the dQ kernel writes the rows in front), so that every row
+// of dqkv is written by the pair.  The Q / dO rows staged for the tail tile are clamped to the sequence's own last query.
+template <typename T, bool PRE, bool VL>
+__device__ __forceinline__ void attn_bwd_dkdv_body(const T* __restrict__ qkv, int ldqkv, const T* __restrict__ d_o, int ldo,
+                                                   const float* __restrict__ ws, int64_t plane, T* __restrict__ dqkv, int lddqkv, int H, int N,
+                                                   int nq, float scale, int nblk, int BH, const int32_t* __restrict__ cu_tok) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using F = typename Frag<T>::type;
     constexpr int NF = Tile<T>::NFRAG, NS = AccSteps<T>::N, TB = Tile<T>::BYTES;
@@ -536,8 +542,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
     if (!attn_block(nblk, BH, blk, bh)) return;
     const int b = bh / H, h = bh % H;
     const int D = H * HD;
-    const T* base = qkv + (int64_t)b * N * ldqkv + h * HD;
-    const T* dobase = d_o + (int64_t)b * nq * ldo + h * HD;     // d_o / lse / delta: nq rows per sequence
+    // VL only (the fixed-length instance keeps its own expressions below, so that it compiles to what it always did)
+    int64_t tok0 = 0, dorow0 = 0;                               // first row of this sequence in qkv / dqkv, in d_o
+    const float* ws_row = ws;                                   // -delta of query 0; -lse * log2(e) lies `plane` floats behind
+    bool zero_q = false;
+    if constexpr (VL) {
+        const int t0 = cu_tok[b], t1 = cu_tok[b + 1];           // wave-uniform: scalar loads
+        const bool all_queries = nq == N;                       // N is max N here
+        N = t1 - t0;
+        tok0 = t0;
+        if (blk * 128 >= N) return;                             // (also N <= 0) a block this sequence does not have: whole workgroup
+        dorow0 = (int64_t)b * nq;
+        ws_row = ws + (int64_t)bh * nq;
+        nq = min(nq, N);
+        if (all_queries) {
+            const int total = cu_tok[BH / H];
+            dorow0 = t0;
+            plane = (int64_t)H * total;
+            ws_row = ws + (int64_t)h * total + t0;
+        }
+        zero_q = !all_queries;
+    }
+    const T* base = VL ? qkv + tok0 * ldqkv + h * HD : qkv + (int64_t)b * N * ldqkv + h * HD;
+    const T* dobase = VL ? d_o + dorow0 * ldo + h * HD : d_o + (int64_t)b * nq * ldo + h * HD;     // d_o / lse / delta: nq rows per sequence
     const int k0 = blk * 128 + wave * 32;
     const int krow = min(k0 + (lane & 31), N - 1);
     const bool active = k0 < N;                                 // wave-uniform
@@ -565,8 +592,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
         stage_tile_off<T>(sb, (const char*)base + (int64_t)qt * TROWS * ldbq, vq, wave);
         stage_tile_off<T>(sb + TB, (const char*)dobase + (int64_t)qt * TROWS * ldbo, vo, wave);
         // both per-query scalars come from the dQ kernel's workspace in the form the score chains take as C operand
-        if (wave == 0) stage_f32x64((float*)(sb + 2 * TB), ws + plane + (int64_t)bh * nq, qt * TROWS, nq, lane);
-        if (wave == 1) stage_f32x64((float*)(sb + 2 * TB) + TROWS, ws + (int64_t)bh * nq, qt * TROWS, nq, lane);
+        if (wave == 0) stage_f32x64((float*)(sb + 2 * TB), VL ? ws_row + plane : ws + plane + (int64_t)bh * nq, qt * TROWS, nq, lane);
+        if (wave == 1) stage_f32x64((float*)(sb + 2 * TB) + TROWS, VL ? ws_row : ws + (int64_t)bh * nq, qt * TROWS, nq, lane);
     };
     auto stage_last = [&](int buf) {
         uint32_t vq[LaneOff<T>::PER_WAVE], vo[LaneOff<T>::PER_WAVE];
@@ -666,21 +693,49 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
         const int qt = ntiles - 1;
         block(std::true_type{}, qt, 0);
         if (qt * TROWS + 32 < nq) block(std::true_type{}, qt, 1);      // else: the second 32 queries do not exist
-        T* out = dqkv + (int64_t)b * N * lddqkv + h * HD;
+        T* out = VL ? dqkv + tok0 * lddqkv + h * HD : dqkv + (int64_t)b * N * lddqkv + h * HD;
         // PRE: the Q rows in memory are Q * scale * log2(e): dK = dS^T Q * scale = acc * ln 2
         store_rows_direct<T>(dk, PRE ? LN2 : scale, out + D, lddqkv, k0, min(32, N - k0), lane);
         store_rows_direct<T>(dv, 1.0f, out + 2 * D, lddqkv, k0, min(32, N - k0), lane);
+        if constexpr (VL) {
+            // compact form: the Q third of this wave's rows that carry no query gradient (two lanes per row, half a head row each)
+            const int row = k0 + (lane & 31);
+            if (zero_q && row >= nq && row < N) {
+                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                u32x4* dst = (u32x4*)(out + (int64_t)row * lddqkv + (lane >> 5) * (HD / 2));
+#pragma unroll
+                for (int i = 0; i < (HD / 2) * (int)sizeof(T) / 16; ++i) dst[i] = u32x4{0u, 0u, 0u, 0u};
+            }
+        }
     }
+}
+
+template <typename T, bool PRE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? DKDV_WAVES : 1))) void attn_bwd_dkdv_kernel(const T* __restrict__ qkv, int ldqkv,
+                                                            const T* __restrict__ d_o, int ldo,
+                                                            const float* __restrict__ ws, int64_t plane,
+                                                            T* __restrict__ dqkv, int lddqkv, int H, int N, int nq, float scale, int nblk, int BH) {
+    attn_bwd_dkdv_body<T, PRE, false>(qkv, ldqkv, d_o, ldo, ws, plane, dqkv, lddqkv, H, N, nq, scale, nblk, BH, nullptr);
+}
+// the packed form (see the note in front of attn_bwd_dkdv_body): N = max N, nq == N: every query
+template <typename T, bool PRE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? DKDV_WAVES : 1))) void attn_bwd_dkdv_varlen_kernel(
+    const T* __restrict__ qkv, int ldqkv, const T* __restrict__ d_o, int ldo, const float* __restrict__ ws, int64_t plane, T* __restrict__ dqkv,
+    int lddqkv, int H, int N, int nq, float scale, int nblk, int BH, const int32_t* __restrict__ cu_tok) {
+    attn_bwd_dkdv_body<T, PRE, true>(qkv, ldqkv, d_o, ldo, ws, plane, dqkv, lddqkv, H, N, nq, scale, nblk, BH, cu_tok);
 }
 
 // ------------------------------------------------------------------------------------------------
 // backward, part 2: dQ.  Workgroup owns 128 queries (lane = query); keys stream through LDS.
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool PRE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? DQ_WAVES : 1))) void attn_bwd_dq_kernel(const T* __restrict__ qkv, int ldqkv,
-                                                          const T* __restrict__ o, const T* __restrict__ d_o, int ldo,
-                                                          const float* __restrict__ lse, float* __restrict__ delta, int64_t plane,
-                                                          T* __restrict__ dqkv, int lddqkv, int H, int N, int nq, float scale, int nblk, int BH) {
+// attn_bwd_dq_body is the kernel; attn_bwd_dq_kernel (fixed length) and attn_bwd_dq_varlen_kernel are its two entry points.  VL: as in
+// attn_bwd_dkdv_body -- base rows and N from cu_tok; nq == max N: o / d_o packed like qkv's rows, lse and the two workspace planes
+// [H][total tokens]; otherwise compact.  The blocks a short sequence does not have return before their first memory access; K / V
+// rows of the tail tile are clamped to the sequence's own last row.
+template <typename T, bool PRE, bool VL>
+__device__ __forceinline__ void attn_bwd_dq_body(const T* __restrict__ qkv, int ldqkv, const T* __restrict__ o, const T* __restrict__ d_o, int ldo,
+                                                 const float* __restrict__ lse, float* __restrict__ delta, int64_t plane, T* __restrict__ dqkv,
+                                                 int lddqkv, int H, int N, int nq, float scale, int nblk, int BH, const int32_t* __restrict__ cu_tok) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using F = typename Frag<T>::type;
     constexpr int NF = Tile<T>::NFRAG, NS = AccSteps<T>::N, TB = Tile<T>::BYTES;
@@ -690,8 +745,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
     if (!attn_block(nblk, BH, blk, bh)) return;
     const int b = bh / H, h = bh % H;
     const int D = H * HD;
-    const T* base = qkv + (int64_t)b * N * ldqkv + h * HD;
-    const T* dobase = d_o + (int64_t)b * nq * ldo + h * HD;     // d_o / lse / delta: nq rows per sequence
+    int64_t tok0 = (int64_t)b * N;                              // first token row of this sequence in qkv / dqkv
+    int64_t orow0 = (int64_t)b * nq;                            // first row of this sequence in o / d_o
+    int64_t srow0 = (int64_t)bh * nq;                           // query 0 of this (sequence, head) in lse and in a workspace plane
+    if constexpr (VL) {
+        const int t0 = cu_tok[b], t1 = cu_tok[b + 1];           // wave-uniform: scalar loads
+        const bool all_queries = nq == N;                       // N is max N here
+        N = t1 - t0;
+        tok0 = t0;
+        const int nqs = min(nq, N);
+        if (blk * 128 >= nqs) return;                           // (also N <= 0) a block this sequence does not have: whole workgroup
+        nq = nqs;
+        if (all_queries) {
+            const int total = cu_tok[BH / H];
+            orow0 = t0;
+            plane = (int64_t)H * total;
+            srow0 = (int64_t)h * total + t0;
+        }
+    }
+    const T* base = qkv + tok0 * ldqkv + h * HD;
+    const T* dobase = d_o + orow0 * ldo + h * HD;               // d_o / lse / delta: nq rows per sequence
     const int q0 = blk * 128 + wave * 32;
     const int q = q0 + (lane & 31);
     const int qrow = min(q, nq - 1);
@@ -704,7 +777,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
     {
         // delta[q] = sum_d dO[q][d] O[q][d]: this lane holds half of row q of dO as fragments already; the same
         // chunks of O are read once here, and the row sum is published for the dK/dV kernel (launched after)
-        const T* obase = o + (int64_t)b * nq * ldo + h * HD;
+        const T* obase = o + orow0 * ldo + h * HD;
 #pragma unroll
         for (int s = 0; s < NF; ++s) {
             const int off = (s * 2 + (lane >> 5)) * Tile<T>::EPC;
@@ -716,11 +789,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
         }
         dlt += other_half(dlt);
     }
-    const float lse2 = lse[(int64_t)bh * nq + qrow] * LOG2E;
+    const float lse2 = lse[srow0 + qrow] * LOG2E;
     // workspace for the dK/dV kernel, already in the form its score chains take as C operand: -delta, -lse*log2(e)
     if (lane < 32 && q < nq) {
-        delta[(int64_t)bh * nq + q] = -dlt;
-        delta[plane + (int64_t)bh * nq + q] = -lse2;
+        delta[srow0 + q] = -dlt;
+        delta[plane + srow0 + q] = -lse2;
     }
     // C operands of the two score chains: -lse stays in a block of 16 registers; -delta is splatted per chain (168
     // registers = 3 waves per SIMD do not hold both blocks, and a spill inside the tile loop makes the compiler drain
@@ -812,8 +885,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
         block(std::true_type{}, kt, 0);
         if (kt * TROWS + 32 < N) block(std::true_type{}, kt, 1);       // else: the second 32 keys do not exist
         // gradient with respect to the TRUE q in both modes (the upstream linear layer is differentiated as unscaled)
-        store_rows_direct<T>(dq, scale, dqkv + (int64_t)b * N * lddqkv + h * HD, lddqkv, q0, min(32, nq - q0), lane);
+        store_rows_direct<T>(dq, scale, dqkv + tok0 * lddqkv + h * HD, lddqkv, q0, min(32, nq - q0), lane);
     }
+}
+
+template <typename T, bool PRE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? DQ_WAVES : 1))) void attn_bwd_dq_kernel(const T* __restrict__ qkv, int ldqkv,
+                                                          const T* __restrict__ o, const T* __restrict__ d_o, int ldo,
+                                                          const float* __restrict__ lse, float* __restrict__ delta, int64_t plane,
+                                                          T* __restrict__ dqkv, int lddqkv, int H, int N, int nq, float scale, int nblk, int BH) {
+    attn_bwd_dq_body<T, PRE, false>(qkv, ldqkv, o, d_o, ldo, lse, delta, plane, dqkv, lddqkv, H, N, nq, scale, nblk, BH, nullptr);
+}
+// the packed form (see the note in front of attn_bwd_dq_body): N = max N, nq == N: every query
+template <typename T, bool PRE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? DQ_WAVES : 1))) void attn_bwd_dq_varlen_kernel(
+    const T* __restrict__ qkv, int ldqkv, const T* __restrict__ o, const T* __restrict__ d_o, int ldo, const float* __restrict__ lse,
+    float* __restrict__ delta, int64_t plane, T* __restrict__ dqkv, int lddqkv, int H, int N, int nq, float scale, int nblk, int BH,
+    const int32_t* __restrict__ cu_tok) {
+    attn_bwd_dq_body<T, PRE, true>(qkv, ldqkv, o, d_o, ldo, lse, delta, plane, dqkv, lddqkv, H, N, nq, scale, nblk, BH, cu_tok);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1297,6 +1386,24 @@ static int attention_bwd_t(const void* qkv, int ldqkv, const void* o, const void
     return check_launch();
 }
 
+// The packed form always runs the kernel pair: the single pass needs one N <= 512 for the whole launch, and the lengths of a packed
+// batch differ (the 10 s evaluation clip has N = 1190 anyway).  Work items as in attention_fwd_varlen_t: cdiv(nq, 128) query blocks and
+// cdiv(max N, 128) key blocks for every (sequence, head), the ones a short sequence does not have returning at once.
+template <typename T, bool PRE>
+static int attention_bwd_varlen_t(const void* qkv, int ldqkv, const void* o, const void* d_o, int ldo, const float* lse, float* ws, void* dqkv,
+                                  int lddqkv, const int32_t* cu_tok, int B, int H, int max_N, int nq, float scale, hipStream_t st) {
+    const int nqk = nq >= max_N ? max_N : nq;                   // == max_N: every query (the kernels' convention)
+    const int64_t plane = (int64_t)B * H * nqk;                 // compact form; the all-queries form takes H * cu_tok[B] on the device
+    const int nblkq = (int)cdiv(nqk, 128), nblkk = (int)cdiv(max_N, 128);
+    hipLaunchKernelGGL((attn_bwd_dq_varlen_kernel<T, PRE>), dim3(attn_grid(nblkq, B * H)), dim3(256), fwd_lds<T>(), st, (const T*)qkv, ldqkv,
+                       (const T*)o, (const T*)d_o, ldo, lse, ws, plane, (T*)dqkv, lddqkv, H, max_N, nqk, scale, nblkq, B * H, cu_tok);
+    int rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL((attn_bwd_dkdv_varlen_kernel<T, PRE>), dim3(attn_grid(nblkk, B * H)), dim3(256), dkdv_lds<T>(), st, (const T*)qkv, ldqkv,
+                       (const T*)d_o, ldo, ws, plane, (T*)dqkv, lddqkv, H, max_N, nqk, scale, nblkk, B * H, cu_tok);
+    return check_launch();
+}
+
 }  // namespace pa
 
 using namespace pa;
@@ -1373,4 +1480,28 @@ extern "C" int pa_attention_bwd(const void* qkv, int ldqkv, const void* o, const
         return pre ? attention_bwd_t<float, true>(qkv, ldqkv, o, d_o, ldo, lse, delta, dqkv, lddqkv, B, H, N, nq, scale, st)
                    : attention_bwd_t<float, false>(qkv, ldqkv, o, d_o, ldo, lse, delta, dqkv, lddqkv, B, H, N, nq, scale, st);
     return PA_EINVAL;
+}
+
+extern "C" int64_t pa_attention_bwd_varlen_ws_floats(int64_t total_tokens, int B, int H, int nq) {
+    if (total_tokens <= 0 || B <= 0 || H <= 0 || nq <= 0) return 0;
+    // either layout fits: [H][total tokens] per plane (every query) or [B][H][nq] (compact)
+    return 2 * (int64_t)H * std::max<int64_t>(total_tokens, (int64_t)B * std::min<int64_t>(nq, total_tokens));
+}
+
+extern "C" int pa_attention_bwd_varlen(const void* qkv, int ldqkv, const void* o, const void* d_o, int ldo, const float* lse, float* ws,
+                                       void* dqkv, int lddqkv, const int32_t* cu_tok, int B, int H, int max_N, int nq, float scale, int dtype,
+                                       int flags, void* stream) {
+    if (!qkv || !o || !d_o || !lse || !ws || !dqkv || !cu_tok || B <= 0 || H <= 0 || max_N <= 0 || nq <= 0 ||
+        (flags & ~(PA_ATTN_Q_PRESCALED | PA_ATTN_BWD_TWO_PASS | PA_ATTN_BWD_SINGLE_PASS | PA_ATTN_BWD_SINGLE_PASS_W16)))
+        return PA_EINVAL;
+    if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
+    if (!attn_args_ok(ldqkv, dtype) || !attn_args_ok(ldo, dtype) || !attn_args_ok(lddqkv, dtype)) return PA_EUNSUPPORTED;
+    if (ldqkv < 3 * H * HD || lddqkv < 3 * H * HD || ldo < H * HD) return PA_EINVAL;
+    const bool pre = flags & PA_ATTN_Q_PRESCALED;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PA_BF16)
+        return pre ? attention_bwd_varlen_t<bf16, true>(qkv, ldqkv, o, d_o, ldo, lse, ws, dqkv, lddqkv, cu_tok, B, H, max_N, nq, scale, st)
+                   : attention_bwd_varlen_t<bf16, false>(qkv, ldqkv, o, d_o, ldo, lse, ws, dqkv, lddqkv, cu_tok, B, H, max_N, nq, scale, st);
+    return pre ? attention_bwd_varlen_t<float, true>(qkv, ldqkv, o, d_o, ldo, lse, ws, dqkv, lddqkv, cu_tok, B, H, max_N, nq, scale, st)
+               : attention_bwd_varlen_t<float, false>(qkv, ldqkv, o, d_o, ldo, lse, ws, dqkv, lddqkv, cu_tok, B, H, max_N, nq, scale, st);
 }

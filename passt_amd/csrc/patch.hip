@@ -252,6 +252,134 @@ __global__ __launch_bounds__(256) void patch_fold_kernel(const T* __restrict__ d
     }
 }
 
+// ---- packed batch of clips of different lengths: backward of the patch stage ----------------------------------------------------
+// Eval mode has no Patchout, so the packed token matrix is regular per clip: clip b owns rows cu_tok[b] .. cu_tok[b + 1], its cls and
+// dist rows first, then Fg x T_eff[b] patch rows in frequency-major order with T_eff[b] = (cu_tok[b + 1] - cu_tok[b] - 2) / Fg.  The
+// row of patch (f, t) of clip b is cu_tok[b] + 2 + f * T_eff[b] + t: no grid -> slot table, no index arrays.
+__device__ __forceinline__ int clip_cols(const int32_t* __restrict__ cu_tok, int b, int Fg, int& row0) {
+    row0 = cu_tok[b];
+    return max((cu_tok[b + 1] - row0 - 2) / Fg, 0);
+}
+
+// patch_fold_kernel for the packed batch: dx[b][f][t] = sum of dcols[cu_tok[b] + 2 + gf * T_eff[b] + gt][(f - gf*fs)*P + (t - gt*ts)] over
+// the clip's patches (gf, gt) that hold (f, t), added in (gf, gt) order.  Every element of dx[B][F][Tt] is written; the columns
+// behind a clip's last patch column (its own frames' end, the time cut) have no covering patch and get 0.
+template <typename T>
+__global__ __launch_bounds__(256) void patch_fold_varlen_kernel(const T* __restrict__ dcols, const int32_t* __restrict__ cu_tok, int P, int fs,
+                                                                int ts, int Fg, int F, int Tt, int64_t n, float* __restrict__ dx) {
+    const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i0 >= n) return;
+    const int64_t row0 = i0 / Tt;
+    const int t0 = (int)(i0 - row0 * Tt);
+    const int PP = P * P;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (t0 + 4 <= Tt) {
+        const int f = (int)(row0 % F);
+        const int b = (int)(row0 / F);
+        int tok0;
+        const int Tg = clip_cols(cu_tok, b, Fg, tok0);
+        int flo, fhi, tlo, thi, unused;
+        cover_range(f, P, fs, Fg, flo, fhi);
+        cover_range(t0, P, ts, Tg, tlo, unused);
+        cover_range(t0 + 3, P, ts, Tg, unused, thi);
+        for (int gf = flo; gf <= fhi; ++gf) {
+            for (int gt = tlo; gt <= thi; ++gt) {
+                const int j0 = t0 - gt * ts;
+                const T* src = dcols + ((int64_t)tok0 + 2 + gf * Tg + gt) * PP + (f - gf * fs) * P;
+                if constexpr (sizeof(T) == 2) {
+                    if (j0 >= 0 && j0 + 4 <= P && !((j0 | P) & 1)) {
+                        const bf16x2 lo = *(const bf16x2*)(src + j0), hi = *(const bf16x2*)(src + j0 + 2);
+                        v[0] += (float)lo[0]; v[1] += (float)lo[1]; v[2] += (float)hi[0]; v[3] += (float)hi[1];
+                        continue;
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if ((unsigned)(j0 + e) < (unsigned)P) v[e] += to_f32<T>(src[j0 + e]);
+            }
+        }
+    } else {                                         // the four elements straddle a row end (T % 4 != 0) or the end of dx
+        for (int e = 0; e < 4 && i0 + e < n; ++e) {
+            const int64_t row = (i0 + e) / Tt;
+            const int t = (int)(i0 + e - row * Tt), f = (int)(row % F);
+            const int b = (int)(row / F);
+            int tok0;
+            const int Tg = clip_cols(cu_tok, b, Fg, tok0);
+            int flo, fhi, tlo, thi;
+            cover_range(f, P, fs, Fg, flo, fhi);
+            cover_range(t, P, ts, Tg, tlo, thi);
+            for (int gf = flo; gf <= fhi; ++gf)
+                for (int gt = tlo; gt <= thi; ++gt)
+                    v[e] += to_f32<T>(dcols[((int64_t)tok0 + 2 + gf * Tg + gt) * PP + (f - gf * fs) * P + (t - gt * ts)]);
+        }
+    }
+    if (i0 + 4 <= n) {
+        *(f32x4*)(dx + i0) = f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+        for (int e = 0; i0 + e < n; ++e) dx[i0 + e] = v[e];
+    }
+}
+
+// Parameter gradients of the patch stage from the packed dtok[M][D]: workgroup = one slot x 16 channels x 16 row groups, as in
+// patch_param_grads_kernel, but the rows of a slot are enumerated from cu_tok (clip after clip, a fixed order) instead of searched:
+// slot 0: conv bias = every patch row, plus the cls / dist rows; 1 .. Tpe: the Fg rows of time column t of every clip that has it;
+// Tpe + 1 .. Tpe + Fpe: the T_eff rows of frequency row f of every clip.  No atomics: every thread adds its rows in ascending
+// order and the 16 partial sums meet in LDS in a fixed order.
+__global__ __launch_bounds__(256) void patch_param_grads_varlen_kernel(const float* __restrict__ dtok, int D, const int32_t* __restrict__ cu_tok,
+                                                                       int B, int Tpe, int Fpe, float* __restrict__ d_cls, float* __restrict__ d_dist,
+                                                                       float* __restrict__ d_npe, float* __restrict__ d_bias, float* __restrict__ d_tpos,
+                                                                       float* __restrict__ d_fpos, int accumulate) {
+    __shared__ float red[16][17];
+    const int cx = threadIdx.x & 15, ry = threadIdx.x >> 4;
+    const int slot = blockIdx.y;
+    const int d = blockIdx.x * 16 + cx;
+    auto put = [&](float* p, float v) { *p = (accumulate ? *p : 0.f) + v; };
+    float s0 = 0.f, s1 = 0.f;
+    if (d < D) {
+        for (int b = 0; b < B; ++b) {
+            int tok0;
+            const int Tg = clip_cols(cu_tok, b, Fpe, tok0);
+            int count, first, step;                    // the slot's rows of this clip: tok0 + 2 + first + j * step, j < count
+            if (slot == 0) { count = Fpe * Tg; first = 0; step = 1; }
+            else if (slot <= Tpe) { count = slot - 1 < Tg ? Fpe : 0; first = slot - 1; step = Tg; }
+            else { count = Tg; first = (slot - 1 - Tpe) * Tg; step = 1; }
+            const float* src = dtok + ((int64_t)tok0 + 2 + first) * D + d;
+            int j = ry;
+            for (; j + 16 < count; j += 32) {          // two rows per step: two loads in flight
+                s0 += src[(int64_t)j * step * D];
+                s1 += src[(int64_t)(j + 16) * step * D];
+            }
+            if (j < count) s0 += src[(int64_t)j * step * D];
+        }
+    }
+    red[ry][cx] = s0 + s1;
+    __syncthreads();
+    if (ry == 0 && d < D) {
+        float s = 0.f;
+#pragma unroll
+        for (int y = 0; y < 16; ++y) s += red[y][cx];
+        if (slot == 0) {
+            float c = 0.f, t = 0.f;
+            for (int b = 0; b < B; ++b) {
+                const int tok0 = cu_tok[b];
+                if (cu_tok[b + 1] - tok0 >= 2) {
+                    c += dtok[(int64_t)tok0 * D + d];
+                    t += dtok[((int64_t)tok0 + 1) * D + d];
+                }
+            }
+            put(d_bias + d, s);
+            put(d_cls + d, c);
+            put(d_dist + d, t);
+            put(d_npe + d, c);
+            put(d_npe + D + d, t);
+        } else if (slot <= Tpe) {
+            put(d_tpos + (int64_t)d * Tpe + (slot - 1), s);
+        } else {
+            put(d_fpos + (int64_t)d * Fpe + (slot - 1 - Tpe), s);
+        }
+    }
+}
+
 }  // namespace pa
 
 using namespace pa;
@@ -357,5 +485,33 @@ extern "C" int pa_patch_input_bwd(const void* dcols, int dtype, int B, int Np, c
         hipLaunchKernelGGL(patch_fold_kernel<bf16>, grid, block, 0, st, (const bf16*)dcols, grid_ws, Np, P, fstride, tstride, Fg, Tg, F, T, n, dx);
     else
         hipLaunchKernelGGL(patch_fold_kernel<float>, grid, block, 0, st, (const float*)dcols, grid_ws, Np, P, fstride, tstride, Fg, Tg, F, T, n, dx);
+    return check_launch();
+}
+
+extern "C" int pa_patch_input_bwd_varlen(const void* dcols, int dtype, const int32_t* cu_tok, int B, int P, int fstride, int tstride, int F,
+                                         int T_max, float* dx, void* stream) {
+    if (!dcols || !cu_tok || !dx || B <= 0 || P <= 0 || fstride <= 0 || tstride <= 0 || F < P || T_max < P) return PA_EINVAL;
+    if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
+    const int Fg = (F - P) / fstride + 1;
+    const int64_t n = (int64_t)B * F * T_max;
+    if (cdiv(n, 1024) >= ((int64_t)1 << 31)) return PA_EUNSUPPORTED;
+    const dim3 grid((unsigned)cdiv(n, 1024)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PA_BF16)
+        hipLaunchKernelGGL(patch_fold_varlen_kernel<bf16>, grid, block, 0, st, (const bf16*)dcols, cu_tok, P, fstride, tstride, Fg, F, T_max, n, dx);
+    else
+        hipLaunchKernelGGL(patch_fold_varlen_kernel<float>, grid, block, 0, st, (const float*)dcols, cu_tok, P, fstride, tstride, Fg, F, T_max, n, dx);
+    return check_launch();
+}
+
+extern "C" int pa_patch_bwd_varlen(const float* dtok, int M, int D, const int32_t* cu_tok, int B, int Tpe, int Fpe, float* d_cls, float* d_dist,
+                                   float* d_npe, float* d_bias, float* d_time_pos, float* d_freq_pos, int accumulate, void* stream) {
+    // all six NULL: nothing to do (frozen network)
+    const bool none = !d_cls && !d_dist && !d_npe && !d_bias && !d_time_pos && !d_freq_pos;
+    if (!dtok || !cu_tok || M <= 0 || D <= 0 || B <= 0 || Tpe <= 0 || Fpe <= 0) return PA_EINVAL;
+    if (none) return PA_OK;
+    if (!d_cls || !d_dist || !d_npe || !d_bias || !d_time_pos || !d_freq_pos) return PA_EINVAL;
+    hipLaunchKernelGGL(patch_param_grads_varlen_kernel, dim3((unsigned)cdiv(D, 16), (unsigned)(1 + Tpe + Fpe)), dim3(256), 0, (hipStream_t)stream,
+                       dtok, D, cu_tok, B, Tpe, Fpe, d_cls, d_dist, d_npe, d_bias, d_time_pos, d_freq_pos, accumulate);
     return check_launch();
 }

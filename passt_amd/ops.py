@@ -742,6 +742,41 @@ def attention_bwd(qkv, o, d_o, lse, B, H, N, scale, nq=None, flags=0):
     return dqkv
 
 
+def attention_bwd_varlen(qkv, o, d_o, lse, cu_tok, B, H, max_N, scale, nq=None, flags=0, ws=None, out=None):
+    """dqkv [total][3D] for packed sequences (attention_fwd_varlen's layouts: nq=None -> o / d_o [total][D], lse [H][total]; nq <
+    max_N -> compact o / d_o [B*nq][D], lse [B*H*nq]).  Every row of dqkv is written: in the compact form the Q third is zero
+    outside each sequence's first nq rows.  Always the dQ + dK/dV kernel pair.  ws / out: an f32 workspace / a [total][3D] tensor of
+    qkv's dtype to use instead of fresh ones (tests put guard rows behind them)."""
+    dtype = PA_DTYPE[qkv.dtype]
+    total, D = qkv.shape[0], H * 64
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * D or cu_tok.dim() != 1 or cu_tok.numel() != B + 1 or not 1 <= max_N <= total:
+        raise _lib.PasstAmdError(f"attention_bwd_varlen: qkv {tuple(qkv.shape)}, cu_tok {tuple(cu_tok.shape)}, B={B}, H={H}, max_N={max_N}")
+    if nq is None or nq >= max_N:
+        nq, rows, nlse = max_N, total, H * total
+    else:
+        if nq < 1:
+            raise _lib.PasstAmdError("attention_bwd_varlen: nq must be >= 1")
+        rows, nlse = B * nq, B * H * nq
+    if o.shape != (rows, D) or d_o.shape != (rows, D) or lse.numel() != nlse or o.stride(0) != d_o.stride(0):
+        raise _lib.PasstAmdError(f"attention_bwd_varlen: o {tuple(o.shape)} / d_o {tuple(d_o.shape)} / lse {tuple(lse.shape)} for {rows} query rows")
+    lib = _lib.load()
+    need = lib.pa_attention_bwd_varlen_ws_floats(total, B, H, nq)
+    if ws is None:
+        ws = torch.empty(need, device=lse.device, dtype=torch.float32)
+    elif ws.numel() < need:
+        raise _lib.PasstAmdError(f"attention_bwd_varlen: workspace of {ws.numel()} floats, {need} needed")
+    dqkv = torch.empty_like(qkv) if out is None else out
+    if dqkv.shape != qkv.shape or dqkv.dtype != qkv.dtype:
+        raise _lib.PasstAmdError(f"attention_bwd_varlen: out is {tuple(dqkv.shape)} {dqkv.dtype}, expected {tuple(qkv.shape)} {qkv.dtype}")
+    # executed FLOPs depend on the lengths, which live on the device: the per-launch profile files the upper bound (see attention_fwd_varlen)
+    _timed("attn_bwd", 10.0 * nq * (max_N if rows == total else total / B) * 64 * B * H,
+           lambda: check(lib.pa_attention_bwd_varlen(_p(qkv, None, True), qkv.stride(0), _p(o, qkv.dtype, True), _p(d_o, qkv.dtype, True),
+                                                     o.stride(0), _p(lse, torch.float32), _p(ws, torch.float32), _p(dqkv, None, True), dqkv.stride(0),
+                                                     _p(cu_tok, torch.int32), B, H, max_N, nq, scale, dtype, flags, _stream()),
+                         "pa_attention_bwd_varlen"))
+    return dqkv
+
+
 def gather_rows(x, idx_i32):
     """out[i] = x[idx[i]] for a 2-D (or 1-D) contiguous tensor."""
     n = idx_i32.numel()
@@ -835,6 +870,29 @@ def patch_input_bwd(dcols, patch_f, patch_t, B, F, T, P, fstride, tstride, out=N
     check(lib.pa_patch_input_bwd(_p(dcols), PA_DTYPE[dcols.dtype], B, Np, _p(patch_f, torch.int32), _p(patch_t, torch.int32), P, fstride, tstride,
                                  F, T, _p(grid, torch.int32), _p(dx, torch.float32), _stream()), "pa_patch_input_bwd")
     return dx
+
+
+def patch_input_bwd_varlen(dcols, cu_tok, B, F, T_max, P, fstride, tstride, out=None):
+    """dx [B][1][F][T_max] f32 = fold of the packed dcols [M][P*P] (f32 or bf16; the rows under the prefix tokens are not read) over
+    every clip's own patches: the gradient w.r.t. the input of patch_gather_varlen.  Every element is written, 0 behind a clip's last
+    patch column; deterministic.  out: an existing (B, 1, F, T_max) f32 tensor to overwrite."""
+    if dcols.dim() != 2 or dcols.shape[1] != P * P or cu_tok.dim() != 1 or cu_tok.numel() != B + 1 or F < P or T_max < P:
+        raise _lib.PasstAmdError(f"patch_input_bwd_varlen: dcols {tuple(dcols.shape)}, cu_tok {tuple(cu_tok.shape)} for B={B}, P={P}, F={F}, T={T_max}")
+    dx = torch.empty((B, 1, F, T_max), device=dcols.device, dtype=torch.float32) if out is None else out
+    if dx.shape != (B, 1, F, T_max):
+        raise _lib.PasstAmdError(f"patch_input_bwd_varlen: out is {tuple(dx.shape)}, expected {(B, 1, F, T_max)}")
+    check(_lib.load().pa_patch_input_bwd_varlen(_p(dcols), PA_DTYPE[dcols.dtype], _p(cu_tok, torch.int32), B, P, fstride, tstride, F, T_max,
+                                                _p(dx, torch.float32), _stream()), "pa_patch_input_bwd_varlen")
+    return dx
+
+
+def patch_bwd_varlen(dtok, cu_tok, B, Tpe, Fpe, d_cls, d_dist, d_npe, d_bias, d_tpos, d_fpos, accumulate=False):
+    """Positional / prefix-token / conv-bias gradients from the packed dtok [M][D] f32 (overwritten or accumulated); deterministic."""
+    if dtok.dim() != 2 or cu_tok.dim() != 1 or cu_tok.numel() != B + 1:
+        raise _lib.PasstAmdError(f"patch_bwd_varlen: dtok {tuple(dtok.shape)}, cu_tok {tuple(cu_tok.shape)} for B={B}")
+    M, D = dtok.shape
+    check(_lib.load().pa_patch_bwd_varlen(_p(dtok, torch.float32), M, D, _p(cu_tok, torch.int32), B, Tpe, Fpe, _p(d_cls), _p(d_dist), _p(d_npe),
+                                          _p(d_bias), _p(d_tpos), _p(d_fpos), int(accumulate), _stream()), "pa_patch_bwd_varlen")
 
 
 # ---- head / loss -----------------------------------------------------------------------------

@@ -411,16 +411,21 @@ def varlen_geometry(lengths, P, tstride, F_dim, Tpe, T_max=None):
     return dict(row_clip=row_clip, row_f=row_f, row_t=row_t, cu_tok=cu.astype(np.int32), T_eff=T_eff, cut=cut, max_N=int(ntok.max()))
 
 
-def passt_forward_varlen(model, x, lengths):
-    """Kernel sequence of the packed eval forward: every clip gets what it would get alone at batch size 1.  Returns (logits, features)."""
+def passt_forward_varlen(model, x, lengths, save=False):
+    """Kernel sequence of the packed eval forward: every clip gets what it would get alone at batch size 1.  Returns (logits, features);
+    ``save=True``: (logits, features, ctx) with what passt_backward_varlen needs.  Without it nothing is kept and the launch sequence is
+    the same."""
     with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
-        return _passt_forward_varlen(model, x, lengths)
+        logits, feat, ctx = _passt_forward_varlen(model, x, lengths, save)
+    return (logits, feat, ctx) if save else (logits, feat)
 
 
-def _passt_forward_varlen(model, x, lengths):
+def _passt_forward_varlen(model, x, lengths, save=False):
     if not x.is_cuda:
         raise PasstAmdError("passt_amd.PaSST runs on a HIP device only (no CPU fallback); got a CPU tensor")
     dt = _precision(model)
+    if save:
+        object.__setattr__(model, "_last_dt", dt)   # the copies a bound optimizer refreshes, as in _passt_forward
     st = model._staged
     x = x.contiguous().float()
     if x.dim() != 4 or x.shape[1] != 1:
@@ -463,25 +468,33 @@ def _passt_forward_varlen(model, x, lengths):
 
     nblk = len(model.blocks)
     aflags = ops.ATTN_Q_PRESCALED
+    saved = []
     for bi, blk in enumerate(model.blocks):
         last = bi == nblk - 1
-        ln1, _, _ = ops.layernorm_fwd(xs, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt, False)
+        ln1, mean1, rstd1 = ops.layernorm_fwd(xs, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt, save)
         qkv = ops.linear(ln1, st.get(blk.attn.qkv.weight, dt, False), blk.attn.qkv.bias, dt, colscale_n=D, colscale=scale * ops.LOG2E)
         if not last:
-            att, _ = ops.attention_fwd_varlen(qkv, cu_tok, B, H, max_N, scale, flags=aflags)
+            att, lse = ops.attention_fwd_varlen(qkv, cu_tok, B, H, max_N, scale, flags=aflags)
             x_res = xs
         else:                                          # prefix-only tail, as in _passt_forward
-            att, _ = ops.attention_fwd_varlen(qkv, cu_tok, B, H, max_N, scale, nq=2, flags=aflags)
+            att, lse = ops.attention_fwd_varlen(qkv, cu_tok, B, H, max_N, scale, nq=2, flags=aflags)
             x_res = ops.gather_rows(xs, pidx)
         x_mid = ops.linear_resid(att, st.get(blk.attn.proj.weight, dt, False), blk.attn.proj.bias, x_res, dt)
-        ln2, _, _ = ops.layernorm_fwd(x_mid, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, False)
-        _, h_act = ops.linear_gelu(ln2, st.get(blk.mlp.fc1.weight, dt, False), blk.mlp.fc1.bias, dt)
-        xs = ops.linear_resid(h_act, st.get(blk.mlp.fc2.weight, dt, False), blk.mlp.fc2.bias, x_mid, dt)
+        ln2, mean2, rstd2 = ops.layernorm_fwd(x_mid, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, save)
+        h_pre, h_act = ops.linear_gelu(ln2, st.get(blk.mlp.fc1.weight, dt, False), blk.mlp.fc1.bias, dt)
+        x_out = ops.linear_resid(h_act, st.get(blk.mlp.fc2.weight, dt, False), blk.mlp.fc2.bias, x_mid, dt)
+        if save:
+            saved.append((xs, ln1, mean1, rstd1, qkv, att, lse, x_mid, ln2, mean2, rstd2, h_pre, h_act))
+        xs = x_out
     xl = xs.view(B, 2, D)
-    feat, hn, _ = ops.head_pre_fwd(xl, model.norm.weight, model.norm.bias, model.norm.eps, model.head[0].weight,
-                                   model.head[0].bias, model.head[0].eps)
+    feat, hn, stats = ops.head_pre_fwd(xl, model.norm.weight, model.norm.bias, model.norm.eps, model.head[0].weight,
+                                       model.head[0].bias, model.head[0].eps)
     logits = ops.linear_f32_fwd(hn, model.head[1].weight, model.head[1].bias)
-    return logits, feat
+    ctx = None
+    if save:
+        ctx = dict(dt=dt, B=B, M=M, max_N=max_N, cu_tok=cu_tok, pidx=pidx, F=F, T=T, cols=cols, saved=saved, xl=xl, feat=feat, hn=hn,
+                   stats=stats, scale=scale)
+    return logits, feat, ctx
 
 
 def _wgrad_pair(dY, X, dW, db, dt, scratch, accumulate):
@@ -681,6 +694,124 @@ def _passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done=None, want_
     return dx_in
 
 
+def passt_backward_varlen(model, ctx, dlogits, dfeat, grads, on_block_done=None, want_dx=False):
+    """Backward of passt_forward_varlen(save=True): passt_backward's contract (``grads`` dict to OVERWRITE or None = the
+    no-weight-gradients mode of a frozen network, ``on_block_done``, ``want_dx`` -> (B, 1, F, T_max) f32 or None) on the packed rows.
+    Everything runs on M = sum of the clips' tokens: the same LayerNorm / GEMM / finishing launches as the fixed path, the packed
+    attention backward (pa_attention_bwd_varlen: always the kernel pair) and the packed patch stage (pa_patch_bwd_varlen,
+    pa_patch_input_bwd_varlen).  A parameter gradient is the sum over the clips of their batch-1 gradients; dx of clip i is what the
+    clip alone gives in its own frames and exactly 0 behind them."""
+    with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
+        return _passt_backward_varlen(model, ctx, dlogits, dfeat, grads, on_block_done, want_dx)
+
+
+def _passt_backward_varlen(model, ctx, dlogits, dfeat, grads, on_block_done=None, want_dx=False):
+    dt, B, M, max_N, cu_tok, pidx = ctx["dt"], ctx["B"], ctx["M"], ctx["max_N"], ctx["cu_tok"], ctx["pidx"]
+    st = model._staged
+    H = model.num_heads
+    scratch = model._scratch
+    frozen = grads is None
+    g = _NoGrads() if frozen else grads
+    if frozen:
+        on_block_done = None
+    side = scratch.get("side")
+    if side is not None and side.enabled != bool(getattr(model, "overlap_wgrad", False)):
+        side = None
+    if side is None:
+        side = scratch["side"] = _SideStream(dlogits.device, enabled=getattr(model, "overlap_wgrad", False))
+
+    def wgrad_async(dY, X, dW, db, done=None):
+        if frozen:
+            return
+        with side.fork(dY, X):
+            _wgrad_pair(dY, X, dW, db, dt, scratch, False)
+            if done is not None and on_block_done:
+                on_block_done(done)
+
+    # as in _passt_backward: bf16 on one stream batches a block's weight gradients and its small finishing reductions
+    pending = [] if (dt == PA_BF16 and not side.enabled and not frozen) else None
+    rowjobs = _NoRowJobs() if frozen else ([] if pending is not None else None)
+
+    def wgrad(dY, X, dW, db, done=None, fuse=False):
+        if frozen:
+            return
+        if pending is None:
+            return wgrad_async(dY, X, dW, db, done)
+        fused_bias = (done is not None or fuse) and db is not None
+        pending.append((dY, X, dW.view(dY.shape[1], -1), False, db if fused_bias else None))
+        if db is not None and not fused_bias:
+            ops.colsum(dY, db)
+        if done is not None:
+            scratch["part"] = ops.wgrad_tn_batched(pending, dt, scratch.get("part"), row_jobs=rowjobs)
+            pending.clear()
+            rowjobs.clear()
+            if on_block_done:
+                on_block_done(done)
+
+    dhn = ops.linear_f32_bwd(dlogits.contiguous(), ctx["hn"], model.head[1].weight, g["head.1.weight"], g["head.1.bias"])
+    dxl, part = ops.head_pre_bwd(dhn, dfeat, ctx["xl"], ctx["feat"], model.norm.weight, model.head[0].weight, ctx["stats"])
+    D = dxl.shape[-1]
+    part4 = part.view(B, 4, D)
+    for j, name in enumerate(("head.0.weight", "head.0.bias", "norm.weight", "norm.bias")):
+        if not frozen:
+            ops.colsum_f32(part4[:, j, :], g[name])
+    nblk = len(model.blocks)
+    if on_block_done:
+        on_block_done(nblk)
+    dx = dxl.view(2 * B, D)                 # gradient w.r.t. the compact (prefix-rows) output of the last block
+    dx_lp = ops.convert(dx, dt)
+    for i in range(nblk - 1, -1, -1):
+        blk = model.blocks[i]
+        last = i == nblk - 1
+        pfx = f"blocks.{i}."
+        xs, ln1, mean1, rstd1, qkv, att, lse, x_mid, ln2, mean2, rstd2, h_pre, h_act = ctx["saved"][i]
+        wgrad(dx_lp, h_act, g[pfx + "mlp.fc2.weight"], g[pfx + "mlp.fc2.bias"] if last else None)
+        if frozen:
+            d_pre = ops.dgelu_gemm(dx_lp, st.get(blk.mlp.fc2.weight, dt, True), h_pre, dt)
+        else:
+            cws = scratch["colsum_ws"] = ops.gemm_colsum_ws(h_pre.shape[0], h_pre.shape[1], dx_lp.device, scratch.get("colsum_ws"))
+            d_pre = ops.dgelu_gemm(dx_lp, st.get(blk.mlp.fc2.weight, dt, True), h_pre, dt, colsum_out=g[pfx + "mlp.fc1.bias"], colsum_ws=cws,
+                                   defer=rowjobs)
+            wgrad(d_pre, ln2, g[pfx + "mlp.fc1.weight"], None)
+        d_ln2 = torch.empty_like(ln2)
+        ops.gemm_nt(d_pre, st.get(blk.mlp.fc1.weight, dt, True), dt, EPI_STORE, out_lp=d_ln2)
+        del d_pre
+        dx, dx_lp = ops.layernorm_bwd(d_ln2, x_mid, blk.norm2.weight, mean2, rstd2, dx, g[pfx + "norm2.weight"], g[pfx + "norm2.bias"], True,
+                                      dcolsum=g[pfx + "attn.proj.bias"], defer=rowjobs)
+        wgrad(dx_lp, att, g[pfx + "attn.proj.weight"], None)
+        d_att = torch.empty_like(att)
+        ops.gemm_nt(dx_lp, st.get(blk.attn.proj.weight, dt, True), dt, EPI_STORE, out_lp=d_att)
+        if not last:
+            d_qkv = ops.attention_bwd_varlen(qkv, att, d_att, lse, cu_tok, B, H, max_N, ctx["scale"], flags=ops.ATTN_Q_PRESCALED)
+            dres = dx
+        else:
+            # only 2 queries per clip carry a gradient (the kernel pair writes the rest of the Q third as zero); the residual
+            # gradient lives on the prefix rows only
+            d_qkv = ops.attention_bwd_varlen(qkv, att, d_att, lse, cu_tok, B, H, max_N, ctx["scale"], nq=2, flags=ops.ATTN_Q_PRESCALED)
+            dres = ops.scatter_rows_into_zeros(dx, pidx, M)
+        d_ln1 = torch.empty_like(ln1)
+        ops.gemm_nt(d_qkv, st.get(blk.attn.qkv.weight, dt, True), dt, EPI_STORE, out_lp=d_ln1)
+        # (block 0 also wants the 16-bit copy: it feeds the patch stage's two GEMMs)
+        dx, dx_lp = ops.layernorm_bwd(d_ln1, xs, blk.norm1.weight, mean1, rstd1, dres, g[pfx + "norm1.weight"], g[pfx + "norm1.bias"], True,
+                                      dcolsum=g[f"blocks.{i - 1}.mlp.fc2.bias"] if i > 0 else None, defer=rowjobs)
+        wgrad(d_qkv, ln1, g[pfx + "attn.qkv.weight"], g[pfx + "attn.qkv.bias"], done=i)
+    # ---- patch embedding / positional parameters / prefix tokens: dx is the packed dtok [M][D].  The packed im2col has a zero row under
+    # every prefix token, so both GEMMs run over all M rows: no compaction pass
+    Tpe, Fpe = model.time_new_pos_embed.shape[-1], model.freq_new_pos_embed.shape[-2]
+    if not frozen:
+        ops.patch_bwd_varlen(dx, cu_tok, B, Tpe, Fpe, g["cls_token"], g["dist_token"], g["new_pos_embed"], g["patch_embed.proj.bias"],
+                             g["time_new_pos_embed"], g["freq_new_pos_embed"])
+    wgrad_async(dx_lp, ctx["cols"], g["patch_embed.proj.weight"], None, done=-1)
+    dx_in = None
+    if want_dx:
+        P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
+        dcols = torch.empty((M, P * P), device=dx_lp.device, dtype=dx_lp.dtype)
+        ops.gemm_nt(dx_lp, st.get(model.patch_embed.proj.weight, dt, True), dt, EPI_STORE, out_lp=dcols)
+        dx_in = ops.patch_input_bwd_varlen(dcols, cu_tok, B, ctx["F"], ctx["T"], P, fs, ts)
+    side.join()
+    return dx_in
+
+
 class _PasstFunction(torch.autograd.Function):
     """One autograd node for the whole network: forward/backward are kernel sequences, torch only
     sees (x, *parameters) -> (logits, features)."""
@@ -702,66 +833,93 @@ class _PasstFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits, dfeat):
-        model, c = ctx.model, ctx.c
-        if c is None:
-            raise RuntimeError("passt_amd.PaSST: the saved activations of this forward were already consumed by a backward "
-                               "pass (retain_graph / double backward are not supported: run the forward again)")
-        # gradient buffers for EVERY parameter the backward writes (all but head_dist.*): the kernel sequence produces
-        # them all; parameters with requires_grad=False are simply not handed back to autograd (frozen backbone, ...)
-        named, total = ctx.named, ctx.total
-        fl = ctx.flat
-        if dlogits is not None:
-            dlogits = dlogits.contiguous()
-        if ctx.frozen:
-            # nothing but the input asked for a gradient: no flat buffer, no weight-gradient launch, no reducer (dx is a local quantity)
-            if dlogits is None:
-                dlogits = torch.zeros((c["B"], model.num_classes), device=dfeat.device, dtype=torch.float32)
-            dx = passt_backward(model, c, dlogits, None if dfeat is None else dfeat.contiguous(), None, want_dx=ctx.want_dx)
-            ctx.c = None
-            return (None, dx) + (None,) * (len(named) if fl is None else 1)
-        if fl is not None and fl["fresh"]:
-            flat, grads = fl["flat_g"], fl["grads"]     # overwritten in place: the caller zeroed (optimizer.zero_grad()) since the last backward
-        else:
-            flat = torch.empty(total, device=(dfeat if dlogits is None else dlogits).device, dtype=torch.float32)
-            # one C++ call makes the 159 views (a Python loop of slice + view costs 1.3 ms of host time in front of the first
-            # backward kernel: exposed whenever the caller synchronised in this step, and the reference's mixup does)
-            views = torch._C._nn.unflatten_dense_tensors(flat, [p for _, p in named])
-            grads = {n: v for (n, _), v in zip(named, views)}
-        # a fresh flat buffer per backward: autograd may keep (not copy) the views as .grad
-        if dlogits is None:                     # only `features` fed the loss
-            dlogits = torch.zeros((c["B"], model.num_classes), device=flat.device, dtype=torch.float32)
+        return _node_backward(ctx, dlogits, dfeat, passt_backward, (None,))
+
+
+class _PasstVarlenFunction(torch.autograd.Function):
+    """_PasstFunction's sibling for the packed ragged-batch forward (``net.varlen_grad = True``): (x, lengths, *parameters) -> (logits,
+    features).  Same ``grads`` / ``on_block_done`` contract, same flat-buffer and reducer routes: the backward is _node_backward over
+    passt_backward_varlen."""
+
+    @staticmethod
+    def forward(ctx, model, lengths, x, *params):
+        logits, feat, c = passt_forward_varlen(model, x, lengths, save=True)
+        ctx.model, ctx.c = model, c
+        ctx.want_dx = bool(ctx.needs_input_grad[2])
+        ctx.frozen = not any(ctx.needs_input_grad[3:])
+        ctx.named, ctx.total = model._graph_params(validate=False)
+        ctx.flat = model._flat if (len(params) == 1 and model._flat is not None and params[0] is model._flat["token"]) else None
+        ctx.set_materialize_grads(False)
+        return logits, feat
+
+    @staticmethod
+    def backward(ctx, dlogits, dfeat):
+        return _node_backward(ctx, dlogits, dfeat, passt_backward_varlen, (None, None))
+
+
+def _node_backward(ctx, dlogits, dfeat, run_backward, lead):
+    """The backward of both autograd nodes.  ``run_backward``: passt_backward / passt_backward_varlen; ``lead``: the Nones handed back for
+    the node's inputs in front of x (the model; the lengths)."""
+    model, c = ctx.model, ctx.c
+    if c is None:
+        raise RuntimeError("passt_amd.PaSST: the saved activations of this forward were already consumed by a backward "
+                           "pass (retain_graph / double backward are not supported: run the forward again)")
+    # gradient buffers for EVERY parameter the backward writes (all but head_dist.*): the kernel sequence produces
+    # them all; parameters with requires_grad=False are simply not handed back to autograd (frozen backbone, ...)
+    named, total = ctx.named, ctx.total
+    fl = ctx.flat
+    if dlogits is not None:
         dlogits = dlogits.contiguous()
-        dfeat = None if dfeat is None else dfeat.contiguous()
-        red = getattr(model, "_ddp", None)
-        if red is not None and red.world > 1:
-            # passt_amd.ddp.attach(net): this node reduces its own gradients.  `flat` is laid out like the reducer's buckets
-            # (named_parameters() order without head_dist.*); every bucket's all-reduce starts from on_block_done while the
-            # rest of the backward runs, and the node returns once the current stream is ordered behind the last bucket.
-            # Mean over ranks (DDP's semantics) = sum of gradients of loss / world: the backward is linear in (dlogits, dfeat).
-            if flat.numel() != red.total:
-                raise RuntimeError("passt_amd.ddp.attach: the parameter set changed since attach(); call attach(net) again")
-            inv = 1.0 / red.world
-            dlogits = dlogits * inv
-            dfeat = None if dfeat is None else dfeat * inv
-            red.flat = flat
-            try:
-                dx = passt_backward(model, c, dlogits, dfeat, grads, on_block_done=red.on_block_done, want_dx=ctx.want_dx)
-            finally:
-                red.wait()              # also after an exception: no collective may stay in flight on a buffer we drop
-            if dx is not None:
-                dx.mul_(float(red.world))       # not reduced: the gradient of THIS rank's loss (dlogits went in divided by world)
-        else:
-            dx = passt_backward(model, c, dlogits, dfeat, grads, want_dx=ctx.want_dx)
+    if ctx.frozen:
+        # nothing but the input asked for a gradient: no flat buffer, no weight-gradient launch, no reducer (dx is a local quantity)
+        if dlogits is None:
+            dlogits = torch.zeros((c["B"], model.num_classes), device=dfeat.device, dtype=torch.float32)
+        dx = run_backward(model, c, dlogits, None if dfeat is None else dfeat.contiguous(), None, want_dx=ctx.want_dx)
         ctx.c = None
-        if fl is not None:
-            if not fl["fresh"]:                 # a second backward without zero_grad (gradient accumulation): add, as AccumulateGrad would
-                fl["flat_g"].add_(flat)
-            fl["fresh"] = False
-            return None, dx, None
-        out = [None, dx]
-        for n, p in named:                      # the same list, in the same order, as PaSST.forward handed to apply()
-            out.append(grads[n] if p.requires_grad else None)
-        return tuple(out)
+        return lead + (dx,) + (None,) * (len(named) if fl is None else 1)
+    if fl is not None and fl["fresh"]:
+        flat, grads = fl["flat_g"], fl["grads"]     # overwritten in place: the caller zeroed (optimizer.zero_grad()) since the last backward
+    else:
+        flat = torch.empty(total, device=(dfeat if dlogits is None else dlogits).device, dtype=torch.float32)
+        # one C++ call makes the 159 views (a Python loop of slice + view costs 1.3 ms of host time in front of the first
+        # backward kernel: exposed whenever the caller synchronised in this step, and the reference's mixup does)
+        views = torch._C._nn.unflatten_dense_tensors(flat, [p for _, p in named])
+        grads = {n: v for (n, _), v in zip(named, views)}
+    # a fresh flat buffer per backward: autograd may keep (not copy) the views as .grad
+    if dlogits is None:                     # only `features` fed the loss
+        dlogits = torch.zeros((c["B"], model.num_classes), device=flat.device, dtype=torch.float32)
+    dlogits = dlogits.contiguous()
+    dfeat = None if dfeat is None else dfeat.contiguous()
+    red = getattr(model, "_ddp", None)
+    if red is not None and red.world > 1:
+        # passt_amd.ddp.attach(net): this node reduces its own gradients.  `flat` is laid out like the reducer's buckets
+        # (named_parameters() order without head_dist.*); every bucket's all-reduce starts from on_block_done while the
+        # rest of the backward runs, and the node returns once the current stream is ordered behind the last bucket.
+        # Mean over ranks (DDP's semantics) = sum of gradients of loss / world: the backward is linear in (dlogits, dfeat).
+        if flat.numel() != red.total:
+            raise RuntimeError("passt_amd.ddp.attach: the parameter set changed since attach(); call attach(net) again")
+        inv = 1.0 / red.world
+        dlogits = dlogits * inv
+        dfeat = None if dfeat is None else dfeat * inv
+        red.flat = flat
+        try:
+            dx = run_backward(model, c, dlogits, dfeat, grads, on_block_done=red.on_block_done, want_dx=ctx.want_dx)
+        finally:
+            red.wait()              # also after an exception: no collective may stay in flight on a buffer we drop
+        if dx is not None:
+            dx.mul_(float(red.world))       # not reduced: the gradient of THIS rank's loss (dlogits went in divided by world)
+    else:
+        dx = run_backward(model, c, dlogits, dfeat, grads, want_dx=ctx.want_dx)
+    ctx.c = None
+    if fl is not None:
+        if not fl["fresh"]:                 # a second backward without zero_grad (gradient accumulation): add, as AccumulateGrad would
+            fl["flat_g"].add_(flat)
+        fl["fresh"] = False
+        return lead + (dx, None)
+    out = list(lead) + [dx]
+    for n, p in named:                      # the same list, in the same order, as PaSST.forward handed to apply()
+        out.append(grads[n] if p.requires_grad else None)
+    return tuple(out)
 
 
 def _tree_signature(root):
@@ -825,6 +983,10 @@ class PaSST(nn.Module):
         # call raises NotImplementedError, as it always did).  A fully frozen network needs no switch: there the input is the only
         # thing that can ask for a gradient
         self.input_grad = False
+        # opt-in: forward(x, lengths=...) in eval mode becomes an autograd node (packed backward) -- x.grad for an input that requires
+        # one, gradients for the parameters that require one, together if both do (input_grad is not looked at on that path).  Off:
+        # the ragged forward records nothing, as it always did
+        self.varlen_grad = False
         self.init_weights(weight_init)
         self._reset_runtime()
 
@@ -980,9 +1142,16 @@ class PaSST(nn.Module):
         in ``x`` (B, 1, n_mels, T_max); clip i is valid in its first lengths[i] frames and whatever lies behind them has no influence
         (it is never read).  Row i of both outputs is what ``forward(x[i:i+1, :, :, :lengths[i]])`` returns at batch size 1 -- the
         reference's own way of evaluating clips of different lengths (ex_fsd50k.py:53-56) -- but the batch runs as ONE packed kernel
-        sequence over sum_i tokens.  Eval mode only, no gradients (outputs carry no grad_fn, also for an ``x`` that requires one).  The token geometry is decided on the
-        host: ``lengths`` given as a device tensor costs one host read.  A clip shorter than one patch raises ValueError; clips whose
-        patch columns reach the time embedding's length are cut to it, with one warning per call.
+        sequence over sum_i tokens.  Eval mode only.  The token geometry is decided on the host: ``lengths`` given as a device tensor
+        costs one host read.  A clip shorter than one patch raises ValueError; clips whose patch columns reach the time embedding's
+        length are cut to it, with one warning per call.
+        Gradients through the ragged forward are opt-in: by default the outputs carry no grad_fn, also for an ``x`` that requires a
+        gradient.  With ``net.varlen_grad = True`` (eval mode, grad enabled) the packed forward is an autograd node with a packed
+        backward: an ``x`` that requires a gradient gets ``x.grad`` in its own shape / dtype / layout, every element written and
+        exactly 0 at frames >= lengths[i] and behind the time cut; every parameter that requires a gradient gets one; a fully frozen
+        network runs no weight-gradient kernel.  For a loss that is a sum over clips, ``x.grad[i, ..., :lengths[i]]`` is what clip i
+        alone gives at batch size 1, and a parameter gradient is the sum over clips of those batch-1 gradients.  ``input_grad`` is not
+        consulted here.  Training mode with ``lengths`` raises NotImplementedError (no Patchout on ragged batches).
 
         ``torch.compile(net)`` (ex_audioset.py:135, model_speed_test :391): the whole forward is ONE opaque call to the
         compiler (``_lib.compile_opaque``: torch.compiler.disable's mechanism without the torch._dynamo import, installed at class
@@ -996,6 +1165,18 @@ class PaSST(nn.Module):
             if self.training:
                 raise NotImplementedError("PaSST.forward(x, lengths=...): training on ragged batches is not supported (eval mode only; "
                                           "no reference flow trains on clips of different lengths)")
+            if getattr(self, "varlen_grad", False) and torch.is_grad_enabled():
+                want_dx = torch.is_tensor(x) and x.requires_grad
+                named = self._graph_params()[0]
+                if want_dx or any(p.requires_grad for _, p in named):
+                    if want_dx:
+                        x = x.contiguous().float()      # where autograd sees it: x.grad comes back in the caller's shape, dtype and layout
+                    fl = self._flat
+                    if fl is not None:
+                        if fl["named"] is named:
+                            return _PasstVarlenFunction.apply(self, lengths, x, fl["token"])
+                        self.unbind_flat_grads()
+                    return _PasstVarlenFunction.apply(self, lengths, x, *[p for _, p in named])
             with torch.no_grad():
                 return passt_forward_varlen(self, x, lengths)
         want_dx = torch.is_grad_enabled() and torch.is_tensor(x) and x.requires_grad
@@ -1114,7 +1295,8 @@ class EnsembelerModel(nn.Module):
         self.models = nn.ModuleList(models)
 
     def forward(self, x, lengths=None):
-        """``lengths``: handed to every member (PaSST.forward's ragged-batch eval forward)."""
+        """``lengths``: handed to every member (PaSST.forward's ragged-batch eval forward; gradients flow through the members that
+        set ``varlen_grad``)."""
         all_out = None
         for m in self.models:
             out, _ = m(x) if lengths is None else m(x, lengths=lengths)
