@@ -88,6 +88,35 @@ int pa_mel_frontend_fwd(const float* wave, int B, int L, const float* window, co
  * kernel form only (PA_MEL_PERSIST is ignored).  wave, lens, the three tables and out are device memory. */
 int pa_mel_frontend_fwd_varlen(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
                                const float* twiddle, float* out, int T_max, float fill, const pa_mel_params* p, void* stream);
+/* Gradient of pa_mel_frontend_fwd w.r.t. the waveform: dout[B][n_mels][n_frames] f32 -> dwave[B][L] f32, every element written.
+ * The forward saves nothing; the spectrum and the band sums are recomputed from `wave` (same tables, same p -- including the mask
+ * ranges of the forward call whose gradient is wanted).  One clip, f32, in the forward's order:
+ *   forward   y[n] = x[n+1] - preemph x[n] (n < L-1);  yp = y reflect-padded by n_fft/2;  f_t[i] = yp[t hop + i] w[i];
+ *             X_t[k] = sum_i f_t[i] exp(-2 pi i k i / n_fft), k = 0..n_fft/2;  P = |X|^2;  mel[b] = sum_k basis[b][k] P[k]
+ *             (column n_fft/2 of the basis is zero);  out = (log(mel + log_eps) + out_add) out_scale, the constant out_add out_scale
+ *             in masked rows / columns
+ *   backward  1. dmel[b][t] = dout[b][t] out_scale / (mel[b][t] + log_eps); 0 at masked positions (dout is not read into the result
+ *                there) and, in the varlen form, at every frame at or behind the clip's own frame count
+ *             2. dP[k] = u_k dmel[j_k] + (1 - u_k) dmel[j_k - 1]   (j_k, u_k: triangle index and up-slope weight of bin k; bands
+ *                outside [0, n_mels) count as 0): the transpose of the forward's band sums, a two-term gather
+ *             3. G[k] = 2 dP[k] X[k] (k < n_fft/2), G[n_fft/2] = 0
+ *             4. df_t[i] = Re sum_{k=0}^{n_fft/2-1} G[k] exp(+2 pi i k i / n_fft): the one-sided sum, no 1/N, no Hermitian doubling
+ *                (the adjoint of the forward's sum, not irfft)
+ *             5. dyp[t hop + i] += df_t[i] w[i], summed per sample over the frames in ascending t
+ *             6. dy[m] = dyp[m + n_fft/2] + dyp[n_fft/2 - m] (1 <= m <= n_fft/2) + dyp[n_fft/2 + 2 (L-2) - m] (L-2-n_fft/2 <= m <= L-3)
+ *             7. dwave[n] = dy[n-1] - preemph dy[n],  dy[-1] = dy[L-1] = 0
+ * No floating-point atomics: the result is bit-repeatable and does not depend on the launch geometry.  The overlap-add happens inside
+ * the workgroups, so no workspace is needed: `workspace` / `workspace_bytes` are reserved (pass NULL / 0) and ignored.
+ * Same argument checks and error codes as pa_mel_frontend_fwd. */
+int pa_mel_frontend_bwd(const float* wave, int B, int L, const float* window, const float* bin_mel, const float* twiddle,
+                        const float* dout, float* dwave, void* workspace, int64_t workspace_bytes, const pa_mel_params* p, void* stream);
+/* Gradient of pa_mel_frontend_fwd_varlen: wave[B][ldw], lens[B] (device), dout[B][n_mels][T_max] -> dwave[B][ldw].  Row b equals, in its
+ * first lens[b] samples, what pa_mel_frontend_bwd returns for that clip alone (steps 6 and 7 at the clip's own end; frames at or behind
+ * the clip's frame count and samples at or behind lens[b] are never read) and is exactly 0 at and behind lens[b] (a row with lens[b] - 1
+ * <= n_fft/2: 0 throughout).  Equal lengths = ldw give pa_mel_frontend_bwd's result bit for bit. */
+int pa_mel_frontend_bwd_varlen(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
+                               const float* twiddle, const float* dout, int T_max, float* dwave, void* workspace, int64_t workspace_bytes,
+                               const pa_mel_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Parameter staging (no reference counterpart: AMP autocast casts weights per op)

@@ -480,6 +480,322 @@ __global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
     }
 }
 
+// ---- gradient w.r.t. the waveform (pa_mel_frontend_bwd / _bwd_varlen; formulas: include/passt_amd.h) ----------
+// Nothing was saved by the forward: a frame's spectrum X and its band sums are recomputed from the wave (the forward's own
+// transform and band stage, one wave per frame), then
+//   dmel = g out_scale / (mel + eps)   (0 where masked)            dP[k] = u_k dmel[j_k] + (1 - u_k) dmel[j_k - 1]
+//   G[k] = 2 dP[k] X[k]                                            df[i] = Re sum_{k < 512} G[k] exp(+2 pi i k i / 1024)
+// The one-sided sum is ONE more 512-point transform: with c[n] = df[2n] + i df[2n+1] the spectrum of c is
+//   H[k] = (G[k] + conj G[512-k]) / 2 + i conj(W^k) (G[k] - conj G[512-k]) / 2  (k > 0),   H[0] = Re G[0] (1 + i)
+// and c = conj(DFT512(conj H)) -- the forward's radix-8 / two-exchange transform between two conjugations (tools/emulate_mel_bwd.py).
+//
+// Overlap-add, reflect adjoint and pre-emphasis adjoint without atomics: a workgroup OWNS `rows` consecutive samples of one clip.
+// It works out the range [qlo, qhi) of the padded signal those samples depend on (their own positions + 512, and for the first /
+// last 512 samples the mirrored positions in the padding), transforms every frame that reaches into that range -- four at a time, one
+// per wave, each leaving its 1024 windowed taps in its LDS scratch -- and between two barriers every thread adds the (up to four)
+// frames to the positions it owns, in frame order.  A position's sum is therefore ((0 + f_t) + f_t+1) + ... over ALL frames covering
+// it in ascending t, whatever `rows` is: the result does not depend on the launch geometry and repeats bit for bit.  The frames in
+// front of the owned run are transformed again by the neighbouring workgroup (hop 320, 5120 samples per workgroup: 20 frames for 16).
+template <bool VL>
+__global__ __launch_bounds__(MEL_WAVES * 64) void mel_frontend_bwd_kernel(const float* __restrict__ wave, const int Lp, const float* __restrict__ window,
+                                                                         const float* __restrict__ bin_mel, const float2* __restrict__ twiddle,
+                                                                         const float* __restrict__ dout, float* __restrict__ dwave,
+                                                                         const pa_mel_params p, const int rows, const int32_t* __restrict__ lens) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* sScr = smem;                                                 // [MEL_WAVES][WAVE_SCRATCH]
+    float* sAcc = (float*)(smem + MEL_WAVES * WAVE_SCRATCH);           // [rows + 2052] overlap-added gradient of the padded signal, from qlo
+    float* sU = sAcc;                                                  // the two per-bin tables live here until the lanes hold their constants
+    int* sJ = (int*)(sU + NC);
+    constexpr int NT = MEL_WAVES * 64;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = (int)blockIdx.y, n0 = (int)blockIdx.x * rows;
+    const int Tp = p.n_frames;
+    const int L = VL ? min(lens[b], Lp) : Lp;
+    const int T = VL ? min(Tp, 1 + (L - 1) / p.hop) : Tp;
+    const int Ly = L - 1;
+    const float* x = wave + (int64_t)b * Lp;
+    float* dx = dwave + (int64_t)b * Lp;
+    const int nend = min(n0 + rows, Lp);
+    if (n0 >= L || Ly <= NFFT / 2) {                                   // behind the clip's end (or a clip too short to reflect): exact zeros
+        for (int n = n0 + tid; n < nend; n += NT) dx[n] = 0.f;
+        return;
+    }
+    // dy[m] is needed for m in [m0, m1); dy[m] = D[m + 512] + D[512 - m] (1 <= m <= 512) + D[512 + 2 (Ly - 1) - m] (Ly - 513 <= m <= Ly - 2)
+    const int n1 = min(nend, L);
+    const int m0 = max(n0 - 1, 0), m1 = min(n1, Ly);
+    int qlo = m0 + NFFT / 2, qhi = m1 + NFFT / 2;
+    if (m0 <= NFFT / 2) qlo = min(qlo, max(0, NFFT / 2 - min(m1 - 1, NFFT / 2)));
+    {
+        const int mr = max(m0, Ly - 1 - NFFT / 2);
+        if (m1 - 1 >= Ly - 1 - NFFT / 2 && mr <= Ly - 2) qhi = max(qhi, NFFT / 2 + 2 * (Ly - 1) - mr + 1);
+    }
+    qhi = min(qhi, Ly + NFFT);
+    const int len = qhi - qlo;                                         // <= rows + 1 + 2048
+    const int tlo = qlo < NFFT ? 0 : (qlo - NFFT) / p.hop + 1;         // first frame with t hop + 1024 > qlo
+    const int thi = min(T - 1, (qhi - 1) / p.hop);                     // last frame with t hop < qhi
+
+    cf tw1[8], tw2[8], tw3[8];
+    float win[16];
+    {
+        const int m = lane, c = lane >> 3;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            tw1[q] = tw1024(twiddle, 2 * m * q);
+            tw2[q] = tw1024(twiddle, 16 * c * q);
+            tw3[q] = tw1024(twiddle, lane + 64 * q);
+            win[2 * q] = window[2 * (64 * q + m)];
+            win[2 * q + 1] = window[2 * (64 * q + m) + 1];
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {                                      // filterbank geometry: the forward's expressions
+        const float t = (bin_mel[tid + h * NT] - p.mel_low) * p.inv_mel_delta;
+        const float fl = floorf(t);
+        sJ[tid + h * NT] = (int)fmaxf(fminf(fl, 100000.f), -1.f);
+        sU[tid + h * NT] = t - fl;
+    }
+    __syncthreads();
+    cf* scr = (cf*)(sScr + wv * WAVE_SCRATCH);
+    float* pex = (float*)scr;                                // [512] power spectrum                       bytes [0, 2048)
+    cf* slot = (cf*)((char*)scr + NC * 4);                   // [n_mels + 1] {U_j, D_j}, pad, 64 dummies   bytes [2048, 3600)
+    float* dmp = (float*)((char*)scr + NC * 4 + (SLOT_DUMMY + 64) * 8);   // [n_mels + 4] dmel, two zeros on each side: bytes [3600, 4128)
+    // band-stage constants of the forward (see mel_frontend_kernel) ...
+    float un[8];
+    cf keep[4];
+    uint32_t sa[4];
+    int j_last;
+    bool sw[6];
+    {
+        const int dummy = SLOT_DUMMY + lane;
+        int jprev = lane == 0 ? -1 : sJ[8 * lane - 1];
+        int heads = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int k = 8 * lane + i;
+            const int jk = sJ[k];
+            const bool boundary = k > 0 && jk != jprev;
+            keep[i >> 1][i & 1] = boundary ? 0.f : 1.f;
+            heads |= boundary;
+            const uint32_t a = (boundary && jprev >= 0 && jprev <= p.n_mels) ? jprev : dummy;
+            sa[i >> 1] = (i & 1) ? (sa[i >> 1] | (a << 16)) : a;
+            un[i] = 0.25f * sU[k];
+            jprev = jk;
+        }
+        j_last = __builtin_amdgcn_readlane(jprev, 63);
+        int f = heads;
+        sw[0] = f == 0; f |= dpp_i<0x111, 0xF>(f);
+        sw[1] = f == 0; f |= dpp_i<0x112, 0xF>(f);
+        sw[2] = f == 0; f |= dpp_i<0x114, 0xF>(f);
+        sw[3] = f == 0; f |= dpp_i<0x118, 0xF>(f);
+        sw[4] = f == 0; f |= dpp_i<0x142, 0xA>(f);
+        sw[5] = f == 0;
+    }
+    // ... and of the band transpose: bin k = lane + 64 s gathers dmel[j_k] and dmel[j_k - 1] from the padded copy (index j + 2 / j + 1)
+    float ug[8];
+    int jg[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+        ug[s] = sU[lane + 64 * s];
+        jg[s] = max(-1, min(sJ[lane + 64 * s], p.n_mels + 1)) + 1;
+    }
+    __syncthreads();                                          // sU / sJ are dead: their LDS is the accumulator
+    for (int idx = tid; idx < len; idx += NT) sAcc[idx] = 0.f;
+
+    for (int tr = tlo; tr <= thi; tr += MEL_WAVES) {
+        const int t = tr + wv;
+        if (t <= thi) {                                       // wave-uniform
+            // upstream gradient of this frame's bands (requested first; strided by the row length)
+            float gv[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int band = lane + 64 * h;
+                gv[h] = band < p.n_mels ? dout[((int64_t)b * p.n_mels + band) * Tp + t] : 0.f;
+            }
+            cf v[8];
+            // stage 1 straight from global memory: y[i] = x[i+1] - preemph x[i], reflect-padded, windowed
+            const int i0 = t * p.hop - NFFT / 2;
+            if (i0 >= 0 && i0 + NFFT + 1 <= Ly && ((((int64_t)b * Lp + i0) & 1) == 0)) {      // interior frame, 8-byte aligned
+#pragma unroll
+                for (int a = 0; a < 8; ++a) {
+                    const float* s2 = x + i0 + 2 * (64 * a + lane);
+                    const cf x01 = *(const cf*)s2;
+                    const float x2 = s2[2];
+                    v[a] = cf{__builtin_fmaf(-p.preemph, x01.x, x01.y) * win[2 * a], __builtin_fmaf(-p.preemph, x01.y, x2) * win[2 * a + 1]};
+                }
+            } else {
+#pragma unroll
+                for (int a = 0; a < 8; ++a) {
+                    float y[2];
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        int i = i0 + 2 * (64 * a + lane) + e;
+                        if (i < 0) i = -i;
+                        if (i >= Ly) i = 2 * (Ly - 1) - i;
+                        i = max(0, min(i, Ly - 1));
+                        y[e] = __builtin_fmaf(-p.preemph, x[i], x[i + 1]);
+                    }
+                    v[a] = cf{y[0] * win[2 * a], y[1] * win[2 * a + 1]};
+                }
+            }
+            dft8(v);
+#pragma unroll
+            for (int q = 1; q < 8; ++q) v[q] = cmul(v[q], tw1[q]);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) scr[q * XROW1 + lane] = v[q];
+            {
+                const int c = lane >> 3, pp = lane & 7;
+#pragma unroll
+                for (int bq = 0; bq < 8; ++bq) v[bq] = scr[pp * XROW1 + 8 * bq + c];
+            }
+            dft8(v);
+#pragma unroll
+            for (int q = 1; q < 8; ++q) v[q] = cmul(v[q], tw2[q]);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) scr[q * XROW2 + lane] = v[q];
+            {
+                const int r = lane >> 3, pp = lane & 7;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) v[c] = scr[r * XROW2 + c * 8 + pp];
+            }
+            dft8(v);
+#pragma unroll
+            for (int s = 0; s < 8; ++s) scr[lane + 64 * s] = v[s];
+            float pk[8];
+            cf X2[8];                                          // 2 X[k], k = lane + 64 s: kept for G
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                const int k = lane + 64 * s;
+                const cf zk = v[s];
+                const cf zc = scr[(NC - k) & (NC - 1)];
+                const cf e2 = addcj(zk, zc);
+                const cf o2 = cmul_negi(subcj(zk, zc));
+                X2[s] = e2 + cmul(o2, tw3[s]);
+                const cf sq = X2[s] * X2[s];
+                pk[s] = sq.x + sq.y;                           // 4 |X|^2
+            }
+            // band sums: the forward's segment recurrence + segmented scan
+#pragma unroll
+            for (int s = 0; s < 8; ++s) pex[lane + 64 * s] = pk[s];
+            const f32x4 pa = *(const f32x4*)(pex + 8 * lane), pb = *(const f32x4*)(pex + 8 * lane + 4);
+            slot[lane] = cf{0.f, 0.f};
+            slot[lane + 64] = cf{0.f, 0.f};
+            if (lane < 2) slot[128 + lane] = cf{0.f, 0.f};
+            cf val[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float pw = i < 4 ? pa[i & 3] : pb[i & 3];
+                const float u = pw * un[i];
+                val[i] = cf{u, __builtin_fmaf(pw, 0.25f, -u)};
+            }
+            cf acc = {0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < 8; ++i) acc = __builtin_elementwise_fma(acc, bcast(keep[i >> 1], i & 1), val[i]);
+            cf ts = acc;
+            ts = seg_step<0x111, 0xF>(ts, sw[0]);
+            ts = seg_step<0x112, 0xF>(ts, sw[1]);
+            ts = seg_step<0x114, 0xF>(ts, sw[2]);
+            ts = seg_step<0x118, 0xF>(ts, sw[3]);
+            ts = seg_step<0x142, 0xA>(ts, sw[4]);
+            ts = seg_step<0x143, 0xC>(ts, sw[5]);
+            acc = dpp_c<0x138, 0xF>(ts);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                slot[(i & 1) ? (sa[i >> 1] >> 16) : (sa[i >> 1] & 0xFFFFu)] = acc;
+                acc = __builtin_elementwise_fma(acc, bcast(keep[i >> 1], i & 1), val[i]);
+            }
+            if (lane == 63 && j_last >= 0 && j_last <= p.n_mels) slot[j_last] = acc;
+            // dmel (0 where the forward wrote the mask constant; the upstream value there is not used), padded with two zeros a side
+            const bool tmasked = t >= p.tmask_start && t < p.tmask_end;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int band = lane + 64 * h;
+                if (band < p.n_mels) {
+                    const float mel = slot[band].x + slot[band + 1].y;
+                    const bool masked = tmasked || (band >= p.fmask_start && band < p.fmask_end);
+                    dmp[band + 2] = masked ? 0.f : gv[h] * p.out_scale / (mel + p.log_eps);
+                }
+            }
+            if (lane < 4) dmp[lane < 2 ? lane : p.n_mels + lane] = 0.f;
+            // band transpose and G = dP * 2 X
+            cf G[8];
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                const float dP = ug[s] * dmp[jg[s] + 1] + (1.f - ug[s]) * dmp[jg[s]];
+                G[s] = X2[s] * cf{dP, dP};
+            }
+            // one-sided inverse: H from G[k] and G[512 - k], conjugated, through the forward's transform
+#pragma unroll
+            for (int s = 0; s < 8; ++s) scr[lane + 64 * s] = G[s];
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                const int k = lane + 64 * s;
+                const cf gc = scr[(NC - k) & (NC - 1)];
+                const cf a2 = addcj(G[s], gc);                 // G + conj Gc
+                const cf d2 = subcj(G[s], gc);                 // G - conj Gc
+                const cf m2 = cmul(d2, cf{tw3[s].x, -tw3[s].y});      // conj(W^k) (G - conj Gc)
+                cf H = cf{a2.x - m2.y, a2.y + m2.x} * 0.5f;
+                if (k == 0) H = cf{G[s].x, G[s].x};
+                v[s] = cf{H.x, -H.y};
+            }
+            dft8(v);
+#pragma unroll
+            for (int q = 1; q < 8; ++q) v[q] = cmul(v[q], tw1[q]);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) scr[q * XROW1 + lane] = v[q];
+            {
+                const int c = lane >> 3, pp = lane & 7;
+#pragma unroll
+                for (int bq = 0; bq < 8; ++bq) v[bq] = scr[pp * XROW1 + 8 * bq + c];
+            }
+            dft8(v);
+#pragma unroll
+            for (int q = 1; q < 8; ++q) v[q] = cmul(v[q], tw2[q]);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) scr[q * XROW2 + lane] = v[q];
+            {
+                const int r = lane >> 3, pp = lane & 7;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) v[c] = scr[r * XROW2 + c * 8 + pp];
+            }
+            dft8(v);
+            // c[n] = conj v, n = lane + 64 s: taps 2n and 2n + 1, times the window
+#pragma unroll
+            for (int s = 0; s < 8; ++s) scr[lane + 64 * s] = cf{v[s].x * win[2 * s], -v[s].y * win[2 * s + 1]};
+        }
+        __syncthreads();
+        for (int idx = tid; idx < len; idx += NT) {           // overlap-add in frame order
+            const int q = qlo + idx;
+            float a = sAcc[idx];
+#pragma unroll
+            for (int w = 0; w < MEL_WAVES; ++w) {
+                const int off = q - (tr + w) * p.hop;
+                if (tr + w <= thi && off >= 0 && off < NFFT) a += ((const float*)(sScr + w * WAVE_SCRATCH))[off];
+            }
+            sAcc[idx] = a;
+        }
+        __syncthreads();
+    }
+    if (tlo > thi) __syncthreads();                            // no frame reaches the run: the zeros are read below
+    // reflect adjoint + pre-emphasis adjoint
+    auto dy = [&](int m) {
+        float d = sAcc[m + NFFT / 2 - qlo];
+        if (m >= 1 && m <= NFFT / 2) d += sAcc[NFFT / 2 - m - qlo];
+        const int i = 2 * (Ly - 1) - m;
+        if (i >= Ly && i < Ly + NFFT / 2) d += sAcc[NFFT / 2 + i - qlo];
+        return d;
+    };
+    for (int n = n0 + tid; n < nend; n += NT) {
+        float r = 0.f;
+        if (n < L) {
+            const float d0 = n >= 1 ? dy(n - 1) : 0.f;
+            const float d1 = n < Ly ? dy(n) : 0.f;
+            r = __builtin_fmaf(-p.preemph, d1, d0);
+        }
+        dx[n] = r;
+    }
+}
+
 }  // namespace pa
 
 using namespace pa;
@@ -561,4 +877,44 @@ extern "C" int pa_mel_frontend_fwd_varlen(const float* wave, int B, int ldw, con
     hipLaunchKernelGGL((mel_frontend_kernel<FR_DEFAULT, false, true>), grid, dim3(MEL_WAVES * 64), lds, (hipStream_t)stream, wave, ldw, window, bin_mel,
                        (const float2*)twiddle, out, *p, (int)cdiv(T_max, fr), (int)(cdiv(T_max, fr) * B), lens, fill);
     return check_launch();
+}
+
+// samples one workgroup of the backward owns: whole hops, at least 16 frames' worth and at least 2048 (the frames in front of the run
+// that are transformed again are then at most half of the work, whatever the hop)
+static int mel_bwd_rows(int hop) { return hop * (int)std::max<int64_t>(FR_DEFAULT, cdiv(2 * NFFT, hop)); }
+
+template <bool VL>
+static int mel_bwd_launch(const float* wave, int B, int Lp, const int32_t* lens, const float* window, const float* bin_mel, const float* twiddle,
+                          const float* dout, float* dwave, const pa_mel_params* p, void* stream) {
+    const int rows = mel_bwd_rows(p->hop);
+    const size_t lds = MEL_WAVES * WAVE_SCRATCH + (size_t)(rows + 2 * NFFT + 4) * 4;
+    if (lds > 160 * 1024) return PA_EUNSUPPORTED;
+    static signed char lds_attr[64] = {0};
+    (void)lds_attr_on_this_device((const void*)mel_frontend_bwd_kernel<VL>, 160 * 1024, lds_attr);
+    dim3 grid((unsigned)cdiv(Lp, rows), (unsigned)B);
+    hipLaunchKernelGGL((mel_frontend_bwd_kernel<VL>), grid, dim3(MEL_WAVES * 64), lds, (hipStream_t)stream, wave, Lp, window, bin_mel,
+                       (const float2*)twiddle, dout, dwave, *p, rows, lens);
+    return check_launch();
+}
+
+// The overlap-add happens inside the workgroups (see mel_frontend_bwd_kernel): no workspace is needed, `workspace` may be NULL.
+extern "C" int pa_mel_frontend_bwd(const float* wave, int B, int L, const float* window, const float* bin_mel, const float* twiddle,
+                                   const float* dout, float* dwave, void* workspace, int64_t workspace_bytes, const pa_mel_params* p, void* stream) {
+    (void)workspace; (void)workspace_bytes;
+    if (!wave || !window || !bin_mel || !twiddle || !dout || !dwave || !p || B <= 0) return PA_EINVAL;
+    if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
+    if (L - 1 <= NFFT / 2) return PA_EUNSUPPORTED;
+    if (p->n_frames != pa_mel_num_frames(L, p->hop)) return PA_EINVAL;
+    return mel_bwd_launch<false>(wave, B, L, nullptr, window, bin_mel, twiddle, dout, dwave, p, stream);
+}
+
+extern "C" int pa_mel_frontend_bwd_varlen(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
+                                          const float* twiddle, const float* dout, int T_max, float* dwave, void* workspace,
+                                          int64_t workspace_bytes, const pa_mel_params* p, void* stream) {
+    (void)workspace; (void)workspace_bytes;
+    if (!wave || !lens || !window || !bin_mel || !twiddle || !dout || !dwave || !p || B <= 0 || T_max <= 0) return PA_EINVAL;
+    if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
+    if (ldw - 1 <= NFFT / 2) return PA_EUNSUPPORTED;
+    if (p->n_frames != T_max || T_max > pa_mel_num_frames(ldw, p->hop)) return PA_EINVAL;
+    return mel_bwd_launch<true>(wave, B, ldw, lens, window, bin_mel, twiddle, dout, dwave, p, stream);
 }

@@ -188,6 +188,39 @@ def mel_frontend_varlen(wave, lens_dev, window, bin_mel, twiddle, params: MelPar
     return out
 
 
+def mel_frontend_bwd(wave, window, bin_mel, twiddle, params: MelParams, dout):
+    """Gradient of mel_frontend w.r.t. ``wave`` (B, L) f32 for the upstream gradient ``dout`` (B, n_mels, n_frames) f32; ``params`` is
+    the forward call's (mask ranges included).  Nothing was saved: the spectrum is recomputed from the wave.  Deterministic."""
+    B, L = wave.shape
+    if tuple(dout.shape) != (B, params.n_mels, params.n_frames):
+        raise _lib.PasstAmdError(f"mel_frontend_bwd: dout {tuple(dout.shape)} for a ({B}, {params.n_mels}, {params.n_frames}) output")
+    dwave = torch.empty_like(wave)
+    _timed("mel_bwd", 4.0 * (2 * B * L + dout.numel()),
+           lambda: check(_lib.load().pa_mel_frontend_bwd(_p(wave, torch.float32), B, L, _p(window, torch.float32), _p(bin_mel, torch.float32),
+                                                         _p(twiddle, torch.float32), _p(dout, torch.float32), _p(dwave), None, 0,
+                                                         C.byref(params), _stream()),
+                         "pa_mel_frontend_bwd"))
+    return dwave
+
+
+def mel_frontend_bwd_varlen(wave, lens_dev, window, bin_mel, twiddle, params: MelParams, dout):
+    """Gradient of mel_frontend_varlen w.r.t. ``wave`` (B, L_max): row i equals the clip's own gradient in its first lens[i] samples and
+    is exactly 0 behind them; ``dout`` behind a clip's frames is not used."""
+    if wave.dim() != 2 or lens_dev.dim() != 1 or lens_dev.numel() != wave.shape[0]:
+        raise _lib.PasstAmdError(f"mel_frontend_bwd_varlen: wave {tuple(wave.shape)} needs one length per row, got {tuple(lens_dev.shape)}")
+    B, L = wave.shape
+    if tuple(dout.shape) != (B, params.n_mels, params.n_frames):
+        raise _lib.PasstAmdError(f"mel_frontend_bwd_varlen: dout {tuple(dout.shape)} for a ({B}, {params.n_mels}, {params.n_frames}) output")
+    dwave = torch.empty_like(wave)
+    _timed("mel_bwd", 4.0 * (2 * B * L + dout.numel()),
+           lambda: check(_lib.load().pa_mel_frontend_bwd_varlen(_p(wave, torch.float32), B, wave.stride(0), _p(lens_dev, torch.int32),
+                                                                _p(window, torch.float32), _p(bin_mel, torch.float32), _p(twiddle, torch.float32),
+                                                                _p(dout, torch.float32), params.n_frames, _p(dwave), None, 0,
+                                                                C.byref(params), _stream()),
+                         "pa_mel_frontend_bwd_varlen"))
+    return dwave
+
+
 # ---- staging ---------------------------------------------------------------------------------
 def convert(x_f32, dtype):
     if dtype == PA_F32:

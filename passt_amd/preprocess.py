@@ -15,6 +15,35 @@ from . import ops
 from ._lib import MelParams, PasstAmdError, compile_opaque
 
 
+class _MelWaveGrad(torch.autograd.Function):
+    """The forward launch with a gradient w.r.t. the waveform (pa_mel_frontend_bwd / _bwd_varlen).  Only entered when autograd
+    records and the waveform requires a gradient; the forward launches exactly what the plain call launches and saves no
+    activation: the node keeps the float waveform and the MelParams the launch used (the jittered fmin / fmax and the drawn masks,
+    so the backward sees the forward's draw), and the backward recomputes the spectrum from the waveform."""
+
+    @staticmethod
+    def forward(ctx, x, window, bin_mel, twiddle, p, lens_dev):
+        ctx.c = (x, window, bin_mel, twiddle, p, lens_dev)
+        if lens_dev is None:
+            return ops.mel_frontend(x, window, bin_mel, twiddle, p)
+        return ops.mel_frontend_varlen(x, lens_dev, window, bin_mel, twiddle, p, fill=0.0)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable          # create_graph=True is not supported: the gradient is a plain tensor
+    def backward(ctx, g):
+        c, ctx.c = ctx.c, None
+        if c is None:
+            raise RuntimeError("passt_amd.AugmentMelSTFT: the saved waveform of this forward was already consumed by a backward "
+                               "pass (retain_graph / double backward are not supported: run the forward again)")
+        x, window, bin_mel, twiddle, p, lens_dev = c
+        g = g.contiguous().float()
+        if lens_dev is None:
+            dx = ops.mel_frontend_bwd(x, window, bin_mel, twiddle, p, g)
+        else:
+            dx = ops.mel_frontend_bwd_varlen(x, lens_dev, window, bin_mel, twiddle, p, g)
+        return dx, None, None, None, None, None
+
+
 def _draw_mask(mask_param, size):
     """The band [start, end) torchaudio.functional.mask_along_axis draws (0.13.1 with the transforms' default p = 1.0 --
     ``_get_mask_param`` leaves mask_param unclamped there -- and 0.11.0, which has no clamp at all; non-iid path, because the
@@ -89,6 +118,10 @@ class AugmentMelSTFT(nn.Module):
     def forward(self, x, lengths=None):
         """x: (B, L) waveforms -> (B, n_mels, 1 + (L-1)//hop).
 
+        A waveform that requires a gradient gets one (train and eval mode, with and without ``lengths``): masked cells and the
+        frames behind a clip's end contribute nothing, samples behind ``lengths[i]`` get exactly 0.  One backward per forward;
+        ``create_graph=True`` is not supported.
+
         ``lengths`` (sequence of ints or 1-D integer tensor): valid samples per row of a zero-padded batch of clips of different
         lengths (left-aligned).  Returns ``(spec, frames)``: spec (B, n_mels, T_max), T_max = frames of the longest clip, row i equal
         to ``forward(x[i:i+1, :lengths[i]])`` in its first frames[i] columns (pre-emphasis and reflect padding at the clip's own
@@ -100,7 +133,7 @@ class AugmentMelSTFT(nn.Module):
             raise PasstAmdError("passt_amd.AugmentMelSTFT runs on a HIP device only (no CPU fallback)")
         if x.dim() != 2:
             raise ValueError("expected (batch, samples)")
-        x = x.contiguous().float()
+        x = x.contiguous().float()                  # outside the autograd node: autograd casts the gradient back to x's dtype / layout
         B, L = x.shape
         # RNG order of the reference: both randint calls always execute (:63-64)
         fmin = self.fmin + torch.randint(self.fmin_aug_range, (1,)).item()
@@ -122,6 +155,8 @@ class AugmentMelSTFT(nn.Module):
                 p.fmask_start, p.fmask_end = self.freqm.draw(self.n_mels)                 # :81
             if isinstance(self.timem, _AxisMasking):
                 p.tmask_start, p.tmask_end = self.timem.draw(p.n_frames)                  # :82
+        if torch.is_grad_enabled() and x.requires_grad:
+            return _MelWaveGrad.apply(x, self._window_padded, self._bin_mel, self._twiddle, p, None)
         return ops.mel_frontend(x, self._window_padded, self._bin_mel, self._twiddle, p)
 
     def _forward_varlen(self, x, lengths):
@@ -162,7 +197,10 @@ class AugmentMelSTFT(nn.Module):
         p.log_eps, p.out_add, p.out_scale = 0.00001, 4.5, 1.0 / 5.0
         p.fmask_start = p.fmask_end = p.tmask_start = p.tmask_end = 0
         lens_dev = ops.upload_small(torch.tensor(lengths, dtype=torch.int32), x.device)
-        spec = ops.mel_frontend_varlen(x, lens_dev, self._window_padded, self._bin_mel, self._twiddle, p, fill=0.0)
+        if torch.is_grad_enabled() and x.requires_grad:
+            spec = _MelWaveGrad.apply(x, self._window_padded, self._bin_mel, self._twiddle, p, lens_dev)
+        else:
+            spec = ops.mel_frontend_varlen(x, lens_dev, self._window_padded, self._bin_mel, self._twiddle, p, fill=0.0)
         return spec, torch.tensor(frames, dtype=torch.int64)
 
     def extra_repr(self):
