@@ -272,6 +272,110 @@ def _precision(model):
     return PA_BF16 if torch.is_autocast_enabled() else PA_F32
 
 
+def _checked_input(model, x, bind_dt):
+    """What every forward checks first: a HIP tensor, the precision of this call, a dense f32 (B, 1, n_mels, frames) spectrogram.
+    ``bind_dt``: remember the precision as the one whose weight copies a bound optimizer refreshes (it steps outside torch.autocast)."""
+    if not x.is_cuda:
+        raise PasstAmdError("passt_amd.PaSST runs on a HIP device only (no CPU fallback); got a CPU tensor")
+    dt = _precision(model)
+    if bind_dt:
+        object.__setattr__(model, "_last_dt", dt)
+    x = x.contiguous().float()
+    if x.dim() != 4 or x.shape[1] != 1:
+        raise ValueError(f"PaSST expects a (B, 1, n_mels, frames) spectrogram, got {tuple(x.shape)} "
+                         "(in_chans = 1 in every reference arch, models/passt.py:961)")
+    return x, dt
+
+
+def _freq_rows(model, F):
+    """Frequency rows of the patch grid of an F-bin spectrogram; they must be the frequency embedding's."""
+    F_dim = (F - model.patch_embed.patch_size[0]) // model.patch_embed.stride[0] + 1
+    Fpe = model.freq_new_pos_embed.shape[-2]
+    if F_dim != Fpe:
+        raise RuntimeError(f"patch grid has {F_dim} frequency rows but freq_new_pos_embed has {Fpe}")
+    return F_dim
+
+
+# The two token layouts.  The shared kernel sequence below (_forward_trunk / _backward_trunk) runs on a token matrix [M][D] and
+# asks the layout for what it cannot know: B, M, the rows of the cls / dist tokens, the attention entries of this layout, and
+# whether the stage in front of block 0 wants block 0's input gradient in 16 bits as well.
+class _FixedLayout:
+    """B clips of Ntok token rows each (every clip keeps the same patches)."""
+    dx0_lp = False                  # the patch stage starts from the f32 dx (pa_patch_bwd makes its own compact 16-bit dpatch)
+
+    def __init__(self, model, B, Ntok):
+        self.model, self.B, self.Ntok, self.M = model, B, Ntok, B * Ntok
+
+    def prefix_rows(self, device):
+        return _prefix_rows(self.model, self.B, self.Ntok, device)
+
+    def attention_fwd(self, qkv, H, scale, **kw):
+        return ops.attention_fwd(qkv, self.B, H, self.Ntok, scale, **kw)
+
+    def attention_bwd(self, qkv, att, d_att, lse, H, scale, **kw):
+        return ops.attention_bwd(qkv, att, d_att, lse, self.B, H, self.Ntok, scale, **kw)
+
+
+class _PackedLayout:
+    """B clips of different token counts back to back: clip b owns rows cu_tok[b] .. cu_tok[b + 1] (device int32), none longer
+    than max_N; ``pidx``: the rows of the cls / dist tokens (device int32).  The attention backward is always the kernel pair."""
+    dx0_lp = True                   # block 0's 16-bit dx feeds the patch stage's two GEMMs as it is
+
+    def __init__(self, B, M, max_N, cu_tok, pidx):
+        self.B, self.M, self.max_N, self.cu_tok, self.pidx = B, M, max_N, cu_tok, pidx
+
+    def prefix_rows(self, device):
+        return self.pidx
+
+    def attention_fwd(self, qkv, H, scale, **kw):
+        return ops.attention_fwd_varlen(qkv, self.cu_tok, self.B, H, self.max_N, scale, **kw)
+
+    def attention_bwd(self, qkv, att, d_att, lse, H, scale, **kw):
+        return ops.attention_bwd_varlen(qkv, att, d_att, lse, self.cu_tok, self.B, H, self.max_N, scale, **kw)
+
+
+def _forward_trunk(model, lay, xs, dt, save, patch):
+    """Token matrix xs [M][D] f32 in layout ``lay`` -> blocks -> prefix-only tail -> head.  Returns (logits, features, ctx); ctx
+    (``save`` only) is what _backward_trunk needs plus ``patch``, the entry path's own state for its patch-stage backward."""
+    st = model._staged
+    D, H = model.embed_dim, model.num_heads
+    scale = (D // H) ** -0.5
+    aflags = ops.ATTN_Q_PRESCALED
+    saved = []
+    nblk = len(model.blocks)
+    for bi, blk in enumerate(model.blocks):
+        last = bi == nblk - 1
+        ln1, mean1, rstd1 = ops.layernorm_fwd(xs, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt, save)
+        # the q third leaves the GEMM as q * scale * log2(e) (one rounding): attention takes "score - row reference"
+        # straight from the matrix pipe (ATTN_Q_PRESCALED); every gradient stays the gradient of the unscaled Linear
+        qkv = ops.linear(ln1, st.get(blk.attn.qkv.weight, dt, False), blk.attn.qkv.bias, dt,
+                         colscale_n=D, colscale=scale * ops.LOG2E)
+        if not last:
+            att, lse = lay.attention_fwd(qkv, H, scale, flags=aflags)
+            x_res = xs
+        else:
+            # PREFIX-ONLY TAIL.  The network output reads the last block at the cls/dist rows only
+            # (models/passt.py:570-574, 583), so from here on just those 2 rows per clip are computed: attention for
+            # 2 queries (keys/values still span every token), then proj / LN2 / MLP on [2B, D].  Exact, not an
+            # approximation: the reference computes the other N-2 rows and discards them.
+            pidx = lay.prefix_rows(xs.device)
+            att, lse = lay.attention_fwd(qkv, H, scale, nq=2, flags=aflags)
+            x_res = ops.gather_rows(xs, pidx)
+        x_mid = ops.linear_resid(att, st.get(blk.attn.proj.weight, dt, False), blk.attn.proj.bias, x_res, dt)
+        ln2, mean2, rstd2 = ops.layernorm_fwd(x_mid, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, save)
+        h_pre, h_act = ops.linear_gelu(ln2, st.get(blk.mlp.fc1.weight, dt, False), blk.mlp.fc1.bias, dt)
+        x_out = ops.linear_resid(h_act, st.get(blk.mlp.fc2.weight, dt, False), blk.mlp.fc2.bias, x_mid, dt)
+        if save:
+            saved.append((xs, ln1, mean1, rstd1, qkv, att, lse, x_mid, ln2, mean2, rstd2, h_pre, h_act))
+        xs = x_out
+    xl = xs.view(lay.B, 2, D)              # compact: the two prefix tokens of every clip
+    feat, hn, stats = ops.head_pre_fwd(xl, model.norm.weight, model.norm.bias, model.norm.eps, model.head[0].weight,
+                                       model.head[0].bias, model.head[0].eps)
+    logits = ops.linear_f32_fwd(hn, model.head[1].weight, model.head[1].bias)
+    ctx = dict(dt=dt, lay=lay, scale=scale, saved=saved, xl=xl, feat=feat, hn=hn, stats=stats, patch=patch) if save else None
+    return logits, feat, ctx
+
+
 def patchout_draws(model, x_shape):
     """The host part of a forward: geometry checks and the reference's Patchout draws (models/passt.py:513-553, same torch CPU
     RNG calls in the same order), as numpy arrays: the grid coordinates of the kept patches (pf, pt) and the time-positional
@@ -282,10 +386,7 @@ def patchout_draws(model, x_shape):
     if not (F == model.patch_embed.img_size[0] and T == model.patch_embed.img_size[1]):
         warnings.warn(f"Input image size ({F}*{T}) doesn't match model "
                       f"({model.patch_embed.img_size[0]}*{model.patch_embed.img_size[1]}).")   # :320-321
-    F_dim, T_dim = (F - P) // fs + 1, (T - P) // ts + 1
-    Fpe = model.freq_new_pos_embed.shape[-2]
-    if F_dim != Fpe:
-        raise RuntimeError(f"patch grid has {F_dim} frequency rows but freq_new_pos_embed has {Fpe}")
+    F_dim, T_dim = _freq_rows(model, F), (T - P) // ts + 1
     toff, T_eff, idx_t, idx_f, idx_u = draw_patchout(model, F_dim, T_dim)
     pf_np, pt_np = kept_patches(F_dim, T_eff, idx_t, idx_f, idx_u)
     return dict(pf=pf_np, pt=pt_np, toff=toff, Np=pf_np.size)
@@ -299,15 +400,7 @@ def passt_forward(model, x, save, draws=None):
 
 
 def _passt_forward(model, x, save, draws=None):
-    if not x.is_cuda:
-        raise PasstAmdError("passt_amd.PaSST runs on a HIP device only (no CPU fallback); got a CPU tensor")
-    dt = _precision(model)
-    object.__setattr__(model, "_last_dt", dt)       # the copies a bound optimizer refreshes (it steps outside torch.autocast)
-    st = model._staged
-    x = x.contiguous().float()
-    if x.dim() != 4 or x.shape[1] != 1:
-        raise ValueError(f"PaSST expects a (B, 1, n_mels, frames) spectrogram, got {tuple(x.shape)} "
-                         "(in_chans = 1 in every reference arch, models/passt.py:961)")
+    x, dt = _checked_input(model, x, True)
     B, Cin, F, T = x.shape
     P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
     if draws is None:
@@ -317,9 +410,7 @@ def _passt_forward(model, x, save, draws=None):
         pt_pos, toff, Np = pt, d["toff"], d["Np"]        # the positional kernels add the offset themselves
     else:
         pf, pt, pt_pos, toff, Np = draws["pf"], draws["pt"], draws["pt_pos"], 0, draws["Np"]
-    D, H, depth = model.embed_dim, model.num_heads, len(model.blocks)
-    Ntok, M = Np + 2, B * (Np + 2)
-    scale = (D // H) ** -0.5
+    D, Ntok = model.embed_dim, Np + 2
 
     # patch embedding: gather-first im2col GEMM, epilogue adds bias + time/freq positional rows and
     # scatters to token rows 2.. ; rows 0,1 = cls/dist + new_pos_embed                 (:323,:527-564)
@@ -327,52 +418,15 @@ def _passt_forward(model, x, save, draws=None):
     tok = torch.empty((B, Ntok, D), device=x.device, dtype=torch.float32)
     table = ops.patch_pos_table(model.patch_embed.proj.bias, model.time_new_pos_embed, model.freq_new_pos_embed,
                                 pf, pt_pos, toff, model.cls_token, model.dist_token, model.new_pos_embed, tok)
-    ops.gemm_nt(cols, st.get(model.patch_embed.proj.weight, dt, False), dt, EPI_RESID, resid=table, out_f32=tok,
+    ops.gemm_nt(cols, model._staged.get(model.patch_embed.proj.weight, dt, False), dt, EPI_RESID, resid=table, out_f32=tok,
                 row_mod=Np, out_batch_rows=Ntok, out_row_off=2)
-
-    xs = tok.view(M, D)
-    saved = []
-    nblk = len(model.blocks)
-    for bi, blk in enumerate(model.blocks):
-        last = bi == nblk - 1
-        ln1, mean1, rstd1 = ops.layernorm_fwd(xs, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt, save)
-        # the q third leaves the GEMM as q * scale * log2(e) (one rounding): attention takes "score - row reference"
-        # straight from the matrix pipe (ATTN_Q_PRESCALED); every gradient stays the gradient of the unscaled Linear
-        qkv = ops.linear(ln1, st.get(blk.attn.qkv.weight, dt, False), blk.attn.qkv.bias, dt,
-                         colscale_n=D, colscale=scale * ops.LOG2E)
-        aflags = ops.ATTN_Q_PRESCALED
-        if not last:
-            att, lse = ops.attention_fwd(qkv, B, H, Ntok, scale, flags=aflags)
-            x_res = xs
-        else:
-            # PREFIX-ONLY TAIL.  The network output reads the last block at the cls/dist rows only
-            # (models/passt.py:570-574, 583), so from here on just those 2 rows per clip are computed: attention for
-            # 2 queries (keys/values still span every token), then proj / LN2 / MLP on [2B, D].  Exact, not an
-            # approximation: the reference computes the other N-2 rows and discards them.
-            pidx = _prefix_rows(model, B, Ntok, x.device)
-            att, lse = ops.attention_fwd(qkv, B, H, Ntok, scale, nq=2, flags=aflags)
-            x_res = ops.gather_rows(xs, pidx)
-        x_mid = ops.linear_resid(att, st.get(blk.attn.proj.weight, dt, False), blk.attn.proj.bias, x_res, dt)
-        ln2, mean2, rstd2 = ops.layernorm_fwd(x_mid, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, save)
-        h_pre, h_act = ops.linear_gelu(ln2, st.get(blk.mlp.fc1.weight, dt, False), blk.mlp.fc1.bias, dt)
-        x_out = ops.linear_resid(h_act, st.get(blk.mlp.fc2.weight, dt, False), blk.mlp.fc2.bias, x_mid, dt)
-        if save:
-            saved.append((xs, ln1, mean1, rstd1, qkv, att, lse, x_mid, ln2, mean2, rstd2, h_pre, h_act))
-        xs = x_out
-    xl = xs.view(B, 2, D)                  # compact: the two prefix tokens of every clip
-    feat, hn, stats = ops.head_pre_fwd(xl, model.norm.weight, model.norm.bias, model.norm.eps, model.head[0].weight,
-                                       model.head[0].bias, model.head[0].eps)
-    logits = ops.linear_f32_fwd(hn, model.head[1].weight, model.head[1].bias)
-    ctx = None
-    if save:
-        # pt_grid: the kept patches' own grid columns (pt may carry the time-positional offset); F, T: the input gradient's shape
-        ctx = dict(dt=dt, B=B, Ntok=Ntok, Np=Np, pf=pf, pt=pt_pos, pt_grid=pt, F=F, T=T, toff=toff, cols=cols, saved=saved, xl=xl,
-                   feat=feat, hn=hn, stats=stats, scale=scale)
-    return logits, feat, ctx
+    # pt_grid: the kept patches' own grid columns (pt may carry the time-positional offset); F, T: the input gradient's shape
+    patch = dict(Np=Np, pf=pf, pt=pt_pos, pt_grid=pt, toff=toff, F=F, T=T, cols=cols) if save else None
+    return _forward_trunk(model, _FixedLayout(model, B, Ntok), tok.view(B * Ntok, D), dt, save, patch)
 
 
 # --------------------------------------------------------------------------------------------
-# packed eval forward for clips of different lengths
+# packed forward for clips of different lengths
 # --------------------------------------------------------------------------------------------
 def varlen_geometry(lengths, P, tstride, F_dim, Tpe, T_max=None):
     """Host geometry of a packed ragged batch (models/passt.py:513-526 per clip, eval mode).  ``lengths``: valid frames per clip.
@@ -421,16 +475,7 @@ def passt_forward_varlen(model, x, lengths, save=False):
 
 
 def _passt_forward_varlen(model, x, lengths, save=False):
-    if not x.is_cuda:
-        raise PasstAmdError("passt_amd.PaSST runs on a HIP device only (no CPU fallback); got a CPU tensor")
-    dt = _precision(model)
-    if save:
-        object.__setattr__(model, "_last_dt", dt)   # the copies a bound optimizer refreshes, as in _passt_forward
-    st = model._staged
-    x = x.contiguous().float()
-    if x.dim() != 4 or x.shape[1] != 1:
-        raise ValueError(f"PaSST expects a (B, 1, n_mels, frames) spectrogram, got {tuple(x.shape)} "
-                         "(in_chans = 1 in every reference arch, models/passt.py:961)")
+    x, dt = _checked_input(model, x, save)
     if torch.is_tensor(lengths):
         if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
             raise ValueError("lengths must be a sequence of ints or a 1-D integer tensor")
@@ -440,17 +485,11 @@ def _passt_forward_varlen(model, x, lengths, save=False):
     if len(lengths) != B:
         raise ValueError(f"lengths has {len(lengths)} entries for a batch of {B} clips")
     P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
-    F_dim = (F - P) // fs + 1
-    Tpe, Fpe = model.time_new_pos_embed.shape[-1], model.freq_new_pos_embed.shape[-2]
-    if F_dim != Fpe:
-        raise RuntimeError(f"patch grid has {F_dim} frequency rows but freq_new_pos_embed has {Fpe}")
-    g = varlen_geometry(lengths, P, ts, F_dim, Tpe, T_max=T)
+    g = varlen_geometry(lengths, P, ts, _freq_rows(model, F), model.time_new_pos_embed.shape[-1], T_max=T)
     if g["cut"]:
         warnings.warn(f"the patches shape of clips {g['cut']} are larger than the expected time encodings "
                       f"{tuple(model.time_new_pos_embed.shape)}, x will be cut")              # :524-526, once per call
-    D, H = model.embed_dim, model.num_heads
-    M, max_N = g["row_f"].size, g["max_N"]
-    scale = (D // H) ** -0.5
+    M = g["row_f"].size
     # one upload: [row_clip | row_f | row_t | cu_tok | prefix rows]
     cu = g["cu_tok"]
     pidx_np = (cu[:-1, None] + np.arange(2, dtype=np.int32)[None, :]).reshape(-1).astype(np.int32)
@@ -463,47 +502,10 @@ def _passt_forward_varlen(model, x, lengths, save=False):
     cols = ops.patch_gather_varlen(x, row_clip, row_f, row_t, P, fs, ts, dt)
     table = ops.patch_pos_table_varlen(model.patch_embed.proj.bias, model.time_new_pos_embed, model.freq_new_pos_embed, row_f, row_t,
                                        model.cls_token, model.dist_token, model.new_pos_embed)
-    xs = torch.empty((M, D), device=x.device, dtype=torch.float32)
-    ops.gemm_nt(cols, st.get(model.patch_embed.proj.weight, dt, False), dt, EPI_RESID, resid=table, out_f32=xs)
-
-    nblk = len(model.blocks)
-    aflags = ops.ATTN_Q_PRESCALED
-    saved = []
-    for bi, blk in enumerate(model.blocks):
-        last = bi == nblk - 1
-        ln1, mean1, rstd1 = ops.layernorm_fwd(xs, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt, save)
-        qkv = ops.linear(ln1, st.get(blk.attn.qkv.weight, dt, False), blk.attn.qkv.bias, dt, colscale_n=D, colscale=scale * ops.LOG2E)
-        if not last:
-            att, lse = ops.attention_fwd_varlen(qkv, cu_tok, B, H, max_N, scale, flags=aflags)
-            x_res = xs
-        else:                                          # prefix-only tail, as in _passt_forward
-            att, lse = ops.attention_fwd_varlen(qkv, cu_tok, B, H, max_N, scale, nq=2, flags=aflags)
-            x_res = ops.gather_rows(xs, pidx)
-        x_mid = ops.linear_resid(att, st.get(blk.attn.proj.weight, dt, False), blk.attn.proj.bias, x_res, dt)
-        ln2, mean2, rstd2 = ops.layernorm_fwd(x_mid, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, save)
-        h_pre, h_act = ops.linear_gelu(ln2, st.get(blk.mlp.fc1.weight, dt, False), blk.mlp.fc1.bias, dt)
-        x_out = ops.linear_resid(h_act, st.get(blk.mlp.fc2.weight, dt, False), blk.mlp.fc2.bias, x_mid, dt)
-        if save:
-            saved.append((xs, ln1, mean1, rstd1, qkv, att, lse, x_mid, ln2, mean2, rstd2, h_pre, h_act))
-        xs = x_out
-    xl = xs.view(B, 2, D)
-    feat, hn, stats = ops.head_pre_fwd(xl, model.norm.weight, model.norm.bias, model.norm.eps, model.head[0].weight,
-                                       model.head[0].bias, model.head[0].eps)
-    logits = ops.linear_f32_fwd(hn, model.head[1].weight, model.head[1].bias)
-    ctx = None
-    if save:
-        ctx = dict(dt=dt, B=B, M=M, max_N=max_N, cu_tok=cu_tok, pidx=pidx, F=F, T=T, cols=cols, saved=saved, xl=xl, feat=feat, hn=hn,
-                   stats=stats, scale=scale)
-    return logits, feat, ctx
-
-
-def _wgrad_pair(dY, X, dW, db, dt, scratch, accumulate):
-    """dW[N][K] = dY^T X, db[N] = colsum(dY) from row-major dY[M][N], X[M][K], both read in place
-    (pa_gemm_tn: transpose-read MFMA operands, deterministic split-K over tokens)."""
-    fused = db is not None and ops.wgrad_tn_fuses_bias(dt) and not os.environ.get("PASST_AMD_NO_FUSED_BIAS")
-    scratch["part"] = ops.wgrad_tn(dY, X, dW.view(dY.shape[1], -1), dt, accumulate, scratch.get("part"), db=db if fused else None)
-    if db is not None and not fused:
-        ops.colsum(dY, db, accumulate=accumulate)
+    xs = torch.empty((M, model.embed_dim), device=x.device, dtype=torch.float32)
+    ops.gemm_nt(cols, model._staged.get(model.patch_embed.proj.weight, dt, False), dt, EPI_RESID, resid=table, out_f32=xs)
+    patch = dict(F=F, T=T, cols=cols) if save else None
+    return _forward_trunk(model, _PackedLayout(B, M, g["max_N"], cu_tok, pidx), xs, dt, save, patch)
 
 
 class _NoRowJobs(list):
@@ -544,6 +546,189 @@ class _NoGrads(dict):
         return None
 
 
+class _WgradSchedule:
+    """Where and when the parameter gradients of ONE backward go out -- the side stream, the per-block batching, the deferred row
+    reductions, who produces which bias gradient, the ``on_block_done`` reports -- decided here, once per call, for both token
+    layouts.  Every A/B switch of the backward is read here, per call (a test toggles one between two models of one process).
+    ``g``: the parameter-name -> output-buffer dict, all None when ``grads`` is None (frozen: no weight-gradient work at all)."""
+
+    def __init__(self, model, dt, grads, on_block_done, device):
+        self.dt, self.scratch = dt, model._scratch
+        self.frozen = frozen = grads is None
+        self.g = _NoGrads() if frozen else grads
+        self.on_block_done = None if frozen else on_block_done
+        overlap = getattr(model, "overlap_wgrad", False)
+        side = self.scratch.get("side")
+        if side is None or side.enabled != bool(overlap):
+            side = self.scratch["side"] = _SideStream(device, enabled=overlap)
+        self.side = side
+        env = os.environ.get
+        self.fused_bias = not env("PASST_AMD_NO_FUSED_BIAS")
+        # bf16, single stream: the four weight gradients of a block wait until the block's last operand exists and go out as
+        # ONE batched launch (+ one batched split-K reduction): no drain / prologue between them, equal-sized work items
+        self.pending = [] if (dt == PA_BF16 and not side.enabled and not frozen and not env("PASST_AMD_NO_BATCH_WGRAD")) else None
+        # ... and so do the block's small finishing reductions: the two LayerNorms' dgamma | dbeta (+ the bias gradient each carries)
+        # and the GELU' epilogue's fc1.bias rows stay as partial rows and are reduced by the SAME finishing launch as the split-K
+        # slabs (three launches per block less; PASST_AMD_NO_DEFER_ROWS=1: A/B, every reduction right behind its producer)
+        self.rowjobs = [] if (self.pending is not None and not env("PASST_AMD_NO_DEFER_ROWS")) else None
+        if frozen:
+            self.rowjobs = _NoRowJobs()     # the LayerNorm backward leaves its parameter-gradient partial rows unreduced
+        # PASST_AMD_BIAS_FROM_WGRAD=1 (A/B; required by PA_EPILOGUE_V3=1): fc1.bias out of the weight-gradient launch instead of the
+        # GELU' epilogue's lane-local column sums
+        self.bias_from_wgrad = (dt == PA_BF16 and ops.wgrad_tn_fuses_bias(dt) and self.fused_bias
+                                and (env("PASST_AMD_BIAS_FROM_WGRAD") == "1" or env("PA_EPILOGUE_V3") == "1"))
+
+    def report(self, i):
+        if self.on_block_done:
+            self.on_block_done(i)
+
+    def launch_async(self, dY, X, dW, db, done=None):
+        """dW[N][K] = dY^T X, db[N] = colsum(dY) from row-major dY[M][N], X[M][K], both read in place (pa_gemm_tn: transpose-read
+        MFMA operands, deterministic split-K over tokens), on the side stream; optionally report block completion from there
+        (DDP bucket launch)."""
+        if self.frozen:
+            return
+        with self.side.fork(dY, X):
+            fused = db is not None and ops.wgrad_tn_fuses_bias(self.dt) and self.fused_bias
+            self.scratch["part"] = ops.wgrad_tn(dY, X, dW.view(dY.shape[1], -1), self.dt, False, self.scratch.get("part"),
+                                                db=db if fused else None)
+            if db is not None and not fused:
+                ops.colsum(dY, db, accumulate=False)
+            if done is not None:
+                self.report(done)
+
+    def launch(self, dY, X, dW, db, done=None, fuse=False):
+        """A block's weight gradient: into the block's batched launch where there is one (``done`` = block index: this is the
+        block's last, send the batch), else launch_async."""
+        if self.frozen:
+            return
+        pending = self.pending
+        if pending is None:
+            return self.launch_async(dY, X, dW, db, done)
+        # the block's last problem (qkv) -- and fc1, `fuse` -- get their bias gradient out of the batched launch itself (a
+        # ninth MFMA per phase in the tiles of the first X-column block); the compact fc2 of the last block uses the
+        # column-sum kernel right away
+        fused_bias = (done is not None or fuse) and db is not None and self.fused_bias
+        pending.append((dY, X, dW.view(dY.shape[1], -1), False, db if fused_bias else None))
+        if db is not None and not fused_bias:
+            ops.colsum(dY, db)
+        if done is not None:
+            self.scratch["part"] = ops.wgrad_tn_batched(pending, self.dt, self.scratch.get("part"), row_jobs=self.rowjobs)
+            pending.clear()
+            if self.rowjobs is not None:
+                self.rowjobs.clear()
+            self.report(done)
+
+
+def _backward_trunk(model, ctx, dlogits, dfeat, wg):
+    """Head stage, then blocks depth-1 .. 0 of either token layout.  Returns the gradient of the token matrix [M][D] f32 and its
+    16-bit copy (None where the layout's patch stage does not ask for one: ``lay.dx0_lp``)."""
+    dt, lay, st, scratch = ctx["dt"], ctx["lay"], model._staged, model._scratch
+    B, D, H = lay.B, model.embed_dim, model.num_heads
+    g, rowjobs = wg.g, wg.rowjobs
+    # head: logits = hn W^T + b ; hn = LN_1e-5(feat) ; feat = mean of the two normed prefix tokens
+    dhn = ops.linear_f32_bwd(dlogits.contiguous(), ctx["hn"], model.head[1].weight, g["head.1.weight"],
+                             g["head.1.bias"])
+    dxl, part = ops.head_pre_bwd(dhn, dfeat, ctx["xl"], ctx["feat"], model.norm.weight, model.head[0].weight,
+                                 ctx["stats"])
+    part4 = part.view(B, 4, D)
+    for j, name in enumerate(("head.0.weight", "head.0.bias", "norm.weight", "norm.bias")):
+        if not wg.frozen:
+            ops.colsum_f32(part4[:, j, :], g[name])
+    nblk = len(model.blocks)
+    wg.report(nblk)
+    dx = dxl.view(2 * B, D)                 # gradient w.r.t. the compact (prefix-rows) output of the last block
+    dx_lp = ops.convert(dx, dt)
+    for i in range(nblk - 1, -1, -1):
+        blk = model.blocks[i]
+        last = i == nblk - 1
+        pfx = f"blocks.{i}."
+        xs, ln1, mean1, rstd1, qkv, att, lse, x_mid, ln2, mean2, rstd2, h_pre, h_act = ctx["saved"][i]
+        # ---- MLP:  x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))      (on [2B, D] rows for the last block)
+        # fc2.bias gradient = column sums of dx: already produced by the LayerNorm backward that made dx (the next
+        # block's norm1) -- except for the last block, whose dx comes from the head
+        wg.launch(dx_lp, h_act, g[pfx + "mlp.fc2.weight"], g[pfx + "mlp.fc2.bias"] if last else None)
+        # the fc1.bias gradient (column sums of d_pre) comes out of the GELU' epilogue -- unless it rides in the weight-gradient
+        # launch, like qkv.bias (the LDS-free GELU' epilogue -- transposed accumulators, lane = token -- has no lane-local column
+        # sums to offer), or nobody wants it
+        from_epilogue, colsum_args = not (wg.bias_from_wgrad or wg.frozen), {}
+        if from_epilogue:
+            cws = scratch["colsum_ws"] = ops.gemm_colsum_ws(h_pre.shape[0], h_pre.shape[1], dx_lp.device, scratch.get("colsum_ws"))
+            colsum_args = dict(colsum_out=g[pfx + "mlp.fc1.bias"], colsum_ws=cws, defer=rowjobs)
+        d_pre = ops.dgelu_gemm(dx_lp, st.get(blk.mlp.fc2.weight, dt, True), h_pre, dt, **colsum_args)
+        wg.launch(d_pre, ln2, g[pfx + "mlp.fc1.weight"], None if from_epilogue else g[pfx + "mlp.fc1.bias"], fuse=not from_epilogue)
+        d_ln2 = torch.empty_like(ln2)
+        ops.gemm_nt(d_pre, st.get(blk.mlp.fc1.weight, dt, True), dt, EPI_STORE, out_lp=d_ln2)
+        del d_pre
+        dx, dx_lp = ops.layernorm_bwd(d_ln2, x_mid, blk.norm2.weight, mean2, rstd2, dx, g[pfx + "norm2.weight"],
+                                      g[pfx + "norm2.bias"], True, dcolsum=g[pfx + "attn.proj.bias"], defer=rowjobs)
+        # ---- attention:  x_mid = x_in + proj(attn(qkv(LN1(x_in))))      (proj.bias gradient came out of LN2' above)
+        wg.launch(dx_lp, att, g[pfx + "attn.proj.weight"], None)
+        d_att = torch.empty_like(att)
+        ops.gemm_nt(dx_lp, st.get(blk.attn.proj.weight, dt, True), dt, EPI_STORE, out_lp=d_att)
+        if not last:
+            d_qkv = lay.attention_bwd(qkv, att, d_att, lse, H, ctx["scale"], flags=ops.ATTN_Q_PRESCALED)
+            dres = dx
+        else:
+            # only 2 queries per sequence carry a gradient (the Q third of d_qkv is zero elsewhere); the residual gradient lives
+            # on the prefix rows only
+            d_qkv = lay.attention_bwd(qkv, att, d_att, lse, H, ctx["scale"], nq=2, flags=ops.ATTN_Q_PRESCALED)
+            dres = ops.scatter_rows_into_zeros(dx, lay.prefix_rows(dx.device), lay.M)
+        d_ln1 = torch.empty_like(ln1)
+        ops.gemm_nt(d_qkv, st.get(blk.attn.qkv.weight, dt, True), dt, EPI_STORE, out_lp=d_ln1)
+        dx, dx_lp = ops.layernorm_bwd(d_ln1, xs, blk.norm1.weight, mean1, rstd1, dres, g[pfx + "norm1.weight"],
+                                      g[pfx + "norm1.bias"], i > 0 or lay.dx0_lp,
+                                      dcolsum=g[f"blocks.{i - 1}.mlp.fc2.bias"] if i > 0 else None, defer=rowjobs)
+        # last weight gradient of the block; the side stream (ordered after the LayerNorm gradients above)
+        # then reports the block complete, so its all-reduce bucket starts without stalling the main stream
+        wg.launch(d_qkv, ln1, g[pfx + "attn.qkv.weight"], g[pfx + "attn.qkv.bias"], done=i)
+    return dx, dx_lp
+
+
+def _patch_backward(model, ctx, wg, dx, dx_lp, want_dx):
+    """Patch embedding / positional parameters / prefix tokens of the fixed layout (also when frozen: pa_patch_bwd makes the
+    compact dpatch the input gradient starts from), then the input spectrogram's gradient."""
+    dt, lay, p, g, st = ctx["dt"], ctx["lay"], ctx["patch"], wg.g, model._staged
+    Tpe, Fpe = model.time_new_pos_embed.shape[-1], model.freq_new_pos_embed.shape[-2]
+    dpatch = ops.patch_bwd(dx.view(lay.B, lay.Ntok, -1), p["pf"], p["pt"], p["toff"], Tpe, Fpe, g["cls_token"],
+                           g["dist_token"], g["new_pos_embed"], g["patch_embed.proj.bias"],
+                           g["time_new_pos_embed"], g["freq_new_pos_embed"], dt)
+    wg.launch_async(dpatch, p["cols"], g["patch_embed.proj.weight"], None, done=-1)
+    if not want_dx:
+        return None
+    # dcols = dpatch W (the im2col GEMM mirrored), then the fold of the kept patches
+    P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
+    dcols = torch.empty((lay.B * p["Np"], P * P), device=dpatch.device, dtype=dpatch.dtype)
+    ops.gemm_nt(dpatch, st.get(model.patch_embed.proj.weight, dt, True), dt, EPI_STORE, out_lp=dcols)
+    return ops.patch_input_bwd(dcols, p["pf"], p["pt_grid"], lay.B, p["F"], p["T"], P, fs, ts)
+
+
+def _patch_backward_varlen(model, ctx, wg, dx, dx_lp, want_dx):
+    """The packed layout's patch stage: dx is the packed dtok [M][D].  The packed im2col has a zero row under every prefix token, so
+    both GEMMs run over all M rows of dx_lp: no compaction pass."""
+    dt, lay, p, g, st = ctx["dt"], ctx["lay"], ctx["patch"], wg.g, model._staged
+    Tpe, Fpe = model.time_new_pos_embed.shape[-1], model.freq_new_pos_embed.shape[-2]
+    if not wg.frozen:
+        ops.patch_bwd_varlen(dx, lay.cu_tok, lay.B, Tpe, Fpe, g["cls_token"], g["dist_token"], g["new_pos_embed"],
+                             g["patch_embed.proj.bias"], g["time_new_pos_embed"], g["freq_new_pos_embed"])
+    wg.launch_async(dx_lp, p["cols"], g["patch_embed.proj.weight"], None, done=-1)
+    if not want_dx:
+        return None
+    P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
+    dcols = torch.empty((lay.M, P * P), device=dx_lp.device, dtype=dx_lp.dtype)
+    ops.gemm_nt(dx_lp, st.get(model.patch_embed.proj.weight, dt, True), dt, EPI_STORE, out_lp=dcols)
+    return ops.patch_input_bwd_varlen(dcols, lay.cu_tok, lay.B, p["F"], p["T"], P, fs, ts)
+
+
+def _backward(model, ctx, dlogits, dfeat, grads, on_block_done, want_dx, patch_stage):
+    with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
+        wg = _WgradSchedule(model, ctx["dt"], grads, on_block_done, dlogits.device)
+        dx, dx_lp = _backward_trunk(model, ctx, dlogits, dfeat, wg)
+        dx_in = patch_stage(model, ctx, wg, dx, dx_lp, want_dx)
+        wg.side.join()
+    return dx_in
+
+
 def passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done=None, want_dx=False):
     """Backward of passt_forward.  ``grads``: dict param-name -> f32 tensor to OVERWRITE.
     ``on_block_done(i)`` is called after block i's parameter gradients are enqueued (i = depth for the
@@ -556,274 +741,36 @@ def passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done=None, want_d
     positional / head parameter reduction and no ``on_block_done``.  What the activation-gradient kernels produce anyway stays
     where it falls and is never reduced: the LayerNorm backward's dgamma / dbeta partial rows (in that call's own workspace) and
     the head's per-clip LayerNorm partials (pa_head_pre_bwd's ``part``)."""
-    with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
-        return _passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done, want_dx)
-
-
-def _passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done=None, want_dx=False):
-    dt, B, Ntok, Np = ctx["dt"], ctx["B"], ctx["Ntok"], ctx["Np"]
-    st = model._staged
-    D, H = model.embed_dim, model.num_heads
-    M = B * Ntok
-    scratch = model._scratch
-    frozen = grads is None
-    g = _NoGrads() if frozen else grads
-    if frozen:
-        on_block_done = None
-    side = scratch.get("side")
-    if side is not None and side.enabled != bool(getattr(model, "overlap_wgrad", False)):
-        side = None
-    if side is None:
-        side = scratch["side"] = _SideStream(dlogits.device, enabled=getattr(model, "overlap_wgrad", False))
-
-    def wgrad_async(dY, X, dW, db, done=None):
-        """dW, db on the side stream; optionally report block completion from there (DDP bucket launch)."""
-        if frozen:
-            return
-        with side.fork(dY, X):
-            _wgrad_pair(dY, X, dW, db, dt, scratch, False)
-            if done is not None and on_block_done:
-                on_block_done(done)
-
-    # bf16, single stream: the four weight gradients of a block wait until the block's last operand exists and go out as
-    # ONE batched launch (+ one batched split-K reduction): no drain / prologue between them, equal-sized work items
-    pending = [] if (dt == PA_BF16 and not side.enabled and not frozen and not os.environ.get("PASST_AMD_NO_BATCH_WGRAD")) else None
-    # ... and so do the block's small finishing reductions: the two LayerNorms' dgamma | dbeta (+ the bias gradient each carries)
-    # and the GELU' epilogue's fc1.bias rows stay as partial rows and are reduced by the SAME finishing launch as the split-K
-    # slabs (three launches per block less; PASST_AMD_NO_DEFER_ROWS=1: A/B, every reduction right behind its producer)
-    rowjobs = [] if (pending is not None and not os.environ.get("PASST_AMD_NO_DEFER_ROWS")) else None
-    if frozen:
-        rowjobs = _NoRowJobs()      # the LayerNorm backward leaves its parameter-gradient partial rows unreduced
-    # PASST_AMD_BIAS_FROM_WGRAD=1 (A/B; required by PA_EPILOGUE_V3=1): fc1.bias out of the weight-gradient launch instead of the
-    # GELU' epilogue's lane-local column sums
-    bias_from_wgrad = (dt == PA_BF16 and ops.wgrad_tn_fuses_bias(dt) and not os.environ.get("PASST_AMD_NO_FUSED_BIAS")
-                       and (os.environ.get("PASST_AMD_BIAS_FROM_WGRAD") == "1" or os.environ.get("PA_EPILOGUE_V3") == "1"))
-
-    def wgrad(dY, X, dW, db, done=None, fuse=False):
-        if frozen:
-            return
-        if pending is None:
-            return wgrad_async(dY, X, dW, db, done)
-        # the block's last problem (qkv) -- and fc1, `fuse` -- get their bias gradient out of the batched launch itself (a
-        # ninth MFMA per phase in the tiles of the first X-column block); the compact fc2 of the last block uses the
-        # column-sum kernel right away
-        fused_bias = (done is not None or fuse) and db is not None and not os.environ.get("PASST_AMD_NO_FUSED_BIAS")
-        pending.append((dY, X, dW.view(dY.shape[1], -1), False, db if fused_bias else None))
-        if db is not None and not fused_bias:
-            ops.colsum(dY, db)
-        if done is not None:
-            scratch["part"] = ops.wgrad_tn_batched(pending, dt, scratch.get("part"), row_jobs=rowjobs)
-            pending.clear()
-            if rowjobs is not None:
-                rowjobs.clear()
-            if on_block_done:
-                on_block_done(done)
-
-    # head: logits = hn W^T + b ; hn = LN_1e-5(feat) ; feat = mean of the two normed prefix tokens
-    dhn = ops.linear_f32_bwd(dlogits.contiguous(), ctx["hn"], model.head[1].weight, g["head.1.weight"],
-                             g["head.1.bias"])
-    dxl, part = ops.head_pre_bwd(dhn, dfeat, ctx["xl"], ctx["feat"], model.norm.weight, model.head[0].weight,
-                                 ctx["stats"])
-    part4 = part.view(B, 4, D)
-    for j, name in enumerate(("head.0.weight", "head.0.bias", "norm.weight", "norm.bias")):
-        if not frozen:
-            ops.colsum_f32(part4[:, j, :], g[name])
-    if on_block_done:
-        on_block_done(len(model.blocks))
-    nblk = len(model.blocks)
-    dx = dxl.view(2 * B, D)                 # gradient w.r.t. the compact (prefix-rows) output of the last block
-    dx_lp = ops.convert(dx, dt)
-    for i in range(nblk - 1, -1, -1):
-        blk = model.blocks[i]
-        last = i == nblk - 1
-        pfx = f"blocks.{i}."
-        xs, ln1, mean1, rstd1, qkv, att, lse, x_mid, ln2, mean2, rstd2, h_pre, h_act = ctx["saved"][i]
-        # ---- MLP:  x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))      (on [2B, D] rows for the last block)
-        # fc2.bias gradient = column sums of dx: already produced by the LayerNorm backward that made dx (the next
-        # block's norm1) -- except for the last block, whose dx comes from the head
-        wgrad(dx_lp, h_act, g[pfx + "mlp.fc2.weight"], g[pfx + "mlp.fc2.bias"] if last else None)
-        if bias_from_wgrad or frozen:
-            # the fc1.bias gradient (column sums of d_pre) rides in the weight-gradient launch, like qkv.bias (the LDS-free
-            # GELU' epilogue -- transposed accumulators, lane = token -- has no lane-local column sums to offer)
-            d_pre = ops.dgelu_gemm(dx_lp, st.get(blk.mlp.fc2.weight, dt, True), h_pre, dt)
-            wgrad(d_pre, ln2, g[pfx + "mlp.fc1.weight"], g[pfx + "mlp.fc1.bias"], fuse=True)
-        else:
-            # the fc1.bias gradient (column sums of d_pre) comes out of the GELU' epilogue
-            cws = scratch["colsum_ws"] = ops.gemm_colsum_ws(h_pre.shape[0], h_pre.shape[1], dx_lp.device, scratch.get("colsum_ws"))
-            d_pre = ops.dgelu_gemm(dx_lp, st.get(blk.mlp.fc2.weight, dt, True), h_pre, dt,
-                                   colsum_out=g[pfx + "mlp.fc1.bias"], colsum_ws=cws, defer=rowjobs)
-            wgrad(d_pre, ln2, g[pfx + "mlp.fc1.weight"], None)
-        d_ln2 = torch.empty_like(ln2)
-        ops.gemm_nt(d_pre, st.get(blk.mlp.fc1.weight, dt, True), dt, EPI_STORE, out_lp=d_ln2)
-        del d_pre
-        dx, dx_lp = ops.layernorm_bwd(d_ln2, x_mid, blk.norm2.weight, mean2, rstd2, dx, g[pfx + "norm2.weight"],
-                                      g[pfx + "norm2.bias"], True, dcolsum=g[pfx + "attn.proj.bias"], defer=rowjobs)
-        # ---- attention:  x_mid = x_in + proj(attn(qkv(LN1(x_in))))      (proj.bias gradient came out of LN2' above)
-        wgrad(dx_lp, att, g[pfx + "attn.proj.weight"], None)
-        d_att = torch.empty_like(att)
-        ops.gemm_nt(dx_lp, st.get(blk.attn.proj.weight, dt, True), dt, EPI_STORE, out_lp=d_att)
-        if not last:
-            d_qkv = ops.attention_bwd(qkv, att, d_att, lse, B, H, Ntok, ctx["scale"], flags=ops.ATTN_Q_PRESCALED)
-            dres = dx
-        else:
-            # only 2 queries per sequence carry a gradient; the residual gradient lives on the prefix rows only
-            d_qkv = ops.attention_bwd(qkv, att, d_att, lse, B, H, Ntok, ctx["scale"], nq=2, flags=ops.ATTN_Q_PRESCALED)
-            dres = ops.scatter_rows_into_zeros(dx, _prefix_rows(model, B, Ntok, dx.device), M)
-        d_ln1 = torch.empty_like(ln1)
-        ops.gemm_nt(d_qkv, st.get(blk.attn.qkv.weight, dt, True), dt, EPI_STORE, out_lp=d_ln1)
-        dx, dx_lp = ops.layernorm_bwd(d_ln1, xs, blk.norm1.weight, mean1, rstd1, dres, g[pfx + "norm1.weight"],
-                                      g[pfx + "norm1.bias"], i > 0,
-                                      dcolsum=g[f"blocks.{i - 1}.mlp.fc2.bias"] if i > 0 else None, defer=rowjobs)
-        # last weight gradient of the block; the side stream (ordered after the LayerNorm gradients above)
-        # then reports the block complete, so its all-reduce bucket starts without stalling the main stream
-        wgrad(d_qkv, ln1, g[pfx + "attn.qkv.weight"], g[pfx + "attn.qkv.bias"], done=i)
-    # ---- patch embedding / positional parameters / prefix tokens
-    Tpe, Fpe = model.time_new_pos_embed.shape[-1], model.freq_new_pos_embed.shape[-2]
-    dpatch = ops.patch_bwd(dx.view(B, Ntok, D), ctx["pf"], ctx["pt"], ctx["toff"], Tpe, Fpe, g["cls_token"],
-                           g["dist_token"], g["new_pos_embed"], g["patch_embed.proj.bias"],
-                           g["time_new_pos_embed"], g["freq_new_pos_embed"], dt)
-    wgrad_async(dpatch, ctx["cols"], g["patch_embed.proj.weight"], None, done=-1)
-    dx_in = None
-    if want_dx:
-        # ---- input spectrogram: dcols = dpatch W (the im2col GEMM mirrored), then the fold of the kept patches
-        P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
-        dcols = torch.empty((B * Np, P * P), device=dpatch.device, dtype=dpatch.dtype)
-        ops.gemm_nt(dpatch, st.get(model.patch_embed.proj.weight, dt, True), dt, EPI_STORE, out_lp=dcols)
-        dx_in = ops.patch_input_bwd(dcols, ctx["pf"], ctx["pt_grid"], B, ctx["F"], ctx["T"], P, fs, ts)
-    side.join()
-    return dx_in
+    return _backward(model, ctx, dlogits, dfeat, grads, on_block_done, want_dx, _patch_backward)
 
 
 def passt_backward_varlen(model, ctx, dlogits, dfeat, grads, on_block_done=None, want_dx=False):
     """Backward of passt_forward_varlen(save=True): passt_backward's contract (``grads`` dict to OVERWRITE or None = the
     no-weight-gradients mode of a frozen network, ``on_block_done``, ``want_dx`` -> (B, 1, F, T_max) f32 or None) on the packed rows.
-    Everything runs on M = sum of the clips' tokens: the same LayerNorm / GEMM / finishing launches as the fixed path, the packed
-    attention backward (pa_attention_bwd_varlen: always the kernel pair) and the packed patch stage (pa_patch_bwd_varlen,
-    pa_patch_input_bwd_varlen).  A parameter gradient is the sum over the clips of their batch-1 gradients; dx of clip i is what the
-    clip alone gives in its own frames and exactly 0 behind them."""
-    with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
-        return _passt_backward_varlen(model, ctx, dlogits, dfeat, grads, on_block_done, want_dx)
-
-
-def _passt_backward_varlen(model, ctx, dlogits, dfeat, grads, on_block_done=None, want_dx=False):
-    dt, B, M, max_N, cu_tok, pidx = ctx["dt"], ctx["B"], ctx["M"], ctx["max_N"], ctx["cu_tok"], ctx["pidx"]
-    st = model._staged
-    H = model.num_heads
-    scratch = model._scratch
-    frozen = grads is None
-    g = _NoGrads() if frozen else grads
-    if frozen:
-        on_block_done = None
-    side = scratch.get("side")
-    if side is not None and side.enabled != bool(getattr(model, "overlap_wgrad", False)):
-        side = None
-    if side is None:
-        side = scratch["side"] = _SideStream(dlogits.device, enabled=getattr(model, "overlap_wgrad", False))
-
-    def wgrad_async(dY, X, dW, db, done=None):
-        if frozen:
-            return
-        with side.fork(dY, X):
-            _wgrad_pair(dY, X, dW, db, dt, scratch, False)
-            if done is not None and on_block_done:
-                on_block_done(done)
-
-    # as in _passt_backward: bf16 on one stream batches a block's weight gradients and its small finishing reductions
-    pending = [] if (dt == PA_BF16 and not side.enabled and not frozen) else None
-    rowjobs = _NoRowJobs() if frozen else ([] if pending is not None else None)
-
-    def wgrad(dY, X, dW, db, done=None, fuse=False):
-        if frozen:
-            return
-        if pending is None:
-            return wgrad_async(dY, X, dW, db, done)
-        fused_bias = (done is not None or fuse) and db is not None
-        pending.append((dY, X, dW.view(dY.shape[1], -1), False, db if fused_bias else None))
-        if db is not None and not fused_bias:
-            ops.colsum(dY, db)
-        if done is not None:
-            scratch["part"] = ops.wgrad_tn_batched(pending, dt, scratch.get("part"), row_jobs=rowjobs)
-            pending.clear()
-            rowjobs.clear()
-            if on_block_done:
-                on_block_done(done)
-
-    dhn = ops.linear_f32_bwd(dlogits.contiguous(), ctx["hn"], model.head[1].weight, g["head.1.weight"], g["head.1.bias"])
-    dxl, part = ops.head_pre_bwd(dhn, dfeat, ctx["xl"], ctx["feat"], model.norm.weight, model.head[0].weight, ctx["stats"])
-    D = dxl.shape[-1]
-    part4 = part.view(B, 4, D)
-    for j, name in enumerate(("head.0.weight", "head.0.bias", "norm.weight", "norm.bias")):
-        if not frozen:
-            ops.colsum_f32(part4[:, j, :], g[name])
-    nblk = len(model.blocks)
-    if on_block_done:
-        on_block_done(nblk)
-    dx = dxl.view(2 * B, D)                 # gradient w.r.t. the compact (prefix-rows) output of the last block
-    dx_lp = ops.convert(dx, dt)
-    for i in range(nblk - 1, -1, -1):
-        blk = model.blocks[i]
-        last = i == nblk - 1
-        pfx = f"blocks.{i}."
-        xs, ln1, mean1, rstd1, qkv, att, lse, x_mid, ln2, mean2, rstd2, h_pre, h_act = ctx["saved"][i]
-        wgrad(dx_lp, h_act, g[pfx + "mlp.fc2.weight"], g[pfx + "mlp.fc2.bias"] if last else None)
-        if frozen:
-            d_pre = ops.dgelu_gemm(dx_lp, st.get(blk.mlp.fc2.weight, dt, True), h_pre, dt)
-        else:
-            cws = scratch["colsum_ws"] = ops.gemm_colsum_ws(h_pre.shape[0], h_pre.shape[1], dx_lp.device, scratch.get("colsum_ws"))
-            d_pre = ops.dgelu_gemm(dx_lp, st.get(blk.mlp.fc2.weight, dt, True), h_pre, dt, colsum_out=g[pfx + "mlp.fc1.bias"], colsum_ws=cws,
-                                   defer=rowjobs)
-            wgrad(d_pre, ln2, g[pfx + "mlp.fc1.weight"], None)
-        d_ln2 = torch.empty_like(ln2)
-        ops.gemm_nt(d_pre, st.get(blk.mlp.fc1.weight, dt, True), dt, EPI_STORE, out_lp=d_ln2)
-        del d_pre
-        dx, dx_lp = ops.layernorm_bwd(d_ln2, x_mid, blk.norm2.weight, mean2, rstd2, dx, g[pfx + "norm2.weight"], g[pfx + "norm2.bias"], True,
-                                      dcolsum=g[pfx + "attn.proj.bias"], defer=rowjobs)
-        wgrad(dx_lp, att, g[pfx + "attn.proj.weight"], None)
-        d_att = torch.empty_like(att)
-        ops.gemm_nt(dx_lp, st.get(blk.attn.proj.weight, dt, True), dt, EPI_STORE, out_lp=d_att)
-        if not last:
-            d_qkv = ops.attention_bwd_varlen(qkv, att, d_att, lse, cu_tok, B, H, max_N, ctx["scale"], flags=ops.ATTN_Q_PRESCALED)
-            dres = dx
-        else:
-            # only 2 queries per clip carry a gradient (the kernel pair writes the rest of the Q third as zero); the residual
-            # gradient lives on the prefix rows only
-            d_qkv = ops.attention_bwd_varlen(qkv, att, d_att, lse, cu_tok, B, H, max_N, ctx["scale"], nq=2, flags=ops.ATTN_Q_PRESCALED)
-            dres = ops.scatter_rows_into_zeros(dx, pidx, M)
-        d_ln1 = torch.empty_like(ln1)
-        ops.gemm_nt(d_qkv, st.get(blk.attn.qkv.weight, dt, True), dt, EPI_STORE, out_lp=d_ln1)
-        # (block 0 also wants the 16-bit copy: it feeds the patch stage's two GEMMs)
-        dx, dx_lp = ops.layernorm_bwd(d_ln1, xs, blk.norm1.weight, mean1, rstd1, dres, g[pfx + "norm1.weight"], g[pfx + "norm1.bias"], True,
-                                      dcolsum=g[f"blocks.{i - 1}.mlp.fc2.bias"] if i > 0 else None, defer=rowjobs)
-        wgrad(d_qkv, ln1, g[pfx + "attn.qkv.weight"], g[pfx + "attn.qkv.bias"], done=i)
-    # ---- patch embedding / positional parameters / prefix tokens: dx is the packed dtok [M][D].  The packed im2col has a zero row under
-    # every prefix token, so both GEMMs run over all M rows: no compaction pass
-    Tpe, Fpe = model.time_new_pos_embed.shape[-1], model.freq_new_pos_embed.shape[-2]
-    if not frozen:
-        ops.patch_bwd_varlen(dx, cu_tok, B, Tpe, Fpe, g["cls_token"], g["dist_token"], g["new_pos_embed"], g["patch_embed.proj.bias"],
-                             g["time_new_pos_embed"], g["freq_new_pos_embed"])
-    wgrad_async(dx_lp, ctx["cols"], g["patch_embed.proj.weight"], None, done=-1)
-    dx_in = None
-    if want_dx:
-        P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
-        dcols = torch.empty((M, P * P), device=dx_lp.device, dtype=dx_lp.dtype)
-        ops.gemm_nt(dx_lp, st.get(model.patch_embed.proj.weight, dt, True), dt, EPI_STORE, out_lp=dcols)
-        dx_in = ops.patch_input_bwd_varlen(dcols, cu_tok, B, ctx["F"], ctx["T"], P, fs, ts)
-    side.join()
-    return dx_in
+    Everything runs on M = sum of the clips' tokens: the same head / block sequence and weight-gradient scheduling as the fixed path
+    (_backward_trunk, _WgradSchedule), the packed attention backward (pa_attention_bwd_varlen: always the kernel pair) and the packed
+    patch stage (pa_patch_bwd_varlen, pa_patch_input_bwd_varlen).  A parameter gradient is the sum over the clips of their batch-1
+    gradients; dx of clip i is what the clip alone gives in its own frames and exactly 0 behind them."""
+    return _backward(model, ctx, dlogits, dfeat, grads, on_block_done, want_dx, _patch_backward_varlen)
 
 
 class _PasstFunction(torch.autograd.Function):
-    """One autograd node for the whole network: forward/backward are kernel sequences, torch only
-    sees (x, *parameters) -> (logits, features)."""
+    """One autograd node for the whole network: forward/backward are kernel sequences, torch only sees
+    (x, *parameters) -> (logits, features).  ``lengths``: None = the fixed path, else the packed ragged-batch forward
+    (``net.varlen_grad = True``) with the packed backward; same ``grads`` / ``on_block_done`` contract, same flat-buffer and reducer
+    routes."""
 
     @staticmethod
-    def forward(ctx, model, x, *params):
-        logits, feat, c = passt_forward(model, x, save=True)
-        ctx.model, ctx.c = model, c
+    def forward(ctx, model, lengths, x, *params):
+        if lengths is None:
+            logits, feat, c = passt_forward(model, x, save=True)
+        else:
+            logits, feat, c = passt_forward_varlen(model, x, lengths, save=True)
+        ctx.model, ctx.c, ctx.varlen = model, c, lengths is not None
         # the input spectrogram's gradient is computed only when asked for; a graph none of whose parameters requires a gradient
         # (a frozen loss network) runs the backward without any weight-gradient work
-        ctx.want_dx = bool(ctx.needs_input_grad[1])
-        ctx.frozen = not any(ctx.needs_input_grad[2:])
+        ctx.want_dx = bool(ctx.needs_input_grad[2])
+        ctx.frozen = not any(ctx.needs_input_grad[3:])
         ctx.named, ctx.total = model._graph_params(validate=False)     # the list forward() just handed to apply()
         # bound to a passt_amd.optim.AdamW (PaSST.bind_flat_grads): the only input is a token; the backward writes the gradients
         # straight into the optimizer's persistent flat buffer -- p.grad are views of it -- and hands autograd nothing
@@ -833,93 +780,69 @@ class _PasstFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits, dfeat):
-        return _node_backward(ctx, dlogits, dfeat, passt_backward, (None,))
-
-
-class _PasstVarlenFunction(torch.autograd.Function):
-    """_PasstFunction's sibling for the packed ragged-batch forward (``net.varlen_grad = True``): (x, lengths, *parameters) -> (logits,
-    features).  Same ``grads`` / ``on_block_done`` contract, same flat-buffer and reducer routes: the backward is _node_backward over
-    passt_backward_varlen."""
-
-    @staticmethod
-    def forward(ctx, model, lengths, x, *params):
-        logits, feat, c = passt_forward_varlen(model, x, lengths, save=True)
-        ctx.model, ctx.c = model, c
-        ctx.want_dx = bool(ctx.needs_input_grad[2])
-        ctx.frozen = not any(ctx.needs_input_grad[3:])
-        ctx.named, ctx.total = model._graph_params(validate=False)
-        ctx.flat = model._flat if (len(params) == 1 and model._flat is not None and params[0] is model._flat["token"]) else None
-        ctx.set_materialize_grads(False)
-        return logits, feat
-
-    @staticmethod
-    def backward(ctx, dlogits, dfeat):
-        return _node_backward(ctx, dlogits, dfeat, passt_backward_varlen, (None, None))
-
-
-def _node_backward(ctx, dlogits, dfeat, run_backward, lead):
-    """The backward of both autograd nodes.  ``run_backward``: passt_backward / passt_backward_varlen; ``lead``: the Nones handed back for
-    the node's inputs in front of x (the model; the lengths)."""
-    model, c = ctx.model, ctx.c
-    if c is None:
-        raise RuntimeError("passt_amd.PaSST: the saved activations of this forward were already consumed by a backward "
-                           "pass (retain_graph / double backward are not supported: run the forward again)")
-    # gradient buffers for EVERY parameter the backward writes (all but head_dist.*): the kernel sequence produces
-    # them all; parameters with requires_grad=False are simply not handed back to autograd (frozen backbone, ...)
-    named, total = ctx.named, ctx.total
-    fl = ctx.flat
-    if dlogits is not None:
+        model, c = ctx.model, ctx.c
+        if c is None:
+            raise RuntimeError("passt_amd.PaSST: the saved activations of this forward were already consumed by a backward "
+                               "pass (retain_graph / double backward are not supported: run the forward again)")
+        run_backward = passt_backward_varlen if ctx.varlen else passt_backward
+        lead = (None, None)                     # the model, the lengths
+        # gradient buffers for EVERY parameter the backward writes (all but head_dist.*): the kernel sequence produces
+        # them all; parameters with requires_grad=False are simply not handed back to autograd (frozen backbone, ...)
+        named, total = ctx.named, ctx.total
+        fl = ctx.flat
+        B = c["lay"].B
+        if dlogits is not None:
+            dlogits = dlogits.contiguous()
+        if ctx.frozen:
+            # nothing but the input asked for a gradient: no flat buffer, no weight-gradient launch, no reducer (dx is a local quantity)
+            if dlogits is None:
+                dlogits = torch.zeros((B, model.num_classes), device=dfeat.device, dtype=torch.float32)
+            dx = run_backward(model, c, dlogits, None if dfeat is None else dfeat.contiguous(), None, want_dx=ctx.want_dx)
+            ctx.c = None
+            return lead + (dx,) + (None,) * (len(named) if fl is None else 1)
+        if fl is not None and fl["fresh"]:
+            flat, grads = fl["flat_g"], fl["grads"]     # overwritten in place: the caller zeroed (optimizer.zero_grad()) since the last backward
+        else:
+            flat = torch.empty(total, device=(dfeat if dlogits is None else dlogits).device, dtype=torch.float32)
+            # one C++ call makes the 159 views (a Python loop of slice + view costs 1.3 ms of host time in front of the first
+            # backward kernel: exposed whenever the caller synchronised in this step, and the reference's mixup does)
+            views = torch._C._nn.unflatten_dense_tensors(flat, [p for _, p in named])
+            grads = {n: v for (n, _), v in zip(named, views)}
+        # a fresh flat buffer per backward: autograd may keep (not copy) the views as .grad
+        if dlogits is None:                     # only `features` fed the loss
+            dlogits = torch.zeros((B, model.num_classes), device=flat.device, dtype=torch.float32)
         dlogits = dlogits.contiguous()
-    if ctx.frozen:
-        # nothing but the input asked for a gradient: no flat buffer, no weight-gradient launch, no reducer (dx is a local quantity)
-        if dlogits is None:
-            dlogits = torch.zeros((c["B"], model.num_classes), device=dfeat.device, dtype=torch.float32)
-        dx = run_backward(model, c, dlogits, None if dfeat is None else dfeat.contiguous(), None, want_dx=ctx.want_dx)
+        dfeat = None if dfeat is None else dfeat.contiguous()
+        red = getattr(model, "_ddp", None)
+        if red is not None and red.world > 1:
+            # passt_amd.ddp.attach(net): this node reduces its own gradients.  `flat` is laid out like the reducer's buckets
+            # (named_parameters() order without head_dist.*); every bucket's all-reduce starts from on_block_done while the
+            # rest of the backward runs, and the node returns once the current stream is ordered behind the last bucket.
+            # Mean over ranks (DDP's semantics) = sum of gradients of loss / world: the backward is linear in (dlogits, dfeat).
+            if flat.numel() != red.total:
+                raise RuntimeError("passt_amd.ddp.attach: the parameter set changed since attach(); call attach(net) again")
+            inv = 1.0 / red.world
+            dlogits = dlogits * inv
+            dfeat = None if dfeat is None else dfeat * inv
+            red.flat = flat
+            try:
+                dx = run_backward(model, c, dlogits, dfeat, grads, on_block_done=red.on_block_done, want_dx=ctx.want_dx)
+            finally:
+                red.wait()              # also after an exception: no collective may stay in flight on a buffer we drop
+            if dx is not None:
+                dx.mul_(float(red.world))       # not reduced: the gradient of THIS rank's loss (dlogits went in divided by world)
+        else:
+            dx = run_backward(model, c, dlogits, dfeat, grads, want_dx=ctx.want_dx)
         ctx.c = None
-        return lead + (dx,) + (None,) * (len(named) if fl is None else 1)
-    if fl is not None and fl["fresh"]:
-        flat, grads = fl["flat_g"], fl["grads"]     # overwritten in place: the caller zeroed (optimizer.zero_grad()) since the last backward
-    else:
-        flat = torch.empty(total, device=(dfeat if dlogits is None else dlogits).device, dtype=torch.float32)
-        # one C++ call makes the 159 views (a Python loop of slice + view costs 1.3 ms of host time in front of the first
-        # backward kernel: exposed whenever the caller synchronised in this step, and the reference's mixup does)
-        views = torch._C._nn.unflatten_dense_tensors(flat, [p for _, p in named])
-        grads = {n: v for (n, _), v in zip(named, views)}
-    # a fresh flat buffer per backward: autograd may keep (not copy) the views as .grad
-    if dlogits is None:                     # only `features` fed the loss
-        dlogits = torch.zeros((c["B"], model.num_classes), device=flat.device, dtype=torch.float32)
-    dlogits = dlogits.contiguous()
-    dfeat = None if dfeat is None else dfeat.contiguous()
-    red = getattr(model, "_ddp", None)
-    if red is not None and red.world > 1:
-        # passt_amd.ddp.attach(net): this node reduces its own gradients.  `flat` is laid out like the reducer's buckets
-        # (named_parameters() order without head_dist.*); every bucket's all-reduce starts from on_block_done while the
-        # rest of the backward runs, and the node returns once the current stream is ordered behind the last bucket.
-        # Mean over ranks (DDP's semantics) = sum of gradients of loss / world: the backward is linear in (dlogits, dfeat).
-        if flat.numel() != red.total:
-            raise RuntimeError("passt_amd.ddp.attach: the parameter set changed since attach(); call attach(net) again")
-        inv = 1.0 / red.world
-        dlogits = dlogits * inv
-        dfeat = None if dfeat is None else dfeat * inv
-        red.flat = flat
-        try:
-            dx = run_backward(model, c, dlogits, dfeat, grads, on_block_done=red.on_block_done, want_dx=ctx.want_dx)
-        finally:
-            red.wait()              # also after an exception: no collective may stay in flight on a buffer we drop
-        if dx is not None:
-            dx.mul_(float(red.world))       # not reduced: the gradient of THIS rank's loss (dlogits went in divided by world)
-    else:
-        dx = run_backward(model, c, dlogits, dfeat, grads, want_dx=ctx.want_dx)
-    ctx.c = None
-    if fl is not None:
-        if not fl["fresh"]:                 # a second backward without zero_grad (gradient accumulation): add, as AccumulateGrad would
-            fl["flat_g"].add_(flat)
-        fl["fresh"] = False
-        return lead + (dx, None)
-    out = list(lead) + [dx]
-    for n, p in named:                      # the same list, in the same order, as PaSST.forward handed to apply()
-        out.append(grads[n] if p.requires_grad else None)
-    return tuple(out)
+        if fl is not None:
+            if not fl["fresh"]:                 # a second backward without zero_grad (gradient accumulation): add, as AccumulateGrad would
+                fl["flat_g"].add_(flat)
+            fl["fresh"] = False
+            return lead + (dx, None)
+        out = list(lead) + [dx]
+        for n, p in named:                      # the same list, in the same order, as PaSST.forward handed to apply()
+            out.append(grads[n] if p.requires_grad else None)
+        return tuple(out)
 
 
 def _tree_signature(root):
@@ -1161,43 +1084,41 @@ class PaSST(nn.Module):
         flow).  Under ``torch.autocast`` of either 16-bit type (Lightning precision=16 / torch.cuda.amp.autocast() are fp16) the
         kernels run the bf16 MFMA path with f32 accumulation and return f32 logits / features: bf16 has f32's exponent range,
         so a GradScaler's loss scale flows through the backward without overflow and its inf checks never fire."""
-        if lengths is not None:
-            if self.training:
-                raise NotImplementedError("PaSST.forward(x, lengths=...): training on ragged batches is not supported (eval mode only; "
-                                          "no reference flow trains on clips of different lengths)")
-            if getattr(self, "varlen_grad", False) and torch.is_grad_enabled():
-                want_dx = torch.is_tensor(x) and x.requires_grad
-                named = self._graph_params()[0]
-                if want_dx or any(p.requires_grad for _, p in named):
-                    if want_dx:
-                        x = x.contiguous().float()      # where autograd sees it: x.grad comes back in the caller's shape, dtype and layout
-                    fl = self._flat
-                    if fl is not None:
-                        if fl["named"] is named:
-                            return _PasstVarlenFunction.apply(self, lengths, x, fl["token"])
-                        self.unbind_flat_grads()
-                    return _PasstVarlenFunction.apply(self, lengths, x, *[p for _, p in named])
-            with torch.no_grad():
-                return passt_forward_varlen(self, x, lengths)
-        want_dx = torch.is_grad_enabled() and torch.is_tensor(x) and x.requires_grad
-        if want_dx and not getattr(self, "input_grad", False) and any(p.requires_grad for _, p in self._graph_params()[0]):
-            raise NotImplementedError("passt_amd.PaSST with trainable parameters produces a gradient w.r.t. its input spectrogram only "
-                                      "when asked to: set net.input_grad = True (or freeze the network: net.requires_grad_(False); "
-                                      "or detach() the input)")
-        if want_dx:
-            # the kernels read a dense f32 spectrogram: the conversion happens where autograd sees it, so x.grad comes back in the
-            # caller's own shape, dtype and layout (a sliced / transposed / 16-bit x)
-            x = x.contiguous().float()
-        if torch.is_grad_enabled() and (want_dx or any(p.requires_grad for p in self.parameters())):
+        if lengths is not None and self.training:
+            raise NotImplementedError("PaSST.forward(x, lengths=...): training on ragged batches is not supported (eval mode only; "
+                                      "no reference flow trains on clips of different lengths)")
+        grad = torch.is_grad_enabled()
+        want_dx = grad and torch.is_tensor(x) and x.requires_grad
+        named = None
+        if lengths is None:
+            if want_dx and not getattr(self, "input_grad", False) and any(p.requires_grad for _, p in self._graph_params()[0]):
+                raise NotImplementedError("passt_amd.PaSST with trainable parameters produces a gradient w.r.t. its input spectrogram only "
+                                          "when asked to: set net.input_grad = True (or freeze the network: net.requires_grad_(False); "
+                                          "or detach() the input)")
             # head_dist.* is not part of the graph -- as in the reference, whose forward never touches it
             # (models/passt.py:583-595; hence find_unused_parameters=True under torch DDP there and here)
+            node = grad and (want_dx or any(p.requires_grad for p in self.parameters()))
+        elif grad and getattr(self, "varlen_grad", False):
             named = self._graph_params()[0]
+            node = want_dx or any(p.requires_grad for _, p in named)
+        else:
+            node = False                                # the ragged forward records nothing unless asked to
+        if node:
+            if want_dx:
+                # the kernels read a dense f32 spectrogram: the conversion happens where autograd sees it, so x.grad comes back in the
+                # caller's own shape, dtype and layout (a sliced / transposed / 16-bit x)
+                x = x.contiguous().float()
+            if named is None:
+                named = self._graph_params()[0]
             fl = self._flat
             if fl is not None:
                 if fl["named"] is named:                # same validated parameter list as at bind time
-                    return _PasstFunction.apply(self, x, fl["token"])
+                    return _PasstFunction.apply(self, lengths, x, fl["token"])
                 self.unbind_flat_grads()                # surgery since: the optimizer re-binds at its next step
-            return _PasstFunction.apply(self, x, *[p for _, p in named])
+            return _PasstFunction.apply(self, lengths, x, *[p for _, p in named])
+        if lengths is not None:
+            with torch.no_grad():
+                return passt_forward_varlen(self, x, lengths)
         logits, feat, _ = passt_forward(self, x, save=False)
         return logits, feat
 
