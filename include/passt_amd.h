@@ -169,6 +169,17 @@ int pa_layernorm_bwd_rows(int M);
 int pa_layernorm_bwd_partial(const void* dy, int dtype, const float* x, const float* gamma,
                              const float* mean, const float* rstd, const float* dres, float* dx,
                              void* dx_lp, float* ws, int M, int D, void* stream);
+/* Both with a second optional addend: dx = (dres ? dres : 0) + (dres2 ? dres2 : 0) + LN'(dy).  dres2 is a gradient injected into
+ * the residual stream at this LayerNorm's input (a loss on a block's output tokens): it enters before the 16-bit copy and the
+ * column sums are formed, so dx_lp and dcolsum (the bias gradient of the Linear behind that output) include it.  With dres2 NULL
+ * the results are bit-identical to pa_layernorm_bwd / pa_layernorm_bwd_partial. */
+int pa_layernorm_bwd2(const void* dy, int dtype, const float* x, const float* gamma,
+                      const float* mean, const float* rstd, const float* dres, const float* dres2, float* dx,
+                      void* dx_lp, float* dgamma, float* dbeta, float* dcolsum, int accumulate, float* ws,
+                      int M, int D, void* stream);
+int pa_layernorm_bwd2_partial(const void* dy, int dtype, const float* x, const float* gamma,
+                              const float* mean, const float* rstd, const float* dres, const float* dres2, float* dx,
+                              void* dx_lp, float* ws, int M, int D, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * GEMM  C[M][N] = A[M][K] * B[N][K]^T  (both operands K-contiguous), MFMA, f32 accumulation.
@@ -291,6 +302,11 @@ int pa_gemm_tn_batched(const pa_gemm_args* a, int n, void* stream);
  * gather: out[i] = in[idx[i]]; scatter: out[idx[i]] = in[i]; rows of row_bytes bytes (multiple of 4). */
 int pa_gather_rows(const void* in, const int32_t* idx, int n_idx, int64_t row_bytes, void* out, void* stream);
 int pa_scatter_rows(const void* in, const int32_t* idx, int n_idx, int64_t row_bytes, void* out, void* stream);
+/* Gradient of the last block's full-rows output: dx[M][D] = (add0 ? add0 : 0) + (add1 ? add1 : 0) + scatter(rows[n_idx][D] at
+ * idx), f32, plus the copy dx_lp (dtype; optional) in the same pass.  idx: strictly ascending rows in [0, M); a row idx does not
+ * name gets the addends only (zero when both are NULL).  Replaces pa_zero2d + pa_scatter_rows + an add. */
+int pa_tail_inject(const float* rows, const int32_t* idx, int n_idx, const float* add0, const float* add1, float* dx,
+                   void* dx_lp, int dtype, int M, int D, void* stream);
 /* zero `rows` rows of width_bytes at pitch_bytes */
 int pa_zero2d(void* ptr, int64_t pitch_bytes, int64_t width_bytes, int64_t rows, void* stream);
 /* out[i] = (accumulate ? out[i] : 0) + sum_z partial[z][i], i < n */

@@ -66,6 +66,9 @@ SIGNATURES = {
     "pa_layernorm_bwd": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp]),
     "pa_layernorm_bwd_rows": (i32, [i32]),
     "pa_layernorm_bwd_partial": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "pa_layernorm_bwd2": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp]),
+    "pa_layernorm_bwd2_partial": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "pa_tail_inject": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp]),
     "pa_gemm_last_colsum_rows": (i32, []),
     "pa_gemm_colsum_ws_floats": (i64, [i32, i32]),
     "pa_gemm_blocked_pre_ok": (i32, [i32, i32, i32]),

@@ -264,6 +264,43 @@ __global__ __launch_bounds__(256) void ce_mixup_kernel(const float* __restrict__
     }
 }
 
+// Gradient of the last block's FULL output (a caller asked for the last block's tokens or for the final norm of every row):
+// dx[r] = (add0 ? add0[r] : 0) + (add1 ? add1[r] : 0) + (r == idx[j] ? rows[j] : 0), f32 plus the 16-bit copy the next GEMM reads,
+// in one pass -- the head's gradient lives on the n_idx prefix rows only and is scattered while the addends stream by.  One wave
+// per row, float4 columns; idx is strictly ascending (cls / dist rows of consecutive clips), so a row finds its entry by a binary
+// search of a table that stays in cache.  No atomics: every output element has one writer.
+template <typename T> __device__ __forceinline__ void tail_store4(T* p, const float4& v);
+template <> __device__ __forceinline__ void tail_store4<float>(float* p, const float4& v) { *(float4*)p = v; }
+template <> __device__ __forceinline__ void tail_store4<bf16>(bf16* p, const float4& v) {
+    bf16x4 o; o[0] = (bf16)v.x; o[1] = (bf16)v.y; o[2] = (bf16)v.z; o[3] = (bf16)v.w;
+    *(bf16x4*)p = o;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void tail_inject_kernel(const float* __restrict__ rows, const int32_t* __restrict__ idx, int n_idx,
+                                                          const float* __restrict__ add0, const float* __restrict__ add1,
+                                                          float* __restrict__ dx, T* __restrict__ dx_lp, int M, int D) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    int lo = 0, hi = n_idx;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (idx[mid] < row) lo = mid + 1; else hi = mid;
+    }
+    const float* src = (lo < n_idx && idx[lo] == row) ? rows + (int64_t)lo * D : nullptr;
+    const int64_t base = (int64_t)row * D;
+    const int nv = D >> 2;
+    for (int c = lane; c < nv; c += 64) {
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (add0) { const float4 a = *(const float4*)(add0 + base + 4 * c); o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w; }
+        if (add1) { const float4 a = *(const float4*)(add1 + base + 4 * c); o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w; }
+        if (src) { const float4 a = *(const float4*)(src + 4 * c); o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w; }
+        *(float4*)(dx + base + 4 * c) = o;
+        if (dx_lp) tail_store4<T>(dx_lp + base + 4 * c, o);
+    }
+}
+
 }  // namespace pa
 
 using namespace pa;
@@ -285,6 +322,17 @@ extern "C" int pa_head_pre_bwd(const float* dhn, const float* dfeat, const float
     if (D > 256 * HEAD_MAXE || D % 4) return PA_EUNSUPPORTED;
     hipLaunchKernelGGL(head_pre_bwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, dhn, dfeat, x, feat, Ntok, D,
                        norm_g, hg, stats, dx, part);
+    return check_launch();
+}
+
+extern "C" int pa_tail_inject(const float* rows, const int32_t* idx, int n_idx, const float* add0, const float* add1, float* dx,
+                              void* dx_lp, int dtype, int M, int D, void* stream) {
+    if (!dx || M <= 0 || D <= 0 || n_idx < 0 || (n_idx > 0 && (!rows || !idx))) return PA_EINVAL;
+    if (D % 4) return PA_EUNSUPPORTED;
+    if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
+    const dim3 grid((unsigned)cdiv(M, 4));
+    if (dtype == PA_BF16) hipLaunchKernelGGL(tail_inject_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, rows, idx, n_idx, add0, add1, dx, (bf16*)dx_lp, M, D);
+    else hipLaunchKernelGGL(tail_inject_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, rows, idx, n_idx, add0, add1, dx, (float*)dx_lp, M, D);
     return check_launch();
 }
 

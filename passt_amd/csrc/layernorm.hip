@@ -81,15 +81,18 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 
 // dx = dres + rstd * (dy*gamma - mean(dy*gamma) - xhat * mean(dy*gamma*xhat));  per-block partial
 // column sums of dy*xhat (dgamma) and dy (dbeta) go to ws[block][2][D].
-template <typename T, int MAXV>
-__global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, const float* __restrict__ x,
+// ADD2: a second addend dres2 (the gradient a caller injects into the residual stream at this block boundary) joins dx before
+// the 16-bit copy and the column sums are taken, so both see it.  ADD2 = false is the kernel as it always was (dres2 is not read).
+template <typename T, int MAXV, bool ADD2>
+__device__ __forceinline__ void ln_bwd_body(const T* __restrict__ dy, const float* __restrict__ x,
                                                      const float* __restrict__ gamma, const float* __restrict__ mean,
                                                      const float* __restrict__ rstd, const float* __restrict__ dres,
+                                                     const float* __restrict__ dres2,
                                                      float* __restrict__ dx, T* __restrict__ dx_lp,
-                                                     float* __restrict__ ws, int M, int D) {
+                                                     float* __restrict__ ws, int M, int D, float* red) {
     // ws[block][3][D]: partial column sums of dy*xhat (dgamma), dy (dbeta) and of the OUTPUT dx (the bias gradient
     // of the Linear that produced this LayerNorm's input: proj for norm2, the previous block's fc2 for norm1)
-    extern __shared__ __attribute__((aligned(16))) float red[];   // [4][3][D]
+    // red: dynamic LDS [4][3][D]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nv = D >> 2;
     float4 g[MAXV], ag[MAXV], ab[MAXV], ac[MAXV];
@@ -132,6 +135,10 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
                     const float4 dr = ldrow4(dres + base + 4 * c);
                     o.x += dr.x; o.y += dr.y; o.z += dr.z; o.w += dr.w;
                 }
+                if (ADD2) {
+                    const float4 dr = ldrow4(dres2 + base + 4 * c);
+                    o.x += dr.x; o.y += dr.y; o.z += dr.z; o.w += dr.w;
+                }
                 {
                     *(float4*)(dx + base + 4 * c) = o;
                 }
@@ -158,6 +165,28 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
         for (int w = 0; w < 4; ++w) s += red[(w * 3 + which) * D + c];
         ws[(int64_t)blockIdx.x * 3 * D + k] = s;
     }
+}
+
+template <typename T, int MAXV>
+__global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, const float* __restrict__ x,
+                                                     const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                     const float* __restrict__ rstd, const float* __restrict__ dres,
+                                                     float* __restrict__ dx, T* __restrict__ dx_lp,
+                                                     float* __restrict__ ws, int M, int D) {
+    extern __shared__ __attribute__((aligned(16))) float red[];   // [4][3][D]
+    ln_bwd_body<T, MAXV, false>(dy, x, gamma, mean, rstd, dres, nullptr, dx, dx_lp, ws, M, D, red);
+}
+
+// the two-addend form (pa_layernorm_bwd2*): a kernel of its own, so the one above stays what it was
+template <typename T, int MAXV>
+__global__ __launch_bounds__(256) void ln_bwd2_kernel(const T* __restrict__ dy, const float* __restrict__ x,
+                                                      const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                      const float* __restrict__ rstd, const float* __restrict__ dres,
+                                                      const float* __restrict__ dres2,
+                                                      float* __restrict__ dx, T* __restrict__ dx_lp,
+                                                      float* __restrict__ ws, int M, int D) {
+    extern __shared__ __attribute__((aligned(16))) float red[];   // [4][3][D]
+    ln_bwd_body<T, MAXV, true>(dy, x, gamma, mean, rstd, dres, dres2, dx, dx_lp, ws, M, D, red);
 }
 
 // out[which][c] (+)= sum_b ws[b][which][c], which = dgamma | dbeta | dcol(optional);  block = 16 columns x 16 row
@@ -229,7 +258,7 @@ extern "C" int64_t pa_layernorm_bwd_ws_floats(int M, int D) { return (int64_t)ln
 extern "C" int pa_layernorm_bwd_rows(int M) { return M > 0 ? ln_bwd_blocks(M) : 0; }
 
 static int ln_bwd_launch(const void* dy, int dtype, const float* x, const float* gamma, const float* mean, const float* rstd,
-                         const float* dres, float* dx, void* dx_lp, float* ws, int M, int D, hipStream_t st);
+                         const float* dres, const float* dres2, float* dx, void* dx_lp, float* ws, int M, int D, hipStream_t st);
 
 extern "C" int pa_layernorm_bwd_partial(const void* dy, int dtype, const float* x, const float* gamma,
                                         const float* mean, const float* rstd, const float* dres, float* dx,
@@ -237,35 +266,63 @@ extern "C" int pa_layernorm_bwd_partial(const void* dy, int dtype, const float* 
     if (!dy || !x || !gamma || !mean || !rstd || !dx || !ws || M <= 0 || D <= 0) return PA_EINVAL;
     if (D % 4 || D > LN_MAXV * 256) return PA_EUNSUPPORTED;
     if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
-    return ln_bwd_launch(dy, dtype, x, gamma, mean, rstd, dres, dx, dx_lp, ws, M, D, (hipStream_t)stream);
+    return ln_bwd_launch(dy, dtype, x, gamma, mean, rstd, dres, nullptr, dx, dx_lp, ws, M, D, (hipStream_t)stream);
+}
+
+extern "C" int pa_layernorm_bwd2_partial(const void* dy, int dtype, const float* x, const float* gamma,
+                                         const float* mean, const float* rstd, const float* dres, const float* dres2,
+                                         float* dx, void* dx_lp, float* ws, int M, int D, void* stream) {
+    if (!dy || !x || !gamma || !mean || !rstd || !dx || !ws || M <= 0 || D <= 0) return PA_EINVAL;
+    if (D % 4 || D > LN_MAXV * 256) return PA_EUNSUPPORTED;
+    if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
+    return ln_bwd_launch(dy, dtype, x, gamma, mean, rstd, dres, dres2, dx, dx_lp, ws, M, D, (hipStream_t)stream);
+}
+
+static int ln_bwd_finish(const void* dy, int dtype, const float* x, const float* gamma, const float* mean, const float* rstd,
+                         const float* dres, const float* dres2, float* dx, void* dx_lp, float* dgamma, float* dbeta, float* dcolsum,
+                         int accumulate, float* ws, int M, int D, void* stream) {
+    if (!dy || !x || !gamma || !mean || !rstd || !dx || !dgamma || !dbeta || !ws || M <= 0 || D <= 0) return PA_EINVAL;
+    if (D % 4 || D > LN_MAXV * 256) return PA_EUNSUPPORTED;
+    if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = ln_bwd_launch(dy, dtype, x, gamma, mean, rstd, dres, dres2, dx, dx_lp, ws, M, D, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((unsigned)cdiv(3 * D, 16)), dim3(256), 0, st, ws, ln_bwd_blocks(M), D, dgamma, dbeta, dcolsum, accumulate);
+    return check_launch();
+}
+
+extern "C" int pa_layernorm_bwd2(const void* dy, int dtype, const float* x, const float* gamma,
+                                 const float* mean, const float* rstd, const float* dres, const float* dres2, float* dx,
+                                 void* dx_lp, float* dgamma, float* dbeta, float* dcolsum, int accumulate, float* ws,
+                                 int M, int D, void* stream) {
+    return ln_bwd_finish(dy, dtype, x, gamma, mean, rstd, dres, dres2, dx, dx_lp, dgamma, dbeta, dcolsum, accumulate, ws, M, D, stream);
 }
 
 extern "C" int pa_layernorm_bwd(const void* dy, int dtype, const float* x, const float* gamma,
                                 const float* mean, const float* rstd, const float* dres, float* dx,
                                 void* dx_lp, float* dgamma, float* dbeta, float* dcolsum, int accumulate, float* ws,
                                 int M, int D, void* stream) {
-    if (!dy || !x || !gamma || !mean || !rstd || !dx || !dgamma || !dbeta || !ws || M <= 0 || D <= 0) return PA_EINVAL;
-    if (D % 4 || D > LN_MAXV * 256) return PA_EUNSUPPORTED;
-    if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = ln_bwd_launch(dy, dtype, x, gamma, mean, rstd, dres, dx, dx_lp, ws, M, D, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((unsigned)cdiv(3 * D, 16)), dim3(256), 0, st, ws, ln_bwd_blocks(M), D, dgamma, dbeta, dcolsum, accumulate);
-    return check_launch();
+    return ln_bwd_finish(dy, dtype, x, gamma, mean, rstd, dres, nullptr, dx, dx_lp, dgamma, dbeta, dcolsum, accumulate, ws, M, D, stream);
 }
 
 static int ln_bwd_launch(const void* dy, int dtype, const float* x, const float* gamma, const float* mean, const float* rstd,
-                         const float* dres, float* dx, void* dx_lp, float* ws, int M, int D, hipStream_t st) {
+                         const float* dres, const float* dres2, float* dx, void* dx_lp, float* ws, int M, int D, hipStream_t st) {
     const int nblk = ln_bwd_blocks(M);
     const size_t lds = (size_t)12 * D * sizeof(float);
     const int nvl = (int)cdiv(D, 256);
+    // both forms are instantiated: without a second addend the launch is the kernel pa_layernorm_bwd always ran
+#define PA_LN_BWD_T(T, V)                                                                                         \
+    do {                                                                                                          \
+        if (dres2) hipLaunchKernelGGL((ln_bwd2_kernel<T, V>), dim3(nblk), dim3(256), lds, st, (const T*)dy, x, gamma, mean, rstd, dres, dres2, dx, (T*)dx_lp, ws, M, D); \
+        else hipLaunchKernelGGL((ln_bwd_kernel<T, V>), dim3(nblk), dim3(256), lds, st, (const T*)dy, x, gamma, mean, rstd, dres, dx, (T*)dx_lp, ws, M, D); \
+    } while (0)
 #define PA_LN_BWD(V)                                                                                              \
     do {                                                                                                          \
-        if (dtype == PA_BF16) hipLaunchKernelGGL((ln_bwd_kernel<bf16, V>), dim3(nblk), dim3(256), lds, st, (const bf16*)dy, x, gamma, mean, rstd, dres, dx, (bf16*)dx_lp, ws, M, D); \
-        else hipLaunchKernelGGL((ln_bwd_kernel<float, V>), dim3(nblk), dim3(256), lds, st, (const float*)dy, x, gamma, mean, rstd, dres, dx, (float*)dx_lp, ws, M, D); \
+        if (dtype == PA_BF16) PA_LN_BWD_T(bf16, V); else PA_LN_BWD_T(float, V);                                   \
     } while (0)
     if (nvl <= 1) PA_LN_BWD(1); else if (nvl == 2) PA_LN_BWD(2); else if (nvl == 3) PA_LN_BWD(3);
     else if (nvl == 4) PA_LN_BWD(4); else PA_LN_BWD(8);
 #undef PA_LN_BWD
+#undef PA_LN_BWD_T
     return check_launch();
 }

@@ -331,6 +331,32 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, want_lp, accumu
     return dx, (dx if dtype == PA_F32 else dx_lp)
 
 
+def layernorm_bwd2(dy, x, gamma, mean, rstd, dres, dres2, dgamma, dbeta, want_lp, accumulate=False, dcolsum=None, defer=None):
+    """layernorm_bwd with a second addend: dx = dres + dres2 + LN'(dy) -- ``dres2`` [M][D] f32 is a gradient injected into the
+    residual stream at this LayerNorm's input; the 16-bit copy and ``dcolsum`` include it.  Same returns and ``defer`` contract."""
+    M, D = x.shape
+    dtype = PA_DTYPE[dy.dtype]
+    lib = _lib.load()
+    if dres2 is None or dres2.shape != (M, D):
+        raise _lib.PasstAmdError(f"layernorm_bwd2: dres2 must be an f32 [{M}][{D}] tensor")
+    dx = torch.empty((M, D), device=x.device, dtype=torch.float32)
+    dx_lp = torch.empty((M, D), device=x.device, dtype=dy.dtype) if (want_lp and dtype != PA_F32) else None
+    ws = torch.empty(lib.pa_layernorm_bwd_ws_floats(M, D), device=x.device, dtype=torch.float32)
+    if defer is not None and not accumulate:
+        check(lib.pa_layernorm_bwd2_partial(_p(dy), dtype, _p(x, torch.float32), _p(gamma, torch.float32), _p(mean, torch.float32),
+                                            _p(rstd, torch.float32), _p(dres, torch.float32), _p(dres2, torch.float32), _p(dx), _p(dx_lp),
+                                            _p(ws), M, D, _stream()), "pa_layernorm_bwd2_partial")
+        rows = lib.pa_layernorm_bwd_rows(M)
+        for j, out in enumerate((dgamma, dbeta, dcolsum)):
+            if out is not None:
+                defer.append((ws[j * D:], rows, 3 * D, D, out))
+        return dx, (dx if dtype == PA_F32 else dx_lp)
+    check(lib.pa_layernorm_bwd2(_p(dy), dtype, _p(x, torch.float32), _p(gamma, torch.float32), _p(mean, torch.float32), _p(rstd, torch.float32),
+                                _p(dres, torch.float32), _p(dres2, torch.float32), _p(dx), _p(dx_lp), _p(dgamma), _p(dbeta), _p(dcolsum),
+                                int(accumulate), _p(ws), M, D, _stream()), "pa_layernorm_bwd2")
+    return dx, (dx if dtype == PA_F32 else dx_lp)
+
+
 # ---- GEMM ------------------------------------------------------------------------------------
 # A/B knobs: the tile variant of every plain-store / residual NT GEMM of the step (PASST_AMD_TUNE_STORE / PASST_AMD_TUNE_RESID =
 # a pa_gemm_args.tune value, e.g. 13 = the 192 x 128 two-workgroups-per-CU tile with epilogue v2)
@@ -827,6 +853,22 @@ def scatter_rows_into_zeros(x_rows, idx_i32, n_rows):
     check(lib.pa_zero2d(_p(out), row_bytes, row_bytes, n_rows, _stream()), "pa_zero2d")
     check(lib.pa_scatter_rows(_p(x_rows), _p(idx_i32, torch.int32), idx_i32.numel(), row_bytes, _p(out), _stream()), "pa_scatter_rows")
     return out
+
+
+def tail_inject(x_rows, idx_i32, n_rows, add0, add1, dtype):
+    """(dx f32 [n_rows][D], its ``dtype`` copy): dx = add0 + add1 + scatter(x_rows at idx) with either addend optional ([n_rows][D]
+    f32 or None) -- the gradient of the last block's full-rows output: what a caller injected at the last block's output (add0),
+    the final norm's backward over all rows (add1) and the head's gradient on the prefix rows.  idx: strictly ascending.  In f32
+    the copy is dx itself."""
+    D = x_rows.shape[1]
+    for a in (add0, add1):
+        if a is not None and a.shape != (n_rows, D):
+            raise _lib.PasstAmdError(f"tail_inject: an addend is {tuple(a.shape)}, expected {(n_rows, D)}")
+    dx = torch.empty((n_rows, D), device=x_rows.device, dtype=torch.float32)
+    dx_lp = torch.empty((n_rows, D), device=x_rows.device, dtype=TORCH_DTYPE[dtype]) if dtype != PA_F32 else None
+    check(_lib.load().pa_tail_inject(_p(x_rows, torch.float32), _p(idx_i32, torch.int32), idx_i32.numel(), _p(add0, torch.float32),
+                                     _p(add1, torch.float32), _p(dx), _p(dx_lp), dtype, n_rows, D, _stream()), "pa_tail_inject")
+    return dx, (dx if dtype == PA_F32 else dx_lp)
 
 
 # ---- patch embedding -------------------------------------------------------------------------

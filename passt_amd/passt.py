@@ -309,6 +309,9 @@ class _FixedLayout:
     def prefix_rows(self, device):
         return _prefix_rows(self.model, self.B, self.Ntok, device)
 
+    def hidden_view(self, h):
+        return h.view(self.B, self.Ntok, -1)
+
     def attention_fwd(self, qkv, H, scale, **kw):
         return ops.attention_fwd(qkv, self.B, H, self.Ntok, scale, **kw)
 
@@ -327,6 +330,9 @@ class _PackedLayout:
     def prefix_rows(self, device):
         return self.pidx
 
+    def hidden_view(self, h):
+        return h.view(self.M, -1)       # a view, not h itself: what the autograd node hands out must not be what its context keeps
+
     def attention_fwd(self, qkv, H, scale, **kw):
         return ops.attention_fwd_varlen(qkv, self.cu_tok, self.B, H, self.max_N, scale, **kw)
 
@@ -334,15 +340,47 @@ class _PackedLayout:
         return ops.attention_bwd_varlen(qkv, att, d_att, lse, self.cu_tok, self.B, H, self.max_N, scale, **kw)
 
 
-def _forward_trunk(model, lay, xs, dt, save, patch):
-    """Token matrix xs [M][D] f32 in layout ``lay`` -> blocks -> prefix-only tail -> head.  Returns (logits, features, ctx); ctx
-    (``save`` only) is what _backward_trunk needs plus ``patch``, the entry path's own state for its patch-stage backward."""
+def parse_hidden(hidden, nblk):
+    """``hidden=`` of PaSST.forward -> a tuple of block indices in [0, nblk) and / or "norm", in the order asked.  ValueError for
+    anything else: a bare int or string, an empty sequence, an index out of range, an entry named twice (also as k and k - nblk)."""
+    if isinstance(hidden, (str, bytes)) or not isinstance(hidden, (list, tuple)):
+        raise ValueError(f"hidden must be a sequence of block indices and/or \"norm\", e.g. hidden=(3, 7, -1, \"norm\"); got {hidden!r}")
+    if not hidden:
+        raise ValueError("hidden is empty: name at least one block index or \"norm\" (hidden=None asks for no token outputs)")
+    out = []
+    for h in hidden:
+        if isinstance(h, str):
+            if h != "norm":
+                raise ValueError(f"hidden: unknown entry {h!r} (the only name is \"norm\")")
+            k = h
+        elif isinstance(h, (int, np.integer)) and not isinstance(h, (bool, np.bool_)):
+            k = int(h)
+            if not -nblk <= k < nblk:
+                raise ValueError(f"hidden: block index {k} is out of range for {nblk} blocks")
+            k %= nblk
+        else:
+            raise ValueError(f"hidden: entries are ints or \"norm\", got {h!r}")
+        if k in out:
+            raise ValueError(f"hidden: {h!r} is named twice")
+        out.append(k)
+    return tuple(out)
+
+
+def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None):
+    """Token matrix xs [M][D] f32 in layout ``lay`` -> blocks -> tail -> head.  Returns (logits, features, ctx, hs); ctx
+    (``save`` only) is what _backward_trunk needs plus ``patch``, the entry path's own state for its patch-stage backward.
+    ``hidden`` (parse_hidden's tuple or None): the token outputs to hand out, hs in that order -- a block's output is the f32
+    residual stream the block wrote (its own fresh buffer, no copy), "norm" the final norm of every row of the last block's output.
+    The last block or "norm" among them makes the last block run on all rows (FULL TAIL) instead of the prefix-only tail."""
     st = model._staged
     D, H = model.embed_dim, model.num_heads
     scale = (D // H) ** -0.5
     aflags = ops.ATTN_Q_PRESCALED
     saved = []
     nblk = len(model.blocks)
+    want = hidden or ()
+    full_tail = (nblk - 1) in want or "norm" in want
+    outs = {}
     for bi, blk in enumerate(model.blocks):
         last = bi == nblk - 1
         ln1, mean1, rstd1 = ops.layernorm_fwd(xs, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt, save)
@@ -350,7 +388,7 @@ def _forward_trunk(model, lay, xs, dt, save, patch):
         # straight from the matrix pipe (ATTN_Q_PRESCALED); every gradient stays the gradient of the unscaled Linear
         qkv = ops.linear(ln1, st.get(blk.attn.qkv.weight, dt, False), blk.attn.qkv.bias, dt,
                          colscale_n=D, colscale=scale * ops.LOG2E)
-        if not last:
+        if not last or full_tail:
             att, lse = lay.attention_fwd(qkv, H, scale, flags=aflags)
             x_res = xs
         else:
@@ -367,13 +405,26 @@ def _forward_trunk(model, lay, xs, dt, save, patch):
         x_out = ops.linear_resid(h_act, st.get(blk.mlp.fc2.weight, dt, False), blk.mlp.fc2.bias, x_mid, dt)
         if save:
             saved.append((xs, ln1, mean1, rstd1, qkv, att, lse, x_mid, ln2, mean2, rstd2, h_pre, h_act))
+        if bi in want:
+            outs[bi] = x_out
         xs = x_out
-    xl = xs.view(lay.B, 2, D)              # compact: the two prefix tokens of every clip
+    tail = None
+    if full_tail:
+        # FULL TAIL: the last block ran like every other one; the head reads its cls / dist rows
+        xl = ops.gather_rows(xs, lay.prefix_rows(xs.device)).view(lay.B, 2, D)
+        stats_n = None
+        if "norm" in want:
+            outs["norm"], mean_n, rstd_n = ops.layernorm_fwd(xs, model.norm.weight, model.norm.bias, model.norm.eps, PA_F32, save)
+            stats_n = (mean_n, rstd_n)
+        tail = dict(x_last=xs, norm=stats_n)
+    else:
+        xl = xs.view(lay.B, 2, D)          # compact: the two prefix tokens of every clip
     feat, hn, stats = ops.head_pre_fwd(xl, model.norm.weight, model.norm.bias, model.norm.eps, model.head[0].weight,
                                        model.head[0].bias, model.head[0].eps)
     logits = ops.linear_f32_fwd(hn, model.head[1].weight, model.head[1].bias)
-    ctx = dict(dt=dt, lay=lay, scale=scale, saved=saved, xl=xl, feat=feat, hn=hn, stats=stats, patch=patch) if save else None
-    return logits, feat, ctx
+    # tail: None = the prefix-only tail; else the full tail's own state (the last block's output, the final norm's row statistics)
+    ctx = dict(dt=dt, lay=lay, scale=scale, saved=saved, xl=xl, feat=feat, hn=hn, stats=stats, patch=patch, tail=tail) if save else None
+    return logits, feat, ctx, [lay.hidden_view(outs[k]) for k in want]
 
 
 def patchout_draws(model, x_shape):
@@ -392,14 +443,16 @@ def patchout_draws(model, x_shape):
     return dict(pf=pf_np, pt=pt_np, toff=toff, Np=pf_np.size)
 
 
-def passt_forward(model, x, save, draws=None):
+def passt_forward(model, x, save, draws=None, hidden=None):
     """Kernel sequence of PaSST.forward (:576-595).  Returns (logits, features, ctx).  ``draws``: device-resident Patchout
-    draws {pf, pt, pt_pos (= pt + time offset), Np} prepared by the caller (captured-graph mode); None = draw here."""
+    draws {pf, pt, pt_pos (= pt + time offset), Np} prepared by the caller (captured-graph mode); None = draw here.
+    ``hidden`` (parse_hidden's tuple): returns (logits, features, ctx, hs), hs = the (B, Ntok, D) f32 token outputs asked for."""
     with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
-        return _passt_forward(model, x, save, draws)
+        out = _passt_forward(model, x, save, draws, hidden)
+    return out[:3] if hidden is None else out
 
 
-def _passt_forward(model, x, save, draws=None):
+def _passt_forward(model, x, save, draws=None, hidden=None):
     x, dt = _checked_input(model, x, True)
     B, Cin, F, T = x.shape
     P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
@@ -422,7 +475,7 @@ def _passt_forward(model, x, save, draws=None):
                 row_mod=Np, out_batch_rows=Ntok, out_row_off=2)
     # pt_grid: the kept patches' own grid columns (pt may carry the time-positional offset); F, T: the input gradient's shape
     patch = dict(Np=Np, pf=pf, pt=pt_pos, pt_grid=pt, toff=toff, F=F, T=T, cols=cols) if save else None
-    return _forward_trunk(model, _FixedLayout(model, B, Ntok), tok.view(B * Ntok, D), dt, save, patch)
+    return _forward_trunk(model, _FixedLayout(model, B, Ntok), tok.view(B * Ntok, D), dt, save, patch, hidden)
 
 
 # --------------------------------------------------------------------------------------------
@@ -470,11 +523,19 @@ def passt_forward_varlen(model, x, lengths, save=False):
     ``save=True``: (logits, features, ctx) with what passt_backward_varlen needs.  Without it nothing is kept and the launch sequence is
     the same."""
     with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
-        logits, feat, ctx = _passt_forward_varlen(model, x, lengths, save)
+        logits, feat, ctx = _passt_forward_varlen(model, x, lengths, save)[:3]
     return (logits, feat, ctx) if save else (logits, feat)
 
 
-def _passt_forward_varlen(model, x, lengths, save=False):
+def passt_forward_varlen_hidden(model, x, lengths, hidden, save=False):
+    """passt_forward_varlen that also hands out token outputs (``hidden``: parse_hidden's tuple): returns (logits, features, ctx or
+    None, hs, tok_offsets) -- hs the packed (M, D) f32 matrices asked for, tok_offsets an int64 CPU tensor of B + 1 row offsets (clip i
+    owns rows tok_offsets[i] : tok_offsets[i + 1])."""
+    with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
+        return _passt_forward_varlen(model, x, lengths, save, hidden)
+
+
+def _passt_forward_varlen(model, x, lengths, save=False, hidden=None):
     x, dt = _checked_input(model, x, save)
     if torch.is_tensor(lengths):
         if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
@@ -505,7 +566,8 @@ def _passt_forward_varlen(model, x, lengths, save=False):
     xs = torch.empty((M, model.embed_dim), device=x.device, dtype=torch.float32)
     ops.gemm_nt(cols, model._staged.get(model.patch_embed.proj.weight, dt, False), dt, EPI_RESID, resid=table, out_f32=xs)
     patch = dict(F=F, T=T, cols=cols) if save else None
-    return _forward_trunk(model, _PackedLayout(B, M, g["max_N"], cu_tok, pidx), xs, dt, save, patch)
+    tok_offsets = torch.from_numpy(cu.astype(np.int64)) if hidden is not None else None
+    return _forward_trunk(model, _PackedLayout(B, M, g["max_N"], cu_tok, pidx), xs, dt, save, patch, hidden) + (tok_offsets,)
 
 
 class _NoRowJobs(list):
@@ -622,7 +684,12 @@ class _WgradSchedule:
 
 def _backward_trunk(model, ctx, dlogits, dfeat, wg):
     """Head stage, then blocks depth-1 .. 0 of either token layout.  Returns the gradient of the token matrix [M][D] f32 and its
-    16-bit copy (None where the layout's patch stage does not ask for one: ``lay.dx0_lp``)."""
+    16-bit copy (None where the layout's patch stage does not ask for one: ``lay.dx0_lp``).
+    ``ctx["dhidden"]`` (optional, put there by the caller): {block index or "norm": gradient [M][D] f32} of the token outputs the
+    forward handed out that fed the loss; an output that did not is simply absent.  A
+    block's enters the residual stream where that block's output gradient is formed: inside the next block's norm1 backward (its
+    second addend; the 16-bit copy and the column sums = this block's fc2.bias gradient see it), or, for the last block of a full
+    tail, in pa_tail_inject together with the final norm's backward and the head's prefix-row gradient."""
     dt, lay, st, scratch = ctx["dt"], ctx["lay"], model._staged, model._scratch
     B, D, H = lay.B, model.embed_dim, model.num_heads
     g, rowjobs = wg.g, wg.rowjobs
@@ -636,15 +703,27 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
         if not wg.frozen:
             ops.colsum_f32(part4[:, j, :], g[name])
     nblk = len(model.blocks)
+    dh, tail = ctx.get("dhidden") or {}, ctx["tail"]
+    d_norm = None
+    if "norm" in dh:
+        # the final norm over ALL rows: its dgamma / dbeta add to what the head's own two rows per clip just gave norm.weight / norm.bias
+        mean_n, rstd_n = tail["norm"]
+        d_norm, _ = ops.layernorm_bwd(dh["norm"], tail["x_last"], model.norm.weight, mean_n, rstd_n, None, g["norm.weight"],
+                                      g["norm.bias"], False, **(dict(defer=rowjobs) if wg.frozen else dict(accumulate=True)))
     wg.report(nblk)
-    dx = dxl.view(2 * B, D)                 # gradient w.r.t. the compact (prefix-rows) output of the last block
-    dx_lp = ops.convert(dx, dt)
+    if tail is None:
+        dx = dxl.view(2 * B, D)             # gradient w.r.t. the compact (prefix-rows) output of the last block
+        dx_lp = ops.convert(dx, dt)
+    else:
+        # FULL TAIL: gradient w.r.t. all M rows of the last block's output, f32 and 16-bit, in one pass
+        dx, dx_lp = ops.tail_inject(dxl.view(2 * B, D), lay.prefix_rows(dxl.device), lay.M, dh.get(nblk - 1), d_norm, dt)
     for i in range(nblk - 1, -1, -1):
         blk = model.blocks[i]
         last = i == nblk - 1
+        prefix_tail = last and tail is None
         pfx = f"blocks.{i}."
         xs, ln1, mean1, rstd1, qkv, att, lse, x_mid, ln2, mean2, rstd2, h_pre, h_act = ctx["saved"][i]
-        # ---- MLP:  x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))      (on [2B, D] rows for the last block)
+        # ---- MLP:  x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))      (on [2B, D] rows for the last block of a prefix-only tail)
         # fc2.bias gradient = column sums of dx: already produced by the LayerNorm backward that made dx (the next
         # block's norm1) -- except for the last block, whose dx comes from the head
         wg.launch(dx_lp, h_act, g[pfx + "mlp.fc2.weight"], g[pfx + "mlp.fc2.bias"] if last else None)
@@ -666,7 +745,7 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
         wg.launch(dx_lp, att, g[pfx + "attn.proj.weight"], None)
         d_att = torch.empty_like(att)
         ops.gemm_nt(dx_lp, st.get(blk.attn.proj.weight, dt, True), dt, EPI_STORE, out_lp=d_att)
-        if not last:
+        if not prefix_tail:
             d_qkv = lay.attention_bwd(qkv, att, d_att, lse, H, ctx["scale"], flags=ops.ATTN_Q_PRESCALED)
             dres = dx
         else:
@@ -676,9 +755,14 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
             dres = ops.scatter_rows_into_zeros(dx, lay.prefix_rows(dx.device), lay.M)
         d_ln1 = torch.empty_like(ln1)
         ops.gemm_nt(d_qkv, st.get(blk.attn.qkv.weight, dt, True), dt, EPI_STORE, out_lp=d_ln1)
-        dx, dx_lp = ops.layernorm_bwd(d_ln1, xs, blk.norm1.weight, mean1, rstd1, dres, g[pfx + "norm1.weight"],
-                                      g[pfx + "norm1.bias"], i > 0 or lay.dx0_lp,
-                                      dcolsum=g[f"blocks.{i - 1}.mlp.fc2.bias"] if i > 0 else None, defer=rowjobs)
+        inject = dh.get(i - 1) if i > 0 else None       # a loss on the previous block's output: this LayerNorm's input
+        if inject is None:
+            dx, dx_lp = ops.layernorm_bwd(d_ln1, xs, blk.norm1.weight, mean1, rstd1, dres, g[pfx + "norm1.weight"],
+                                          g[pfx + "norm1.bias"], i > 0 or lay.dx0_lp,
+                                          dcolsum=g[f"blocks.{i - 1}.mlp.fc2.bias"] if i > 0 else None, defer=rowjobs)
+        else:
+            dx, dx_lp = ops.layernorm_bwd2(d_ln1, xs, blk.norm1.weight, mean1, rstd1, dres, inject, g[pfx + "norm1.weight"],
+                                           g[pfx + "norm1.bias"], True, dcolsum=g[f"blocks.{i - 1}.mlp.fc2.bias"], defer=rowjobs)
         # last weight gradient of the block; the side stream (ordered after the LayerNorm gradients above)
         # then reports the block complete, so its all-reduce bucket starts without stalling the main stream
         wg.launch(d_qkv, ln1, g[pfx + "attn.qkv.weight"], g[pfx + "attn.qkv.bias"], done=i)
@@ -740,7 +824,9 @@ def passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done=None, want_d
     ``grads=None``: the no-weight-gradients mode of a fully frozen network (a loss network): no weight-gradient GEMM, no bias /
     positional / head parameter reduction and no ``on_block_done``.  What the activation-gradient kernels produce anyway stays
     where it falls and is never reduced: the LayerNorm backward's dgamma / dbeta partial rows (in that call's own workspace) and
-    the head's per-clip LayerNorm partials (pa_head_pre_bwd's ``part``)."""
+    the head's per-clip LayerNorm partials (pa_head_pre_bwd's ``part``).
+    Gradients of the token outputs of a forward run with ``hidden=`` travel in the context: ``ctx["dhidden"] = {block index (>= 0)
+    or "norm": (B * Ntok, D) f32}`` before this call (see _backward_trunk)."""
     return _backward(model, ctx, dlogits, dfeat, grads, on_block_done, want_dx, _patch_backward)
 
 
@@ -758,34 +844,47 @@ class _PasstFunction(torch.autograd.Function):
     """One autograd node for the whole network: forward/backward are kernel sequences, torch only sees
     (x, *parameters) -> (logits, features).  ``lengths``: None = the fixed path, else the packed ragged-batch forward
     (``net.varlen_grad = True``) with the packed backward; same ``grads`` / ``on_block_done`` contract, same flat-buffer and reducer
-    routes."""
+    routes.  ``hidden`` (parse_hidden's tuple or None): the token outputs asked for are further outputs of this node, behind
+    (logits, features) and in the order asked (then, on the packed path, the int64 row offsets, which carry no gradient)."""
 
     @staticmethod
-    def forward(ctx, model, lengths, x, *params):
+    def forward(ctx, model, lengths, hidden, x, *params):
+        hs = ()
         if lengths is None:
-            logits, feat, c = passt_forward(model, x, save=True)
+            logits, feat, c, *more = passt_forward(model, x, save=True, hidden=hidden)
+            if hidden is not None:
+                hs = tuple(more[0])
         else:
-            logits, feat, c = passt_forward_varlen(model, x, lengths, save=True)
-        ctx.model, ctx.c, ctx.varlen = model, c, lengths is not None
+            if hidden is None:
+                logits, feat, c = passt_forward_varlen(model, x, lengths, save=True)
+            else:
+                logits, feat, c, h, tok_offsets = passt_forward_varlen_hidden(model, x, lengths, hidden, save=True)
+                hs = tuple(h) + (tok_offsets,)
+        ctx.model, ctx.c, ctx.varlen, ctx.hidden = model, c, lengths is not None, hidden
         # the input spectrogram's gradient is computed only when asked for; a graph none of whose parameters requires a gradient
         # (a frozen loss network) runs the backward without any weight-gradient work
-        ctx.want_dx = bool(ctx.needs_input_grad[2])
-        ctx.frozen = not any(ctx.needs_input_grad[3:])
+        ctx.want_dx = bool(ctx.needs_input_grad[3])
+        ctx.frozen = not any(ctx.needs_input_grad[4:])
         ctx.named, ctx.total = model._graph_params(validate=False)     # the list forward() just handed to apply()
         # bound to a passt_amd.optim.AdamW (PaSST.bind_flat_grads): the only input is a token; the backward writes the gradients
         # straight into the optimizer's persistent flat buffer -- p.grad are views of it -- and hands autograd nothing
         ctx.flat = model._flat if (len(params) == 1 and model._flat is not None and params[0] is model._flat["token"]) else None
         ctx.set_materialize_grads(False)        # an unused `features` output arrives as None, not as a zero tensor
-        return logits, feat
+        return (logits, feat) + hs
 
     @staticmethod
-    def backward(ctx, dlogits, dfeat):
+    def backward(ctx, dlogits, dfeat, *dhs):
         model, c = ctx.model, ctx.c
         if c is None:
             raise RuntimeError("passt_amd.PaSST: the saved activations of this forward were already consumed by a backward "
                                "pass (retain_graph / double backward are not supported: run the forward again)")
         run_backward = passt_backward_varlen if ctx.varlen else passt_backward
-        lead = (None, None)                     # the model, the lengths
+        lead = (None, None, None)               # the model, the lengths, the hidden request
+        dev = c["feat"].device
+        # gradients of the token outputs that fed the loss, as [M][D] rows (an unused one arrives as None and costs nothing)
+        dhidden = {k: d.contiguous().view(c["lay"].M, -1) for k, d in zip(ctx.hidden or (), dhs) if d is not None}
+        if dhidden:
+            c["dhidden"] = dhidden
         # gradient buffers for EVERY parameter the backward writes (all but head_dist.*): the kernel sequence produces
         # them all; parameters with requires_grad=False are simply not handed back to autograd (frozen backbone, ...)
         named, total = ctx.named, ctx.total
@@ -796,14 +895,14 @@ class _PasstFunction(torch.autograd.Function):
         if ctx.frozen:
             # nothing but the input asked for a gradient: no flat buffer, no weight-gradient launch, no reducer (dx is a local quantity)
             if dlogits is None:
-                dlogits = torch.zeros((B, model.num_classes), device=dfeat.device, dtype=torch.float32)
+                dlogits = torch.zeros((B, model.num_classes), device=dev, dtype=torch.float32)
             dx = run_backward(model, c, dlogits, None if dfeat is None else dfeat.contiguous(), None, want_dx=ctx.want_dx)
             ctx.c = None
             return lead + (dx,) + (None,) * (len(named) if fl is None else 1)
         if fl is not None and fl["fresh"]:
             flat, grads = fl["flat_g"], fl["grads"]     # overwritten in place: the caller zeroed (optimizer.zero_grad()) since the last backward
         else:
-            flat = torch.empty(total, device=(dfeat if dlogits is None else dlogits).device, dtype=torch.float32)
+            flat = torch.empty(total, device=dev, dtype=torch.float32)
             # one C++ call makes the 159 views (a Python loop of slice + view costs 1.3 ms of host time in front of the first
             # backward kernel: exposed whenever the caller synchronised in this step, and the reference's mixup does)
             views = torch._C._nn.unflatten_dense_tensors(flat, [p for _, p in named])
@@ -824,6 +923,8 @@ class _PasstFunction(torch.autograd.Function):
             inv = 1.0 / red.world
             dlogits = dlogits * inv
             dfeat = None if dfeat is None else dfeat * inv
+            for k in dhidden:
+                dhidden[k] = dhidden[k] * inv
             red.flat = flat
             try:
                 dx = run_backward(model, c, dlogits, dfeat, grads, on_block_done=red.on_block_done, want_dx=ctx.want_dx)
@@ -1046,15 +1147,33 @@ class PaSST(nn.Module):
                                   "(models/passt.py:500-504); build a new model with n_classes instead")
 
     def forward_features(self, x):
-        raise NotImplementedError("only forward() is on the accelerated path (returns (logits, features))")
+        raise NotImplementedError("only forward() is on the accelerated path (returns (logits, features)); the token sequence the "
+                                  "reference's forward_features holds before it pools is forward(x, hidden=(\"norm\",))")
 
     def mark_params_updated(self):
         """Call after updating parameters through raw device pointers (passt_amd.optim does)."""
         self._staged.epoch += 1
 
     @compile_opaque
-    def forward(self, x, lengths=None):
+    def forward(self, x, lengths=None, hidden=None):
         """x: (B,1,F,T) -> (logits (B,C), features (B,D)); always a tuple (models/passt.py:588,595).
+
+        ``hidden`` (a list / tuple of block indices, negative allowed, and / or the string "norm"): also return the token sequence
+        at those depths, ``(logits, features, hidden)`` -- with ``lengths``: ``(logits, features, hidden, tok_offsets)`` -- where
+        ``hidden`` is a list in the order asked.  Entry ``i`` is the output of ``blocks[i]`` (what a forward hook on the reference's
+        ``blocks[i]`` sees), f32 (B, Ntok, D): rows 0 / 1 are cls / dist, the others the kept patches in the reference's order --
+        frequency-major in eval mode, so ``h[:, 2:].view(B, F', T', D)`` is the (frequency, time) grid; in training mode the
+        patches Patchout kept (the draws are those of a call without ``hidden``).  "norm" is ``net.norm`` applied to every row of the
+        last block's output: what the reference's ``forward_features`` holds before it pools; its rows 0 / 1 are the tokens whose mean
+        is ``features``.  With ``lengths`` every entry is the packed (M, D) matrix and ``tok_offsets`` an int64 CPU tensor of B + 1
+        row offsets (the convention of ``frames`` from ``mel(..., lengths=)``): clip i owns rows tok_offsets[i] : tok_offsets[i + 1],
+        which are what the clip gets alone at batch size 1.  The entries are outputs of the same autograd node under the same rules
+        as (logits, features): a loss on them reaches ``x.grad`` and the parameter gradients; one that does not feed the loss costs
+        nothing.  They are the network's own buffers handed out (no copy): do not write into them before the backward.  Blocks
+        below the last one cost nothing to ask for; the last block or "norm" makes the last block run on all rows instead of the
+        two prefix rows (about one more block of forward and backward), and logits / features then agree with a call without
+        ``hidden`` to rounding, not bit for bit (the all-queries attention kernel orders its sums differently).  A bare int, an
+        empty sequence, an index out of range or an entry named twice raises ValueError before anything is launched or drawn.
 
         An ``x`` that requires a gradient gets one (``x.grad`` / ``torch.autograd.grad``), as in the reference: PaSST as a
         differentiable loss network.  With every parameter frozen (``net.requires_grad_(False)``) this needs no switch and the backward
@@ -1084,6 +1203,7 @@ class PaSST(nn.Module):
         flow).  Under ``torch.autocast`` of either 16-bit type (Lightning precision=16 / torch.cuda.amp.autocast() are fp16) the
         kernels run the bf16 MFMA path with f32 accumulation and return f32 logits / features: bf16 has f32's exponent range,
         so a GradScaler's loss scale flows through the backward without overflow and its inf checks never fire."""
+        hid = None if hidden is None else parse_hidden(hidden, len(self.blocks))
         if lengths is not None and self.training:
             raise NotImplementedError("PaSST.forward(x, lengths=...): training on ragged batches is not supported (eval mode only; "
                                       "no reference flow trains on clips of different lengths)")
@@ -1113,14 +1233,27 @@ class PaSST(nn.Module):
             fl = self._flat
             if fl is not None:
                 if fl["named"] is named:                # same validated parameter list as at bind time
-                    return _PasstFunction.apply(self, lengths, x, fl["token"])
+                    return self._with_hidden(_PasstFunction.apply(self, lengths, hid, x, fl["token"]), hid)
                 self.unbind_flat_grads()                # surgery since: the optimizer re-binds at its next step
-            return _PasstFunction.apply(self, lengths, x, *[p for _, p in named])
+            return self._with_hidden(_PasstFunction.apply(self, lengths, hid, x, *[p for _, p in named]), hid)
         if lengths is not None:
             with torch.no_grad():
-                return passt_forward_varlen(self, x, lengths)
-        logits, feat, _ = passt_forward(self, x, save=False)
-        return logits, feat
+                if hid is None:
+                    return passt_forward_varlen(self, x, lengths)
+                logits, feat, _, hs, tok_offsets = passt_forward_varlen_hidden(self, x, lengths, hid)
+                return logits, feat, hs, tok_offsets
+        if hid is None:
+            logits, feat, _ = passt_forward(self, x, save=False)
+            return logits, feat
+        logits, feat, _, hs = passt_forward(self, x, save=False, hidden=hid)
+        return logits, feat, hs
+
+    @staticmethod
+    def _with_hidden(out, hid):
+        """The autograd node's flat outputs in forward()'s shape: (logits, features[, [token outputs][, tok_offsets]])."""
+        if hid is None:
+            return out
+        return out[:2] + (list(out[2:2 + len(hid)]),) + tuple(out[2 + len(hid):])
 
 
 # --------------------------------------------------------------------------------------------
@@ -1215,9 +1348,12 @@ class EnsembelerModel(nn.Module):
         super().__init__()
         self.models = nn.ModuleList(models)
 
-    def forward(self, x, lengths=None):
+    def forward(self, x, lengths=None, hidden=None):
         """``lengths``: handed to every member (PaSST.forward's ragged-batch eval forward; gradients flow through the members that
-        set ``varlen_grad``)."""
+        set ``varlen_grad``).  ``hidden`` is not for an ensemble: its members have different depths and widths."""
+        if hidden is not None:
+            raise ValueError("EnsembelerModel.forward: hidden= is not supported (the members' token sequences have different widths "
+                             "and depths and cannot be averaged); call the member you want: model.models[i](x, hidden=...)")
         all_out = None
         for m in self.models:
             out, _ = m(x) if lengths is None else m(x, lengths=lengths)
