@@ -389,6 +389,22 @@ int pa_attention_fwd(const void* qkv, int ldqkv, void* o, int ldo, float* lse, i
  * flags as pa_attention_fwd.  qkv, o, lse, cu_tok are device memory. */
 int pa_attention_fwd_varlen(const void* qkv, int ldqkv, void* o, int ldo, float* lse, const int32_t* cu_tok, int B, int H,
                             int max_N, int nq, float scale, int dtype, int flags, void* stream);
+/* The attention probabilities themselves, softmax((Q K^T) * scale), f32: what the fused forward never writes (a forward hook on the
+ * reference's attn_drop sees them, models/passt.py:348-352).  qkv, ldqkv, nq, scale, dtype (PA_F32 / PA_BF16) and flags
+ * (PA_ATTN_Q_PRESCALED) are those of the pa_attention_fwd / pa_attention_fwd_varlen call that wrote `lse`, which is read in the layout
+ * that call left: lse[(b*H + h)*nq + q] (fixed, or packed with nq < max_N) or lse[h*cu_tok[B] + cu_tok[b] + q] (packed, nq >= max_N).
+ * A probability is exp2(score * log2 e - lse * log2 e) with the score from the matrix pipe: every (32 queries x 32 keys) tile stands
+ * alone -- no second pass, no atomics, deterministic.  Ho = head_mean ? 1 : H output planes per sequence; head_mean (0 / 1) averages
+ * the H heads in f32 registers, in head order.
+ *   cu_tok == NULL (out_off must be NULL): B sequences of N tokens, out[((b*Ho + h)*nq + q)*N + k], nq <= N.
+ *   cu_tok != NULL: packed sequences as in pa_attention_fwd_varlen, N = max_N; sequence b lies dense at out[out_off[b]] as
+ *     [Ho][min(nq, N_b)][N_b]; out_off: B int64 offsets in device memory.  Tail tiles are clamped to the sequence's own last row (no
+ *     row of a neighbour and none at or behind cu_tok[B] is read) and every sequence gets bit for bit what the fixed form gives it
+ *     alone at B = 1.
+ * Every element of the output is written and nothing else.  Key lanes at or behind N_b are masked before the exponential. */
+int pa_attention_probs(const void* qkv, int ldqkv, const float* lse, float* out, const int32_t* cu_tok, const int64_t* out_off,
+                       int B, int H, int N /* max_N when cu_tok != NULL */, int nq, int head_mean, float scale, int dtype, int flags,
+                       void* stream);
 /* number of floats of pa_attention_bwd's `delta` workspace */
 int64_t pa_attention_bwd_ws_floats(int B, int H, int nq);
 /* dqkv[B*N][3*H*64] from d_o[B*nq][H*64]; lse from the forward; delta: f32 workspace of pa_attention_bwd_ws_floats()

@@ -9,6 +9,7 @@ import functools
 import threading
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -782,6 +783,67 @@ def attention_fwd_varlen(qkv, cu_tok, B, H, max_N, scale, nq=None, flags=0):
                                                              _p(cu_tok, torch.int32), B, H, max_N, nq, scale, dtype, flags, _stream()),
                          "pa_attention_fwd_varlen"))
     return o, lse
+
+
+def attention_probs(qkv, lse, B, H, N, scale, nq=None, head_mean=False, flags=0, out=None):
+    """The attention probabilities softmax(q k^T * scale) of the attention_fwd call that made ``lse`` (same qkv, nq, flags): f32
+    (B, H, nq, N), or (B, 1, nq, N) = the mean over heads with ``head_mean``.  out: an f32 tensor of that many elements to write
+    instead of a fresh one (tests put guard rows behind it)."""
+    dtype = PA_DTYPE[qkv.dtype]
+    nq = N if nq is None else nq
+    Ho = 1 if head_mean else H
+    if qkv.dim() != 2 or qkv.shape[0] != B * N or qkv.shape[1] != 3 * H * 64 or lse.numel() != B * H * nq or not 1 <= nq <= N:
+        raise _lib.PasstAmdError(f"attention_probs: qkv {tuple(qkv.shape)}, lse {tuple(lse.shape)}, B={B}, H={H}, N={N}, nq={nq}")
+    if out is None:
+        out = torch.empty((B, Ho, nq, N), device=qkv.device, dtype=torch.float32)
+    elif out.numel() != B * Ho * nq * N:
+        raise _lib.PasstAmdError(f"attention_probs: out has {out.numel()} elements, expected {B * Ho * nq * N}")
+    _timed("attn_probs", 4.0 * out.numel(),
+           lambda: check(_lib.load().pa_attention_probs(_p(qkv, None, True), qkv.stride(0), _p(lse, torch.float32), _p(out, torch.float32),
+                                                        None, None, B, H, N, nq, int(bool(head_mean)), scale, dtype, flags, _stream()),
+                         "pa_attention_probs"))
+    return out.view(B, Ho, nq, N)
+
+
+def attention_probs_offsets(ntok, H_out, nq=None):
+    """Host layout of the packed attention maps: sequence b of ntok[b] tokens owns H_out * min(nq, ntok[b]) * ntok[b] floats, the
+    sequences back to back.  Returns (int64 numpy array of len(ntok) element offsets, total elements).  nq=None: every query."""
+    n = np.asarray(ntok, dtype=np.int64).reshape(-1)
+    if n.size == 0 or (n < 1).any() or H_out < 1 or (nq is not None and nq < 1):
+        raise ValueError(f"attention_probs_offsets: ntok={list(n)}, H_out={H_out}, nq={nq}")
+    rows = n if nq is None else np.minimum(n, int(nq))
+    size = int(H_out) * rows * n
+    off = np.zeros(n.size, dtype=np.int64)
+    np.cumsum(size[:-1], out=off[1:])
+    return off, int(size.sum())
+
+
+def attention_probs_varlen(qkv, lse, cu_tok, out_off, total_out, B, H, max_N, scale, nq=None, head_mean=False, flags=0, out=None):
+    """Packed sequences (attention_fwd_varlen's qkv / cu_tok / lse for the same nq): one flat f32 buffer of ``total_out`` elements,
+    sequence b dense at out_off[b] as [H or 1][min(nq, N_b)][N_b] (out_off: B int64 on the device, attention_probs_offsets)."""
+    dtype = PA_DTYPE[qkv.dtype]
+    total = qkv.shape[0]
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * H * 64 or cu_tok.dim() != 1 or cu_tok.numel() != B + 1 or not 1 <= max_N <= total or \
+            out_off.dim() != 1 or out_off.numel() != B:
+        raise _lib.PasstAmdError(f"attention_probs_varlen: qkv {tuple(qkv.shape)}, cu_tok {tuple(cu_tok.shape)}, out_off "
+                                 f"{tuple(out_off.shape)}, B={B}, H={H}, max_N={max_N}")
+    if nq is None or nq >= max_N:
+        nq, nlse = max_N, H * total
+    else:
+        if nq < 1:
+            raise _lib.PasstAmdError("attention_probs_varlen: nq must be >= 1")
+        nlse = B * H * nq
+    if lse.numel() != nlse:
+        raise _lib.PasstAmdError(f"attention_probs_varlen: lse has {lse.numel()} elements, expected {nlse}")
+    if out is None:
+        out = torch.empty((total_out,), device=qkv.device, dtype=torch.float32)
+    elif out.numel() != total_out:
+        raise _lib.PasstAmdError(f"attention_probs_varlen: out has {out.numel()} elements, expected {total_out}")
+    _timed("attn_probs", 4.0 * total_out,
+           lambda: check(_lib.load().pa_attention_probs(_p(qkv, None, True), qkv.stride(0), _p(lse, torch.float32), _p(out, torch.float32),
+                                                        _p(cu_tok, torch.int32), _p(out_off, torch.int64), B, H, max_N, nq,
+                                                        int(bool(head_mean)), scale, dtype, flags, _stream()), "pa_attention_probs"))
+    return out.view(-1)
 
 
 def attention_bwd(qkv, o, d_o, lse, B, H, N, scale, nq=None, flags=0):

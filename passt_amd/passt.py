@@ -318,14 +318,28 @@ class _FixedLayout:
     def attention_bwd(self, qkv, att, d_att, lse, H, scale, **kw):
         return ops.attention_bwd(qkv, att, d_att, lse, self.B, H, self.Ntok, scale, **kw)
 
+    def prefix_lse(self, lse, H):
+        """The all-queries lse [(b*H + h)*Ntok + q] cut to its cls / dist rows, compact as attention_fwd(nq=2) leaves it."""
+        return lse.view(self.B * H, self.Ntok)[:, :2].contiguous().view(-1)
+
+    def attention_probs(self, qkv, lse, H, scale, nq, head_mean, flags):
+        """One attention map in the shape PaSST.forward hands out: (B, H, Nq, Ntok), or (B, Nq, Ntok) for the mean over heads."""
+        p = ops.attention_probs(qkv, lse, self.B, H, self.Ntok, scale, nq=nq, head_mean=head_mean, flags=flags)
+        return p.view(self.B, -1, self.Ntok) if head_mean else p
+
+    @staticmethod
+    def attn_views(p, tok_offsets, H, prefix, head_mean):
+        return p
+
 
 class _PackedLayout:
     """B clips of different token counts back to back: clip b owns rows cu_tok[b] .. cu_tok[b + 1] (device int32), none longer
     than max_N; ``pidx``: the rows of the cls / dist tokens (device int32).  The attention backward is always the kernel pair."""
     dx0_lp = True                   # block 0's 16-bit dx feeds the patch stage's two GEMMs as it is
 
-    def __init__(self, B, M, max_N, cu_tok, pidx):
+    def __init__(self, B, M, max_N, cu_tok, pidx, ntok=None):
         self.B, self.M, self.max_N, self.cu_tok, self.pidx = B, M, max_N, cu_tok, pidx
+        self.ntok, self._map_off = ntok, {}      # host token counts per clip (attention maps only); their uploaded output offsets
 
     def prefix_rows(self, device):
         return self.pidx
@@ -338,6 +352,33 @@ class _PackedLayout:
 
     def attention_bwd(self, qkv, att, d_att, lse, H, scale, **kw):
         return ops.attention_bwd_varlen(qkv, att, d_att, lse, self.cu_tok, self.B, H, self.max_N, scale, **kw)
+
+    def prefix_lse(self, lse, H):
+        """The all-queries lse [h][total tokens] cut to every clip's cls / dist rows, compact [(b*H + h)*2 + q] as
+        attention_fwd_varlen(nq=2) leaves it."""
+        return lse.view(H, self.M).index_select(1, self.pidx).view(H, self.B, 2).permute(1, 0, 2).contiguous().view(-1)
+
+    def attention_probs(self, qkv, lse, H, scale, nq, head_mean, flags):
+        """One attention map of the packed batch as ONE flat f32 buffer (attn_views cuts it into the clips' tensors)."""
+        Ho = 1 if head_mean else H
+        key = (Ho, nq)
+        if key not in self._map_off:
+            off, total = ops.attention_probs_offsets(self.ntok, Ho, nq)
+            self._map_off[key] = (ops.upload_small(off, qkv.device), total)
+        off_dev, total = self._map_off[key]
+        return ops.attention_probs_varlen(qkv, lse, self.cu_tok, off_dev, total, self.B, H, self.max_N, scale, nq=nq,
+                                          head_mean=head_mean, flags=flags)
+
+    @staticmethod
+    def attn_views(p, tok_offsets, H, prefix, head_mean):
+        """The flat buffer of a packed map -> a list of B views: clip i's (H, Nq_i, N_i), or (Nq_i, N_i) for the mean over heads."""
+        ntok = (tok_offsets[1:] - tok_offsets[:-1]).tolist()
+        off, _ = ops.attention_probs_offsets(ntok, 1 if head_mean else H, 2 if prefix else None)
+        out = []
+        for o, n in zip(off.tolist(), ntok):
+            nq = min(2, n) if prefix else n
+            out.append(p[o:o + nq * n].view(nq, n) if head_mean else p[o:o + H * nq * n].view(H, nq, n))
+        return out
 
 
 def parse_hidden(hidden, nblk):
@@ -366,12 +407,42 @@ def parse_hidden(hidden, nblk):
     return tuple(out)
 
 
-def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None):
+def parse_attn(attn, nblk, attn_rows="all", attn_heads="each"):
+    """``attn=`` / ``attn_rows=`` / ``attn_heads=`` of PaSST.forward -> (block indices in [0, nblk) in the order asked, prefix rows
+    only?, mean over heads?).  parse_hidden's rules without "norm": ValueError for a bare int or string, an empty sequence, an index
+    out of range, an index named twice (also as k and k - nblk), and for any other value of the two modes."""
+    if attn_rows not in ("all", "prefix"):
+        raise ValueError(f"attn_rows must be \"all\" or \"prefix\" (the cls and dist query rows), got {attn_rows!r}")
+    if attn_heads not in ("each", "mean"):
+        raise ValueError(f"attn_heads must be \"each\" or \"mean\", got {attn_heads!r}")
+    if isinstance(attn, (str, bytes)) or not isinstance(attn, (list, tuple, range)):
+        raise ValueError(f"attn must be a sequence of block indices, e.g. attn=(0, -1); got {attn!r}")
+    if not attn:
+        raise ValueError("attn is empty: name at least one block index (attn=None asks for no attention maps)")
+    out = []
+    for a in attn:
+        if not isinstance(a, (int, np.integer)) or isinstance(a, (bool, np.bool_)):
+            raise ValueError(f"attn: entries are block indices (ints), got {a!r}")
+        k = int(a)
+        if not -nblk <= k < nblk:
+            raise ValueError(f"attn: block index {k} is out of range for {nblk} blocks")
+        k %= nblk
+        if k in out:
+            raise ValueError(f"attn: block {a!r} is named twice")
+        out.append(k)
+    return tuple(out), attn_rows == "prefix", attn_heads == "mean"
+
+
+def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None):
     """Token matrix xs [M][D] f32 in layout ``lay`` -> blocks -> tail -> head.  Returns (logits, features, ctx, hs); ctx
     (``save`` only) is what _backward_trunk needs plus ``patch``, the entry path's own state for its patch-stage backward.
     ``hidden`` (parse_hidden's tuple or None): the token outputs to hand out, hs in that order -- a block's output is the f32
     residual stream the block wrote (its own fresh buffer, no copy), "norm" the final norm of every row of the last block's output.
-    The last block or "norm" among them makes the last block run on all rows (FULL TAIL) instead of the prefix-only tail."""
+    The last block or "norm" among them makes the last block run on all rows (FULL TAIL) instead of the prefix-only tail.
+    ``attn`` (parse_attn's triple or None): the attention maps to hand out, as a fifth result in the order asked (layout's
+    attention_probs: a shaped tensor, or the packed batch's flat buffer) -- made right behind the block's attention launch from the
+    qkv and lse it used.  All rows of the last block's map need the FULL TAIL too; its prefix rows come from the prefix-only tail's
+    own compact lse, and the tail is unchanged."""
     st = model._staged
     D, H = model.embed_dim, model.num_heads
     scale = (D // H) ** -0.5
@@ -379,8 +450,9 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None):
     saved = []
     nblk = len(model.blocks)
     want = hidden or ()
-    full_tail = (nblk - 1) in want or "norm" in want
-    outs = {}
+    amaps, aprefix, amean = attn or ((), False, False)
+    full_tail = (nblk - 1) in want or "norm" in want or ((nblk - 1) in amaps and not aprefix)
+    outs, maps = {}, {}
     for bi, blk in enumerate(model.blocks):
         last = bi == nblk - 1
         ln1, mean1, rstd1 = ops.layernorm_fwd(xs, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt, save)
@@ -391,6 +463,9 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None):
         if not last or full_tail:
             att, lse = lay.attention_fwd(qkv, H, scale, flags=aflags)
             x_res = xs
+            if bi in amaps:
+                maps[bi] = lay.attention_probs(qkv, lay.prefix_lse(lse, H) if aprefix else lse, H, scale, 2 if aprefix else None,
+                                               amean, aflags)
         else:
             # PREFIX-ONLY TAIL.  The network output reads the last block at the cls/dist rows only
             # (models/passt.py:570-574, 583), so from here on just those 2 rows per clip are computed: attention for
@@ -399,6 +474,8 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None):
             pidx = lay.prefix_rows(xs.device)
             att, lse = lay.attention_fwd(qkv, H, scale, nq=2, flags=aflags)
             x_res = ops.gather_rows(xs, pidx)
+            if bi in amaps:                 # aprefix: the two rows this launch produced
+                maps[bi] = lay.attention_probs(qkv, lse, H, scale, 2, amean, aflags)
         x_mid = ops.linear_resid(att, st.get(blk.attn.proj.weight, dt, False), blk.attn.proj.bias, x_res, dt)
         ln2, mean2, rstd2 = ops.layernorm_fwd(x_mid, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, save)
         h_pre, h_act = ops.linear_gelu(ln2, st.get(blk.mlp.fc1.weight, dt, False), blk.mlp.fc1.bias, dt)
@@ -424,7 +501,7 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None):
     logits = ops.linear_f32_fwd(hn, model.head[1].weight, model.head[1].bias)
     # tail: None = the prefix-only tail; else the full tail's own state (the last block's output, the final norm's row statistics)
     ctx = dict(dt=dt, lay=lay, scale=scale, saved=saved, xl=xl, feat=feat, hn=hn, stats=stats, patch=patch, tail=tail) if save else None
-    return logits, feat, ctx, [lay.hidden_view(outs[k]) for k in want]
+    return logits, feat, ctx, [lay.hidden_view(outs[k]) for k in want], [maps[k] for k in amaps]
 
 
 def patchout_draws(model, x_shape):
@@ -443,16 +520,19 @@ def patchout_draws(model, x_shape):
     return dict(pf=pf_np, pt=pt_np, toff=toff, Np=pf_np.size)
 
 
-def passt_forward(model, x, save, draws=None, hidden=None):
+def passt_forward(model, x, save, draws=None, hidden=None, attn=None):
     """Kernel sequence of PaSST.forward (:576-595).  Returns (logits, features, ctx).  ``draws``: device-resident Patchout
     draws {pf, pt, pt_pos (= pt + time offset), Np} prepared by the caller (captured-graph mode); None = draw here.
-    ``hidden`` (parse_hidden's tuple): returns (logits, features, ctx, hs), hs = the (B, Ntok, D) f32 token outputs asked for."""
+    ``hidden`` (parse_hidden's tuple): returns (logits, features, ctx, hs), hs = the (B, Ntok, D) f32 token outputs asked for.
+    ``attn`` (parse_attn's triple): returns (logits, features, ctx, hs, maps), maps = the attention maps asked for."""
     with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
-        out = _passt_forward(model, x, save, draws, hidden)
-    return out[:3] if hidden is None else out
+        out = _passt_forward(model, x, save, draws, hidden, attn)
+    if attn is not None:
+        return out
+    return out[:3] if hidden is None else out[:4]
 
 
-def _passt_forward(model, x, save, draws=None, hidden=None):
+def _passt_forward(model, x, save, draws=None, hidden=None, attn=None):
     x, dt = _checked_input(model, x, True)
     B, Cin, F, T = x.shape
     P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
@@ -475,7 +555,7 @@ def _passt_forward(model, x, save, draws=None, hidden=None):
                 row_mod=Np, out_batch_rows=Ntok, out_row_off=2)
     # pt_grid: the kept patches' own grid columns (pt may carry the time-positional offset); F, T: the input gradient's shape
     patch = dict(Np=Np, pf=pf, pt=pt_pos, pt_grid=pt, toff=toff, F=F, T=T, cols=cols) if save else None
-    return _forward_trunk(model, _FixedLayout(model, B, Ntok), tok.view(B * Ntok, D), dt, save, patch, hidden)
+    return _forward_trunk(model, _FixedLayout(model, B, Ntok), tok.view(B * Ntok, D), dt, save, patch, hidden, attn)
 
 
 # --------------------------------------------------------------------------------------------
@@ -527,15 +607,17 @@ def passt_forward_varlen(model, x, lengths, save=False):
     return (logits, feat, ctx) if save else (logits, feat)
 
 
-def passt_forward_varlen_hidden(model, x, lengths, hidden, save=False):
+def passt_forward_varlen_hidden(model, x, lengths, hidden, save=False, attn=None):
     """passt_forward_varlen that also hands out token outputs (``hidden``: parse_hidden's tuple): returns (logits, features, ctx or
     None, hs, tok_offsets) -- hs the packed (M, D) f32 matrices asked for, tok_offsets an int64 CPU tensor of B + 1 row offsets (clip i
-    owns rows tok_offsets[i] : tok_offsets[i + 1])."""
+    owns rows tok_offsets[i] : tok_offsets[i + 1]).  ``attn`` (parse_attn's triple; ``hidden`` may then be None): returns (logits,
+    features, ctx or None, hs, maps, tok_offsets), maps = one flat buffer per attention map asked for (_PackedLayout.attn_views)."""
     with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
-        return _passt_forward_varlen(model, x, lengths, save, hidden)
+        out = _passt_forward_varlen(model, x, lengths, save, hidden, attn)
+    return out if attn is not None else out[:4] + out[5:]
 
 
-def _passt_forward_varlen(model, x, lengths, save=False, hidden=None):
+def _passt_forward_varlen(model, x, lengths, save=False, hidden=None, attn=None):
     x, dt = _checked_input(model, x, save)
     if torch.is_tensor(lengths):
         if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
@@ -566,8 +648,9 @@ def _passt_forward_varlen(model, x, lengths, save=False, hidden=None):
     xs = torch.empty((M, model.embed_dim), device=x.device, dtype=torch.float32)
     ops.gemm_nt(cols, model._staged.get(model.patch_embed.proj.weight, dt, False), dt, EPI_RESID, resid=table, out_f32=xs)
     patch = dict(F=F, T=T, cols=cols) if save else None
-    tok_offsets = torch.from_numpy(cu.astype(np.int64)) if hidden is not None else None
-    return _forward_trunk(model, _PackedLayout(B, M, g["max_N"], cu_tok, pidx), xs, dt, save, patch, hidden) + (tok_offsets,)
+    tok_offsets = torch.from_numpy(cu.astype(np.int64)) if (hidden is not None or attn is not None) else None
+    lay = _PackedLayout(B, M, g["max_N"], cu_tok, pidx, ntok=np.diff(cu))
+    return _forward_trunk(model, lay, xs, dt, save, patch, hidden, attn) + (tok_offsets,)
 
 
 class _NoRowJobs(list):
@@ -845,32 +928,39 @@ class _PasstFunction(torch.autograd.Function):
     (x, *parameters) -> (logits, features).  ``lengths``: None = the fixed path, else the packed ragged-batch forward
     (``net.varlen_grad = True``) with the packed backward; same ``grads`` / ``on_block_done`` contract, same flat-buffer and reducer
     routes.  ``hidden`` (parse_hidden's tuple or None): the token outputs asked for are further outputs of this node, behind
-    (logits, features) and in the order asked (then, on the packed path, the int64 row offsets, which carry no gradient)."""
+    (logits, features) and in the order asked (then, on the packed path, the int64 row offsets, which carry no gradient).
+    ``attn`` (parse_attn's triple or None): the attention maps asked for follow the token outputs as outputs marked
+    non-differentiable (on the packed path one flat buffer per map); the backward ignores their (None) gradients."""
 
     @staticmethod
-    def forward(ctx, model, lengths, hidden, x, *params):
-        hs = ()
+    def forward(ctx, model, lengths, hidden, attn, x, *params):
+        hs = maps = ()
         if lengths is None:
-            logits, feat, c, *more = passt_forward(model, x, save=True, hidden=hidden)
+            logits, feat, c, *more = passt_forward(model, x, save=True, hidden=hidden, attn=attn)
             if hidden is not None:
                 hs = tuple(more[0])
+            if attn is not None:
+                maps = tuple(more[1])
         else:
-            if hidden is None:
+            if hidden is None and attn is None:
                 logits, feat, c = passt_forward_varlen(model, x, lengths, save=True)
             else:
-                logits, feat, c, h, tok_offsets = passt_forward_varlen_hidden(model, x, lengths, hidden, save=True)
-                hs = tuple(h) + (tok_offsets,)
+                logits, feat, c, h, *more = passt_forward_varlen_hidden(model, x, lengths, hidden, save=True, attn=attn)
+                if attn is not None:
+                    maps = tuple(more[0])
+                hs, maps = tuple(h), maps + (more[-1],)         # the row offsets come last
+        ctx.mark_non_differentiable(*[m for m in maps if m.is_floating_point()])
         ctx.model, ctx.c, ctx.varlen, ctx.hidden = model, c, lengths is not None, hidden
         # the input spectrogram's gradient is computed only when asked for; a graph none of whose parameters requires a gradient
         # (a frozen loss network) runs the backward without any weight-gradient work
-        ctx.want_dx = bool(ctx.needs_input_grad[3])
-        ctx.frozen = not any(ctx.needs_input_grad[4:])
+        ctx.want_dx = bool(ctx.needs_input_grad[4])
+        ctx.frozen = not any(ctx.needs_input_grad[5:])
         ctx.named, ctx.total = model._graph_params(validate=False)     # the list forward() just handed to apply()
         # bound to a passt_amd.optim.AdamW (PaSST.bind_flat_grads): the only input is a token; the backward writes the gradients
         # straight into the optimizer's persistent flat buffer -- p.grad are views of it -- and hands autograd nothing
         ctx.flat = model._flat if (len(params) == 1 and model._flat is not None and params[0] is model._flat["token"]) else None
         ctx.set_materialize_grads(False)        # an unused `features` output arrives as None, not as a zero tensor
-        return (logits, feat) + hs
+        return (logits, feat) + hs + maps
 
     @staticmethod
     def backward(ctx, dlogits, dfeat, *dhs):
@@ -879,7 +969,7 @@ class _PasstFunction(torch.autograd.Function):
             raise RuntimeError("passt_amd.PaSST: the saved activations of this forward were already consumed by a backward "
                                "pass (retain_graph / double backward are not supported: run the forward again)")
         run_backward = passt_backward_varlen if ctx.varlen else passt_backward
-        lead = (None, None, None)               # the model, the lengths, the hidden request
+        lead = (None, None, None, None)         # the model, the lengths, the hidden request, the attention-map request
         dev = c["feat"].device
         # gradients of the token outputs that fed the loss, as [M][D] rows (an unused one arrives as None and costs nothing)
         dhidden = {k: d.contiguous().view(c["lay"].M, -1) for k, d in zip(ctx.hidden or (), dhs) if d is not None}
@@ -1155,8 +1245,9 @@ class PaSST(nn.Module):
         self._staged.epoch += 1
 
     @compile_opaque
-    def forward(self, x, lengths=None, hidden=None):
-        """x: (B,1,F,T) -> (logits (B,C), features (B,D)); always a tuple (models/passt.py:588,595).
+    def forward(self, x, lengths=None, hidden=None, attn=None, attn_rows="all", attn_heads="each"):
+        """x: (B,1,F,T) -> (logits (B,C), features (B,D)); always a tuple (models/passt.py:588,595).  With the keywords below:
+        ``(logits, features[, hidden][, attn][, tok_offsets])``, tok_offsets whenever ``lengths`` comes with ``hidden`` or ``attn``.
 
         ``hidden`` (a list / tuple of block indices, negative allowed, and / or the string "norm"): also return the token sequence
         at those depths, ``(logits, features, hidden)`` -- with ``lengths``: ``(logits, features, hidden, tok_offsets)`` -- where
@@ -1174,6 +1265,22 @@ class PaSST(nn.Module):
         two prefix rows (about one more block of forward and backward), and logits / features then agree with a call without
         ``hidden`` to rounding, not bit for bit (the all-queries attention kernel orders its sums differently).  A bare int, an
         empty sequence, an index out of range or an entry named twice raises ValueError before anything is launched or drawn.
+
+        ``attn`` (a list / tuple / range of block indices, negative allowed): also return the attention probabilities
+        softmax(q k^T * scale) of those blocks -- what a forward hook on the reference's ``blocks[i].attn.attn_drop`` sees as its
+        input -- as a list in the order asked, f32, computed by a kernel of their own right behind the block's fused attention from
+        the same qkv and row statistics.  An entry is (B, H, Nq, Ntok), or (B, Nq, Ntok) with ``attn_heads="mean"`` (the mean over
+        heads, taken in f32 in head order); ``attn_rows="all"`` gives every query row (Nq = Ntok), ``"prefix"`` the cls and dist
+        query rows only (Nq = 2: the usual saliency rows, and cheap).  Rows and columns are in the token order of ``hidden``: cls,
+        dist, then the kept patches.  With ``lengths`` an entry is a list of B tensors, views of one device buffer: clip i's
+        (H, Nq_i, N_i) or (Nq_i, N_i), what the clip gets alone at batch size 1.  The maps carry no gradient (no grad_fn; they are
+        non-differentiable outputs of the autograd node) and change nothing else: same Patchout draws, and logits, features and
+        every gradient are bit for bit those of a call without ``attn`` -- except that ``attn_rows="all"`` on the last block makes
+        the last block run on all rows instead of the two prefix rows (about one more block of forward and backward), and logits /
+        features then agree with a call without ``attn`` to rounding, not bit for bit (the all-queries attention kernel orders its
+        sums differently); the last block's ``"prefix"`` rows come from the prefix-only tail as it is.  A map costs its own bytes:
+        B * H * Nq * Ntok * 4.  A bare int, an empty sequence, an index out of range or named twice, or another value of
+        ``attn_rows`` / ``attn_heads`` raises ValueError before anything is launched or drawn.
 
         An ``x`` that requires a gradient gets one (``x.grad`` / ``torch.autograd.grad``), as in the reference: PaSST as a
         differentiable loss network.  With every parameter frozen (``net.requires_grad_(False)``) this needs no switch and the backward
@@ -1204,6 +1311,12 @@ class PaSST(nn.Module):
         kernels run the bf16 MFMA path with f32 accumulation and return f32 logits / features: bf16 has f32's exponent range,
         so a GradScaler's loss scale flows through the backward without overflow and its inf checks never fire."""
         hid = None if hidden is None else parse_hidden(hidden, len(self.blocks))
+        if attn is None:
+            if attn_rows not in ("all", "prefix") or attn_heads not in ("each", "mean"):
+                parse_attn((0,), 1, attn_rows, attn_heads)     # raises
+            amap = None
+        else:
+            amap = parse_attn(attn, len(self.blocks), attn_rows, attn_heads)
         if lengths is not None and self.training:
             raise NotImplementedError("PaSST.forward(x, lengths=...): training on ragged batches is not supported (eval mode only; "
                                       "no reference flow trains on clips of different lengths)")
@@ -1233,27 +1346,35 @@ class PaSST(nn.Module):
             fl = self._flat
             if fl is not None:
                 if fl["named"] is named:                # same validated parameter list as at bind time
-                    return self._with_hidden(_PasstFunction.apply(self, lengths, hid, x, fl["token"]), hid)
+                    return self._with_hidden(_PasstFunction.apply(self, lengths, hid, amap, x, fl["token"]), hid, amap)
                 self.unbind_flat_grads()                # surgery since: the optimizer re-binds at its next step
-            return self._with_hidden(_PasstFunction.apply(self, lengths, hid, x, *[p for _, p in named]), hid)
+            return self._with_hidden(_PasstFunction.apply(self, lengths, hid, amap, x, *[p for _, p in named]), hid, amap)
         if lengths is not None:
             with torch.no_grad():
-                if hid is None:
+                if hid is None and amap is None:
                     return passt_forward_varlen(self, x, lengths)
-                logits, feat, _, hs, tok_offsets = passt_forward_varlen_hidden(self, x, lengths, hid)
-                return logits, feat, hs, tok_offsets
-        if hid is None:
+                logits, feat, _, hs, *more = passt_forward_varlen_hidden(self, x, lengths, hid, attn=amap)
+                return self._with_hidden((logits, feat) + tuple(hs) + tuple(more[0] if amap is not None else ()) + (more[-1],), hid, amap)
+        if hid is None and amap is None:
             logits, feat, _ = passt_forward(self, x, save=False)
             return logits, feat
-        logits, feat, _, hs = passt_forward(self, x, save=False, hidden=hid)
-        return logits, feat, hs
+        logits, feat, _, hs, *more = passt_forward(self, x, save=False, hidden=hid, attn=amap)
+        return self._with_hidden((logits, feat) + tuple(hs) + tuple(more[0] if more else ()), hid, amap)
 
-    @staticmethod
-    def _with_hidden(out, hid):
-        """The autograd node's flat outputs in forward()'s shape: (logits, features[, [token outputs][, tok_offsets]])."""
-        if hid is None:
-            return out
-        return out[:2] + (list(out[2:2 + len(hid)]),) + tuple(out[2 + len(hid):])
+    def _with_hidden(self, out, hid, amap=None):
+        """The autograd node's flat outputs in forward()'s shape: (logits, features[, [token outputs]][, [attention maps]]
+        [, tok_offsets]); a packed batch's maps (one flat buffer each) are cut into the clips' views here."""
+        nh, na = len(hid or ()), len(amap[0]) if amap is not None else 0
+        res = tuple(out[:2])
+        if hid is not None:
+            res += (list(out[2:2 + nh]),)
+        rest = tuple(out[2 + nh + na:])                 # the packed path's tok_offsets, or nothing
+        if amap is not None:
+            maps = list(out[2 + nh:2 + nh + na])
+            if rest:
+                maps = [_PackedLayout.attn_views(m, rest[0], self.num_heads, amap[1], amap[2]) for m in maps]
+            res += (maps,)
+        return res + rest
 
 
 # --------------------------------------------------------------------------------------------
@@ -1348,12 +1469,15 @@ class EnsembelerModel(nn.Module):
         super().__init__()
         self.models = nn.ModuleList(models)
 
-    def forward(self, x, lengths=None, hidden=None):
+    def forward(self, x, lengths=None, hidden=None, attn=None):
         """``lengths``: handed to every member (PaSST.forward's ragged-batch eval forward; gradients flow through the members that
-        set ``varlen_grad``).  ``hidden`` is not for an ensemble: its members have different depths and widths."""
+        set ``varlen_grad``).  ``hidden`` and ``attn`` are not for an ensemble: its members have different depths, widths and heads."""
         if hidden is not None:
             raise ValueError("EnsembelerModel.forward: hidden= is not supported (the members' token sequences have different widths "
                              "and depths and cannot be averaged); call the member you want: model.models[i](x, hidden=...)")
+        if attn is not None:
+            raise ValueError("EnsembelerModel.forward: attn= is not supported (the members have different depths, heads and token "
+                             "counts; their attention maps cannot be averaged); call the member you want: model.models[i](x, attn=...)")
         all_out = None
         for m in self.models:
             out, _ = m(x) if lengths is None else m(x, lengths=lengths)
