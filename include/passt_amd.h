@@ -497,6 +497,24 @@ int pa_patch_input_bwd_varlen(const void* dcols, int dtype, const int32_t* cu_to
                               int T_max, float* dx, void* stream);
 int pa_patch_bwd_varlen(const float* dtok, int M, int D, const int32_t* cu_tok, int B, int Tpe, int Fpe, float* d_cls, float* d_dist,
                         float* d_npe, float* d_bias, float* d_time_pos, float* d_freq_pos, int accumulate, void* stream);
+/* Backward of the packed patch stage WITH Patchout (training on a packed batch: every clip keeps its own patches and, in front of a
+ * time embedding longer than the clip, its own random offset into it, models/passt.py:513-553 per clip).  A row's grid position no
+ * longer follows from its place in the clip, so both entry points walk a slot table IN DEVICE MEMORY: slot[B][Fg][Tg] int32 = the
+ * packed row of the kept patch (f, t) of clip b, -1 where there is none (dropped, behind the clip's last column, behind the time cut);
+ * Tg = the patch columns of the widest clip.  An entry outside [0, M) counts as -1.  The forward needs no new entry point:
+ * pa_patch_gather_varlen takes the kept patches' coordinates per row, pa_patch_pos_table_varlen takes row_t + the clip's offset.
+ * pa_patch_input_bwd_rows: the fold.  dcols[M][P*P] (dtype) -> dx[B][1][F][T_max] f32, Fg = (F - P) / fstride + 1.  Gather form as
+ *   pa_patch_input_bwd: one output element adds the KEPT patches that cover it, found through the slot table, in (frequency row, time
+ *   column) order, no atomics.  EVERY element of dx is written; it is exactly 0 where no kept patch covers it.
+ * pa_patch_bwd_rows: d_cls, d_dist, d_npe[2][D], d_bias[D], d_time_pos[D][Tpe], d_freq_pos[D][Fpe] (overwritten or accumulated) from
+ *   dtok[M][D] f32; cu_tok: B + 1 row offsets, toff: B time-embedding offsets (int32, device memory), Fg = Fpe.  Time position p
+ *   collects grid column p - toff[b] of every clip b.  Deterministic: a positional slot enumerates its rows through the slot table
+ *   in a fixed order (clip, then frequency row, then column), no atomics.  All six NULL (frozen network): nothing is launched. */
+int pa_patch_input_bwd_rows(const void* dcols, int dtype, int M, const int32_t* slot, int B, int Tg, int P, int fstride, int tstride,
+                            int F, int T_max, float* dx, void* stream);
+int pa_patch_bwd_rows(const float* dtok, int M, int D, const int32_t* slot, const int32_t* cu_tok, const int32_t* toff, int B, int Tg,
+                      int Tpe, int Fpe, float* d_cls, float* d_dist, float* d_npe, float* d_bias, float* d_time_pos, float* d_freq_pos,
+                      int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Head: final norm on the two prefix tokens, their mean, head LayerNorm + Linear

@@ -102,6 +102,8 @@ SIGNATURES = {
     "pa_patch_pos_table_varlen": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "pa_patch_input_bwd_varlen": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "pa_patch_bwd_varlen": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "pa_patch_input_bwd_rows": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "pa_patch_bwd_rows": (i32, [vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]),
     "pa_patch_bwd": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp]),
     "pa_patch_input_bwd_ws_ints": (i64, [i32, i32, i32, i32, i32]),
     "pa_patch_input_bwd": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),

@@ -380,6 +380,148 @@ __global__ __launch_bounds__(256) void patch_param_grads_varlen_kernel(const flo
     }
 }
 
+// ---- packed batch with Patchout (training): backward of the patch stage through a slot table -----------------------------------------
+// With patches dropped a row's grid position no longer follows from its place in the clip, so both kernels walk
+// slot[B][Fg][Tg] (int32): the packed row of the kept patch (f, t) of clip b, or -1 (dropped, behind the clip's last column, behind
+// the time cut); Tg = the patch columns of the widest clip.  An entry outside [0, M) is treated as -1.
+
+// patch_fold_varlen_kernel with the covering patches looked up in the slot table: dx[b][f][t] = sum of dcols[slot[b][gf][gt]][(f - gf*fs)*P +
+// (t - gt*ts)] over the KEPT patches (gf, gt) of clip b that hold (f, t), added in (gf, gt) order.  Every element of dx[B][F][Tt] is
+// written; a pixel no kept patch covers gets exactly 0.
+template <typename T>
+__global__ __launch_bounds__(256) void patch_fold_rows_kernel(const T* __restrict__ dcols, int M, const int32_t* __restrict__ slot, int P,
+                                                              int fs, int ts, int Fg, int Tg, int F, int Tt, int64_t n, float* __restrict__ dx) {
+    const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i0 >= n) return;
+    const int64_t row0 = i0 / Tt;
+    const int t0 = (int)(i0 - row0 * Tt);
+    const int PP = P * P;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (t0 + 4 <= Tt) {
+        const int f = (int)(row0 % F);
+        const int32_t* tab = slot + (row0 / F) * Fg * Tg;
+        int flo, fhi, tlo, thi, unused;
+        cover_range(f, P, fs, Fg, flo, fhi);
+        cover_range(t0, P, ts, Tg, tlo, unused);
+        cover_range(t0 + 3, P, ts, Tg, unused, thi);
+        for (int gf = flo; gf <= fhi; ++gf) {
+            for (int gt = tlo; gt <= thi; ++gt) {
+                const int r = tab[gf * Tg + gt];
+                if ((unsigned)r >= (unsigned)M) continue;
+                const int j0 = t0 - gt * ts;
+                const T* src = dcols + (int64_t)r * PP + (f - gf * fs) * P;
+                if constexpr (sizeof(T) == 2) {
+                    if (j0 >= 0 && j0 + 4 <= P && !((j0 | P) & 1)) {
+                        const bf16x2 lo = *(const bf16x2*)(src + j0), hi = *(const bf16x2*)(src + j0 + 2);
+                        v[0] += (float)lo[0]; v[1] += (float)lo[1]; v[2] += (float)hi[0]; v[3] += (float)hi[1];
+                        continue;
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if ((unsigned)(j0 + e) < (unsigned)P) v[e] += to_f32<T>(src[j0 + e]);
+            }
+        }
+    } else {                                         // the four elements straddle a row end (T % 4 != 0) or the end of dx
+        for (int e = 0; e < 4 && i0 + e < n; ++e) {
+            const int64_t row = (i0 + e) / Tt;
+            const int t = (int)(i0 + e - row * Tt), f = (int)(row % F);
+            const int32_t* tab = slot + (row / F) * Fg * Tg;
+            int flo, fhi, tlo, thi;
+            cover_range(f, P, fs, Fg, flo, fhi);
+            cover_range(t, P, ts, Tg, tlo, thi);
+            for (int gf = flo; gf <= fhi; ++gf)
+                for (int gt = tlo; gt <= thi; ++gt) {
+                    const int r = tab[gf * Tg + gt];
+                    if ((unsigned)r < (unsigned)M) v[e] += to_f32<T>(dcols[(int64_t)r * PP + (f - gf * fs) * P + (t - gt * ts)]);
+                }
+        }
+    }
+    if (i0 + 4 <= n) {
+        *(f32x4*)(dx + i0) = f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+        for (int e = 0; i0 + e < n; ++e) dx[i0 + e] = v[e];
+    }
+}
+
+// patch_param_grads_varlen_kernel for a batch with Patchout: workgroup = one slot x 16 channels x 16 row groups.  Slot 0 (conv bias,
+// cls / dist) needs no table: a clip's patch rows are cu_tok[b] + 2 .. cu_tok[b + 1].  A positional slot enumerates its CANDIDATE
+// cells of the slot table clip after clip -- time position p: the Fg cells of grid column p - toff[b] (the clip's own random offset
+// into the time embedding), frequency row f: the Tg cells of that row -- and adds the rows of the kept ones.  Thread group ry takes
+// candidates ry, ry + 16, ... of every clip in ascending order and the 16 partial sums meet in LDS in a fixed order: no atomics,
+// bit-identical from run to run.
+__global__ __launch_bounds__(256) void patch_param_grads_rows_kernel(const float* __restrict__ dtok, int M, int D, const int32_t* __restrict__ slot,
+                                                                     const int32_t* __restrict__ cu_tok, const int32_t* __restrict__ toff, int B,
+                                                                     int Tg, int Tpe, int Fpe, float* __restrict__ d_cls, float* __restrict__ d_dist,
+                                                                     float* __restrict__ d_npe, float* __restrict__ d_bias, float* __restrict__ d_tpos,
+                                                                     float* __restrict__ d_fpos, int accumulate) {
+    __shared__ float red[16][17];
+    const int cx = threadIdx.x & 15, ry = threadIdx.x >> 4;
+    const int slot_id = blockIdx.y;                    // 0: bias + prefix tokens; 1 .. Tpe: time; Tpe + 1 .. Tpe + Fpe: frequency
+    const int d = blockIdx.x * 16 + cx;
+    auto put = [&](float* p, float v) { *p = (accumulate ? *p : 0.f) + v; };
+    float s0 = 0.f, s1 = 0.f;
+    if (d < D) {
+        const float* src = dtok + d;
+        for (int b = 0; b < B; ++b) {
+            if (slot_id == 0) {
+                const int lo = max(cu_tok[b] + 2, 0), hi = min(cu_tok[b + 1], M);
+                int r = lo + ry;
+                for (; r + 16 < hi; r += 32) {         // two rows per step: two loads in flight
+                    s0 += src[(int64_t)r * D];
+                    s1 += src[(int64_t)(r + 16) * D];
+                }
+                if (r < hi) s0 += src[(int64_t)r * D];
+                continue;
+            }
+            const int32_t* tab = slot + (int64_t)b * Fpe * Tg;
+            int count, step;                           // the slot's candidate cells of this clip: tab[j * step], j < count
+            if (slot_id <= Tpe) {
+                const int t = slot_id - 1 - toff[b];
+                count = (unsigned)t < (unsigned)Tg ? Fpe : 0; step = Tg; tab += count ? t : 0;
+            } else {
+                count = Tg; step = 1; tab += (slot_id - 1 - Tpe) * Tg;
+            }
+            int j = ry;
+            for (; j + 16 < count; j += 32) {
+                const int r0 = tab[j * step], r1 = tab[(j + 16) * step];
+                if ((unsigned)r0 < (unsigned)M) s0 += src[(int64_t)r0 * D];
+                if ((unsigned)r1 < (unsigned)M) s1 += src[(int64_t)r1 * D];
+            }
+            if (j < count) {
+                const int r0 = tab[j * step];
+                if ((unsigned)r0 < (unsigned)M) s0 += src[(int64_t)r0 * D];
+            }
+        }
+    }
+    red[ry][cx] = s0 + s1;
+    __syncthreads();
+    if (ry == 0 && d < D) {
+        float s = 0.f;
+#pragma unroll
+        for (int y = 0; y < 16; ++y) s += red[y][cx];
+        if (slot_id == 0) {
+            float c = 0.f, t = 0.f;
+            for (int b = 0; b < B; ++b) {
+                const int tok0 = cu_tok[b];
+                if (tok0 >= 0 && cu_tok[b + 1] - tok0 >= 2 && tok0 + 2 <= M) {
+                    c += dtok[(int64_t)tok0 * D + d];
+                    t += dtok[((int64_t)tok0 + 1) * D + d];
+                }
+            }
+            put(d_bias + d, s);
+            put(d_cls + d, c);
+            put(d_dist + d, t);
+            put(d_npe + d, c);
+            put(d_npe + D + d, t);
+        } else if (slot_id <= Tpe) {
+            put(d_tpos + (int64_t)d * Tpe + (slot_id - 1), s);
+        } else {
+            put(d_fpos + (int64_t)d * Fpe + (slot_id - 1 - Tpe), s);
+        }
+    }
+}
+
 }  // namespace pa
 
 using namespace pa;
@@ -513,5 +655,36 @@ extern "C" int pa_patch_bwd_varlen(const float* dtok, int M, int D, const int32_
     if (!d_cls || !d_dist || !d_npe || !d_bias || !d_time_pos || !d_freq_pos) return PA_EINVAL;
     hipLaunchKernelGGL(patch_param_grads_varlen_kernel, dim3((unsigned)cdiv(D, 16), (unsigned)(1 + Tpe + Fpe)), dim3(256), 0, (hipStream_t)stream,
                        dtok, D, cu_tok, B, Tpe, Fpe, d_cls, d_dist, d_npe, d_bias, d_time_pos, d_freq_pos, accumulate);
+    return check_launch();
+}
+
+extern "C" int pa_patch_input_bwd_rows(const void* dcols, int dtype, int M, const int32_t* slot, int B, int Tg, int P, int fstride, int tstride,
+                                       int F, int T_max, float* dx, void* stream) {
+    if (!dcols || !slot || !dx || M <= 0 || B <= 0 || Tg <= 0 || P <= 0 || fstride <= 0 || tstride <= 0 || F < P || T_max < P) return PA_EINVAL;
+    if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
+    const int Fg = (F - P) / fstride + 1;
+    const int64_t n = (int64_t)B * F * T_max;
+    // int32 indexing of the table and of the launch grid
+    if ((int64_t)B * Fg * Tg >= ((int64_t)1 << 31) || cdiv(n, 1024) >= ((int64_t)1 << 31)) return PA_EUNSUPPORTED;
+    const dim3 grid((unsigned)cdiv(n, 1024)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PA_BF16)
+        hipLaunchKernelGGL(patch_fold_rows_kernel<bf16>, grid, block, 0, st, (const bf16*)dcols, M, slot, P, fstride, tstride, Fg, Tg, F, T_max, n, dx);
+    else
+        hipLaunchKernelGGL(patch_fold_rows_kernel<float>, grid, block, 0, st, (const float*)dcols, M, slot, P, fstride, tstride, Fg, Tg, F, T_max, n, dx);
+    return check_launch();
+}
+
+extern "C" int pa_patch_bwd_rows(const float* dtok, int M, int D, const int32_t* slot, const int32_t* cu_tok, const int32_t* toff, int B, int Tg,
+                                 int Tpe, int Fpe, float* d_cls, float* d_dist, float* d_npe, float* d_bias, float* d_time_pos, float* d_freq_pos,
+                                 int accumulate, void* stream) {
+    // all six NULL: nothing to do (frozen network)
+    const bool none = !d_cls && !d_dist && !d_npe && !d_bias && !d_time_pos && !d_freq_pos;
+    if (!dtok || !slot || !cu_tok || !toff || M <= 0 || D <= 0 || B <= 0 || Tg <= 0 || Tpe <= 0 || Fpe <= 0) return PA_EINVAL;
+    if ((int64_t)B * Fpe * Tg >= ((int64_t)1 << 31)) return PA_EUNSUPPORTED;
+    if (none) return PA_OK;
+    if (!d_cls || !d_dist || !d_npe || !d_bias || !d_time_pos || !d_freq_pos) return PA_EINVAL;
+    hipLaunchKernelGGL(patch_param_grads_rows_kernel, dim3((unsigned)cdiv(D, 16), (unsigned)(1 + Tpe + Fpe)), dim3(256), 0, (hipStream_t)stream,
+                       dtok, M, D, slot, cu_tok, toff, B, Tg, Tpe, Fpe, d_cls, d_dist, d_npe, d_bias, d_time_pos, d_freq_pos, accumulate);
     return check_launch();
 }

@@ -1032,6 +1032,36 @@ def patch_bwd_varlen(dtok, cu_tok, B, Tpe, Fpe, d_cls, d_dist, d_npe, d_bias, d_
                                           _p(d_bias), _p(d_tpos), _p(d_fpos), int(accumulate), _stream()), "pa_patch_bwd_varlen")
 
 
+def patch_input_bwd_rows(dcols, slot, F, T_max, P, fstride, tstride, out=None):
+    """patch_input_bwd_varlen for a packed batch with Patchout: the kept patches that cover a pixel are found through ``slot``, the
+    (B, Fg, Tg) int32 device table of their packed rows (-1: no kept patch there).  dx [B][1][F][T_max] f32, every element written,
+    exactly 0 where no kept patch covers it; deterministic.  out: an existing (B, 1, F, T_max) f32 tensor to overwrite."""
+    if dcols.dim() != 2 or dcols.shape[1] != P * P or slot.dim() != 3 or F < P or T_max < P or slot.shape[1] != (F - P) // fstride + 1 \
+            or slot.shape[2] < 1:
+        raise _lib.PasstAmdError(f"patch_input_bwd_rows: dcols {tuple(dcols.shape)}, slot {tuple(slot.shape)} for P={P}, F={F}, T={T_max}")
+    B, _, Tg = slot.shape
+    dx = torch.empty((B, 1, F, T_max), device=dcols.device, dtype=torch.float32) if out is None else out
+    if dx.shape != (B, 1, F, T_max):
+        raise _lib.PasstAmdError(f"patch_input_bwd_rows: out is {tuple(dx.shape)}, expected {(B, 1, F, T_max)}")
+    check(_lib.load().pa_patch_input_bwd_rows(_p(dcols), PA_DTYPE[dcols.dtype], dcols.shape[0], _p(slot, torch.int32), B, Tg, P, fstride, tstride,
+                                              F, T_max, _p(dx, torch.float32), _stream()), "pa_patch_input_bwd_rows")
+    return dx
+
+
+def patch_bwd_rows(dtok, slot, cu_tok, toff, Tpe, Fpe, d_cls, d_dist, d_npe, d_bias, d_tpos, d_fpos, accumulate=False):
+    """patch_bwd_varlen for a packed batch with Patchout: ``slot`` as in patch_input_bwd_rows, ``toff`` the (B,) int32 device array of
+    the clips' offsets into the time embedding.  Overwritten or accumulated; deterministic."""
+    if dtok.dim() != 2 or slot.dim() != 3 or slot.shape[1] != Fpe or slot.shape[2] < 1 or cu_tok.dim() != 1 \
+            or cu_tok.numel() != slot.shape[0] + 1 or toff.dim() != 1 or toff.numel() != slot.shape[0]:
+        raise _lib.PasstAmdError(f"patch_bwd_rows: dtok {tuple(dtok.shape)}, slot {tuple(slot.shape)}, cu_tok {tuple(cu_tok.shape)}, "
+                                 f"toff {tuple(toff.shape)} for Fpe={Fpe}")
+    M, D = dtok.shape
+    B, _, Tg = slot.shape
+    check(_lib.load().pa_patch_bwd_rows(_p(dtok, torch.float32), M, D, _p(slot, torch.int32), _p(cu_tok, torch.int32), _p(toff, torch.int32), B, Tg,
+                                        Tpe, Fpe, _p(d_cls), _p(d_dist), _p(d_npe), _p(d_bias), _p(d_tpos), _p(d_fpos), int(accumulate), _stream()),
+          "pa_patch_bwd_rows")
+
+
 # ---- head / loss -----------------------------------------------------------------------------
 def head_pre_fwd(x, norm_g, norm_b, eps_norm, hg, hb, eps_head):
     B, Ntok, D = x.shape

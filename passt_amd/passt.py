@@ -598,10 +598,81 @@ def varlen_geometry(lengths, P, tstride, F_dim, Tpe, T_max=None):
     return dict(row_clip=row_clip, row_f=row_f, row_t=row_t, cu_tok=cu.astype(np.int32), T_eff=T_eff, cut=cut, max_N=int(ntok.max()))
 
 
+def varlen_geometry_train(model, lengths, F_dim=None, T_max=None):
+    """varlen_geometry for a packed batch in training mode: every clip gets the Patchout it would get alone at batch size 1.  The
+    draws are made clip after clip, i = 0 .. B - 1, each with the reference's own torch CPU RNG calls in the reference's order
+    (draw_patchout: randint for the time-positional offset when the clip has fewer patch columns than the time embedding, then
+    randperm for s_patchout_t, s_patchout_f, u_patchout), so after torch.manual_seed(s) one call leaves the CPU generator where
+    the loop ``for i: net(x[i:i+1, :, :, :lengths[i]])`` leaves it, with the same kept patches and offsets.  ``F_dim``: frequency
+    rows of the patch grid (default: the frequency embedding's).  Returns varlen_geometry's dict -- ``row_clip`` / ``row_f`` /
+    ``row_t`` / ``cu_tok`` / ``T_eff`` / ``cut`` / ``max_N``, the patch rows of a clip being its KEPT patches in sequence order -- plus
+    ``row_tpos`` (= row_t + the clip's offset on the patch rows: the column of the time embedding; row_t on the prefix rows),
+    ``toff`` (int32, one per clip), ``Tg`` (patch columns of the widest clip) and ``slot`` (int32 [B][F_dim][Tg]: the packed row of the
+    kept patch (f, t) of clip b, -1 where there is none).
+    ValueError -- BEFORE any RNG call, so a rejected batch consumes nothing -- names the first clip that is shorter than one patch or
+    longer than ``T_max``, or that cannot satisfy the configured counts: no more patch columns than s_patchout_t, no more frequency
+    rows than s_patchout_f, no more patches left than u_patchout, or structured time Patchout on a clip with more patch columns than
+    the time embedding (the reference indexes the cut grid with indices of the uncut one and fails, models/passt.py:536)."""
+    P, ts = model.patch_embed.patch_size[0], model.patch_embed.stride[1]
+    Tpe = model.time_new_pos_embed.shape[-1]
+    if F_dim is None:
+        F_dim = model.freq_new_pos_embed.shape[-2]
+    s_t, s_f, u = (int(model.s_patchout_t or 0), int(model.s_patchout_f or 0), int(model.u_patchout or 0)) if model.training else (0, 0, 0)
+    lens = [int(v) for v in lengths]
+    if not lens:
+        raise ValueError("lengths is empty")
+    T_dims, cut = [], []
+    for i, n in enumerate(lens):
+        if n < P:
+            raise ValueError(f"clip {i}: {n} frames are shorter than one patch ({P} frames): no patch column")
+        if T_max is not None and n > T_max:
+            raise ValueError(f"clip {i}: length {n} exceeds the input's {T_max} frames")
+        T_dim = (n - P) // ts + 1
+        if s_t and T_dim <= s_t:
+            raise ValueError(f"clip {i}: {T_dim} patch columns ({n} frames) leave nothing after s_patchout_t={s_t}")
+        if s_t and T_dim > Tpe:
+            raise ValueError(f"clip {i}: {T_dim} patch columns ({n} frames) exceed the time embedding's {Tpe}; structured time Patchout "
+                             "cannot be drawn for a clip that is cut (the reference fails at models/passt.py:536)")
+        if s_f and F_dim <= s_f:
+            raise ValueError(f"clip {i}: {F_dim} frequency rows leave nothing after s_patchout_f={s_f}")
+        left = (F_dim - s_f) * ((T_dim - s_t) if s_t else min(T_dim, Tpe))
+        if u and u >= left:
+            raise ValueError(f"clip {i}: u_patchout={u} needs more than the {left} patches the clip has left ({n} frames)")
+        if T_dim >= Tpe:
+            cut.append(i)
+        T_dims.append(T_dim)
+    B = len(lens)
+    pfs, pts, toffs, T_eff = [], [], [], []
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                 # draw_patchout's "x will be cut", per clip: the caller warns once, from ``cut``
+        for T_dim in T_dims:
+            toff, Te, idx_t, idx_f, idx_u = draw_patchout(model, F_dim, T_dim)
+            pf, pt = kept_patches(F_dim, Te, idx_t, idx_f, idx_u)
+            pfs.append(pf), pts.append(pt), toffs.append(toff), T_eff.append(Te)
+    ntok = np.array([2 + pf.size for pf in pfs], dtype=np.int64)
+    cu = np.zeros(B + 1, dtype=np.int64)
+    np.cumsum(ntok, out=cu[1:])
+    M = int(cu[-1])
+    if M >= 2 ** 31:
+        raise ValueError("packed batch has too many tokens")
+    Tg = max(T_eff)
+    row_clip = np.repeat(np.arange(B, dtype=np.int32), ntok)
+    row_f, row_t, row_tpos = (np.empty(M, dtype=np.int32) for _ in range(3))
+    slot = np.full((B, F_dim, Tg), -1, dtype=np.int32)
+    for i, (pf, pt) in enumerate(zip(pfs, pts)):
+        o = int(cu[i])
+        row_f[o:o + 2], row_t[o:o + 2], row_tpos[o:o + 2] = -1, (0, 1), (0, 1)
+        row_f[o + 2:o + 2 + pf.size], row_t[o + 2:o + 2 + pf.size], row_tpos[o + 2:o + 2 + pf.size] = pf, pt, pt + toffs[i]
+        slot[i, pf, pt] = o + 2 + np.arange(pf.size, dtype=np.int32)
+    return dict(row_clip=row_clip, row_f=row_f, row_t=row_t, row_tpos=row_tpos, cu_tok=cu.astype(np.int32), T_eff=T_eff, cut=cut,
+                max_N=int(ntok.max()), toff=np.array(toffs, dtype=np.int32), Tg=Tg, slot=slot)
+
+
 def passt_forward_varlen(model, x, lengths, save=False):
-    """Kernel sequence of the packed eval forward: every clip gets what it would get alone at batch size 1.  Returns (logits, features);
+    """Kernel sequence of the packed forward: every clip gets what it would get alone at batch size 1.  Returns (logits, features);
     ``save=True``: (logits, features, ctx) with what passt_backward_varlen needs.  Without it nothing is kept and the launch sequence is
-    the same."""
+    the same.  Eval geometry (no Patchout) -- except for a model in training mode with ``varlen_train`` set: then every clip gets its own
+    Patchout draws (varlen_geometry_train) and the context carries the slot table the packed patch-stage backward walks."""
     with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
         logits, feat, ctx = _passt_forward_varlen(model, x, lengths, save)[:3]
     return (logits, feat, ctx) if save else (logits, feat)
@@ -628,26 +699,39 @@ def _passt_forward_varlen(model, x, lengths, save=False, hidden=None, attn=None)
     if len(lengths) != B:
         raise ValueError(f"lengths has {len(lengths)} entries for a batch of {B} clips")
     P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
-    g = varlen_geometry(lengths, P, ts, _freq_rows(model, F), model.time_new_pos_embed.shape[-1], T_max=T)
+    train = model.training and getattr(model, "varlen_train", False)       # Patchout per clip (PaSST.forward lets no other training call in)
+    if train:
+        g = varlen_geometry_train(model, lengths, _freq_rows(model, F), T_max=T)
+    else:
+        g = varlen_geometry(lengths, P, ts, _freq_rows(model, F), model.time_new_pos_embed.shape[-1], T_max=T)
     if g["cut"]:
         warnings.warn(f"the patches shape of clips {g['cut']} are larger than the expected time encodings "
                       f"{tuple(model.time_new_pos_embed.shape)}, x will be cut")              # :524-526, once per call
     M = g["row_f"].size
-    # one upload: [row_clip | row_f | row_t | cu_tok | prefix rows]
+    # one upload: [row_clip | row_f | row_t | cu_tok | prefix rows], in training mode followed by [row_tpos | clip offsets | slot table]
     cu = g["cu_tok"]
     pidx_np = (cu[:-1, None] + np.arange(2, dtype=np.int32)[None, :]).reshape(-1).astype(np.int32)
-    idx = ops.upload_small(np.concatenate([g["row_clip"], g["row_f"], g["row_t"], cu, pidx_np]), x.device)
+    parts = [g["row_clip"], g["row_f"], g["row_t"], cu, pidx_np]
+    if train:
+        parts += [g["row_tpos"], g["toff"], g["slot"].reshape(-1)]
+    idx = ops.upload_small(np.concatenate(parts), x.device)
     row_clip, row_f, row_t = idx[:M], idx[M:2 * M], idx[2 * M:3 * M]
-    cu_tok, pidx = idx[3 * M:3 * M + B + 1], idx[3 * M + B + 1:]
+    cu_tok, pidx = idx[3 * M:3 * M + B + 1], idx[3 * M + B + 1:3 * M + 3 * B + 1]
+    row_tpos = row_t                                 # eval: the time embedding is read from offset 0
+    if train:
+        o = 3 * M + 3 * B + 1
+        row_tpos, toff, slot = idx[o:o + M], idx[o + M:o + M + B], idx[o + M + B:].view(g["slot"].shape)
 
     # patch embedding: the packed im2col has a zero row under every prefix token and the table holds the token there, so the one
     # GEMM with the residual epilogue writes the whole token matrix (no scatter pass)
     cols = ops.patch_gather_varlen(x, row_clip, row_f, row_t, P, fs, ts, dt)
-    table = ops.patch_pos_table_varlen(model.patch_embed.proj.bias, model.time_new_pos_embed, model.freq_new_pos_embed, row_f, row_t,
+    table = ops.patch_pos_table_varlen(model.patch_embed.proj.bias, model.time_new_pos_embed, model.freq_new_pos_embed, row_f, row_tpos,
                                        model.cls_token, model.dist_token, model.new_pos_embed)
     xs = torch.empty((M, model.embed_dim), device=x.device, dtype=torch.float32)
     ops.gemm_nt(cols, model._staged.get(model.patch_embed.proj.weight, dt, False), dt, EPI_RESID, resid=table, out_f32=xs)
     patch = dict(F=F, T=T, cols=cols) if save else None
+    if save and train:
+        patch.update(slot=slot, toff=toff)           # Patchout: the patch-stage backward finds a row's grid position through the table
     tok_offsets = torch.from_numpy(cu.astype(np.int64)) if (hidden is not None or attn is not None) else None
     lay = _PackedLayout(B, M, g["max_N"], cu_tok, pidx, ntok=np.diff(cu))
     return _forward_trunk(model, lay, xs, dt, save, patch, hidden, attn) + (tok_offsets,)
@@ -875,15 +959,22 @@ def _patch_backward_varlen(model, ctx, wg, dx, dx_lp, want_dx):
     both GEMMs run over all M rows of dx_lp: no compaction pass."""
     dt, lay, p, g, st = ctx["dt"], ctx["lay"], ctx["patch"], wg.g, model._staged
     Tpe, Fpe = model.time_new_pos_embed.shape[-1], model.freq_new_pos_embed.shape[-2]
+    slot = p.get("slot")                             # training mode (Patchout): the rows of a clip are not a regular grid
     if not wg.frozen:
-        ops.patch_bwd_varlen(dx, lay.cu_tok, lay.B, Tpe, Fpe, g["cls_token"], g["dist_token"], g["new_pos_embed"],
-                             g["patch_embed.proj.bias"], g["time_new_pos_embed"], g["freq_new_pos_embed"])
+        d_pos = (g["cls_token"], g["dist_token"], g["new_pos_embed"], g["patch_embed.proj.bias"], g["time_new_pos_embed"],
+                 g["freq_new_pos_embed"])
+        if slot is None:
+            ops.patch_bwd_varlen(dx, lay.cu_tok, lay.B, Tpe, Fpe, *d_pos)
+        else:
+            ops.patch_bwd_rows(dx, slot, lay.cu_tok, p["toff"], Tpe, Fpe, *d_pos)
     wg.launch_async(dx_lp, p["cols"], g["patch_embed.proj.weight"], None, done=-1)
     if not want_dx:
         return None
     P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
     dcols = torch.empty((lay.M, P * P), device=dx_lp.device, dtype=dx_lp.dtype)
     ops.gemm_nt(dx_lp, st.get(model.patch_embed.proj.weight, dt, True), dt, EPI_STORE, out_lp=dcols)
+    if slot is not None:
+        return ops.patch_input_bwd_rows(dcols, slot, p["F"], p["T"], P, fs, ts)
     return ops.patch_input_bwd_varlen(dcols, lay.cu_tok, lay.B, p["F"], p["T"], P, fs, ts)
 
 
@@ -1101,6 +1192,10 @@ class PaSST(nn.Module):
         # one, gradients for the parameters that require one, together if both do (input_grad is not looked at on that path).  Off:
         # the ragged forward records nothing, as it always did
         self.varlen_grad = False
+        # opt-in: forward(x, lengths=...) in TRAINING mode -- Patchout per clip, drawn clip after clip as at batch size 1 -- as an autograd
+        # node under the fixed path's rule (grad enabled and anything requires a gradient; varlen_grad / input_grad are not looked at).
+        # Off: such a call raises NotImplementedError, as it always did
+        self.varlen_train = False
         self.init_weights(weight_init)
         self._reset_runtime()
 
@@ -1291,7 +1386,7 @@ class PaSST(nn.Module):
         in ``x`` (B, 1, n_mels, T_max); clip i is valid in its first lengths[i] frames and whatever lies behind them has no influence
         (it is never read).  Row i of both outputs is what ``forward(x[i:i+1, :, :, :lengths[i]])`` returns at batch size 1 -- the
         reference's own way of evaluating clips of different lengths (ex_fsd50k.py:53-56) -- but the batch runs as ONE packed kernel
-        sequence over sum_i tokens.  Eval mode only.  The token geometry is decided on the host: ``lengths`` given as a device tensor
+        sequence over sum_i tokens.  Eval mode (training mode: ``varlen_train``, below).  The token geometry is decided on the host: ``lengths`` given as a device tensor
         costs one host read.  A clip shorter than one patch raises ValueError; clips whose patch columns reach the time embedding's
         length are cut to it, with one warning per call.
         Gradients through the ragged forward are opt-in: by default the outputs carry no grad_fn, also for an ``x`` that requires a
@@ -1300,7 +1395,21 @@ class PaSST(nn.Module):
         exactly 0 at frames >= lengths[i] and behind the time cut; every parameter that requires a gradient gets one; a fully frozen
         network runs no weight-gradient kernel.  For a loss that is a sum over clips, ``x.grad[i, ..., :lengths[i]]`` is what clip i
         alone gives at batch size 1, and a parameter gradient is the sum over clips of those batch-1 gradients.  ``input_grad`` is not
-        consulted here.  Training mode with ``lengths`` raises NotImplementedError (no Patchout on ragged batches).
+        consulted here.
+        Training mode with ``lengths`` raises NotImplementedError unless ``net.varlen_train = True``.  With it the contract above carries
+        over to training: EVERY CLIP GETS WHAT IT WOULD GET ALONE AT BATCH SIZE 1 IN TRAINING MODE.  Patchout is drawn clip after clip,
+        i = 0 .. B - 1, with the reference's own torch CPU RNG calls in the reference's order (randint for the time-positional offset
+        of a clip with fewer patch columns than the time embedding, then randperm for s_patchout_t, s_patchout_f, u_patchout): after
+        ``torch.manual_seed(s)`` one packed call leaves the CPU generator where the loop ``for i: net(x[i:i+1, :, :, :lengths[i]])``
+        leaves it and gives clip i the same kept patches and offset, and the Patchout counts keep the reference's absolute meaning (not
+        scaled to a clip's length).  A clip that cannot satisfy them -- no more patch columns than s_patchout_t, no more frequency rows
+        than s_patchout_f, no more patches left than u_patchout, structured time Patchout on a clip with more patch columns than the
+        time embedding (the reference itself fails there) -- raises a ValueError that names the clip, before any RNG call.  The call is
+        an autograd node under the fixed path's rule -- grad enabled and anything requires a gradient; an ``x`` that requires one
+        gets ``x.grad``, exactly 0 behind lengths[i] and on pixels that only dropped patches cover; ``varlen_grad`` and ``input_grad``
+        are not consulted -- and a plain forward with Patchout under ``torch.no_grad()``.  ``hidden`` / ``attn`` hand out the kept
+        tokens per clip, as above.  Not covered: ``AugmentMelSTFT(..., lengths=)`` in training mode (pad, run the train-mode mel, then
+        ``net(spec, lengths=frames)``), a ragged TrainStep, mixup of clips of different lengths, EnsembelerModel.
 
         ``torch.compile(net)`` (ex_audioset.py:135, model_speed_test :391): the whole forward is ONE opaque call to the
         compiler (``_lib.compile_opaque``: torch.compiler.disable's mechanism without the torch._dynamo import, installed at class
@@ -1317,9 +1426,11 @@ class PaSST(nn.Module):
             amap = None
         else:
             amap = parse_attn(attn, len(self.blocks), attn_rows, attn_heads)
-        if lengths is not None and self.training:
+        train_ragged = lengths is not None and self.training
+        if train_ragged and not getattr(self, "varlen_train", False):
             raise NotImplementedError("PaSST.forward(x, lengths=...): training on ragged batches is not supported (eval mode only; "
-                                      "no reference flow trains on clips of different lengths)")
+                                      "no reference flow trains on clips of different lengths) unless asked for: net.varlen_train = True "
+                                      "gives every clip the Patchout it would get alone at batch size 1")
         grad = torch.is_grad_enabled()
         want_dx = grad and torch.is_tensor(x) and x.requires_grad
         named = None
@@ -1331,7 +1442,7 @@ class PaSST(nn.Module):
             # head_dist.* is not part of the graph -- as in the reference, whose forward never touches it
             # (models/passt.py:583-595; hence find_unused_parameters=True under torch DDP there and here)
             node = grad and (want_dx or any(p.requires_grad for p in self.parameters()))
-        elif grad and getattr(self, "varlen_grad", False):
+        elif grad and (train_ragged or getattr(self, "varlen_grad", False)):
             named = self._graph_params()[0]
             node = want_dx or any(p.requires_grad for _, p in named)
         else:
