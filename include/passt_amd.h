@@ -117,6 +117,29 @@ int pa_mel_frontend_bwd(const float* wave, int B, int L, const float* window, co
 int pa_mel_frontend_bwd_varlen(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
                                const float* twiddle, const float* dout, int T_max, float* dwave, void* workspace, int64_t workspace_bytes,
                                const pa_mel_params* p, void* stream);
+/* Training-time augmentation of a ragged batch (additive to ABI 6).  In the reference every clip that is processed alone gets its own
+ * fmin / fmax jitter and its own two SpecAugment bands (models/preprocess.py:63-64, 80-82), the time band drawn against the clip's own
+ * frame count.  One entry of this table per clip carries that draw: 24 bytes, the six per-clip fields of pa_mel_params. */
+typedef struct {
+    float mel_low;        /* mel(fmin) of this clip */
+    float inv_mel_delta;  /* (n_mels+1) / (mel(fmax) - mel(fmin)) of this clip */
+    int32_t fmask_start, fmask_end;   /* [start,end) mel rows of this clip forced to (0+out_add)*out_scale; empty if start>=end */
+    int32_t tmask_start, tmask_end;   /* same along time (start may be negative) */
+} pa_mel_clip_params;
+/* pa_mel_frontend_fwd_varlen / pa_mel_frontend_bwd_varlen with clip[B] IN DEVICE MEMORY: row b is transformed with clip[b].mel_low /
+ * .inv_mel_delta and masked with clip[b]'s two bands; p->mel_low, p->inv_mel_delta, p->fmask_* and p->tmask_* are ignored, everything
+ * else in *p holds.  Row b equals, in its first pa_mel_num_frames(lens[b], hop) columns (its first lens[b] samples), what
+ * pa_mel_frontend_fwd (pa_mel_frontend_bwd) returns for that clip alone with clip[b]'s six values in its pa_mel_params; the columns
+ * behind them hold `fill`, never the mask constant (dwave: exactly 0 at and behind lens[b]).  A table whose entries all repeat *p's six
+ * values gives the _varlen entry points' results bit for bit.  The library cannot read the table: the caller guarantees finite mel_low
+ * and inv_mel_delta > 0 in every entry, as it guarantees lens.  Same argument checks and error codes as the _varlen entry points, plus
+ * PA_EINVAL for clip == NULL. */
+int pa_mel_frontend_fwd_varlen_aug(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
+                                   const float* twiddle, float* out, int T_max, float fill, const pa_mel_params* p,
+                                   const pa_mel_clip_params* clip, void* stream);
+int pa_mel_frontend_bwd_varlen_aug(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
+                                   const float* twiddle, const float* dout, int T_max, float* dwave, void* workspace, int64_t workspace_bytes,
+                                   const pa_mel_params* p, const pa_mel_clip_params* clip, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Parameter staging (no reference counterpart: AMP autocast casts weights per op)

@@ -24,6 +24,11 @@ class MelParams(C.Structure):
                 ("fmask_start", i32), ("fmask_end", i32), ("tmask_start", i32), ("tmask_end", i32)]
 
 
+class MelClipParams(C.Structure):     # == pa_mel_clip_params: one clip's own filterbank edges and mask bands (24 bytes)
+    _fields_ = [("mel_low", f32), ("inv_mel_delta", f32),
+                ("fmask_start", i32), ("fmask_end", i32), ("tmask_start", i32), ("tmask_end", i32)]
+
+
 class GemmArgs(C.Structure):
     _fields_ = [("dtype", i32), ("epilogue", i32), ("M", i32), ("N", i32), ("K", i32),
                 ("lda", i32), ("ldb", i32), ("A", vp), ("B", vp), ("bias", vp), ("resid", vp),
@@ -57,6 +62,8 @@ SIGNATURES = {
     "pa_mel_frontend_fwd_varlen": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i32, f32, C.POINTER(MelParams), vp]),
     "pa_mel_frontend_bwd": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, i64, C.POINTER(MelParams), vp]),
     "pa_mel_frontend_bwd_varlen": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, i64, C.POINTER(MelParams), vp]),
+    "pa_mel_frontend_fwd_varlen_aug": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i32, f32, C.POINTER(MelParams), vp, vp]),
+    "pa_mel_frontend_bwd_varlen_aug": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, i64, C.POINTER(MelParams), vp, vp]),
     "pa_convert_f32": (i32, [vp, vp, i64, i32, vp]),
     "pa_convert_to_f32": (i32, [vp, i32, vp, i64, vp]),
     "pa_transpose": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp]),

@@ -31,11 +31,18 @@
 // stored instead of P) in loops unrolled four-fold with independent accumulators.  (Rejected: LDS float atomics for a
 // bin-parallel mel product -- 2.4x slower than the band loops, 402 vs 164 us: same-address ds_add_f32 serialise.)
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
 
 #include "pa_common.h"
 
 namespace pa {
+
+// the per-clip table is read as six consecutive dwords (include/passt_amd.h; passt_amd/_lib.py MelClipParams mirrors it)
+static_assert(sizeof(pa_mel_clip_params) == 24 && offsetof(pa_mel_clip_params, mel_low) == 0 && offsetof(pa_mel_clip_params, inv_mel_delta) == 4 &&
+                  offsetof(pa_mel_clip_params, fmask_start) == 8 && offsetof(pa_mel_clip_params, fmask_end) == 12 &&
+                  offsetof(pa_mel_clip_params, tmask_start) == 16 && offsetof(pa_mel_clip_params, tmask_end) == 20,
+              "pa_mel_clip_params layout");
 
 static constexpr int NFFT = 1024;
 static constexpr int NC = 512;            // complex points
@@ -133,15 +140,24 @@ __device__ __forceinline__ cf tw1024(const float2* __restrict__ tw, int j) {
 // frames equal those of the clip transformed alone and nothing at or behind lens[b] is read.  The output keeps p.n_frames (the
 // longest clip's) columns per row; a workgroup whose frames all lie behind its clip's end writes `fill` and leaves, and the frames
 // behind the end inside the clip's last tile get `fill` from the epilogue.
-template <int FR_PER_WG, bool PERSIST, bool VL>
-__global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void mel_frontend_kernel(const float* __restrict__ wave, const int Lp,
-                                                            const float* __restrict__ window,
-                                                            const float* __restrict__ bin_mel,
-                                                            const float2* __restrict__ twiddle,
-                                                            float* __restrict__ out, const pa_mel_params p,
-                                                            const int tiles_per_clip, const int n_tiles,
-                                                            const int32_t* __restrict__ lens, const float fill) {
+//
+// AUG (pa_mel_frontend_fwd_varlen_aug, packed form only): every clip has its OWN filterbank edges and its own two mask bands -- what the
+// reference's training mode draws for a clip processed alone.  clip[b] replaces the six per-clip fields of p (mel_low, inv_mel_delta,
+// fmask_*, tmask_*); a workgroup belongs to one clip, so they are six more wave-uniform scalar loads next to lens[b].  The fast exit
+// for tiles behind the clip's end stays in front of every use of the bands: `fill` there is never replaced by the mask constant.
+// The body is shared (forced inline); the kernels below only name the instantiations, so the ones behind the entry points that existed
+// before AUG keep their names, kernel arguments and register allocation.
+template <int FR_PER_WG, bool PERSIST, bool VL, bool AUG>
+__device__ __forceinline__ void mel_frontend_body(const float* __restrict__ wave, const int Lp,
+                                                  const float* __restrict__ window,
+                                                  const float* __restrict__ bin_mel,
+                                                  const float2* __restrict__ twiddle,
+                                                  float* __restrict__ out, const pa_mel_params& p,
+                                                  const int tiles_per_clip, const int n_tiles,
+                                                  const int32_t* __restrict__ lens, const float fill,
+                                                  const pa_mel_clip_params* __restrict__ clip) {
     static_assert(!(VL && PERSIST), "the packed form is the one-tile kernel");
+    static_assert(!AUG || VL, "per-clip parameters belong to the packed form");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int span = (FR_PER_WG - 1) * p.hop + NFFT;
     // one span buffer holds span (+ 4: the sample behind the last one, for the pre-emphasis) floats, rounded up to whole 1 KiB DMA pieces
@@ -173,6 +189,13 @@ __global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
     const int L = VL ? lens[b] : Lp;                         // VL: this clip's own length (wave-uniform: a scalar load)
     const int T = VL ? min(Tp, 1 + (L - 1) / p.hop) : Tp;    // frames this clip has
     const int Ly = L - 1;
+    float mel_low = p.mel_low, inv_mel_delta = p.inv_mel_delta;
+    int fmask_start = p.fmask_start, fmask_end = p.fmask_end, tmask_start = p.tmask_start, tmask_end = p.tmask_end;
+    if constexpr (AUG) {                                     // this clip's own draw (wave-uniform: scalar loads)
+        const pa_mel_clip_params c = clip[b];
+        mel_low = c.mel_low, inv_mel_delta = c.inv_mel_delta;
+        fmask_start = c.fmask_start, fmask_end = c.fmask_end, tmask_start = c.tmask_start, tmask_end = c.tmask_end;
+    }
     if constexpr (VL) {
         if (f0 >= T || Ly <= NFFT / 2) {                     // every frame of the tile lies behind the clip's end (or the clip is too short to reflect)
             for (int idx = tid; idx < p.n_mels * FR_PER_WG; idx += NT) {
@@ -276,7 +299,7 @@ __global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
     // ---- filterbank geometry for this call's (fmin, fmax): bin k -> triangle j_k, weight u_k ----
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const float t = ((h ? bm1 : bm0) - p.mel_low) * p.inv_mel_delta;
+        const float t = ((h ? bm1 : bm0) - mel_low) * inv_mel_delta;
         const float fl = floorf(t);
         sJ[tid + h * NT] = (int)fmaxf(fminf(fl, 100000.f), -1.f);
         sU[tid + h * NT] = t - fl;
@@ -459,7 +482,7 @@ __global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
         if (VL && t >= T && t < Tp) out[((int64_t)b * p.n_mels + mel) * Tp + t] = fill;
         if (t >= T) continue;
         float v = __logf(sOut[mel * (FR_PER_WG + 1) + fl] + p.log_eps);
-        const bool masked = (mel >= p.fmask_start && mel < p.fmask_end) || (t >= p.tmask_start && t < p.tmask_end);
+        const bool masked = (mel >= fmask_start && mel < fmask_end) || (t >= tmask_start && t < tmask_end);
         if (masked) v = 0.f;
         out[((int64_t)b * p.n_mels + mel) * Tp + t] = (v + p.out_add) * p.out_scale;
     }
@@ -480,6 +503,28 @@ __global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
     }
 }
 
+template <int FR_PER_WG, bool PERSIST, bool VL>
+__global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void mel_frontend_kernel(const float* __restrict__ wave, const int Lp,
+                                                            const float* __restrict__ window,
+                                                            const float* __restrict__ bin_mel,
+                                                            const float2* __restrict__ twiddle,
+                                                            float* __restrict__ out, const pa_mel_params p,
+                                                            const int tiles_per_clip, const int n_tiles,
+                                                            const int32_t* __restrict__ lens, const float fill) {
+    mel_frontend_body<FR_PER_WG, PERSIST, VL, false>(wave, Lp, window, bin_mel, twiddle, out, p, tiles_per_clip, n_tiles, lens, fill, nullptr);
+}
+
+__global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void mel_frontend_aug_kernel(const float* __restrict__ wave, const int Lp,
+                                                            const float* __restrict__ window,
+                                                            const float* __restrict__ bin_mel,
+                                                            const float2* __restrict__ twiddle,
+                                                            float* __restrict__ out, const pa_mel_params p,
+                                                            const int tiles_per_clip, const int n_tiles,
+                                                            const int32_t* __restrict__ lens, const float fill,
+                                                            const pa_mel_clip_params* __restrict__ clip) {
+    mel_frontend_body<FR_DEFAULT, false, true, true>(wave, Lp, window, bin_mel, twiddle, out, p, tiles_per_clip, n_tiles, lens, fill, clip);
+}
+
 // ---- gradient w.r.t. the waveform (pa_mel_frontend_bwd / _bwd_varlen; formulas: include/passt_amd.h) ----------
 // Nothing was saved by the forward: a frame's spectrum X and its band sums are recomputed from the wave (the forward's own
 // transform and band stage, one wave per frame), then
@@ -496,11 +541,16 @@ __global__ __launch_bounds__(MEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
 // frames to the positions it owns, in frame order.  A position's sum is therefore ((0 + f_t) + f_t+1) + ... over ALL frames covering
 // it in ascending t, whatever `rows` is: the result does not depend on the launch geometry and repeats bit for bit.  The frames in
 // front of the owned run are transformed again by the neighbouring workgroup (hop 320, 5120 samples per workgroup: 20 frames for 16).
-template <bool VL>
-__global__ __launch_bounds__(MEL_WAVES * 64) void mel_frontend_bwd_kernel(const float* __restrict__ wave, const int Lp, const float* __restrict__ window,
-                                                                         const float* __restrict__ bin_mel, const float2* __restrict__ twiddle,
-                                                                         const float* __restrict__ dout, float* __restrict__ dwave,
-                                                                         const pa_mel_params p, const int rows, const int32_t* __restrict__ lens) {
+//
+// AUG (pa_mel_frontend_bwd_varlen_aug): clip[b] replaces the six per-clip fields of p, as in the forward -- the geometry (and with it the
+// band sums and the two-term gather) and the masking of dmel follow the clip's own draw.  Shared body, as in the forward.
+template <bool VL, bool AUG>
+__device__ __forceinline__ void mel_frontend_bwd_body(const float* __restrict__ wave, const int Lp, const float* __restrict__ window,
+                                                      const float* __restrict__ bin_mel, const float2* __restrict__ twiddle,
+                                                      const float* __restrict__ dout, float* __restrict__ dwave,
+                                                      const pa_mel_params& p, const int rows, const int32_t* __restrict__ lens,
+                                                      const pa_mel_clip_params* __restrict__ clip) {
+    static_assert(!AUG || VL, "per-clip parameters belong to the packed form");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sScr = smem;                                                 // [MEL_WAVES][WAVE_SCRATCH]
     float* sAcc = (float*)(smem + MEL_WAVES * WAVE_SCRATCH);           // [rows + 2052] overlap-added gradient of the padded signal, from qlo
@@ -514,6 +564,13 @@ __global__ __launch_bounds__(MEL_WAVES * 64) void mel_frontend_bwd_kernel(const 
     const int L = VL ? min(lens[b], Lp) : Lp;
     const int T = VL ? min(Tp, 1 + (L - 1) / p.hop) : Tp;
     const int Ly = L - 1;
+    float mel_low = p.mel_low, inv_mel_delta = p.inv_mel_delta;
+    int fmask_start = p.fmask_start, fmask_end = p.fmask_end, tmask_start = p.tmask_start, tmask_end = p.tmask_end;
+    if constexpr (AUG) {                                               // this clip's own draw (wave-uniform: scalar loads)
+        const pa_mel_clip_params c = clip[b];
+        mel_low = c.mel_low, inv_mel_delta = c.inv_mel_delta;
+        fmask_start = c.fmask_start, fmask_end = c.fmask_end, tmask_start = c.tmask_start, tmask_end = c.tmask_end;
+    }
     const float* x = wave + (int64_t)b * Lp;
     float* dx = dwave + (int64_t)b * Lp;
     const int nend = min(n0 + rows, Lp);
@@ -550,7 +607,7 @@ __global__ __launch_bounds__(MEL_WAVES * 64) void mel_frontend_bwd_kernel(const 
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {                                      // filterbank geometry: the forward's expressions
-        const float t = (bin_mel[tid + h * NT] - p.mel_low) * p.inv_mel_delta;
+        const float t = (bin_mel[tid + h * NT] - mel_low) * inv_mel_delta;
         const float fl = floorf(t);
         sJ[tid + h * NT] = (int)fmaxf(fminf(fl, 100000.f), -1.f);
         sU[tid + h * NT] = t - fl;
@@ -706,13 +763,13 @@ __global__ __launch_bounds__(MEL_WAVES * 64) void mel_frontend_bwd_kernel(const 
             }
             if (lane == 63 && j_last >= 0 && j_last <= p.n_mels) slot[j_last] = acc;
             // dmel (0 where the forward wrote the mask constant; the upstream value there is not used), padded with two zeros a side
-            const bool tmasked = t >= p.tmask_start && t < p.tmask_end;
+            const bool tmasked = t >= tmask_start && t < tmask_end;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int band = lane + 64 * h;
                 if (band < p.n_mels) {
                     const float mel = slot[band].x + slot[band + 1].y;
-                    const bool masked = tmasked || (band >= p.fmask_start && band < p.fmask_end);
+                    const bool masked = tmasked || (band >= fmask_start && band < fmask_end);
                     dmp[band + 2] = masked ? 0.f : gv[h] * p.out_scale / (mel + p.log_eps);
                 }
             }
@@ -794,6 +851,22 @@ __global__ __launch_bounds__(MEL_WAVES * 64) void mel_frontend_bwd_kernel(const 
         }
         dx[n] = r;
     }
+}
+
+template <bool VL>
+__global__ __launch_bounds__(MEL_WAVES * 64) void mel_frontend_bwd_kernel(const float* __restrict__ wave, const int Lp, const float* __restrict__ window,
+                                                                         const float* __restrict__ bin_mel, const float2* __restrict__ twiddle,
+                                                                         const float* __restrict__ dout, float* __restrict__ dwave,
+                                                                         const pa_mel_params p, const int rows, const int32_t* __restrict__ lens) {
+    mel_frontend_bwd_body<VL, false>(wave, Lp, window, bin_mel, twiddle, dout, dwave, p, rows, lens, nullptr);
+}
+
+__global__ __launch_bounds__(MEL_WAVES * 64) void mel_frontend_aug_bwd_kernel(const float* __restrict__ wave, const int Lp, const float* __restrict__ window,
+                                                                             const float* __restrict__ bin_mel, const float2* __restrict__ twiddle,
+                                                                             const float* __restrict__ dout, float* __restrict__ dwave,
+                                                                             const pa_mel_params p, const int rows, const int32_t* __restrict__ lens,
+                                                                             const pa_mel_clip_params* __restrict__ clip) {
+    mel_frontend_bwd_body<true, true>(wave, Lp, window, bin_mel, twiddle, dout, dwave, p, rows, lens, clip);
 }
 
 }  // namespace pa
@@ -879,6 +952,26 @@ extern "C" int pa_mel_frontend_fwd_varlen(const float* wave, int B, int ldw, con
     return check_launch();
 }
 
+// the packed forward with every clip's own filterbank edges and mask bands (clip[b]; the six per-clip fields of *p are not read)
+extern "C" int pa_mel_frontend_fwd_varlen_aug(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
+                                              const float* twiddle, float* out, int T_max, float fill, const pa_mel_params* p,
+                                              const pa_mel_clip_params* clip, void* stream) {
+    if (!wave || !lens || !window || !bin_mel || !twiddle || !out || !p || !clip || B <= 0 || T_max <= 0) return PA_EINVAL;
+    if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
+    if (ldw - 1 <= NFFT / 2) return PA_EUNSUPPORTED;
+    if (p->n_frames != T_max || T_max > pa_mel_num_frames(ldw, p->hop)) return PA_EINVAL;
+    const int fr = FR_DEFAULT;
+    const int span = (fr - 1) * p->hop + NFFT;
+    const size_t lds = ((span * 4 + 15) & ~15) + MEL_WAVES * WAVE_SCRATCH + std::max<size_t>((size_t)p->n_mels * (fr + 1) * 4, 2 * NC * 4);
+    if (lds > 160 * 1024) return PA_EUNSUPPORTED;
+    static signed char lds_attr[64] = {0};
+    (void)lds_attr_on_this_device((const void*)mel_frontend_aug_kernel, 160 * 1024, lds_attr);
+    dim3 grid((unsigned)cdiv(T_max, fr), (unsigned)B);
+    hipLaunchKernelGGL(mel_frontend_aug_kernel, grid, dim3(MEL_WAVES * 64), lds, (hipStream_t)stream, wave, ldw, window, bin_mel,
+                       (const float2*)twiddle, out, *p, (int)cdiv(T_max, fr), (int)(cdiv(T_max, fr) * B), lens, fill, clip);
+    return check_launch();
+}
+
 // samples one workgroup of the backward owns: whole hops, at least 16 frames' worth and at least 2048 (the frames in front of the run
 // that are transformed again are then at most half of the work, whatever the hop)
 static int mel_bwd_rows(int hop) { return hop * (int)std::max<int64_t>(FR_DEFAULT, cdiv(2 * NFFT, hop)); }
@@ -917,4 +1010,23 @@ extern "C" int pa_mel_frontend_bwd_varlen(const float* wave, int B, int ldw, con
     if (ldw - 1 <= NFFT / 2) return PA_EUNSUPPORTED;
     if (p->n_frames != T_max || T_max > pa_mel_num_frames(ldw, p->hop)) return PA_EINVAL;
     return mel_bwd_launch<true>(wave, B, ldw, lens, window, bin_mel, twiddle, dout, dwave, p, stream);
+}
+
+extern "C" int pa_mel_frontend_bwd_varlen_aug(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
+                                              const float* twiddle, const float* dout, int T_max, float* dwave, void* workspace,
+                                              int64_t workspace_bytes, const pa_mel_params* p, const pa_mel_clip_params* clip, void* stream) {
+    (void)workspace; (void)workspace_bytes;
+    if (!wave || !lens || !window || !bin_mel || !twiddle || !dout || !dwave || !p || !clip || B <= 0 || T_max <= 0) return PA_EINVAL;
+    if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
+    if (ldw - 1 <= NFFT / 2) return PA_EUNSUPPORTED;
+    if (p->n_frames != T_max || T_max > pa_mel_num_frames(ldw, p->hop)) return PA_EINVAL;
+    const int rows = mel_bwd_rows(p->hop);
+    const size_t lds = MEL_WAVES * WAVE_SCRATCH + (size_t)(rows + 2 * NFFT + 4) * 4;
+    if (lds > 160 * 1024) return PA_EUNSUPPORTED;
+    static signed char lds_attr[64] = {0};
+    (void)lds_attr_on_this_device((const void*)mel_frontend_aug_bwd_kernel, 160 * 1024, lds_attr);
+    dim3 grid((unsigned)cdiv(ldw, rows), (unsigned)B);
+    hipLaunchKernelGGL(mel_frontend_aug_bwd_kernel, grid, dim3(MEL_WAVES * 64), lds, (hipStream_t)stream, wave, ldw, window, bin_mel,
+                       (const float2*)twiddle, dout, dwave, *p, rows, lens, clip);
+    return check_launch();
 }

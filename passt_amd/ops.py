@@ -222,6 +222,60 @@ def mel_frontend_bwd_varlen(wave, lens_dev, window, bin_mel, twiddle, params: Me
     return dwave
 
 
+def upload_mel_clips(clips, device):
+    """The per-clip table of the ragged training front end -- a (B, 6) float64 / int array-like or a ctypes array of MelClipParams, one
+    row (mel_low, inv_mel_delta, fmask_start, fmask_end, tmask_start, tmask_end) per clip -- as the device bytes pa_mel_clip_params[B]
+    (uint8, 24 per clip), through the pinned ring like the lengths."""
+    if not isinstance(clips, C.Array):
+        rows = [tuple(r) for r in clips]
+        clips = (_lib.MelClipParams * len(rows))(*[_lib.MelClipParams(float(r[0]), float(r[1]), *(int(v) for v in r[2:])) for r in rows])
+    host = torch.frombuffer(bytearray(bytes(clips)), dtype=torch.uint8)
+    return upload_small(host, device)
+
+
+def _mel_clip_table(clip_dev, B, what):
+    if clip_dev.dtype != torch.uint8 or clip_dev.dim() != 1 or clip_dev.numel() != B * C.sizeof(_lib.MelClipParams):
+        raise _lib.PasstAmdError(f"{what}: the per-clip table must be {B} x {C.sizeof(_lib.MelClipParams)} bytes (ops.upload_mel_clips), got "
+                                 f"{clip_dev.dtype} {tuple(clip_dev.shape)}")
+    return clip_dev
+
+
+def mel_frontend_varlen_aug(wave, lens_dev, clip_dev, window, bin_mel, twiddle, params: MelParams, fill=0.0):
+    """mel_frontend_varlen with every clip's own filterbank edges and SpecAugment bands: ``clip_dev`` is ops.upload_mel_clips' table
+    (its six values replace params.mel_low / inv_mel_delta / fmask_* / tmask_*, which are not read; the caller guarantees finite
+    mel_low and inv_mel_delta > 0).  The frames behind a clip's own end hold ``fill``, never the mask constant."""
+    if wave.dim() != 2 or lens_dev.dim() != 1 or lens_dev.numel() != wave.shape[0]:
+        raise _lib.PasstAmdError(f"mel_frontend_varlen_aug: wave {tuple(wave.shape)} needs one length per row, got {tuple(lens_dev.shape)}")
+    B, L = wave.shape
+    _mel_clip_table(clip_dev, B, "mel_frontend_varlen_aug")
+    out = torch.empty((B, params.n_mels, params.n_frames), device=wave.device, dtype=torch.float32)
+    _timed("mel", 4.0 * (B * L + out.numel()),
+           lambda: check(_lib.load().pa_mel_frontend_fwd_varlen_aug(_p(wave, torch.float32), B, wave.stride(0), _p(lens_dev, torch.int32),
+                                                                    _p(window, torch.float32), _p(bin_mel, torch.float32),
+                                                                    _p(twiddle, torch.float32), _p(out), params.n_frames, float(fill),
+                                                                    C.byref(params), _p(clip_dev, torch.uint8), _stream()),
+                         "pa_mel_frontend_fwd_varlen_aug"))
+    return out
+
+
+def mel_frontend_bwd_varlen_aug(wave, lens_dev, clip_dev, window, bin_mel, twiddle, params: MelParams, dout):
+    """Gradient of mel_frontend_varlen_aug w.r.t. ``wave``; ``clip_dev`` is the forward call's table."""
+    if wave.dim() != 2 or lens_dev.dim() != 1 or lens_dev.numel() != wave.shape[0]:
+        raise _lib.PasstAmdError(f"mel_frontend_bwd_varlen_aug: wave {tuple(wave.shape)} needs one length per row, got {tuple(lens_dev.shape)}")
+    B, L = wave.shape
+    _mel_clip_table(clip_dev, B, "mel_frontend_bwd_varlen_aug")
+    if tuple(dout.shape) != (B, params.n_mels, params.n_frames):
+        raise _lib.PasstAmdError(f"mel_frontend_bwd_varlen_aug: dout {tuple(dout.shape)} for a ({B}, {params.n_mels}, {params.n_frames}) output")
+    dwave = torch.empty_like(wave)
+    _timed("mel_bwd", 4.0 * (2 * B * L + dout.numel()),
+           lambda: check(_lib.load().pa_mel_frontend_bwd_varlen_aug(_p(wave, torch.float32), B, wave.stride(0), _p(lens_dev, torch.int32),
+                                                                    _p(window, torch.float32), _p(bin_mel, torch.float32),
+                                                                    _p(twiddle, torch.float32), _p(dout, torch.float32), params.n_frames,
+                                                                    _p(dwave), None, 0, C.byref(params), _p(clip_dev, torch.uint8), _stream()),
+                         "pa_mel_frontend_bwd_varlen_aug"))
+    return dwave
+
+
 # ---- staging ---------------------------------------------------------------------------------
 def convert(x_f32, dtype):
     if dtype == PA_F32:

@@ -12,20 +12,23 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from ._lib import MelParams, PasstAmdError, compile_opaque
+from ._lib import MelClipParams, MelParams, PasstAmdError, compile_opaque
 
 
 class _MelWaveGrad(torch.autograd.Function):
     """The forward launch with a gradient w.r.t. the waveform (pa_mel_frontend_bwd / _bwd_varlen).  Only entered when autograd
     records and the waveform requires a gradient; the forward launches exactly what the plain call launches and saves no
     activation: the node keeps the float waveform and the MelParams the launch used (the jittered fmin / fmax and the drawn masks,
-    so the backward sees the forward's draw), and the backward recomputes the spectrum from the waveform."""
+    so the backward sees the forward's draw) -- for a ragged training batch the per-clip table on the device as well -- and the
+    backward recomputes the spectrum from the waveform."""
 
     @staticmethod
-    def forward(ctx, x, window, bin_mel, twiddle, p, lens_dev):
-        ctx.c = (x, window, bin_mel, twiddle, p, lens_dev)
+    def forward(ctx, x, window, bin_mel, twiddle, p, lens_dev, clip_dev):
+        ctx.c = (x, window, bin_mel, twiddle, p, lens_dev, clip_dev)
         if lens_dev is None:
             return ops.mel_frontend(x, window, bin_mel, twiddle, p)
+        if clip_dev is not None:
+            return ops.mel_frontend_varlen_aug(x, lens_dev, clip_dev, window, bin_mel, twiddle, p, fill=0.0)
         return ops.mel_frontend_varlen(x, lens_dev, window, bin_mel, twiddle, p, fill=0.0)
 
     @staticmethod
@@ -35,13 +38,15 @@ class _MelWaveGrad(torch.autograd.Function):
         if c is None:
             raise RuntimeError("passt_amd.AugmentMelSTFT: the saved waveform of this forward was already consumed by a backward "
                                "pass (retain_graph / double backward are not supported: run the forward again)")
-        x, window, bin_mel, twiddle, p, lens_dev = c
+        x, window, bin_mel, twiddle, p, lens_dev, clip_dev = c
         g = g.contiguous().float()
         if lens_dev is None:
             dx = ops.mel_frontend_bwd(x, window, bin_mel, twiddle, p, g)
+        elif clip_dev is not None:
+            dx = ops.mel_frontend_bwd_varlen_aug(x, lens_dev, clip_dev, window, bin_mel, twiddle, p, g)
         else:
             dx = ops.mel_frontend_bwd_varlen(x, lens_dev, window, bin_mel, twiddle, p, g)
-        return dx, None, None, None, None, None
+        return dx, None, None, None, None, None, None
 
 
 def _draw_mask(mask_param, size):
@@ -86,6 +91,52 @@ class TimeMasking(_AxisMasking):
         super().__init__(time_mask_param, 2, iid_masks)
 
 
+def checked_lengths(mel, lengths, B=None, L=None):
+    """``lengths`` of ``forward(x, lengths=)`` as a list of ints, after every check the ragged call makes (``B``, ``L``: rows and
+    samples per row of the batch, None = not known).  Pure host code; raises before any random number is drawn."""
+    if torch.is_tensor(lengths):
+        if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+            raise ValueError("lengths must be a sequence of ints or a 1-D integer tensor")
+        lengths = lengths.tolist()
+    lengths = [int(v) for v in lengths]
+    if B is not None and len(lengths) != B:
+        raise ValueError(f"lengths has {len(lengths)} entries for a batch of {B} waveforms")
+    for i, n in enumerate(lengths):
+        if L is not None and n > L:
+            raise ValueError(f"clip {i}: length {n} exceeds the batch's {L} samples")
+        if n - 1 <= mel.n_fft // 2:
+            raise PasstAmdError(f"pa_mel_frontend_fwd_varlen failed: unsupported configuration: clip {i} has {n} samples; the "
+                                f"centred reflect padding needs more than {mel.n_fft // 2 + 1} (torch.stft rule)")
+    return lengths
+
+
+def varlen_clip_draws(mel, lengths, B=None, L=None):
+    """The training-mode draws of a ragged batch, clip after clip in the order the reference consumes the CPU generator when it
+    processes the clips one at a time (models/preprocess.py:63-64, 80-82): per clip ``randint(fmin_aug_range)``,
+    ``randint(fmax_aug_range)``, two ``rand(1)`` for the frequency band (if ``freqm``), two ``rand(1)`` for the time band (if
+    ``timem``) -- the time band against the clip's OWN frame count.  ``torch.manual_seed(s)`` + this function therefore leaves the
+    generator where ``torch.manual_seed(s)`` + the batch-1 loop leaves it.  Pure host code (``mel`` is an AugmentMelSTFT on any
+    device); every check of ``lengths`` runs before the first draw.
+
+    Returns a dict: ``frames`` (B,), ``fmin`` / ``fmax`` (B,), ``fmask`` / ``tmask`` (B, 2) [start, end) and ``table``, the
+    ``pa_mel_clip_params[B]`` (ctypes array of MelClipParams) the kernels read."""
+    lengths = checked_lengths(mel, lengths, B, L)
+    frames = [1 + (n - 1) // mel.hopsize for n in lengths]
+    table = (MelClipParams * len(lengths))()
+    fmins, fmaxs, fmask, tmask = [], [], [], []
+    for c, T in zip(table, frames):
+        fmin = mel.fmin + torch.randint(mel.fmin_aug_range, (1,)).item()                                  # :63
+        fmax = mel.fmax + mel.fmax_aug_range // 2 - torch.randint(mel.fmax_aug_range, (1,)).item()        # :64
+        fm = mel.freqm.draw(mel.n_mels) if isinstance(mel.freqm, _AxisMasking) else (0, 0)                # :81
+        tm = mel.timem.draw(T) if isinstance(mel.timem, _AxisMasking) else (0, 0)                         # :82
+        mel_low = 1127.0 * math.log(1.0 + fmin / 700.0)
+        mel_high = 1127.0 * math.log(1.0 + fmax / 700.0)
+        c.mel_low, c.inv_mel_delta = mel_low, (mel.n_mels + 1) / (mel_high - mel_low)
+        (c.fmask_start, c.fmask_end), (c.tmask_start, c.tmask_end) = fm, tm
+        fmins.append(fmin), fmaxs.append(fmax), fmask.append(fm), tmask.append(tm)
+    return dict(frames=frames, fmin=fmins, fmax=fmaxs, fmask=fmask, tmask=tmask, table=table)
+
+
 class AugmentMelSTFT(nn.Module):
     def __init__(self, n_mels=128, sr=32000, win_length=800, hopsize=320, n_fft=1024, freqm=48, timem=192,
                  htk=False, fmin=0.0, fmax=None, norm=1, fmin_aug_range=1, fmax_aug_range=1000):
@@ -113,6 +164,7 @@ class AugmentMelSTFT(nn.Module):
         self.register_buffer("_window_padded", wpad, persistent=False)
         self.register_buffer("_bin_mel", bin_mel.float(), persistent=False)
         self.register_buffer("_twiddle", tw.float().contiguous(), persistent=False)
+        self.varlen_train = False       # True: train mode accepts lengths= (every clip its own jitter and masks, see forward)
 
     @compile_opaque                 # ONE opaque eager call under torch.compile, like PaSST.forward
     def forward(self, x, lengths=None):
@@ -126,7 +178,14 @@ class AugmentMelSTFT(nn.Module):
         lengths (left-aligned).  Returns ``(spec, frames)``: spec (B, n_mels, T_max), T_max = frames of the longest clip, row i equal
         to ``forward(x[i:i+1, :lengths[i]])`` in its first frames[i] columns (pre-emphasis and reflect padding at the clip's own
         end; samples behind lengths[i] are never read) and exactly 0.0 behind them; ``frames``: int64 CPU tensor, ready for
-        ``PaSST.forward(spec[:, None], lengths=frames)``.  Eval mode only.  A device tensor of lengths costs one host read."""
+        ``PaSST.forward(spec[:, None], lengths=frames)``.  A device tensor of lengths costs one host read.
+
+        ``lengths`` in train mode needs ``self.varlen_train = True`` (off by default: NotImplementedError).  Every clip then gets what
+        ``self.train()(x[i:i+1, :lengths[i]])`` gives it alone: its own fmin / fmax jitter, its own frequency band and its own time
+        band, drawn against its own frames[i]; the CPU generator is consumed clip after clip in the reference's order
+        (``varlen_clip_draws``), so the same seed in front of this call and in front of the batch-1 loop gives the same draws and the
+        same final generator state.  Masked cells hold 0.9, the columns behind a clip's frames exactly 0.0.  Eval mode ignores the
+        switch (two ``randint`` per call, no masks)."""
         if lengths is not None:
             return self._forward_varlen(x, lengths)
         if not x.is_cuda:
@@ -156,39 +215,22 @@ class AugmentMelSTFT(nn.Module):
             if isinstance(self.timem, _AxisMasking):
                 p.tmask_start, p.tmask_end = self.timem.draw(p.n_frames)                  # :82
         if torch.is_grad_enabled() and x.requires_grad:
-            return _MelWaveGrad.apply(x, self._window_padded, self._bin_mel, self._twiddle, p, None)
+            return _MelWaveGrad.apply(x, self._window_padded, self._bin_mel, self._twiddle, p, None, None)
         return ops.mel_frontend(x, self._window_padded, self._bin_mel, self._twiddle, p)
 
     def _forward_varlen(self, x, lengths):
-        if self.training:
-            raise NotImplementedError("AugmentMelSTFT.forward(x, lengths=...): eval mode only (the frequency / time masks and the "
-                                      "fmin / fmax jitter are training-time augmentations; no reference flow trains on ragged batches)")
+        if self.training and not self.varlen_train:
+            raise NotImplementedError("AugmentMelSTFT.forward(x, lengths=...) in train mode needs the switch varlen_train = True (every "
+                                      "clip then gets its own fmin / fmax jitter and its own frequency / time masks, as if it were "
+                                      "processed alone); it is off by default")
         if not x.is_cuda:
             raise PasstAmdError("passt_amd.AugmentMelSTFT runs on a HIP device only (no CPU fallback)")
         if x.dim() != 2:
             raise ValueError("expected (batch, samples)")
-        if torch.is_tensor(lengths):
-            if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
-                raise ValueError("lengths must be a sequence of ints or a 1-D integer tensor")
-            lengths = lengths.tolist()
-        lengths = [int(v) for v in lengths]
+        lengths = checked_lengths(self, lengths, *x.shape)
         x = x.contiguous().float()
-        B, L = x.shape
-        if len(lengths) != B:
-            raise ValueError(f"lengths has {len(lengths)} entries for a batch of {B} waveforms")
-        for i, n in enumerate(lengths):
-            if n > L:
-                raise ValueError(f"clip {i}: length {n} exceeds the batch's {L} samples")
-            if n - 1 <= self.n_fft // 2:
-                raise PasstAmdError(f"pa_mel_frontend_fwd_varlen failed: unsupported configuration: clip {i} has {n} samples; the "
-                                    f"centred reflect padding needs more than {self.n_fft // 2 + 1} (torch.stft rule)")
-        # RNG order of the reference: both randint calls always execute (:63-64), once per call here
-        torch.randint(self.fmin_aug_range, (1,))
-        torch.randint(self.fmax_aug_range, (1,))
-        frames = [1 + (n - 1) // self.hopsize for n in lengths]
         p = MelParams()
         p.n_fft, p.hop, p.n_mels = self.n_fft, self.hopsize, self.n_mels
-        p.n_frames = max(frames)
         p.preemph = 0.97
         mel_low = 1127.0 * math.log(1.0 + self.fmin / 700.0)
         mel_high = 1127.0 * math.log(1.0 + self.fmax / 700.0)
@@ -196,9 +238,23 @@ class AugmentMelSTFT(nn.Module):
         p.inv_mel_delta = (self.n_mels + 1) / (mel_high - mel_low)
         p.log_eps, p.out_add, p.out_scale = 0.00001, 4.5, 1.0 / 5.0
         p.fmask_start = p.fmask_end = p.tmask_start = p.tmask_end = 0
+        clip_dev = None
+        if self.training:
+            # every clip its own draws, in the order of the batch-1 loop; the kernel reads them from the table, not from p
+            draws = varlen_clip_draws(self, lengths)
+            frames = draws["frames"]
+            clip_dev = ops.upload_mel_clips(draws["table"], x.device)
+        else:
+            # RNG order of the reference: both randint calls always execute (:63-64), once per call here
+            torch.randint(self.fmin_aug_range, (1,))
+            torch.randint(self.fmax_aug_range, (1,))
+            frames = [1 + (n - 1) // self.hopsize for n in lengths]
+        p.n_frames = max(frames)
         lens_dev = ops.upload_small(torch.tensor(lengths, dtype=torch.int32), x.device)
         if torch.is_grad_enabled() and x.requires_grad:
-            spec = _MelWaveGrad.apply(x, self._window_padded, self._bin_mel, self._twiddle, p, lens_dev)
+            spec = _MelWaveGrad.apply(x, self._window_padded, self._bin_mel, self._twiddle, p, lens_dev, clip_dev)
+        elif clip_dev is not None:
+            spec = ops.mel_frontend_varlen_aug(x, lens_dev, clip_dev, self._window_padded, self._bin_mel, self._twiddle, p, fill=0.0)
         else:
             spec = ops.mel_frontend_varlen(x, lens_dev, self._window_padded, self._bin_mel, self._twiddle, p, fill=0.0)
         return spec, torch.tensor(frames, dtype=torch.int64)
