@@ -19,11 +19,16 @@ with f32 accumulation, f32 residual stream / LayerNorm / softmax (the reference'
 Patchout indices are drawn with the reference's own torch CPU RNG calls in the reference's order
 (:513-553), hence bit-exact.
 """
+import contextlib
+import copy
 import math
 import os
 import warnings
+import weakref
 from collections import OrderedDict
 from functools import partial
+from itertools import islice
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -133,13 +138,13 @@ def draw_patchout(model, F_dim, T_dim):
 
 def kept_patches(F_dim, T_eff, idx_t, idx_f, idx_u):
     """Grid coordinates of the surviving patches in sequence order (frequency-major flatten, :546)."""
-    ts = np.arange(T_eff) if idx_t is None else idx_t
-    fs = np.arange(F_dim) if idx_f is None else idx_f
+    ts = np.arange(T_eff, dtype=np.int32) if idx_t is None else idx_t
+    fs = np.arange(F_dim, dtype=np.int32) if idx_f is None else idx_f
     pf = np.repeat(fs, ts.size)
     pt = np.tile(ts, fs.size)
     if idx_u is not None:
         pf, pt = pf[idx_u], pt[idx_u]
-    return pf.astype(np.int32), pt.astype(np.int32)
+    return pf.astype(np.int32, copy=False), pt.astype(np.int32, copy=False)
 
 
 # --------------------------------------------------------------------------------------------
@@ -327,10 +332,6 @@ class _FixedLayout:
         p = ops.attention_probs(qkv, lse, self.B, H, self.Ntok, scale, nq=nq, head_mean=head_mean, flags=flags)
         return p.view(self.B, -1, self.Ntok) if head_mean else p
 
-    @staticmethod
-    def attn_views(p, tok_offsets, H, prefix, head_mean):
-        return p
-
 
 class _PackedLayout:
     """B clips of different token counts back to back: clip b owns rows cu_tok[b] .. cu_tok[b + 1] (device int32), none longer
@@ -433,13 +434,36 @@ def parse_attn(attn, nblk, attn_rows="all", attn_heads="each"):
     return tuple(out), attn_rows == "prefix", attn_heads == "mean"
 
 
+class _Fwd(NamedTuple):
+    """What ONE forward produces, on every entry path.  ``ctx``: what the backward needs (None for a forward that saves nothing, and
+    on a record rebuilt from the autograd node's outputs); ``hidden``: the token outputs asked for, in the order asked -- (B, Ntok, D)
+    views, packed: (M, D); ``maps``: the attention maps asked for, in the order asked -- shaped tensors, packed: one flat buffer per
+    map (_PackedLayout.attn_views cuts it); both empty when not asked for.  ``tok_offsets``: None on the fixed path; on the packed path
+    the int64 CPU tensor of B + 1 row offsets whenever token outputs or maps were asked for."""
+    logits: torch.Tensor
+    feat: torch.Tensor
+    ctx: Optional[dict]
+    hidden: tuple = ()
+    maps: tuple = ()
+    tok_offsets: Optional[torch.Tensor] = None
+
+    def flat(self):
+        """The tensors in the order the autograd node hands them out (and from_flat reads them back)."""
+        return (self.logits, self.feat) + self.hidden + self.maps + (() if self.tok_offsets is None else (self.tok_offsets,))
+
+    @classmethod
+    def from_flat(cls, out, n_hidden, n_maps):
+        it = iter(out)
+        return cls(next(it), next(it), None, tuple(islice(it, n_hidden)), tuple(islice(it, n_maps)), next(it, None))
+
+
 def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None):
-    """Token matrix xs [M][D] f32 in layout ``lay`` -> blocks -> tail -> head.  Returns (logits, features, ctx, hs); ctx
+    """Token matrix xs [M][D] f32 in layout ``lay`` -> blocks -> tail -> head.  Returns a _Fwd (tok_offsets left to the caller); ctx
     (``save`` only) is what _backward_trunk needs plus ``patch``, the entry path's own state for its patch-stage backward.
-    ``hidden`` (parse_hidden's tuple or None): the token outputs to hand out, hs in that order -- a block's output is the f32
+    ``hidden`` (parse_hidden's tuple or None): the token outputs to hand out, in that order -- a block's output is the f32
     residual stream the block wrote (its own fresh buffer, no copy), "norm" the final norm of every row of the last block's output.
     The last block or "norm" among them makes the last block run on all rows (FULL TAIL) instead of the prefix-only tail.
-    ``attn`` (parse_attn's triple or None): the attention maps to hand out, as a fifth result in the order asked (layout's
+    ``attn`` (parse_attn's triple or None): the attention maps to hand out, in the order asked (layout's
     attention_probs: a shaped tensor, or the packed batch's flat buffer) -- made right behind the block's attention launch from the
     qkv and lse it used.  All rows of the last block's map need the FULL TAIL too; its prefix rows come from the prefix-only tail's
     own compact lse, and the tail is unchanged."""
@@ -501,7 +525,7 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None):
     logits = ops.linear_f32_fwd(hn, model.head[1].weight, model.head[1].bias)
     # tail: None = the prefix-only tail; else the full tail's own state (the last block's output, the final norm's row statistics)
     ctx = dict(dt=dt, lay=lay, scale=scale, saved=saved, xl=xl, feat=feat, hn=hn, stats=stats, patch=patch, tail=tail) if save else None
-    return logits, feat, ctx, [lay.hidden_view(outs[k]) for k in want], [maps[k] for k in amaps]
+    return _Fwd(logits, feat, ctx, tuple(lay.hidden_view(outs[k]) for k in want), tuple(maps[k] for k in amaps))
 
 
 def patchout_draws(model, x_shape):
@@ -525,11 +549,20 @@ def passt_forward(model, x, save, draws=None, hidden=None, attn=None):
     draws {pf, pt, pt_pos (= pt + time offset), Np} prepared by the caller (captured-graph mode); None = draw here.
     ``hidden`` (parse_hidden's tuple): returns (logits, features, ctx, hs), hs = the (B, Ntok, D) f32 token outputs asked for.
     ``attn`` (parse_attn's triple): returns (logits, features, ctx, hs, maps), maps = the attention maps asked for."""
+    r = _run_forward(model, x, None, save, draws, hidden, attn)
+    out = (r.logits, r.feat, r.ctx)
+    if hidden is not None or attn is not None:
+        out += (list(r.hidden),)
+    return out if attn is None else out + (list(r.maps),)
+
+
+def _run_forward(model, x, lengths=None, save=False, draws=None, hidden=None, attn=None):
+    """The one way into the kernel sequence of a forward: the fixed path, or with ``lengths`` the packed one, under this model's GEMM
+    flags.  Returns the _Fwd."""
     with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
-        out = _passt_forward(model, x, save, draws, hidden, attn)
-    if attn is not None:
-        return out
-    return out[:3] if hidden is None else out[:4]
+        if lengths is None:
+            return _passt_forward(model, x, save, draws, hidden, attn)
+        return _passt_forward_varlen(model, x, lengths, save, hidden, attn)
 
 
 def _passt_forward(model, x, save, draws=None, hidden=None, attn=None):
@@ -561,41 +594,64 @@ def _passt_forward(model, x, save, draws=None, hidden=None, attn=None):
 # --------------------------------------------------------------------------------------------
 # packed forward for clips of different lengths
 # --------------------------------------------------------------------------------------------
+def _clip_columns(lengths, P, tstride, T_max):
+    """What both ragged geometries check first, clip after clip: yields (clip index, frames, patch columns (len_i - P) // tstride + 1).
+    ValueError for an empty batch and for the first clip shorter than one patch or longer than ``T_max``."""
+    lens = [int(v) for v in lengths]
+    if not lens:
+        raise ValueError("lengths is empty")
+    for i, n in enumerate(lens):
+        if n < P:
+            raise ValueError(f"clip {i}: {n} frames are shorter than one patch ({P} frames): no patch column")
+        if T_max is not None and n > T_max:
+            raise ValueError(f"clip {i}: length {n} exceeds the input's {T_max} frames")
+        yield i, n, (n - P) // tstride + 1
+
+
+def _pack_clips(F_dim, T_eff, clips, slot=False):
+    """The token rows of a packed batch.  ``clips``: per clip (pf, pt, toff) -- the grid coordinates of its patches in sequence order
+    (kept_patches) and its offset into the time embedding; ``T_eff``: its patch columns.  Clip i owns cls, dist and its patches, the
+    clips back to back.  Returns int32 numpy arrays per token row -- ``row_clip`` / ``row_f`` / ``row_t`` (row_f = -1 on the prefix
+    rows, row_t = 0 cls / 1 dist there) / ``row_tpos`` (row_t + the clip's offset on the patch rows) -- ``cu_tok`` (B + 1 row offsets),
+    ``toff`` (one per clip), plus ``max_N``, ``Tg`` (patch columns of the widest clip) and, asked for with ``slot``, ``slot`` (int32
+    [B][F_dim][Tg]: the packed row of patch (f, t) of clip b, -1 where there is none)."""
+    B = len(clips)
+    ntok = np.array([2 + pf.size for pf, _, _ in clips], dtype=np.int64)
+    cu = np.zeros(B + 1, dtype=np.int64)
+    np.cumsum(ntok, out=cu[1:])
+    M = int(cu[-1])
+    if M >= 2 ** 31:
+        raise ValueError("packed batch has too many tokens")
+    row_clip = np.repeat(np.arange(B, dtype=np.int32), ntok)
+    row_f, row_t = np.empty(M, dtype=np.int32), np.empty(M, dtype=np.int32)
+    toff = np.array([toff for _, _, toff in clips], dtype=np.int32)
+    g = dict(row_clip=row_clip, row_f=row_f, row_t=row_t, cu_tok=cu.astype(np.int32), max_N=int(ntok.max()), toff=toff, Tg=max(T_eff))
+    if slot:
+        g["slot"] = np.full((B, F_dim, g["Tg"]), -1, dtype=np.int32)
+    for i, (pf, pt, _) in enumerate(clips):
+        o = int(cu[i])
+        row_f[o:o + 2], row_t[o:o + 2] = -1, (0, 1)
+        row_f[o + 2:o + 2 + pf.size], row_t[o + 2:o + 2 + pf.size] = pf, pt
+        if slot:
+            g["slot"][i, pf, pt] = o + 2 + np.arange(pf.size, dtype=np.int32)
+    g["row_tpos"] = row_t + toff[row_clip] * (row_f >= 0) if toff.any() else row_t       # without offsets: row_t itself, not a copy
+    return g
+
+
 def varlen_geometry(lengths, P, tstride, F_dim, Tpe, T_max=None):
     """Host geometry of a packed ragged batch (models/passt.py:513-526 per clip, eval mode).  ``lengths``: valid frames per clip.
     Clip i has T_i = (len_i - P) // tstride + 1 patch columns, cut to the time embedding's ``Tpe``; its tokens are cls, dist and
     the F_dim x T_i patches in frequency-major order (:546), and the clips lie back to back.  Returns a dict of int32 numpy arrays
     -- per token row ``row_clip`` / ``row_f`` / ``row_t`` (row_f = -1 on the prefix rows, row_t = 0 cls / 1 dist there), ``cu_tok``
     (B + 1 row offsets) -- plus ``T_eff`` (patch columns kept per clip), ``cut`` (clips whose columns reach or exceed Tpe: the
-    reference warns for them) and ``max_N``.  ValueError names the first clip shorter than one patch or longer than ``T_max``."""
-    lens = [int(v) for v in lengths]
-    if not lens:
-        raise ValueError("lengths is empty")
+    reference warns for them) and ``max_N`` (and _pack_clips' other keys: ``row_tpos`` = row_t, ``toff`` = 0, ``Tg``).  ValueError names
+    the first clip shorter than one patch or longer than ``T_max``."""
     T_eff, cut = [], []
-    for i, n in enumerate(lens):
-        if n < P:
-            raise ValueError(f"clip {i}: {n} frames are shorter than one patch ({P} frames): no patch column")
-        if T_max is not None and n > T_max:
-            raise ValueError(f"clip {i}: length {n} exceeds the input's {T_max} frames")
-        T_dim = (n - P) // tstride + 1
+    for i, n, T_dim in _clip_columns(lengths, P, tstride, T_max):
         if T_dim >= Tpe:
             cut.append(i)
         T_eff.append(min(T_dim, Tpe))
-    ntok = np.array([2 + F_dim * t for t in T_eff], dtype=np.int64)
-    cu = np.zeros(len(lens) + 1, dtype=np.int64)
-    np.cumsum(ntok, out=cu[1:])
-    M = int(cu[-1])
-    if M >= 2 ** 31:
-        raise ValueError("packed batch has too many tokens")
-    row_clip = np.repeat(np.arange(len(lens), dtype=np.int32), ntok)
-    row_f = np.empty(M, dtype=np.int32)
-    row_t = np.empty(M, dtype=np.int32)
-    for i, t in enumerate(T_eff):
-        o = int(cu[i])
-        row_f[o:o + 2], row_t[o:o + 2] = -1, (0, 1)
-        row_f[o + 2:o + 2 + F_dim * t] = np.repeat(np.arange(F_dim, dtype=np.int32), t)
-        row_t[o + 2:o + 2 + F_dim * t] = np.tile(np.arange(t, dtype=np.int32), F_dim)
-    return dict(row_clip=row_clip, row_f=row_f, row_t=row_t, cu_tok=cu.astype(np.int32), T_eff=T_eff, cut=cut, max_N=int(ntok.max()))
+    return dict(_pack_clips(F_dim, T_eff, [kept_patches(F_dim, t, None, None, None) + (0,) for t in T_eff]), T_eff=T_eff, cut=cut)
 
 
 def varlen_geometry_train(model, lengths, F_dim=None, T_max=None):
@@ -618,16 +674,8 @@ def varlen_geometry_train(model, lengths, F_dim=None, T_max=None):
     if F_dim is None:
         F_dim = model.freq_new_pos_embed.shape[-2]
     s_t, s_f, u = (int(model.s_patchout_t or 0), int(model.s_patchout_f or 0), int(model.u_patchout or 0)) if model.training else (0, 0, 0)
-    lens = [int(v) for v in lengths]
-    if not lens:
-        raise ValueError("lengths is empty")
     T_dims, cut = [], []
-    for i, n in enumerate(lens):
-        if n < P:
-            raise ValueError(f"clip {i}: {n} frames are shorter than one patch ({P} frames): no patch column")
-        if T_max is not None and n > T_max:
-            raise ValueError(f"clip {i}: length {n} exceeds the input's {T_max} frames")
-        T_dim = (n - P) // ts + 1
+    for i, n, T_dim in _clip_columns(lengths, P, ts, T_max):
         if s_t and T_dim <= s_t:
             raise ValueError(f"clip {i}: {T_dim} patch columns ({n} frames) leave nothing after s_patchout_t={s_t}")
         if s_t and T_dim > Tpe:
@@ -641,31 +689,14 @@ def varlen_geometry_train(model, lengths, F_dim=None, T_max=None):
         if T_dim >= Tpe:
             cut.append(i)
         T_dims.append(T_dim)
-    B = len(lens)
-    pfs, pts, toffs, T_eff = [], [], [], []
+    clips, T_eff = [], []
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")                 # draw_patchout's "x will be cut", per clip: the caller warns once, from ``cut``
         for T_dim in T_dims:
             toff, Te, idx_t, idx_f, idx_u = draw_patchout(model, F_dim, T_dim)
-            pf, pt = kept_patches(F_dim, Te, idx_t, idx_f, idx_u)
-            pfs.append(pf), pts.append(pt), toffs.append(toff), T_eff.append(Te)
-    ntok = np.array([2 + pf.size for pf in pfs], dtype=np.int64)
-    cu = np.zeros(B + 1, dtype=np.int64)
-    np.cumsum(ntok, out=cu[1:])
-    M = int(cu[-1])
-    if M >= 2 ** 31:
-        raise ValueError("packed batch has too many tokens")
-    Tg = max(T_eff)
-    row_clip = np.repeat(np.arange(B, dtype=np.int32), ntok)
-    row_f, row_t, row_tpos = (np.empty(M, dtype=np.int32) for _ in range(3))
-    slot = np.full((B, F_dim, Tg), -1, dtype=np.int32)
-    for i, (pf, pt) in enumerate(zip(pfs, pts)):
-        o = int(cu[i])
-        row_f[o:o + 2], row_t[o:o + 2], row_tpos[o:o + 2] = -1, (0, 1), (0, 1)
-        row_f[o + 2:o + 2 + pf.size], row_t[o + 2:o + 2 + pf.size], row_tpos[o + 2:o + 2 + pf.size] = pf, pt, pt + toffs[i]
-        slot[i, pf, pt] = o + 2 + np.arange(pf.size, dtype=np.int32)
-    return dict(row_clip=row_clip, row_f=row_f, row_t=row_t, row_tpos=row_tpos, cu_tok=cu.astype(np.int32), T_eff=T_eff, cut=cut,
-                max_N=int(ntok.max()), toff=np.array(toffs, dtype=np.int32), Tg=Tg, slot=slot)
+            clips.append(kept_patches(F_dim, Te, idx_t, idx_f, idx_u) + (toff,))
+            T_eff.append(Te)
+    return dict(_pack_clips(F_dim, T_eff, clips, slot=True), T_eff=T_eff, cut=cut)
 
 
 def passt_forward_varlen(model, x, lengths, save=False):
@@ -673,19 +704,16 @@ def passt_forward_varlen(model, x, lengths, save=False):
     ``save=True``: (logits, features, ctx) with what passt_backward_varlen needs.  Without it nothing is kept and the launch sequence is
     the same.  Eval geometry (no Patchout) -- except for a model in training mode with ``varlen_train`` set: then every clip gets its own
     Patchout draws (varlen_geometry_train) and the context carries the slot table the packed patch-stage backward walks."""
-    with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
-        logits, feat, ctx = _passt_forward_varlen(model, x, lengths, save)[:3]
-    return (logits, feat, ctx) if save else (logits, feat)
+    r = _run_forward(model, x, lengths, save)
+    return (r.logits, r.feat, r.ctx) if save else (r.logits, r.feat)
 
 
-def passt_forward_varlen_hidden(model, x, lengths, hidden, save=False, attn=None):
-    """passt_forward_varlen that also hands out token outputs (``hidden``: parse_hidden's tuple): returns (logits, features, ctx or
-    None, hs, tok_offsets) -- hs the packed (M, D) f32 matrices asked for, tok_offsets an int64 CPU tensor of B + 1 row offsets (clip i
-    owns rows tok_offsets[i] : tok_offsets[i + 1]).  ``attn`` (parse_attn's triple; ``hidden`` may then be None): returns (logits,
-    features, ctx or None, hs, maps, tok_offsets), maps = one flat buffer per attention map asked for (_PackedLayout.attn_views)."""
-    with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
-        out = _passt_forward_varlen(model, x, lengths, save, hidden, attn)
-    return out if attn is not None else out[:4] + out[5:]
+def _upload_parts(parts, device):
+    """ONE upload of the int32 host arrays ``parts`` (name -> array) laid back to back in the order given; returns name -> the device
+    view of that part, in the array's own shape."""
+    buf = ops.upload_small(np.concatenate([a.reshape(-1) for a in parts.values()]), device)
+    views = buf.split([a.size for a in parts.values()])
+    return {name: v.view(a.shape) for (name, a), v in zip(parts.items(), views)}
 
 
 def _passt_forward_varlen(model, x, lengths, save=False, hidden=None, attn=None):
@@ -707,34 +735,28 @@ def _passt_forward_varlen(model, x, lengths, save=False, hidden=None, attn=None)
     if g["cut"]:
         warnings.warn(f"the patches shape of clips {g['cut']} are larger than the expected time encodings "
                       f"{tuple(model.time_new_pos_embed.shape)}, x will be cut")              # :524-526, once per call
-    M = g["row_f"].size
+    M, cu = g["row_f"].size, g["cu_tok"]
     # one upload: [row_clip | row_f | row_t | cu_tok | prefix rows], in training mode followed by [row_tpos | clip offsets | slot table]
-    cu = g["cu_tok"]
-    pidx_np = (cu[:-1, None] + np.arange(2, dtype=np.int32)[None, :]).reshape(-1).astype(np.int32)
-    parts = [g["row_clip"], g["row_f"], g["row_t"], cu, pidx_np]
+    parts = {k: g[k] for k in ("row_clip", "row_f", "row_t", "cu_tok")}
+    parts["pidx"] = (cu[:-1, None] + np.arange(2, dtype=np.int32)[None, :]).reshape(-1).astype(np.int32)
     if train:
-        parts += [g["row_tpos"], g["toff"], g["slot"].reshape(-1)]
-    idx = ops.upload_small(np.concatenate(parts), x.device)
-    row_clip, row_f, row_t = idx[:M], idx[M:2 * M], idx[2 * M:3 * M]
-    cu_tok, pidx = idx[3 * M:3 * M + B + 1], idx[3 * M + B + 1:3 * M + 3 * B + 1]
-    row_tpos = row_t                                 # eval: the time embedding is read from offset 0
-    if train:
-        o = 3 * M + 3 * B + 1
-        row_tpos, toff, slot = idx[o:o + M], idx[o + M:o + M + B], idx[o + M + B:].view(g["slot"].shape)
+        parts.update((k, g[k]) for k in ("row_tpos", "toff", "slot"))
+    d = _upload_parts(parts, x.device)
 
     # patch embedding: the packed im2col has a zero row under every prefix token and the table holds the token there, so the one
     # GEMM with the residual epilogue writes the whole token matrix (no scatter pass)
-    cols = ops.patch_gather_varlen(x, row_clip, row_f, row_t, P, fs, ts, dt)
-    table = ops.patch_pos_table_varlen(model.patch_embed.proj.bias, model.time_new_pos_embed, model.freq_new_pos_embed, row_f, row_tpos,
-                                       model.cls_token, model.dist_token, model.new_pos_embed)
+    cols = ops.patch_gather_varlen(x, d["row_clip"], d["row_f"], d["row_t"], P, fs, ts, dt)
+    # eval: the time embedding is read from offset 0, row_t is the column
+    table = ops.patch_pos_table_varlen(model.patch_embed.proj.bias, model.time_new_pos_embed, model.freq_new_pos_embed, d["row_f"],
+                                       d["row_tpos" if train else "row_t"], model.cls_token, model.dist_token, model.new_pos_embed)
     xs = torch.empty((M, model.embed_dim), device=x.device, dtype=torch.float32)
     ops.gemm_nt(cols, model._staged.get(model.patch_embed.proj.weight, dt, False), dt, EPI_RESID, resid=table, out_f32=xs)
     patch = dict(F=F, T=T, cols=cols) if save else None
     if save and train:
-        patch.update(slot=slot, toff=toff)           # Patchout: the patch-stage backward finds a row's grid position through the table
+        patch.update(slot=d["slot"], toff=d["toff"])   # Patchout: the patch-stage backward finds a row's grid position through the table
     tok_offsets = torch.from_numpy(cu.astype(np.int64)) if (hidden is not None or attn is not None) else None
-    lay = _PackedLayout(B, M, g["max_N"], cu_tok, pidx, ntok=np.diff(cu))
-    return _forward_trunk(model, lay, xs, dt, save, patch, hidden, attn) + (tok_offsets,)
+    lay = _PackedLayout(B, M, g["max_N"], d["cu_tok"], d["pidx"], ntok=np.diff(cu))
+    return _forward_trunk(model, lay, xs, dt, save, patch, hidden, attn)._replace(tok_offsets=tok_offsets)
 
 
 class _NoRowJobs(list):
@@ -1025,23 +1047,9 @@ class _PasstFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, lengths, hidden, attn, x, *params):
-        hs = maps = ()
-        if lengths is None:
-            logits, feat, c, *more = passt_forward(model, x, save=True, hidden=hidden, attn=attn)
-            if hidden is not None:
-                hs = tuple(more[0])
-            if attn is not None:
-                maps = tuple(more[1])
-        else:
-            if hidden is None and attn is None:
-                logits, feat, c = passt_forward_varlen(model, x, lengths, save=True)
-            else:
-                logits, feat, c, h, *more = passt_forward_varlen_hidden(model, x, lengths, hidden, save=True, attn=attn)
-                if attn is not None:
-                    maps = tuple(more[0])
-                hs, maps = tuple(h), maps + (more[-1],)         # the row offsets come last
-        ctx.mark_non_differentiable(*[m for m in maps if m.is_floating_point()])
-        ctx.model, ctx.c, ctx.varlen, ctx.hidden = model, c, lengths is not None, hidden
+        r = _run_forward(model, x, lengths, True, hidden=hidden, attn=attn)
+        ctx.mark_non_differentiable(*r.maps)            # the integer row offsets of the packed path are non-differentiable as they are
+        ctx.model, ctx.c, ctx.varlen, ctx.hidden = model, r.ctx, lengths is not None, hidden
         # the input spectrogram's gradient is computed only when asked for; a graph none of whose parameters requires a gradient
         # (a frozen loss network) runs the backward without any weight-gradient work
         ctx.want_dx = bool(ctx.needs_input_grad[4])
@@ -1051,7 +1059,7 @@ class _PasstFunction(torch.autograd.Function):
         # straight into the optimizer's persistent flat buffer -- p.grad are views of it -- and hands autograd nothing
         ctx.flat = model._flat if (len(params) == 1 and model._flat is not None and params[0] is model._flat["token"]) else None
         ctx.set_materialize_grads(False)        # an unused `features` output arrives as None, not as a zero tensor
-        return (logits, feat) + hs + maps
+        return r.flat()
 
     @staticmethod
     def backward(ctx, dlogits, dfeat, *dhs):
@@ -1135,8 +1143,6 @@ def _tree_signature(root):
     return [(m, tuple(map(id, m._parameters.values())), tuple(map(id, m._modules.values()))) for m in root.modules()]
 
 
-import weakref
-
 _LIVE = weakref.WeakSet()            # live PaSST instances: how passt_amd.optim.AdamW finds the model its parameters belong to
 _RUNTIME_ATTRS = ("_staged", "_scratch", "_ddp", "_gemm_flags", "_flat", "_last_dt")
 
@@ -1213,7 +1219,6 @@ class PaSST(nn.Module):
         cls = self.__class__
         new = cls.__new__(cls)
         memo[id(self)] = new
-        import copy
         for k, v in self.__dict__.items():
             if k in _RUNTIME_ATTRS:
                 continue
@@ -1386,9 +1391,9 @@ class PaSST(nn.Module):
         in ``x`` (B, 1, n_mels, T_max); clip i is valid in its first lengths[i] frames and whatever lies behind them has no influence
         (it is never read).  Row i of both outputs is what ``forward(x[i:i+1, :, :, :lengths[i]])`` returns at batch size 1 -- the
         reference's own way of evaluating clips of different lengths (ex_fsd50k.py:53-56) -- but the batch runs as ONE packed kernel
-        sequence over sum_i tokens.  Eval mode (training mode: ``varlen_train``, below).  The token geometry is decided on the host: ``lengths`` given as a device tensor
-        costs one host read.  A clip shorter than one patch raises ValueError; clips whose patch columns reach the time embedding's
-        length are cut to it, with one warning per call.
+        sequence over sum_i tokens.  Eval mode (training mode: ``varlen_train``, below).  The token geometry is decided on the host:
+        ``lengths`` given as a device tensor costs one host read.  A clip shorter than one patch raises ValueError; clips whose patch
+        columns reach the time embedding's length are cut to it, with one warning per call.
         Gradients through the ragged forward are opt-in: by default the outputs carry no grad_fn, also for an ``x`` that requires a
         gradient.  With ``net.varlen_grad = True`` (eval mode, grad enabled) the packed forward is an autograd node with a packed
         backward: an ``x`` that requires a gradient gets ``x.grad`` in its own shape / dtype / layout, every element written and
@@ -1455,37 +1460,30 @@ class PaSST(nn.Module):
             if named is None:
                 named = self._graph_params()[0]
             fl = self._flat
-            if fl is not None:
-                if fl["named"] is named:                # same validated parameter list as at bind time
-                    return self._with_hidden(_PasstFunction.apply(self, lengths, hid, amap, x, fl["token"]), hid, amap)
-                self.unbind_flat_grads()                # surgery since: the optimizer re-binds at its next step
-            return self._with_hidden(_PasstFunction.apply(self, lengths, hid, amap, x, *[p for _, p in named]), hid, amap)
-        if lengths is not None:
-            with torch.no_grad():
-                if hid is None and amap is None:
-                    return passt_forward_varlen(self, x, lengths)
-                logits, feat, _, hs, *more = passt_forward_varlen_hidden(self, x, lengths, hid, attn=amap)
-                return self._with_hidden((logits, feat) + tuple(hs) + tuple(more[0] if amap is not None else ()) + (more[-1],), hid, amap)
-        if hid is None and amap is None:
-            logits, feat, _ = passt_forward(self, x, save=False)
-            return logits, feat
-        logits, feat, _, hs, *more = passt_forward(self, x, save=False, hidden=hid, attn=amap)
-        return self._with_hidden((logits, feat) + tuple(hs) + tuple(more[0] if more else ()), hid, amap)
+            if fl is not None and fl["named"] is not named:     # surgery since bind time: the optimizer re-binds at its next step
+                self.unbind_flat_grads()
+                fl = None
+            # bound (same validated parameter list as at bind time): the single token stands for every parameter
+            params = (fl["token"],) if fl is not None else [p for _, p in named]
+            r = _Fwd.from_flat(_PasstFunction.apply(self, lengths, hid, amap, x, *params), len(hid or ()), len(amap[0]) if amap else 0)
+        elif lengths is None and hid is None and amap is None:
+            return passt_forward(self, x, save=False)[:2]       # the plain call stays on the public entry (callers stand in for it)
+        else:
+            # the ragged forward records nothing unless asked to; the fixed one leaves that to the caller's own grad mode
+            with torch.no_grad() if lengths is not None else contextlib.nullcontext():
+                r = _run_forward(self, x, lengths, hidden=hid, attn=amap)
+        return self._outputs(r, hid, amap)
 
-    def _with_hidden(self, out, hid, amap=None):
-        """The autograd node's flat outputs in forward()'s shape: (logits, features[, [token outputs]][, [attention maps]]
-        [, tok_offsets]); a packed batch's maps (one flat buffer each) are cut into the clips' views here."""
-        nh, na = len(hid or ()), len(amap[0]) if amap is not None else 0
-        res = tuple(out[:2])
+    def _outputs(self, r, hid, amap):
+        """A forward's record in forward()'s shape: (logits, features[, [token outputs]][, [attention maps]][, tok_offsets]); a packed
+        batch's maps (one flat buffer each) are cut into the clips' views here."""
+        res = (r.logits, r.feat)
         if hid is not None:
-            res += (list(out[2:2 + nh]),)
-        rest = tuple(out[2 + nh + na:])                 # the packed path's tok_offsets, or nothing
+            res += (list(r.hidden),)
         if amap is not None:
-            maps = list(out[2 + nh:2 + nh + na])
-            if rest:
-                maps = [_PackedLayout.attn_views(m, rest[0], self.num_heads, amap[1], amap[2]) for m in maps]
-            res += (maps,)
-        return res + rest
+            res += ([m if r.tok_offsets is None else _PackedLayout.attn_views(m, r.tok_offsets, self.num_heads, amap[1], amap[2])
+                     for m in r.maps],)
+        return res if r.tok_offsets is None else res + (r.tok_offsets,)
 
 
 # --------------------------------------------------------------------------------------------

@@ -191,26 +191,7 @@ def test_generator_holds_no_reference_text_and_variants_cover_the_interface():
 from tests import test_sequence_cpu as S  # noqa: E402
 
 
-def _probs(qkv, lse, B, H, N, scale, nq=None, head_mean=False, flags=0, out=None):
-    nq = N if nq is None else nq
-    assert lse.numel() == B * H * nq and lse.dtype == torch.float32 and flags == ops.ATTN_Q_PRESCALED
-    return S._e((B, 1 if head_mean else H, nq, N))
-
-
-def _probs_varlen(qkv, lse, cu_tok, out_off, total_out, B, H, max_N, scale, nq=None, head_mean=False, flags=0, out=None):
-    assert lse.numel() == (H * qkv.shape[0] if nq is None else B * H * nq) and out_off.dtype == torch.int64 and out_off.numel() == B
-    return S._e((total_out,))
-
-
-def _record(run, seed=1234):
-    rec = S._Recorder()
-    with pytest.MonkeyPatch.context() as mp:
-        S._install(mp, rec)
-        mp.setattr(ops, "attention_probs", rec.op("attention_probs", _probs))
-        mp.setattr(ops, "attention_probs_varlen", rec.op("attention_probs_varlen", _probs_varlen))
-        torch.manual_seed(seed)
-        run(rec)
-    return rec.trace
+_record = S._record_run
 
 
 def _without_maps(trace):

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import passt_amd
-from passt_amd import _lib, ops
+from passt_amd import _lib
 from passt_amd import passt as P
 from tests import test_sequence_cpu as S
 
@@ -25,26 +25,7 @@ def _net(depth=2, train=False, frozen=False, precision="bf16", **kw):
     return net
 
 
-def _layernorm_bwd2(dy, x, gamma, mean, rstd, dres, dres2, dgamma, dbeta, want_lp, accumulate=False, dcolsum=None, defer=None):
-    assert dres2 is not None and dres2.shape == x.shape and dres2.dtype == torch.float32
-    return S._layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, want_lp, accumulate=accumulate, dcolsum=dcolsum, defer=defer)
-
-
-def _tail_inject(rows, idx, n, add0, add1, dt):
-    dx = S._e((n, rows.shape[1]))
-    return dx, dx if S._lp(dt) == torch.float32 else S._e(dx.shape, S._lp(dt))
-
-
-def _record(run, seed=1234):
-    """trace of ``run(rec)`` with every op replaced by the recorder's stand-in (the two new ops included)"""
-    rec = S._Recorder()
-    with pytest.MonkeyPatch.context() as mp:
-        S._install(mp, rec)
-        mp.setattr(ops, "layernorm_bwd2", rec.op("layernorm_bwd2", _layernorm_bwd2))
-        mp.setattr(ops, "tail_inject", rec.op("tail_inject", _tail_inject))
-        torch.manual_seed(seed)
-        run(rec)
-    return rec.trace
+_record = S._record_run         # trace of ``run(rec)`` with every op replaced by the recorder's stand-in
 
 
 def _names(trace):

@@ -9,12 +9,17 @@ and the packed path, forward and backward, through the public functions and thro
 
 The expected traces (tests/golden/sequence_traces.json) were recorded by this same harness on the commit named in the fixture's
 note, when passt.py still held the fixed and the packed kernel sequence as two copies: the shared trunk must launch exactly what
-each copy launched, in the same order, on the same stream.  ``python -m tests.test_sequence_cpu --write`` records them again.
+each copy launched, in the same order, on the same stream.  The cases added since (``hidden=``, ``attn=``, ``varlen_train``, the
+bound flat gradient buffer) were recorded on the commit the fixture's ``notes_added`` names, before the host code around the trunk
+was reshaped; they also end in ["rng", digest of the CPU generator's state after the call], so the order and number of the Patchout
+draws is part of the trace (the first ten cases keep their traces as recorded and have their digests in the fixture's ``rng``).
+``python -m tests.test_sequence_cpu --write`` records the cases the fixture does not hold yet and leaves the others as they are.
 
 One case has no recorded trace: ``packed_bf16_no_defer_rows``.  The packed copy of the backward never read the A/B switches; going
 through the shared weight-gradient scheduling it honours them now, which is new behaviour, so the test asserts what the switch
 means (no reduction is deferred to the block's finishing launch) instead of equality with the parent."""
 import contextlib
+import hashlib
 import json
 import os
 import warnings
@@ -106,6 +111,27 @@ def _layernorm_fwd(x, g, b, eps, dt, save_stats=True):
     return _e(x.shape, _lp(dt)), (_e(x.shape[:1]) if save_stats else None), (_e(x.shape[:1]) if save_stats else None)
 
 
+def _layernorm_bwd2(dy, x, gamma, mean, rstd, dres, dres2, dgamma, dbeta, want_lp, accumulate=False, dcolsum=None, defer=None):
+    assert dres2 is not None and dres2.shape == x.shape and dres2.dtype == torch.float32
+    return _layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, want_lp, accumulate=accumulate, dcolsum=dcolsum, defer=defer)
+
+
+def _tail_inject(rows, idx, n, add0, add1, dt):
+    dx = _e((n, rows.shape[1]))
+    return dx, dx if _lp(dt) == torch.float32 else _e(dx.shape, _lp(dt))
+
+
+def _probs(qkv, lse, B, H, N, scale, nq=None, head_mean=False, flags=0, out=None):
+    nq = N if nq is None else nq
+    assert lse.numel() == B * H * nq and lse.dtype == torch.float32 and flags == ops.ATTN_Q_PRESCALED
+    return _e((B, 1 if head_mean else H, nq, N))
+
+
+def _probs_varlen(qkv, lse, cu_tok, out_off, total_out, B, H, max_N, scale, nq=None, head_mean=False, flags=0, out=None):
+    assert lse.numel() == (H * qkv.shape[0] if nq is None else B * H * nq) and out_off.dtype == torch.int64 and out_off.numel() == B
+    return _e((total_out,))
+
+
 # op name -> what the stand-in returns (shapes and dtypes as passt_amd/ops.py documents them)
 _RESULTS = {
     "upload_small": lambda host, device: torch.from_numpy(np.ascontiguousarray(host)),
@@ -141,6 +167,12 @@ _RESULTS = {
     "patch_input_bwd": lambda dcols, pf, pt, B, F, T, *a, **k: _e((B, 1, F, T)),
     "patch_bwd_varlen": lambda *a, **k: None,
     "patch_input_bwd_varlen": lambda dcols, cu, B, F, T, *a, **k: _e((B, 1, F, T)),
+    "patch_bwd_rows": lambda *a, **k: None,
+    "patch_input_bwd_rows": lambda dcols, slot, F, T, *a, **k: _e((slot.shape[0], 1, F, T)),
+    "layernorm_bwd2": _layernorm_bwd2,
+    "tail_inject": _tail_inject,
+    "attention_probs": _probs,
+    "attention_probs_varlen": _probs_varlen,
 }
 
 
@@ -245,6 +277,56 @@ def _case_packed_frozen_want_dx(rec, mp):
     _autograd(rec, net, LENGTHS)
 
 
+def _step(rec, net, x_grad, lengths=None, **kw):
+    """``net(x, ...)`` with the keywords of the newer modes + a backward of a loss on logits, features and every token output; logs
+    the whole returned structure."""
+    x = torch.zeros(X_SHAPE, requires_grad=x_grad)
+    out = net(x, **kw) if lengths is None else net(x, lengths=lengths, **kw)
+    loss = out[0].sum() + out[1].sum()
+    for h in (out[2] if "hidden" in kw else ()):
+        loss = loss + h.sum()
+    loss.backward()
+    rec.log("returned", (out, x.grad, [n for n, p in net.named_parameters() if p.grad is not None]))
+
+
+def _case_fixed_keywords(rec, mp, precision, x_grad, **kw):
+    net = _net(True)
+    net.precision, net.input_grad = precision, x_grad
+    _step(rec, net, x_grad, **kw)
+
+
+def _case_keywords_nograd(rec, mp, lengths=None):
+    net = _net(False)
+    net.precision = "bf16"
+    args = {} if lengths is None else dict(lengths=lengths)
+    with torch.no_grad():
+        out = net(torch.zeros(X_SHAPE), hidden=(0, "norm"), attn=(1, 0), **args)
+    rec.log("returned", out)
+    rec.log("last_dt", (net._last_dt,))
+
+
+def _case_packed_keywords_grad(rec, mp):
+    net = _net(False)
+    net.precision, net.varlen_grad = "bf16", True
+    _step(rec, net, True, LENGTHS, hidden=(0,), attn=(0,))
+
+
+def _case_packed_varlen_train(rec, mp, frozen=False):
+    net = _net(True).requires_grad_(not frozen)
+    net.precision, net.varlen_train = "fp32", True
+    _step(rec, net, True, LENGTHS)
+
+
+def _case_fixed_flat_bound(rec, mp):
+    """The single-token ``apply`` route of a model bound to an optimizer's flat gradient buffer."""
+    net = _net(True)
+    net.precision = "bf16"
+    fl = net.bind_flat_grads(torch.zeros(net._graph_params()[1]))
+    assert fl is not None and net._flat is fl and fl["fresh"]
+    _step(rec, net, False)
+    rec.log("flat", (fl["fresh"], all(p.grad is fl["grads"][n] for n, p in fl["named"])))
+
+
 CASES = {
     "fixed_train_fp32": lambda r, mp: _case_fixed_train(r, mp, "fp32"),
     "fixed_train_bf16": lambda r, mp: _case_fixed_train(r, mp, "bf16"),
@@ -256,22 +338,41 @@ CASES = {
     "packed_train": lambda r, mp: _case_packed_train(r, mp),
     "packed_frozen_want_dx": _case_packed_frozen_want_dx,
     "fixed_bf16_no_defer_rows": lambda r, mp: _case_fixed_train(r, mp, "bf16", env="PASST_AMD_NO_DEFER_ROWS"),
+    "fixed_hidden_mid": lambda r, mp: _case_fixed_keywords(r, mp, "bf16", False, hidden=(0,)),
+    "fixed_hidden_full_tail": lambda r, mp: _case_fixed_keywords(r, mp, "fp32", True, hidden=(-1, "norm")),
+    "fixed_attn_prefix_mean": lambda r, mp: _case_fixed_keywords(r, mp, "bf16", False, attn=(-1, 0), attn_rows="prefix", attn_heads="mean"),
+    "fixed_hidden_attn_nograd": lambda r, mp: _case_keywords_nograd(r, mp),
+    "packed_hidden_attn_nograd": lambda r, mp: _case_keywords_nograd(r, mp, LENGTHS),
+    "packed_hidden_attn_grad": _case_packed_keywords_grad,
+    "packed_varlen_train": lambda r, mp: _case_packed_varlen_train(r, mp),
+    "packed_varlen_train_frozen": lambda r, mp: _case_packed_varlen_train(r, mp, frozen=True),
+    "fixed_flat_bound": _case_fixed_flat_bound,
 }
 
 
-def _record(case):
+def _record(case, seed=1234):
+    """Trace of ``case(rec, mp)`` with every op replaced by its stand-in, closed by the digest of the CPU generator's state."""
     rec = _Recorder()
     with pytest.MonkeyPatch.context() as mp:
         _install(mp, rec)
-        torch.manual_seed(1234)                    # the Patchout draws decide the token count
+        torch.manual_seed(seed)                    # the Patchout draws decide the token count
         case(rec, mp)
+        rec.log("rng", (hashlib.sha1(torch.get_rng_state().numpy().tobytes()).hexdigest()[:16],))
     return json.loads(json.dumps(rec.trace))
+
+
+def _record_run(run, seed=1234):
+    """_record for a test body that needs the recorder only: the trace of ``run(rec)`` without the closing digest."""
+    return _record(lambda rec, mp: run(rec), seed)[:-1]
 
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_launch_sequence_is_the_recorded_one(name):
     with open(FIXTURE) as f:
-        want = json.load(f)["traces"][name]
+        fixture = json.load(f)
+    want = fixture["traces"][name]
+    if want[-1][0] != "rng":                       # the first ten traces stay as recorded: their digests are kept beside them
+        want = want + [fixture["rng"][name]]
     got = _record(CASES[name])
     assert len(want) > 20 and [e[0] for e in got] == [e[0] for e in want]
     for i, (g, w) in enumerate(zip(got, want)):
@@ -280,8 +381,8 @@ def test_launch_sequence_is_the_recorded_one(name):
 
 def test_packed_backward_honours_the_switches_of_the_shared_scheduling():
     """New behaviour (see the module docstring): under PASST_AMD_NO_DEFER_ROWS=1 the packed backward defers nothing either."""
-    plain = _record(lambda r, mp: _case_packed_train(r, mp))
-    got = _record(lambda r, mp: _case_packed_train(r, mp, env="PASST_AMD_NO_DEFER_ROWS"))
+    plain = _record(lambda r, mp: _case_packed_train(r, mp))[:-1]
+    got = _record(lambda r, mp: _case_packed_train(r, mp, env="PASST_AMD_NO_DEFER_ROWS"))[:-1]
     deferring = [e for e in plain if e[0] in ("layernorm_bwd", "dgelu_gemm")]
     assert deferring and all(e[2].get("defer") is not None for e in deferring)
     for e in got:
@@ -299,9 +400,17 @@ if __name__ == "__main__":
         sys.exit("usage: python -m tests.test_sequence_cpu --write")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     commit = subprocess.run(["git", "log", "-1", "--format=%h %s"], cwd=root, capture_output=True, text=True).stdout.strip()
-    note = ("Launch traces of passt_amd/passt.py recorded by `python -m tests.test_sequence_cpu --write` at commit "
-            f"{commit}.")
-    with open(FIXTURE, "w") as f:
-        json.dump({"note": note, "traces": {name: _record(case) for name, case in CASES.items()}}, f, separators=(",", ":"))
-        f.write("\n")
-    print(note)
+    with open(FIXTURE) as f:
+        fixture = json.load(f)                      # what is recorded stays: only the cases it does not hold are added
+    new = [name for name in CASES if name not in fixture["traces"]]
+    for name in new:
+        fixture["traces"][name] = _record(CASES[name])
+    no_rng = [name for name, t in fixture["traces"].items() if t[-1][0] != "rng" and name not in fixture.setdefault("rng", {})]
+    for name in no_rng:
+        fixture["rng"][name] = _record(CASES[name])[-1]
+    if new or no_rng:
+        fixture.setdefault("notes_added", []).append(f"Traces {new} and the generator digests of {no_rng} recorded at commit {commit}.")
+        with open(FIXTURE, "w") as f:
+            json.dump(fixture, f, separators=(",", ":"))
+            f.write("\n")
+    print(f"added {new}, digests {no_rng} at {commit}")
