@@ -428,6 +428,22 @@ int pa_attention_fwd_varlen(const void* qkv, int ldqkv, void* o, int ldo, float*
 int pa_attention_probs(const void* qkv, int ldqkv, const float* lse, float* out, const int32_t* cu_tok, const int64_t* out_off,
                        int B, int H, int N /* max_N when cu_tok != NULL */, int nq, int head_mean, float scale, int dtype, int flags,
                        void* stream);
+/* The gradient of the loss with respect to those probabilities, f32: what the fused backward forms tile by tile in registers and
+ * never writes (retain_grad() on the input of the reference's attn_drop holds it after the backward).  A sibling of
+ * pa_attention_probs: same arguments with the same meaning, same work decomposition, same clamping, same two output layouts, every
+ * element of the output written and nothing else, no LDS / barrier / atomics, bit-repeatable.  Per (32 x 32) tile and head
+ *   g[q][k] = sum_d d_o[q][h*64 + d] * v[k][h*64 + d]      (f32 accumulation)
+ * d_o, ldo: the output gradient of the fused attention as the block's pa_attention_bwd / pa_attention_bwd_varlen call reads it
+ * (dtype of qkv, ldo >= H*64 elements).  do_compact = 0: d_o's rows are qkv's token rows and only the rows q < nq of a sequence are
+ * read; do_compact = 1: the compact prefix form d_o[(b*nq + q)][H*64].
+ *   mode PA_ATTN_PGRAD_GRAD: out = g.  head_mean must be 0; lse is not read and may be NULL.
+ *   mode PA_ATTN_PGRAD_CAM:  out = max(p * g, 0) with p formed exactly as pa_attention_probs forms it from qkv and lse; with
+ *     head_mean = 1 the mean over the heads of that, added in f32 registers in head order. */
+#define PA_ATTN_PGRAD_GRAD 0
+#define PA_ATTN_PGRAD_CAM 1
+int pa_attention_probs_grad(const void* qkv, int ldqkv, const float* lse, const void* d_o, int ldo, int do_compact, float* out,
+                            const int32_t* cu_tok, const int64_t* out_off, int B, int H, int N /* max_N when cu_tok != NULL */, int nq,
+                            int head_mean, int mode, float scale, int dtype, int flags, void* stream);
 /* number of floats of pa_attention_bwd's `delta` workspace */
 int64_t pa_attention_bwd_ws_floats(int B, int H, int nq);
 /* dqkv[B*N][3*H*64] from d_o[B*nq][H*64]; lse from the forward; delta: f32 workspace of pa_attention_bwd_ws_floats()

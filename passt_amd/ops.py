@@ -900,6 +900,80 @@ def attention_probs_varlen(qkv, lse, cu_tok, out_off, total_out, B, H, max_N, sc
     return out.view(-1)
 
 
+ATTN_PGRAD_GRAD, ATTN_PGRAD_CAM = 0, 1      # include/passt_amd.h PA_ATTN_PGRAD_*
+
+
+def _pgrad_d_o(name, d_o, qkv, H, rows_tok, rows_compact, do_compact):
+    rows = rows_compact if do_compact else rows_tok
+    if d_o.dim() != 2 or d_o.shape[1] != H * 64 or d_o.shape[0] != rows or d_o.dtype != qkv.dtype or d_o.stride(1) != 1:
+        raise _lib.PasstAmdError(f"{name}: d_o {tuple(d_o.shape)} {d_o.dtype} for {rows} rows of {H * 64} ({qkv.dtype}, "
+                                 f"do_compact={bool(do_compact)})")
+
+
+def attention_probs_grad(qkv, lse, d_o, B, H, N, scale, nq=None, head_mean=False, mode=ATTN_PGRAD_GRAD, do_compact=False, flags=0,
+                         out=None):
+    """The gradient with respect to the attention probabilities of the attention_fwd call on ``qkv``, from ``d_o``, the gradient of
+    that call's output (what attention_bwd reads): f32 (B, H, nq, N).  mode=ATTN_PGRAD_GRAD: the gradient itself, ``lse`` may be None.
+    mode=ATTN_PGRAD_CAM: max(probability * gradient, 0), with ``head_mean`` its mean over heads (B, 1, nq, N); ``lse`` as for
+    attention_probs.  d_o: [B*N][H*64] (token rows; only rows q < nq of a sequence are read), or with ``do_compact`` [B*nq][H*64].
+    out: an f32 tensor of that many elements to write instead of a fresh one (tests put guard rows behind it)."""
+    dtype = PA_DTYPE[qkv.dtype]
+    nq = N if nq is None else nq
+    Ho = 1 if head_mean else H
+    cam = mode == ATTN_PGRAD_CAM
+    if qkv.dim() != 2 or qkv.shape[0] != B * N or qkv.shape[1] != 3 * H * 64 or not 1 <= nq <= N or \
+            (lse is None if cam else head_mean) or (lse is not None and lse.numel() != B * H * nq):
+        raise _lib.PasstAmdError(f"attention_probs_grad: qkv {tuple(qkv.shape)}, lse {None if lse is None else tuple(lse.shape)}, "
+                                 f"B={B}, H={H}, N={N}, nq={nq}, mode={mode}, head_mean={head_mean}")
+    _pgrad_d_o("attention_probs_grad", d_o, qkv, H, B * N, B * nq, do_compact)
+    if out is None:
+        out = torch.empty((B, Ho, nq, N), device=qkv.device, dtype=torch.float32)
+    elif out.numel() != B * Ho * nq * N:
+        raise _lib.PasstAmdError(f"attention_probs_grad: out has {out.numel()} elements, expected {B * Ho * nq * N}")
+    _timed("attn_probs_grad", 4.0 * out.numel(),
+           lambda: check(_lib.load().pa_attention_probs_grad(_p(qkv, None, True), qkv.stride(0), None if lse is None else _p(lse, torch.float32),
+                                                             _p(d_o, qkv.dtype, True), d_o.stride(0), int(bool(do_compact)),
+                                                             _p(out, torch.float32), None, None, B, H, N, nq, int(bool(head_mean)),
+                                                             int(mode), scale, dtype, flags, _stream()), "pa_attention_probs_grad"))
+    return out.view(B, Ho, nq, N)
+
+
+def attention_probs_grad_varlen(qkv, lse, d_o, cu_tok, out_off, total_out, B, H, max_N, scale, nq=None, head_mean=False,
+                                mode=ATTN_PGRAD_GRAD, do_compact=False, flags=0, out=None):
+    """attention_probs_grad over packed sequences, in attention_probs_varlen's output layout: one flat f32 buffer of ``total_out``
+    elements, sequence b dense at out_off[b] as [H or 1][min(nq, N_b)][N_b].  d_o: [total][H*64] packed like qkv's rows, or with
+    ``do_compact`` (nq < max_N) [B*nq][H*64]."""
+    dtype = PA_DTYPE[qkv.dtype]
+    total = qkv.shape[0]
+    cam = mode == ATTN_PGRAD_CAM
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * H * 64 or cu_tok.dim() != 1 or cu_tok.numel() != B + 1 or not 1 <= max_N <= total or \
+            out_off.dim() != 1 or out_off.numel() != B or (lse is None if cam else head_mean):
+        raise _lib.PasstAmdError(f"attention_probs_grad_varlen: qkv {tuple(qkv.shape)}, cu_tok {tuple(cu_tok.shape)}, out_off "
+                                 f"{tuple(out_off.shape)}, B={B}, H={H}, max_N={max_N}, mode={mode}, head_mean={head_mean}")
+    if nq is None or nq >= max_N:
+        nq, nlse = max_N, H * total
+        if do_compact:
+            raise _lib.PasstAmdError("attention_probs_grad_varlen: do_compact needs nq < max_N")
+    else:
+        if nq < 1:
+            raise _lib.PasstAmdError("attention_probs_grad_varlen: nq must be >= 1")
+        nlse = B * H * nq
+    if lse is not None and lse.numel() != nlse:
+        raise _lib.PasstAmdError(f"attention_probs_grad_varlen: lse has {lse.numel()} elements, expected {nlse}")
+    _pgrad_d_o("attention_probs_grad_varlen", d_o, qkv, H, total, B * nq, do_compact)
+    if out is None:
+        out = torch.empty((total_out,), device=qkv.device, dtype=torch.float32)
+    elif out.numel() != total_out:
+        raise _lib.PasstAmdError(f"attention_probs_grad_varlen: out has {out.numel()} elements, expected {total_out}")
+    _timed("attn_probs_grad", 4.0 * total_out,
+           lambda: check(_lib.load().pa_attention_probs_grad(_p(qkv, None, True), qkv.stride(0), None if lse is None else _p(lse, torch.float32),
+                                                             _p(d_o, qkv.dtype, True), d_o.stride(0), int(bool(do_compact)),
+                                                             _p(out, torch.float32), _p(cu_tok, torch.int32), _p(out_off, torch.int64), B, H,
+                                                             max_N, nq, int(bool(head_mean)), int(mode), scale, dtype, flags, _stream()),
+                         "pa_attention_probs_grad"))
+    return out.view(-1)
+
+
 def attention_bwd(qkv, o, d_o, lse, B, H, N, scale, nq=None, flags=0):
     """dqkv [B*N][3D]; with nq < N (o, d_o, lse compact) the Q third is zero outside the first nq rows."""
     dtype = PA_DTYPE[qkv.dtype]

@@ -332,6 +332,12 @@ class _FixedLayout:
         p = ops.attention_probs(qkv, lse, self.B, H, self.Ntok, scale, nq=nq, head_mean=head_mean, flags=flags)
         return p.view(self.B, -1, self.Ntok) if head_mean else p
 
+    def attention_probs_grad(self, qkv, lse, d_att, H, scale, nq, head_mean, flags, mode, do_compact):
+        """The gradient of one attention map (ops.attention_probs_grad), in the map's own shape."""
+        p = ops.attention_probs_grad(qkv, lse, d_att, self.B, H, self.Ntok, scale, nq=nq, head_mean=head_mean, mode=mode,
+                                     do_compact=do_compact, flags=flags)
+        return p.view(self.B, -1, self.Ntok) if head_mean else p
+
 
 class _PackedLayout:
     """B clips of different token counts back to back: clip b owns rows cu_tok[b] .. cu_tok[b + 1] (device int32), none longer
@@ -359,14 +365,23 @@ class _PackedLayout:
         attention_fwd_varlen(nq=2) leaves it."""
         return lse.view(H, self.M).index_select(1, self.pidx).view(H, self.B, 2).permute(1, 0, 2).contiguous().view(-1)
 
-    def attention_probs(self, qkv, lse, H, scale, nq, head_mean, flags):
-        """One attention map of the packed batch as ONE flat f32 buffer (attn_views cuts it into the clips' tensors)."""
-        Ho = 1 if head_mean else H
+    def _map_offsets(self, Ho, nq, device):
         key = (Ho, nq)
         if key not in self._map_off:
             off, total = ops.attention_probs_offsets(self.ntok, Ho, nq)
-            self._map_off[key] = (ops.upload_small(off, qkv.device), total)
-        off_dev, total = self._map_off[key]
+            self._map_off[key] = (ops.upload_small(off, device), total)
+        return self._map_off[key]
+
+    def attention_probs_grad(self, qkv, lse, d_att, H, scale, nq, head_mean, flags, mode, do_compact):
+        """The gradient of one attention map of the packed batch as ONE flat f32 buffer, cut like the map (attn_views); the offsets
+        are the ones the map's own launch uploaded."""
+        off_dev, total = self._map_offsets(1 if head_mean else H, nq, qkv.device)
+        return ops.attention_probs_grad_varlen(qkv, lse, d_att, self.cu_tok, off_dev, total, self.B, H, self.max_N, scale, nq=nq,
+                                               head_mean=head_mean, mode=mode, do_compact=do_compact, flags=flags)
+
+    def attention_probs(self, qkv, lse, H, scale, nq, head_mean, flags):
+        """One attention map of the packed batch as ONE flat f32 buffer (attn_views cuts it into the clips' tensors)."""
+        off_dev, total = self._map_offsets(1 if head_mean else H, nq, qkv.device)
         return ops.attention_probs_varlen(qkv, lse, self.cu_tok, off_dev, total, self.B, H, self.max_N, scale, nq=nq,
                                           head_mean=head_mean, flags=flags)
 
@@ -432,6 +447,34 @@ def parse_attn(attn, nblk, attn_rows="all", attn_heads="each"):
             raise ValueError(f"attn: block {a!r} is named twice")
         out.append(k)
     return tuple(out), attn_rows == "prefix", attn_heads == "mean"
+
+
+def parse_attn_grad(attn_grad, attn, attn_heads="each"):
+    """``attn_grad=`` of PaSST.forward -> None, "grad" or "cam" (True means "grad").  ValueError for any other value, for a request
+    without ``attn=`` and for "grad" with ``attn_heads="mean"`` (the network never forms a mean over heads of the probabilities, so
+    there is no gradient with respect to one)."""
+    if attn_grad is None or attn_grad is False:
+        return None
+    mode = "grad" if attn_grad is True else attn_grad
+    if not isinstance(mode, str) or mode not in ("grad", "cam"):
+        raise ValueError(f"attn_grad must be None, \"grad\" (or True) or \"cam\", got {attn_grad!r}")
+    if attn is None:
+        raise ValueError("attn_grad needs attn=: it fills .grad of the attention maps that attn= returns")
+    if mode == "grad" and attn_heads == "mean":
+        raise ValueError("attn_grad=\"grad\" needs attn_heads=\"each\": the network forms no mean over heads, so nothing is the "
+                         "gradient with respect to one (attn_grad=\"cam\" gives the head mean of relu(map * gradient))")
+    return mode
+
+
+class _AttnGradRequest:
+    """What a call with ``attn_grad=`` hands the autograd node in the place of parse_attn's triple.  ``triple``: that triple (blocks,
+    prefix rows only?, mean over heads?); ``mode``: "grad" / "cam"; ``targets``: per requested block the tensor forward() returned
+    for it (packed: the list of the clips' tensors), put there by forward() once it has cut them; the backward fills their .grad
+    (_map_grad).  The maps have no grad_fn, so holding them makes no cycle."""
+    __slots__ = ("triple", "mode", "targets")
+
+    def __init__(self, triple, mode):
+        self.triple, self.mode, self.targets = triple, mode, None
 
 
 class _Fwd(NamedTuple):
@@ -893,6 +936,7 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
             ops.colsum_f32(part4[:, j, :], g[name])
     nblk = len(model.blocks)
     dh, tail = ctx.get("dhidden") or {}, ctx["tail"]
+    ag = ctx.get("attn_grad")               # the _AttnGradRequest of a forward run with attn_grad=, put there by the caller
     d_norm = None
     if "norm" in dh:
         # the final norm over ALL rows: its dgamma / dbeta add to what the head's own two rows per clip just gave norm.weight / norm.bias
@@ -934,13 +978,18 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
         wg.launch(dx_lp, att, g[pfx + "attn.proj.weight"], None)
         d_att = torch.empty_like(att)
         ops.gemm_nt(dx_lp, st.get(blk.attn.proj.weight, dt, True), dt, EPI_STORE, out_lp=d_att)
+        want_map_grad = ag is not None and i in ag.triple[0]       # the map's gradient: right behind the attention backward, from what it read
         if not prefix_tail:
             d_qkv = lay.attention_bwd(qkv, att, d_att, lse, H, ctx["scale"], flags=ops.ATTN_Q_PRESCALED)
+            if want_map_grad:
+                _map_grad(lay, ag, ag.triple[0].index(i), qkv, lse, d_att, H, ctx["scale"], False)
             dres = dx
         else:
             # only 2 queries per sequence carry a gradient (the Q third of d_qkv is zero elsewhere); the residual gradient lives
             # on the prefix rows only
             d_qkv = lay.attention_bwd(qkv, att, d_att, lse, H, ctx["scale"], nq=2, flags=ops.ATTN_Q_PRESCALED)
+            if want_map_grad:
+                _map_grad(lay, ag, ag.triple[0].index(i), qkv, lse, d_att, H, ctx["scale"], True)
             dres = ops.scatter_rows_into_zeros(dx, lay.prefix_rows(dx.device), lay.M)
         d_ln1 = torch.empty_like(ln1)
         ops.gemm_nt(d_qkv, st.get(blk.attn.qkv.weight, dt, True), dt, EPI_STORE, out_lp=d_ln1)
@@ -956,6 +1005,28 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
         # then reports the block complete, so its all-reduce bucket starts without stalling the main stream
         wg.launch(d_qkv, ln1, g[pfx + "attn.qkv.weight"], g[pfx + "attn.qkv.bias"], done=i)
     return dx, dx_lp
+
+
+def _map_grad(lay, ag, j, qkv, lse, d_att, H, scale, prefix_tail):
+    """.grad of the j-th requested attention map, from what its block's attention backward just read: the gradient with respect to
+    the probabilities ("grad") or relu(map * gradient) ("cam", with the head mean where the map has it), one pa_attention_probs_grad
+    launch.  Prefix rows below a prefix-only tail read the first two rows per clip of the token-row d_att and, for "cam", the lse cut
+    to those rows as the map's own launch had it; the prefix-only tail hands over its compact d_att and two-row lse as they are."""
+    _, aprefix, amean = ag.triple
+    cam = ag.mode == "cam"
+    if not cam:
+        lse = None
+    elif aprefix and not prefix_tail:
+        lse = lay.prefix_lse(lse, H)
+    g = lay.attention_probs_grad(qkv, lse, d_att, H, scale, 2 if aprefix else None, amean, ops.ATTN_Q_PRESCALED,
+                                 ops.ATTN_PGRAD_CAM if cam else ops.ATTN_PGRAD_GRAD, prefix_tail)
+    target = ag.targets[j]
+    if isinstance(target, list):            # packed: one flat buffer, cut like the map
+        tok = torch.tensor([0] + [t.shape[-1] for t in target]).cumsum(0)
+        for t, v in zip(target, _PackedLayout.attn_views(g, tok, H, aprefix, amean)):
+            t.grad = v
+    else:
+        target.grad = g
 
 
 def _patch_backward(model, ctx, wg, dx, dx_lp, want_dx):
@@ -1047,9 +1118,11 @@ class _PasstFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, lengths, hidden, attn, x, *params):
-        r = _run_forward(model, x, lengths, True, hidden=hidden, attn=attn)
+        req = attn if isinstance(attn, _AttnGradRequest) else None        # the maps' gradients were asked for as well
+        r = _run_forward(model, x, lengths, True, hidden=hidden, attn=attn if req is None else req.triple)
         ctx.mark_non_differentiable(*r.maps)            # the integer row offsets of the packed path are non-differentiable as they are
         ctx.model, ctx.c, ctx.varlen, ctx.hidden = model, r.ctx, lengths is not None, hidden
+        ctx.attn_grad = req
         # the input spectrogram's gradient is computed only when asked for; a graph none of whose parameters requires a gradient
         # (a frozen loss network) runs the backward without any weight-gradient work
         ctx.want_dx = bool(ctx.needs_input_grad[4])
@@ -1074,6 +1147,9 @@ class _PasstFunction(torch.autograd.Function):
         dhidden = {k: d.contiguous().view(c["lay"].M, -1) for k, d in zip(ctx.hidden or (), dhs) if d is not None}
         if dhidden:
             c["dhidden"] = dhidden
+        ag, ctx.attn_grad = ctx.attn_grad, None
+        if ag is not None and ag.targets is not None:
+            c["attn_grad"] = ag
         # gradient buffers for EVERY parameter the backward writes (all but head_dist.*): the kernel sequence produces
         # them all; parameters with requires_grad=False are simply not handed back to autograd (frozen backbone, ...)
         named, total = ctx.named, ctx.total
@@ -1121,6 +1197,12 @@ class _PasstFunction(torch.autograd.Function):
                 red.wait()              # also after an exception: no collective may stay in flight on a buffer we drop
             if dx is not None:
                 dx.mul_(float(red.world))       # not reduced: the gradient of THIS rank's loss (dlogits went in divided by world)
+            if ag is not None:
+                # so are the maps' gradients: d_att came down divided by world, "grad" is linear in it and relu(map * gradient)
+                # commutes with a positive factor.  One more f32 rounding than a single rank's unless world is a power of two.
+                for t in ag.targets:
+                    for u in (t if isinstance(t, list) else [t]):
+                        u.grad.mul_(float(red.world))
         else:
             dx = run_backward(model, c, dlogits, dfeat, grads, want_dx=ctx.want_dx)
         ctx.c = None
@@ -1345,7 +1427,7 @@ class PaSST(nn.Module):
         self._staged.epoch += 1
 
     @compile_opaque
-    def forward(self, x, lengths=None, hidden=None, attn=None, attn_rows="all", attn_heads="each"):
+    def forward(self, x, lengths=None, hidden=None, attn=None, attn_rows="all", attn_heads="each", attn_grad=None):
         """x: (B,1,F,T) -> (logits (B,C), features (B,D)); always a tuple (models/passt.py:588,595).  With the keywords below:
         ``(logits, features[, hidden][, attn][, tok_offsets])``, tok_offsets whenever ``lengths`` comes with ``hidden`` or ``attn``.
 
@@ -1381,6 +1463,19 @@ class PaSST(nn.Module):
         sums differently); the last block's ``"prefix"`` rows come from the prefix-only tail as it is.  A map costs its own bytes:
         B * H * Nq * Ntok * 4.  A bare int, an empty sequence, an index out of range or named twice, or another value of
         ``attn_rows`` / ``attn_heads`` raises ValueError before anything is launched or drawn.
+
+        ``attn_grad`` ("grad", "cam"; True means "grad"; needs ``attn``): the call returns exactly what it returns without it, and the
+        BACKWARD of this forward also fills ``.grad`` of every returned map tensor (None before it), same shape, f32.  "grad": the
+        gradient of the loss with respect to the block's attention probabilities -- what ``retain_grad()`` on the tensor a forward hook
+        on the reference's ``blocks[i].attn.attn_drop`` sees holds after ``loss.backward()``; it needs ``attn_heads="each"``, and
+        ``attn_rows="prefix"`` gives its cls / dist query rows.  "cam": relu(map * gradient), with ``attn_heads="mean"`` the mean over
+        heads of that, (B, Nq, Ntok): the factor of gradient-weighted attention rollout.  One launch per requested block right behind the
+        block's fused attention backward, from the qkv, row statistics and output gradient that one read; a gradient costs what its
+        map costs.  With ``lengths`` clip i's tensor gets a view of one flat buffer, what the clip gets alone at batch size 1.  Logits,
+        features, ``x.grad`` and every parameter gradient are bit for bit those of the call with ``attn`` alone.  The call must
+        record a graph: under ``torch.no_grad()``, or when nothing requires a gradient (with ``lengths``: without ``varlen_grad`` /
+        ``varlen_train``), it raises ValueError -- as do an unknown value, ``attn_grad`` without ``attn`` and "grad" with
+        ``attn_heads="mean"`` -- before anything is launched or drawn.  Not taken by TrainStep or captured graphs.
 
         An ``x`` that requires a gradient gets one (``x.grad`` / ``torch.autograd.grad``), as in the reference: PaSST as a
         differentiable loss network.  With every parameter frozen (``net.requires_grad_(False)``) this needs no switch and the backward
@@ -1431,6 +1526,7 @@ class PaSST(nn.Module):
             amap = None
         else:
             amap = parse_attn(attn, len(self.blocks), attn_rows, attn_heads)
+        agrad = parse_attn_grad(attn_grad, attn, attn_heads)
         train_ragged = lengths is not None and self.training
         if train_ragged and not getattr(self, "varlen_train", False):
             raise NotImplementedError("PaSST.forward(x, lengths=...): training on ragged batches is not supported (eval mode only; "
@@ -1452,6 +1548,11 @@ class PaSST(nn.Module):
             node = want_dx or any(p.requires_grad for _, p in named)
         else:
             node = False                                # the ragged forward records nothing unless asked to
+        if agrad is not None:
+            if not node:
+                raise ValueError("attn_grad: the gradients of the maps come out of a backward, and this call records no graph (nothing "
+                                 "requires a gradient, torch.no_grad() is active, or lengths= without net.varlen_grad / net.varlen_train)")
+            req = _AttnGradRequest(amap, agrad)
         if node:
             if want_dx:
                 # the kernels read a dense f32 spectrogram: the conversion happens where autograd sees it, so x.grad comes back in the
@@ -1465,14 +1566,17 @@ class PaSST(nn.Module):
                 fl = None
             # bound (same validated parameter list as at bind time): the single token stands for every parameter
             params = (fl["token"],) if fl is not None else [p for _, p in named]
-            r = _Fwd.from_flat(_PasstFunction.apply(self, lengths, hid, amap, x, *params), len(hid or ()), len(amap[0]) if amap else 0)
+            r = _Fwd.from_flat(_PasstFunction.apply(self, lengths, hid, amap if agrad is None else req, x, *params), len(hid or ()), len(amap[0]) if amap else 0)
         elif lengths is None and hid is None and amap is None:
             return passt_forward(self, x, save=False)[:2]       # the plain call stays on the public entry (callers stand in for it)
         else:
             # the ragged forward records nothing unless asked to; the fixed one leaves that to the caller's own grad mode
             with torch.no_grad() if lengths is not None else contextlib.nullcontext():
                 r = _run_forward(self, x, lengths, hidden=hid, attn=amap)
-        return self._outputs(r, hid, amap)
+        res = self._outputs(r, hid, amap)
+        if agrad is not None:
+            req.targets = list(res[2 if hid is None else 3])      # the tensors the caller holds: the backward fills their .grad
+        return res
 
     def _outputs(self, r, hid, amap):
         """A forward's record in forward()'s shape: (logits, features[, [token outputs]][, [attention maps]][, tok_offsets]); a packed
@@ -1578,12 +1682,15 @@ class EnsembelerModel(nn.Module):
         super().__init__()
         self.models = nn.ModuleList(models)
 
-    def forward(self, x, lengths=None, hidden=None, attn=None):
+    def forward(self, x, lengths=None, hidden=None, attn=None, attn_grad=None):
         """``lengths``: handed to every member (PaSST.forward's ragged-batch eval forward; gradients flow through the members that
         set ``varlen_grad``).  ``hidden`` and ``attn`` are not for an ensemble: its members have different depths, widths and heads."""
         if hidden is not None:
             raise ValueError("EnsembelerModel.forward: hidden= is not supported (the members' token sequences have different widths "
                              "and depths and cannot be averaged); call the member you want: model.models[i](x, hidden=...)")
+        if attn_grad is not None and attn_grad is not False:
+            raise ValueError("EnsembelerModel.forward: attn_grad= is not supported, as attn= is not; call the member you want: "
+                             "model.models[i](x, attn=..., attn_grad=...)")
         if attn is not None:
             raise ValueError("EnsembelerModel.forward: attn= is not supported (the members have different depths, heads and token "
                              "counts; their attention maps cannot be averaged); call the member you want: model.models[i](x, attn=...)")
