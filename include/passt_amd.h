@@ -444,6 +444,33 @@ int pa_attention_probs(const void* qkv, int ldqkv, const float* lse, float* out,
 int pa_attention_probs_grad(const void* qkv, int ldqkv, const float* lse, const void* d_o, int ldo, int do_compact, float* out,
                             const int32_t* cu_tok, const int64_t* out_off, int B, int H, int N /* max_N when cu_tok != NULL */, int nq,
                             int head_mean, int mode, float scale, int dtype, int flags, void* stream);
+/* One step of an attention rollout on nr row vectors per sequence, without the attention map (additive: the ABI version stays 6):
+ *   r_out[b][j][k] = a * r_in[b][j][k] + b_ * sum_{q < nq_b} r_in[b][j][q] * M_b[q][k]        j < nr, k < N_b
+ *   mode PA_ATTN_ROLLOUT_ATTN: M = (1/H) sum_h P_h                          P_h = softmax(q_h k_h^T * scale), formed from qkv and lse
+ *   mode PA_ATTN_ROLLOUT_CAM:  M = (1/H) sum_h max(P_h * (g_scale * G_h), 0)     G_h = d_o_h v_h^T
+ * Every (32 queries x 32 keys) tile of P is formed as pa_attention_probs forms it, of G as pa_attention_probs_grad forms it, the heads
+ * added in head order in f32 registers; the tile is multiplied by r_in's 32 entries and summed over its queries in registers, so no
+ * element of M reaches memory.  a = b_ = 0.5 is a step of attention rollout (Abnar & Zuidema), a = b_ = 1 with CAM a step of the
+ * gradient-weighted rollout (Chefer et al.); applied from the last block down to the first to one-hot start rows it gives those rows
+ * of the rolled-out matrix.  qkv, ldqkv, lse, nq, scale, dtype, flags mean what they mean for pa_attention_probs; d_o, ldo, do_compact
+ * what they mean for pa_attention_probs_grad (ATTN: d_o must be NULL, do_compact 0).  Query rows at or behind nq_b = min(nq, N_b)
+ * contribute exactly nothing, key columns at or behind N_b are neither summed nor written.
+ *   r_in, r_out: f32, nr * total_tok floats each that share no float (PA_EINVAL).  cu_tok == NULL: [B][nr][N], total_tok = B * N.  cu_tok != NULL: packed sequences as in
+ *     pa_attention_fwd_varlen, N = max_N, total_tok = cu_tok[B]; sequence b's block is (nr, N_b) at float offset nr * cu_tok[b].  No
+ *     row of a neighbour and none at or behind cu_tok[B] is read.  1 <= nr <= PA_ATTN_ROLLOUT_MAX_ROWS.
+ *   slices: 0 = the query tiles are cut into S slices chosen from B, N and the device's CU count; > 0 = that many (capped at the
+ *     number of query tiles; tests, A/B).  Each slice's partial rows go to `ws` and a finishing kernel adds them in slice order; S = 1
+ *     (always so for nq <= 32) finishes in the one launch.  ws: pa_attention_rollout_ws_floats(same arguments) floats, may be NULL
+ *     when that is 0.  No atomics: launches on the same inputs are bit-identical, and a sequence's result depends on its own inputs
+ *     and the number of query tiles per slice only. */
+#define PA_ATTN_ROLLOUT_ATTN 0
+#define PA_ATTN_ROLLOUT_CAM 1
+#define PA_ATTN_ROLLOUT_MAX_ROWS 4
+int64_t pa_attention_rollout_ws_floats(int64_t total_tok, int B, int N /* max_N when packed */, int nq, int nr, int slices);
+int pa_attention_rollout(const void* qkv, int ldqkv, const float* lse, const void* d_o, int ldo, int do_compact, const float* r_in,
+                         float* r_out, float* ws, const int32_t* cu_tok, int64_t total_tok, int B, int H,
+                         int N /* max_N when cu_tok != NULL */, int nq, int nr, int mode, int slices, float a, float b_, float g_scale,
+                         float scale, int dtype, int flags, void* stream);
 /* number of floats of pa_attention_bwd's `delta` workspace */
 int64_t pa_attention_bwd_ws_floats(int B, int H, int nq);
 /* dqkv[B*N][3*H*64] from d_o[B*nq][H*64]; lse from the forward; delta: f32 workspace of pa_attention_bwd_ws_floats()

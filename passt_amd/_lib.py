@@ -97,6 +97,9 @@ SIGNATURES = {
     "pa_attention_fwd_varlen": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp]),
     "pa_attention_probs": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp]),
     "pa_attention_probs_grad": (i32, [vp, i32, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp]),
+    "pa_attention_rollout_ws_floats": (i64, [i64, i32, i32, i32, i32, i32]),
+    "pa_attention_rollout": (i32, [vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, f32, f32, f32, f32,
+                                   i32, i32, vp]),
     "pa_attention_bwd_ws_floats": (i64, [i32, i32, i32]),
     "pa_attention_bwd": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp]),
     "pa_attention_bwd_varlen_ws_floats": (i64, [i64, i32, i32, i32]),

@@ -14,6 +14,9 @@
 // Key lanes at or behind N are masked to -inf BEFORE the exponential (exp2(0 - lse * log2 e) overflows for strongly negative
 // scores) and are never stored; rows are clamped to the sequence's own last query / key row, so the packed form reads no row of
 // a neighbour and none behind cu_tok[B].
+//
+// KEEP IN STEP: attn_probs_grad_kernel (attention_probs_grad.hip) and attn_rollout_kernel (attention_rollout.hip) form their probability tiles with a copy of this kernel's
+// arithmetic, operation for operation, and their tests rest on that: change it in all three files or in none.
 #include "pa_mma.h"
 
 namespace pa {

@@ -18,6 +18,9 @@
 // its output bytes in the per-head modes.
 // Rows are clamped to the sequence's own last query / key row, so the packed form reads no row of a neighbour and none behind
 // cu_tok[B]; key lanes at or behind N are never stored.
+//
+// KEEP IN STEP: attn_rollout_kernel (attention_rollout.hip) forms its tiles with a copy of this kernel's
+// arithmetic, operation for operation, and their tests rest on that: change it in all three files or in none.
 #include "pa_mma.h"
 
 namespace pa {

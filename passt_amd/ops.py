@@ -974,6 +974,91 @@ def attention_probs_grad_varlen(qkv, lse, d_o, cu_tok, out_off, total_out, B, H,
     return out.view(-1)
 
 
+ATTN_ROLLOUT_ATTN, ATTN_ROLLOUT_CAM = 0, 1     # include/passt_amd.h PA_ATTN_ROLLOUT_*
+ATTN_ROLLOUT_MAX_ROWS = 4                       # PA_ATTN_ROLLOUT_MAX_ROWS
+
+
+def _rollout_launch(name, qkv, lse, d_o, r_in, out, cu_tok, total, B, H, N, nq, nr, mode, slices, a, b, g_scale, scale, do_compact, flags):
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty_like(r_in)
+    elif out.shape != r_in.shape or out.dtype != torch.float32 or \
+            (out.data_ptr() < r_in.data_ptr() + r_in.numel() * 4 and r_in.data_ptr() < out.data_ptr() + out.numel() * 4):
+        raise _lib.PasstAmdError(f"{name}: out must be an f32 tensor of r_in's shape {tuple(r_in.shape)} that shares no byte with it, got "
+                                 f"{tuple(out.shape)} {out.dtype}")
+    need = lib.pa_attention_rollout_ws_floats(total, B, N, nq, nr, slices)
+    if need < 0:
+        check(int(need), "pa_attention_rollout_ws_floats")
+    ws = torch.empty(need, device=qkv.device, dtype=torch.float32) if need else None
+    _timed("attn_rollout", (8.0 if mode == ATTN_ROLLOUT_CAM else 4.0) * min(nq, N) * total * 64 * H,
+           lambda: check(lib.pa_attention_rollout(_p(qkv, None, True), qkv.stride(0), _p(lse, torch.float32),
+                                                  None if d_o is None else _p(d_o, qkv.dtype, True), 0 if d_o is None else d_o.stride(0),
+                                                  int(bool(do_compact)), _p(r_in, torch.float32), _p(out, torch.float32),
+                                                  _p(ws, torch.float32), None if cu_tok is None else _p(cu_tok, torch.int32), total, B, H,
+                                                  N, nq, nr, int(mode), int(slices), a, b, g_scale, scale, PA_DTYPE[qkv.dtype], flags,
+                                                  _stream()), "pa_attention_rollout"))
+    return out
+
+
+def attention_rollout(qkv, lse, r_in, B, H, N, scale, a, b, nq=None, d_o=None, mode=ATTN_ROLLOUT_ATTN, g_scale=1.0, do_compact=False,
+                      flags=0, slices=0, out=None):
+    """One rollout step on row vectors, without the attention map: out[b, j] = a * r_in[b, j] + b * (r_in[b, j, :nq] @ M_b), f32
+    (B, nr, N), with M the mean over heads of the attention probabilities of the attention_fwd call that made ``lse`` (same qkv, nq,
+    flags; mode=ATTN_ROLLOUT_ATTN) or of max(probability * g_scale * gradient, 0) (ATTN_ROLLOUT_CAM; ``d_o`` / ``do_compact`` as for
+    attention_probs_grad).  Query rows at or behind nq contribute nothing.  slices: 0 = the library cuts the query tiles by B, N and
+    the device's CU count, > 0 = that many slices (tests).  out: another f32 tensor of r_in's shape to write instead of a fresh one."""
+    nq = N if nq is None else nq
+    cam = mode == ATTN_ROLLOUT_CAM
+    if qkv.dim() != 2 or qkv.shape[0] != B * N or qkv.shape[1] != 3 * H * 64 or not 1 <= nq <= N or lse.numel() != B * H * nq or \
+            r_in.dim() != 3 or r_in.shape[0] != B or r_in.shape[2] != N or not 1 <= r_in.shape[1] <= ATTN_ROLLOUT_MAX_ROWS or \
+            (d_o is None) == cam or (do_compact and not cam):
+        raise _lib.PasstAmdError(f"attention_rollout: qkv {tuple(qkv.shape)}, lse {tuple(lse.shape)}, r_in {tuple(r_in.shape)}, B={B}, "
+                                 f"H={H}, N={N}, nq={nq}, mode={mode}, d_o {'given' if d_o is not None else 'missing'}")
+    if cam:
+        _pgrad_d_o("attention_rollout", d_o, qkv, H, B * N, B * nq, do_compact)
+    return _rollout_launch("attention_rollout", qkv, lse, d_o, r_in, out, None, B * N, B, H, N, nq, r_in.shape[1], mode, slices, a, b,
+                           g_scale, scale, do_compact, flags)
+
+
+def attention_rollout_varlen(qkv, lse, r_in, cu_tok, B, H, max_N, scale, a, b, nq=None, d_o=None, mode=ATTN_ROLLOUT_ATTN, g_scale=1.0,
+                             do_compact=False, flags=0, slices=0, out=None):
+    """attention_rollout over packed sequences (attention_fwd_varlen's qkv / cu_tok / lse for the same nq): r_in and the result are
+    f32 (nr, total) buffers read as one flat array in which sequence b's dense (nr, N_b) block starts at float nr * cu_tok[b] -- NOT
+    rows of length total (rollout_views cuts it).  Every sequence gets what attention_rollout gives it alone with the same number of
+    query tiles per slice."""
+    total = qkv.shape[0]
+    cam = mode == ATTN_ROLLOUT_CAM
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * H * 64 or cu_tok.dim() != 1 or cu_tok.numel() != B + 1 or not 1 <= max_N <= total or \
+            r_in.dim() != 2 or r_in.shape[1] != total or not 1 <= r_in.shape[0] <= ATTN_ROLLOUT_MAX_ROWS or (d_o is None) == cam or \
+            (do_compact and not cam):
+        raise _lib.PasstAmdError(f"attention_rollout_varlen: qkv {tuple(qkv.shape)}, cu_tok {tuple(cu_tok.shape)}, r_in {tuple(r_in.shape)}, "
+                                 f"B={B}, H={H}, max_N={max_N}, mode={mode}, d_o {'given' if d_o is not None else 'missing'}")
+    if nq is None or nq >= max_N:
+        nq, nlse = max_N, H * total
+        if do_compact:
+            raise _lib.PasstAmdError("attention_rollout_varlen: do_compact needs nq < max_N")
+    else:
+        if nq < 1:
+            raise _lib.PasstAmdError("attention_rollout_varlen: nq must be >= 1")
+        nlse = B * H * nq
+    if lse.numel() != nlse:
+        raise _lib.PasstAmdError(f"attention_rollout_varlen: lse has {lse.numel()} elements, expected {nlse}")
+    if cam:
+        _pgrad_d_o("attention_rollout_varlen", d_o, qkv, H, total, B * nq, do_compact)
+    return _rollout_launch("attention_rollout_varlen", qkv, lse, d_o, r_in, out, cu_tok, total, B, H, max_N, nq, r_in.shape[0], mode, slices,
+                           a, b, g_scale, scale, do_compact, flags)
+
+
+def rollout_views(r, ntok):
+    """The packed rollout buffer (nr, total) -> a list of views: sequence b's (nr, N_b)."""
+    nr, flat, out, o = r.shape[0], r.view(-1), [], 0
+    for n in ntok:
+        n = int(n)
+        out.append(flat[o:o + nr * n].view(nr, n))
+        o += nr * n
+    return out
+
+
 def attention_bwd(qkv, o, d_o, lse, B, H, N, scale, nq=None, flags=0):
     """dqkv [B*N][3D]; with nq < N (o, d_o, lse compact) the Q third is zero outside the first nq rows."""
     dtype = PA_DTYPE[qkv.dtype]

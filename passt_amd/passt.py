@@ -338,6 +338,17 @@ class _FixedLayout:
                                      do_compact=do_compact, flags=flags)
         return p.view(self.B, -1, self.Ntok) if head_mean else p
 
+    def rollout_start(self, device):
+        """The one-hot start rows of a rollout, (B, 2, Ntok) f32: row 0 = cls, row 1 = dist."""
+        r = torch.zeros((self.B, 2, self.Ntok), device=device, dtype=torch.float32)
+        r[:, 0, 0] = 1.0
+        r[:, 1, 1] = 1.0
+        return r
+
+    def attention_rollout(self, qkv, lse, r_in, H, scale, a, b, nq, flags, **kw):
+        """One rollout step on the (B, 2, Ntok) rows (ops.attention_rollout): no map is formed."""
+        return ops.attention_rollout(qkv, lse, r_in, self.B, H, self.Ntok, scale, a, b, nq=nq, flags=flags, **kw)
+
 
 class _PackedLayout:
     """B clips of different token counts back to back: clip b owns rows cu_tok[b] .. cu_tok[b + 1] (device int32), none longer
@@ -384,6 +395,24 @@ class _PackedLayout:
         off_dev, total = self._map_offsets(1 if head_mean else H, nq, qkv.device)
         return ops.attention_probs_varlen(qkv, lse, self.cu_tok, off_dev, total, self.B, H, self.max_N, scale, nq=nq,
                                           head_mean=head_mean, flags=flags)
+
+    def rollout_start(self, device):
+        """The one-hot start rows of a rollout as ONE f32 buffer (2, M): clip b's dense (2, N_b) block starts at float 2 * cu_tok[b]
+        (rollout_views cuts it); row 0 = cls, row 1 = dist."""
+        n = np.asarray(self.ntok, dtype=np.int64)
+        base = 2 * (np.cumsum(n) - n)
+        r = np.zeros((2, self.M), dtype=np.float32)
+        r.reshape(-1)[np.concatenate([base, base + n + 1])] = 1.0
+        return ops.upload_small(r, device)
+
+    def attention_rollout(self, qkv, lse, r_in, H, scale, a, b, nq, flags, **kw):
+        """One rollout step on the packed (2, M) buffer (ops.attention_rollout_varlen)."""
+        return ops.attention_rollout_varlen(qkv, lse, r_in, self.cu_tok, self.B, H, self.max_N, scale, a, b, nq=nq, flags=flags, **kw)
+
+    @staticmethod
+    def rollout_views(r, tok_offsets):
+        """The packed rollout buffer -> a list of B views: clip i's (2, N_i)."""
+        return ops.rollout_views(r, (tok_offsets[1:] - tok_offsets[:-1]).tolist())
 
     @staticmethod
     def attn_views(p, tok_offsets, H, prefix, head_mean):
@@ -466,6 +495,35 @@ def parse_attn_grad(attn_grad, attn, attn_heads="each"):
     return mode
 
 
+def parse_rollout(rollout, rollout_from, nblk):
+    """``rollout=`` / ``rollout_from=`` of PaSST.forward -> None or (mode, first block in [0, nblk)).  ValueError for any value other
+    than None, "attn", "cam", for a ``rollout_from`` that is no int or out of range, and for one without ``rollout``."""
+    if rollout is not None and (not isinstance(rollout, str) or rollout not in ("attn", "cam")):
+        raise ValueError(f"rollout must be None, \"attn\" or \"cam\", got {rollout!r}")
+    if not isinstance(rollout_from, (int, np.integer)) or isinstance(rollout_from, (bool, np.bool_)):
+        raise ValueError(f"rollout_from must be a block index (an int), got {rollout_from!r}")
+    k = int(rollout_from)
+    if not -nblk <= k < nblk:
+        raise ValueError(f"rollout_from: block index {k} is out of range for {nblk} blocks")
+    if rollout is None:
+        if k != 0:
+            raise ValueError("rollout_from needs rollout=: it names the first block of the rollout that rollout= asks for")
+        return None
+    return rollout, k % nblk
+
+
+class _RolloutRequest:
+    """What a call with ``rollout="cam"`` hands the autograd node in the place of parse_rollout's pair.  ``first``: the first block of
+    the product; ``start``: the one-hot start rows the forward made (the node's own tensor); ``target``: the tensor forward() returned
+    for them (packed: the list of the clips' views), put there by forward(): the backward fills its .grad with the rolled-out rows;
+    ``g_scale``: what the backward multiplies the maps' gradients by (the world size under an attached reducer, whose node divides
+    dlogits by it: the product of (I + C_l) is not linear in that factor, so it cannot be repaired afterwards)."""
+    __slots__ = ("first", "start", "target", "g_scale", "result")
+
+    def __init__(self, first):
+        self.first, self.start, self.target, self.g_scale, self.result = first, None, None, 1.0, None
+
+
 class _AttnGradRequest:
     """What a call with ``attn_grad=`` hands the autograd node in the place of parse_attn's triple.  ``triple``: that triple (blocks,
     prefix rows only?, mean over heads?); ``mode``: "grad" / "cam"; ``targets``: per requested block the tensor forward() returned
@@ -489,18 +547,22 @@ class _Fwd(NamedTuple):
     hidden: tuple = ()
     maps: tuple = ()
     tok_offsets: Optional[torch.Tensor] = None
+    roll: Optional[torch.Tensor] = None      # rollout=: the cls / dist rows, (B, 2, Ntok); packed: one (2, M) buffer (rollout_views cuts it)
 
     def flat(self):
         """The tensors in the order the autograd node hands them out (and from_flat reads them back)."""
-        return (self.logits, self.feat) + self.hidden + self.maps + (() if self.tok_offsets is None else (self.tok_offsets,))
+        return (self.logits, self.feat) + self.hidden + self.maps + (() if self.roll is None else (self.roll,)) + \
+            (() if self.tok_offsets is None else (self.tok_offsets,))
 
     @classmethod
-    def from_flat(cls, out, n_hidden, n_maps):
+    def from_flat(cls, out, n_hidden, n_maps, has_roll=False):
         it = iter(out)
-        return cls(next(it), next(it), None, tuple(islice(it, n_hidden)), tuple(islice(it, n_maps)), next(it, None))
+        logits, feat, hidden, maps = next(it), next(it), tuple(islice(it, n_hidden)), tuple(islice(it, n_maps))
+        roll = next(it) if has_roll else None
+        return cls(logits, feat, None, hidden, maps, next(it, None), roll)
 
 
-def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None):
+def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, rollout=None):
     """Token matrix xs [M][D] f32 in layout ``lay`` -> blocks -> tail -> head.  Returns a _Fwd (tok_offsets left to the caller); ctx
     (``save`` only) is what _backward_trunk needs plus ``patch``, the entry path's own state for its patch-stage backward.
     ``hidden`` (parse_hidden's tuple or None): the token outputs to hand out, in that order -- a block's output is the f32
@@ -509,7 +571,12 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None):
     ``attn`` (parse_attn's triple or None): the attention maps to hand out, in the order asked (layout's
     attention_probs: a shaped tensor, or the packed batch's flat buffer) -- made right behind the block's attention launch from the
     qkv and lse it used.  All rows of the last block's map need the FULL TAIL too; its prefix rows come from the prefix-only tail's
-    own compact lse, and the tail is unchanged."""
+    own compact lse, and the tail is unchanged.
+    ``rollout`` (parse_rollout's pair, a _RolloutRequest, or None): "attn" keeps (qkv, lse) of the blocks from its first one on for the
+    duration of the call and, behind the last block, runs the chain r <- 0.5 r + 0.5 r A_l from the one-hot cls / dist rows, last block
+    first, one pa_attention_rollout step per block; the prefix-only tail's block enters with its two query rows and its own two-row
+    lse, which is exact because the start rows are one-hot in the prefix.  A _RolloutRequest ("cam") only gets its start rows here: the
+    chain rides with the backward (_backward_trunk)."""
     st = model._staged
     D, H = model.embed_dim, model.num_heads
     scale = (D // H) ** -0.5
@@ -520,6 +587,8 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None):
     amaps, aprefix, amean = attn or ((), False, False)
     full_tail = (nblk - 1) in want or "norm" in want or ((nblk - 1) in amaps and not aprefix)
     outs, maps = {}, {}
+    roll_first = nblk if rollout is None or isinstance(rollout, _RolloutRequest) else rollout[1]
+    roll_keep = []                          # (qkv, lse, query rows) of the blocks an "attn" rollout multiplies through
     for bi, blk in enumerate(model.blocks):
         last = bi == nblk - 1
         ln1, mean1, rstd1 = ops.layernorm_fwd(xs, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt, save)
@@ -543,6 +612,8 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None):
             x_res = ops.gather_rows(xs, pidx)
             if bi in amaps:                 # aprefix: the two rows this launch produced
                 maps[bi] = lay.attention_probs(qkv, lse, H, scale, 2, amean, aflags)
+        if bi >= roll_first:
+            roll_keep.append((qkv, lse, None if (not last or full_tail) else 2))
         x_mid = ops.linear_resid(att, st.get(blk.attn.proj.weight, dt, False), blk.attn.proj.bias, x_res, dt)
         ln2, mean2, rstd2 = ops.layernorm_fwd(x_mid, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, save)
         h_pre, h_act = ops.linear_gelu(ln2, st.get(blk.mlp.fc1.weight, dt, False), blk.mlp.fc1.bias, dt)
@@ -566,9 +637,17 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None):
     feat, hn, stats = ops.head_pre_fwd(xl, model.norm.weight, model.norm.bias, model.norm.eps, model.head[0].weight,
                                        model.head[0].bias, model.head[0].eps)
     logits = ops.linear_f32_fwd(hn, model.head[1].weight, model.head[1].bias)
+    roll = None
+    if rollout is not None:
+        roll = lay.rollout_start(xs.device)
+        if isinstance(rollout, _RolloutRequest):
+            rollout.start = roll
+        while roll_keep:                    # later blocks on the left: the row vectors meet the last block first
+            qkv, lse, nq = roll_keep.pop()
+            roll = lay.attention_rollout(qkv, lse, roll, H, scale, 0.5, 0.5, nq, aflags)
     # tail: None = the prefix-only tail; else the full tail's own state (the last block's output, the final norm's row statistics)
     ctx = dict(dt=dt, lay=lay, scale=scale, saved=saved, xl=xl, feat=feat, hn=hn, stats=stats, patch=patch, tail=tail) if save else None
-    return _Fwd(logits, feat, ctx, tuple(lay.hidden_view(outs[k]) for k in want), tuple(maps[k] for k in amaps))
+    return _Fwd(logits, feat, ctx, tuple(lay.hidden_view(outs[k]) for k in want), tuple(maps[k] for k in amaps), roll=roll)
 
 
 def patchout_draws(model, x_shape):
@@ -599,16 +678,16 @@ def passt_forward(model, x, save, draws=None, hidden=None, attn=None):
     return out if attn is None else out + (list(r.maps),)
 
 
-def _run_forward(model, x, lengths=None, save=False, draws=None, hidden=None, attn=None):
+def _run_forward(model, x, lengths=None, save=False, draws=None, hidden=None, attn=None, rollout=None):
     """The one way into the kernel sequence of a forward: the fixed path, or with ``lengths`` the packed one, under this model's GEMM
     flags.  Returns the _Fwd."""
     with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
         if lengths is None:
-            return _passt_forward(model, x, save, draws, hidden, attn)
-        return _passt_forward_varlen(model, x, lengths, save, hidden, attn)
+            return _passt_forward(model, x, save, draws, hidden, attn, rollout)
+        return _passt_forward_varlen(model, x, lengths, save, hidden, attn, rollout)
 
 
-def _passt_forward(model, x, save, draws=None, hidden=None, attn=None):
+def _passt_forward(model, x, save, draws=None, hidden=None, attn=None, rollout=None):
     x, dt = _checked_input(model, x, True)
     B, Cin, F, T = x.shape
     P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
@@ -631,7 +710,7 @@ def _passt_forward(model, x, save, draws=None, hidden=None, attn=None):
                 row_mod=Np, out_batch_rows=Ntok, out_row_off=2)
     # pt_grid: the kept patches' own grid columns (pt may carry the time-positional offset); F, T: the input gradient's shape
     patch = dict(Np=Np, pf=pf, pt=pt_pos, pt_grid=pt, toff=toff, F=F, T=T, cols=cols) if save else None
-    return _forward_trunk(model, _FixedLayout(model, B, Ntok), tok.view(B * Ntok, D), dt, save, patch, hidden, attn)
+    return _forward_trunk(model, _FixedLayout(model, B, Ntok), tok.view(B * Ntok, D), dt, save, patch, hidden, attn, rollout)
 
 
 # --------------------------------------------------------------------------------------------
@@ -759,7 +838,7 @@ def _upload_parts(parts, device):
     return {name: v.view(a.shape) for (name, a), v in zip(parts.items(), views)}
 
 
-def _passt_forward_varlen(model, x, lengths, save=False, hidden=None, attn=None):
+def _passt_forward_varlen(model, x, lengths, save=False, hidden=None, attn=None, rollout=None):
     x, dt = _checked_input(model, x, save)
     if torch.is_tensor(lengths):
         if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
@@ -797,9 +876,9 @@ def _passt_forward_varlen(model, x, lengths, save=False, hidden=None, attn=None)
     patch = dict(F=F, T=T, cols=cols) if save else None
     if save and train:
         patch.update(slot=d["slot"], toff=d["toff"])   # Patchout: the patch-stage backward finds a row's grid position through the table
-    tok_offsets = torch.from_numpy(cu.astype(np.int64)) if (hidden is not None or attn is not None) else None
+    tok_offsets = torch.from_numpy(cu.astype(np.int64)) if (hidden is not None or attn is not None or rollout is not None) else None
     lay = _PackedLayout(B, M, g["max_N"], d["cu_tok"], d["pidx"], ntok=np.diff(cu))
-    return _forward_trunk(model, lay, xs, dt, save, patch, hidden, attn)._replace(tok_offsets=tok_offsets)
+    return _forward_trunk(model, lay, xs, dt, save, patch, hidden, attn, rollout)._replace(tok_offsets=tok_offsets)
 
 
 class _NoRowJobs(list):
@@ -937,6 +1016,8 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
     nblk = len(model.blocks)
     dh, tail = ctx.get("dhidden") or {}, ctx["tail"]
     ag = ctx.get("attn_grad")               # the _AttnGradRequest of a forward run with attn_grad=, put there by the caller
+    rr = ctx.get("rollout")                 # the _RolloutRequest of a forward run with rollout="cam", put there by the caller
+    roll = None if rr is None else rr.start
     d_norm = None
     if "norm" in dh:
         # the final norm over ALL rows: its dgamma / dbeta add to what the head's own two rows per clip just gave norm.weight / norm.bias
@@ -983,6 +1064,8 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
             d_qkv = lay.attention_bwd(qkv, att, d_att, lse, H, ctx["scale"], flags=ops.ATTN_Q_PRESCALED)
             if want_map_grad:
                 _map_grad(lay, ag, ag.triple[0].index(i), qkv, lse, d_att, H, ctx["scale"], False)
+            if rr is not None and i >= rr.first:
+                roll = _rollout_cam_step(lay, rr, roll, qkv, lse, d_att, H, ctx["scale"], False)
             dres = dx
         else:
             # only 2 queries per sequence carry a gradient (the Q third of d_qkv is zero elsewhere); the residual gradient lives
@@ -990,6 +1073,8 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
             d_qkv = lay.attention_bwd(qkv, att, d_att, lse, H, ctx["scale"], nq=2, flags=ops.ATTN_Q_PRESCALED)
             if want_map_grad:
                 _map_grad(lay, ag, ag.triple[0].index(i), qkv, lse, d_att, H, ctx["scale"], True)
+            if rr is not None and i >= rr.first:
+                roll = _rollout_cam_step(lay, rr, roll, qkv, lse, d_att, H, ctx["scale"], True)
             dres = ops.scatter_rows_into_zeros(dx, lay.prefix_rows(dx.device), lay.M)
         d_ln1 = torch.empty_like(ln1)
         ops.gemm_nt(d_qkv, st.get(blk.attn.qkv.weight, dt, True), dt, EPI_STORE, out_lp=d_ln1)
@@ -1004,7 +1089,17 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
         # last weight gradient of the block; the side stream (ordered after the LayerNorm gradients above)
         # then reports the block complete, so its all-reduce bucket starts without stalling the main stream
         wg.launch(d_qkv, ln1, g[pfx + "attn.qkv.weight"], g[pfx + "attn.qkv.bias"], done=i)
+    if rr is not None:
+        rr.result = roll
     return dx, dx_lp
+
+
+def _rollout_cam_step(lay, rr, roll, qkv, lse, d_att, H, scale, prefix_tail):
+    """One step r <- r + r mean_h relu(A_l * dA_l) of the gradient-weighted rollout, from what the block's attention backward just
+    read (one pa_attention_rollout launch in CAM mode; no map and no gradient of one is formed).  The prefix-only tail hands over its
+    compact d_att and two-row lse with nq = 2: only its cls / dist query rows carry a gradient, and the rows are one-hot there."""
+    return lay.attention_rollout(qkv, lse, roll, H, scale, 1.0, 1.0, 2 if prefix_tail else None, ops.ATTN_Q_PRESCALED, d_o=d_att,
+                                 mode=ops.ATTN_ROLLOUT_CAM, g_scale=rr.g_scale, do_compact=prefix_tail)
 
 
 def _map_grad(lay, ag, j, qkv, lse, d_att, H, scale, prefix_tail):
@@ -1117,16 +1212,18 @@ class _PasstFunction(torch.autograd.Function):
     non-differentiable (on the packed path one flat buffer per map); the backward ignores their (None) gradients."""
 
     @staticmethod
-    def forward(ctx, model, lengths, hidden, attn, x, *params):
+    def forward(ctx, model, lengths, hidden, attn, rollout, x, *params):
         req = attn if isinstance(attn, _AttnGradRequest) else None        # the maps' gradients were asked for as well
-        r = _run_forward(model, x, lengths, True, hidden=hidden, attn=attn if req is None else req.triple)
-        ctx.mark_non_differentiable(*r.maps)            # the integer row offsets of the packed path are non-differentiable as they are
+        r = _run_forward(model, x, lengths, True, hidden=hidden, attn=attn if req is None else req.triple, rollout=rollout)
+        # the integer row offsets of the packed path are non-differentiable as they are
+        ctx.mark_non_differentiable(*r.maps, *(() if r.roll is None else (r.roll,)))
+        ctx.rollout = rollout if isinstance(rollout, _RolloutRequest) else None   # "cam": the backward runs the chain
         ctx.model, ctx.c, ctx.varlen, ctx.hidden = model, r.ctx, lengths is not None, hidden
         ctx.attn_grad = req
         # the input spectrogram's gradient is computed only when asked for; a graph none of whose parameters requires a gradient
         # (a frozen loss network) runs the backward without any weight-gradient work
-        ctx.want_dx = bool(ctx.needs_input_grad[4])
-        ctx.frozen = not any(ctx.needs_input_grad[5:])
+        ctx.want_dx = bool(ctx.needs_input_grad[5])
+        ctx.frozen = not any(ctx.needs_input_grad[6:])
         ctx.named, ctx.total = model._graph_params(validate=False)     # the list forward() just handed to apply()
         # bound to a passt_amd.optim.AdamW (PaSST.bind_flat_grads): the only input is a token; the backward writes the gradients
         # straight into the optimizer's persistent flat buffer -- p.grad are views of it -- and hands autograd nothing
@@ -1141,7 +1238,7 @@ class _PasstFunction(torch.autograd.Function):
             raise RuntimeError("passt_amd.PaSST: the saved activations of this forward were already consumed by a backward "
                                "pass (retain_graph / double backward are not supported: run the forward again)")
         run_backward = passt_backward_varlen if ctx.varlen else passt_backward
-        lead = (None, None, None, None)         # the model, the lengths, the hidden request, the attention-map request
+        lead = (None, None, None, None, None)   # the model, the lengths, the hidden request, the attention-map request, the rollout request
         dev = c["feat"].device
         # gradients of the token outputs that fed the loss, as [M][D] rows (an unused one arrives as None and costs nothing)
         dhidden = {k: d.contiguous().view(c["lay"].M, -1) for k, d in zip(ctx.hidden or (), dhs) if d is not None}
@@ -1150,6 +1247,11 @@ class _PasstFunction(torch.autograd.Function):
         ag, ctx.attn_grad = ctx.attn_grad, None
         if ag is not None and ag.targets is not None:
             c["attn_grad"] = ag
+        rr, ctx.rollout = ctx.rollout, None
+        if rr is not None and rr.target is not None:
+            red = getattr(model, "_ddp", None)
+            rr.g_scale = float(red.world) if (red is not None and red.world > 1 and not ctx.frozen) else 1.0
+            c["rollout"] = rr
         # gradient buffers for EVERY parameter the backward writes (all but head_dist.*): the kernel sequence produces
         # them all; parameters with requires_grad=False are simply not handed back to autograd (frozen backbone, ...)
         named, total = ctx.named, ctx.total
@@ -1163,6 +1265,7 @@ class _PasstFunction(torch.autograd.Function):
                 dlogits = torch.zeros((B, model.num_classes), device=dev, dtype=torch.float32)
             dx = run_backward(model, c, dlogits, None if dfeat is None else dfeat.contiguous(), None, want_dx=ctx.want_dx)
             ctx.c = None
+            _fill_rollout_grad(rr)
             return lead + (dx,) + (None,) * (len(named) if fl is None else 1)
         if fl is not None and fl["fresh"]:
             flat, grads = fl["flat_g"], fl["grads"]     # overwritten in place: the caller zeroed (optimizer.zero_grad()) since the last backward
@@ -1206,6 +1309,7 @@ class _PasstFunction(torch.autograd.Function):
         else:
             dx = run_backward(model, c, dlogits, dfeat, grads, want_dx=ctx.want_dx)
         ctx.c = None
+        _fill_rollout_grad(rr)
         if fl is not None:
             if not fl["fresh"]:                 # a second backward without zero_grad (gradient accumulation): add, as AccumulateGrad would
                 fl["flat_g"].add_(flat)
@@ -1215,6 +1319,19 @@ class _PasstFunction(torch.autograd.Function):
         for n, p in named:                      # the same list, in the same order, as PaSST.forward handed to apply()
             out.append(grads[n] if p.requires_grad else None)
         return tuple(out)
+
+
+def _fill_rollout_grad(rr):
+    """.grad of what a ``rollout="cam"`` forward returned: the rows the backward's chain ended on (packed: every clip's view gets its
+    own view of the one buffer)."""
+    if rr is None or rr.target is None or rr.result is None:
+        return
+    if isinstance(rr.target, list):
+        for t, v in zip(rr.target, ops.rollout_views(rr.result, [t.shape[-1] for t in rr.target])):
+            t.grad = v
+    else:
+        rr.target.grad = rr.result
+    rr.result = rr.start = None
 
 
 def _tree_signature(root):
@@ -1427,9 +1544,11 @@ class PaSST(nn.Module):
         self._staged.epoch += 1
 
     @compile_opaque
-    def forward(self, x, lengths=None, hidden=None, attn=None, attn_rows="all", attn_heads="each", attn_grad=None):
+    def forward(self, x, lengths=None, hidden=None, attn=None, attn_rows="all", attn_heads="each", attn_grad=None, rollout=None,
+                rollout_from=0):
         """x: (B,1,F,T) -> (logits (B,C), features (B,D)); always a tuple (models/passt.py:588,595).  With the keywords below:
-        ``(logits, features[, hidden][, attn][, tok_offsets])``, tok_offsets whenever ``lengths`` comes with ``hidden`` or ``attn``.
+        ``(logits, features[, hidden][, attn][, roll][, tok_offsets])``, tok_offsets whenever ``lengths`` comes with ``hidden``, ``attn``
+        or ``rollout``.
 
         ``hidden`` (a list / tuple of block indices, negative allowed, and / or the string "norm"): also return the token sequence
         at those depths, ``(logits, features, hidden)`` -- with ``lengths``: ``(logits, features, hidden, tok_offsets)`` -- where
@@ -1476,6 +1595,21 @@ class PaSST(nn.Module):
         record a graph: under ``torch.no_grad()``, or when nothing requires a gradient (with ``lengths``: without ``varlen_grad`` /
         ``varlen_train``), it raises ValueError -- as do an unknown value, ``attn_grad`` without ``attn`` and "grad" with
         ``attn_heads="mean"`` -- before anything is launched or drawn.  Not taken by TrainStep or captured graphs.
+
+        ``rollout`` ("attn", "cam") with ``rollout_from`` (a block index k, negative allowed; default 0): also return ``roll``, the cls
+        and dist ROWS of an attention rollout through blocks k .. depth-1, f32 (B, 2, Ntok) -- row 0 the cls row, row 1 the dist row,
+        columns in ``hidden``'s token order -- without forming a single attention map: a row of a product of matrices is a chain of
+        row-vector x matrix products, and every product is taken tile by tile in registers (pa_attention_rollout), one launch per
+        block.  With ``lengths``: a list of B views (2, N_i) of one buffer, and ``tok_offsets`` is returned.  "attn": the rows of
+        prod_{l = depth-1 .. k} (0.5 mean_h A_l + 0.5 I), later blocks on the left (attention rollout, Abnar & Zuidema; its rows
+        already sum to 1); computed behind the last block, in eval and train mode (kept patches), with or without a graph; no grad_fn.
+        "cam": the forward launches nothing more and ``roll`` holds the one-hot start rows; the BACKWARD of this forward fills
+        ``roll.grad`` (ragged: every view's) with the rows of prod_{l = depth-1 .. k} (I + mean_h relu(A_l * dA_l)) (gradient-weighted
+        rollout, Chefer et al.), one launch right behind every block's attention backward.  "cam" must record a graph under
+        ``attn_grad``'s rules and raises its ValueErrors; under ``passt_amd.ddp.attach`` the rows are this rank's own.  Independent
+        of ``attn`` / ``attn_grad``; everything else the call returns or accumulates is bit for bit what it is without ``rollout``.
+        Any other value, a ``rollout_from`` that is no int or out of range, or one without ``rollout`` raises ValueError before
+        anything is launched or drawn.  Not taken by TrainStep or captured graphs.
 
         An ``x`` that requires a gradient gets one (``x.grad`` / ``torch.autograd.grad``), as in the reference: PaSST as a
         differentiable loss network.  With every parameter frozen (``net.requires_grad_(False)``) this needs no switch and the backward
@@ -1527,6 +1661,7 @@ class PaSST(nn.Module):
         else:
             amap = parse_attn(attn, len(self.blocks), attn_rows, attn_heads)
         agrad = parse_attn_grad(attn_grad, attn, attn_heads)
+        roll = parse_rollout(rollout, rollout_from, len(self.blocks))
         train_ragged = lengths is not None and self.training
         if train_ragged and not getattr(self, "varlen_train", False):
             raise NotImplementedError("PaSST.forward(x, lengths=...): training on ragged batches is not supported (eval mode only; "
@@ -1553,6 +1688,11 @@ class PaSST(nn.Module):
                 raise ValueError("attn_grad: the gradients of the maps come out of a backward, and this call records no graph (nothing "
                                  "requires a gradient, torch.no_grad() is active, or lengths= without net.varlen_grad / net.varlen_train)")
             req = _AttnGradRequest(amap, agrad)
+        if roll is not None and roll[0] == "cam":
+            if not node:
+                raise ValueError("rollout=\"cam\": the rows come out of a backward, and this call records no graph (nothing requires a "
+                                 "gradient, torch.no_grad() is active, or lengths= without net.varlen_grad / net.varlen_train)")
+            roll = _RolloutRequest(roll[1])
         if node:
             if want_dx:
                 # the kernels read a dense f32 spectrogram: the conversion happens where autograd sees it, so x.grad comes back in the
@@ -1566,16 +1706,19 @@ class PaSST(nn.Module):
                 fl = None
             # bound (same validated parameter list as at bind time): the single token stands for every parameter
             params = (fl["token"],) if fl is not None else [p for _, p in named]
-            r = _Fwd.from_flat(_PasstFunction.apply(self, lengths, hid, amap if agrad is None else req, x, *params), len(hid or ()), len(amap[0]) if amap else 0)
-        elif lengths is None and hid is None and amap is None:
+            r = _Fwd.from_flat(_PasstFunction.apply(self, lengths, hid, amap if agrad is None else req, roll, x, *params), len(hid or ()),
+                               len(amap[0]) if amap else 0, roll is not None)
+        elif lengths is None and hid is None and amap is None and roll is None:
             return passt_forward(self, x, save=False)[:2]       # the plain call stays on the public entry (callers stand in for it)
         else:
             # the ragged forward records nothing unless asked to; the fixed one leaves that to the caller's own grad mode
             with torch.no_grad() if lengths is not None else contextlib.nullcontext():
-                r = _run_forward(self, x, lengths, hidden=hid, attn=amap)
+                r = _run_forward(self, x, lengths, hidden=hid, attn=amap, rollout=roll)
         res = self._outputs(r, hid, amap)
         if agrad is not None:
             req.targets = list(res[2 if hid is None else 3])      # the tensors the caller holds: the backward fills their .grad
+        if isinstance(roll, _RolloutRequest):
+            roll.target = res[2 + (hid is not None) + (amap is not None)]
         return res
 
     def _outputs(self, r, hid, amap):
@@ -1587,6 +1730,8 @@ class PaSST(nn.Module):
         if amap is not None:
             res += ([m if r.tok_offsets is None else _PackedLayout.attn_views(m, r.tok_offsets, self.num_heads, amap[1], amap[2])
                      for m in r.maps],)
+        if r.roll is not None:
+            res += (r.roll if r.tok_offsets is None else _PackedLayout.rollout_views(r.roll, r.tok_offsets),)
         return res if r.tok_offsets is None else res + (r.tok_offsets,)
 
 
@@ -1682,12 +1827,15 @@ class EnsembelerModel(nn.Module):
         super().__init__()
         self.models = nn.ModuleList(models)
 
-    def forward(self, x, lengths=None, hidden=None, attn=None, attn_grad=None):
+    def forward(self, x, lengths=None, hidden=None, attn=None, attn_grad=None, rollout=None, rollout_from=0):
         """``lengths``: handed to every member (PaSST.forward's ragged-batch eval forward; gradients flow through the members that
         set ``varlen_grad``).  ``hidden`` and ``attn`` are not for an ensemble: its members have different depths, widths and heads."""
         if hidden is not None:
             raise ValueError("EnsembelerModel.forward: hidden= is not supported (the members' token sequences have different widths "
                              "and depths and cannot be averaged); call the member you want: model.models[i](x, hidden=...)")
+        if rollout is not None or rollout_from != 0:
+            raise ValueError("EnsembelerModel.forward: rollout= is not supported, as attn= is not; call the member you want: "
+                             "model.models[i](x, rollout=...)")
         if attn_grad is not None and attn_grad is not False:
             raise ValueError("EnsembelerModel.forward: attn_grad= is not supported, as attn= is not; call the member you want: "
                              "model.models[i](x, attn=..., attn_grad=...)")
