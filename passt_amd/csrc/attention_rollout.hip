@@ -6,9 +6,8 @@
 // entries and sums over the queries.  What reaches memory is nr * N floats per sequence instead of N * N.
 //
 // Decomposition.  One wave owns 32 consecutive KEYS (col = lane & 31, as in the sibling kernels) and walks a SLICE of the query tiles;
-// per tile the head loop adds the H tiles in head order in f32 registers (the CAM / head_mean instance of attn_probs_grad_kernel,
-// operation for operation: same PRE handling, hi + lo lse * log2 e, key lanes at or behind N masked before the exponential, the four
-// short f32 chains), then for every row vector j
+// per tile the head loop adds the H tiles in head order in f32 registers (what the head_mean instances of the sibling kernels add:
+// all three take the probability tile and the chained product from pa_attn_tile.h), then for every row vector j
 //   t = sum over the 16 accumulator registers of acc[i] * r[j][row(i)]      (one fma chain, register order)
 //   t += the other lane half's t                                              (rows 4..7, 12..15, ... live there)
 //   part[j] += t                                                              (tiles of the slice in ascending order)
@@ -25,24 +24,15 @@
 //   ATTN  bf16 187 / 205 | 175 / 193     f32 244 / 246 | 232 / 234
 //   CAM   bf16 230 / 232 | 218 / 220     f32 236 / 238 | 254 / 256
 // no scratch and no AGPRs in any instance; every instance runs at 2 waves per SIMD (the finishing kernel: 10 VGPRs, 8 waves).  The
-// sibling kernels need 116 (bf16 probabilities) to 220 (f32 CAM): with a loop over the query tiles around the head loop the
+// sibling kernels need 108 (bf16 probabilities) to 224 (f32 CAM): with a loop over the query tiles around the head loop the
 // scheduler hoists the next tile's loads and addresses as far as __launch_bounds__(256) lets it.  Holding the bf16 instances to 3
 // waves (amdgpu_waves_per_eu) brings them to 164 - 168 VGPRs but spills 12 - 76 bytes per lane in three of the CAM ones, so the
 // bound is left alone: no scratch comes first.  r is loaded behind the head loop, when the fragments and score chains of the tile
 // are dead.
-//
-// KEEP IN STEP: the tile formation below (fragment loads, hi + lo lse * log2 e, score and gradient chains, exponent, masking) is a
-// copy of attn_probs_kernel (attention_probs.hip) and of the CAM path of attn_probs_grad_kernel (attention_probs_grad.hip).  The
-// kernel tests take their reference matrix from those two kernels, so a change to the arithmetic of any of the three must be made
-// in all three.
-#include "pa_mma.h"
+#include "pa_attn_tile.h"
 
 namespace pa {
 
-static constexpr int R_HD = 64;                                  // head dim
-static constexpr double R_LOG2E_D = 1.4426950408889634;
-static constexpr float R_LOG2E = (float)R_LOG2E_D, R_LOG2E_LO = (float)(R_LOG2E_D - (double)R_LOG2E);      // log2 e = hi + lo
-static constexpr int R_KT = 128, R_QT = 32;                       // keys per workgroup (4 waves x 32 keys) / queries per tile
 static constexpr int R_MAX_NR = PA_ATTN_ROLLOUT_MAX_ROWS;
 
 // Work item -> (key tile, slice, sequence), key tile fastest.  VL: sequences packed back to back (cu_tok), N / nq hold max N and the
@@ -55,10 +45,6 @@ __global__ __launch_bounds__(256) void attn_rollout_kernel(const T* __restrict__
                                                            const int32_t* __restrict__ cu_tok, int B, int H, int N, int nq, int nr,
                                                            int nkt, int S, int tps, int direct, int64_t ws_pitch, float a, float b_,
                                                            float g_scale, float scale) {
-    using F = typename Frag<T>::type;
-    constexpr int NF = R_HD * (int)sizeof(T) / 32;                // 16-byte fragments per lane and row: 4 (bf16) / 8 (f32)
-    constexpr int EPC = 16 / (int)sizeof(T);
-    constexpr int NC = sizeof(T) == 4 ? 4 : 1;                    // accumulation chains per product (see attn_probs_kernel)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int L = blockIdx.x;
@@ -67,106 +53,44 @@ __global__ __launch_bounds__(256) void attn_rollout_kernel(const T* __restrict__
     const int s = L % S;
     const int b = L / S;
 
-    int64_t tok0 = (int64_t)b * N;                               // first token row of this sequence in qkv
-    const int64_t do0 = compact ? (int64_t)b * nq : -1;          // first row of this sequence in the compact d_o
-    const float* lse_b = lse + (int64_t)b * H * nq;              // lse of (head 0, query 0) of this sequence
-    int64_t lse_pitch = nq;                                      // floats between two heads
-    if constexpr (VL) {
-        const int t0 = cu_tok[b], t1 = cu_tok[b + 1];            // wave-uniform: scalar loads
-        const bool all_queries = nq >= N;                        // N is max N here
-        N = t1 - t0;
-        tok0 = t0;
-        if (all_queries) {
-            lse_pitch = cu_tok[B];
-            lse_b = lse + t0;
-        }
-        nq = min(nq, N);
-    }
-    const int64_t roff = (int64_t)nr * tok0;                     // this sequence's (nr, N) block in r_in / r_out / a workspace slice
-    const int k0 = kt * R_KT + wave * 32;
-    const int t_begin = s * tps, t_end = min(t_begin + tps, (int)cdiv(nq, R_QT));
+    const SeqGeom sg = seq_geom<VL>(b, B, H, N, nq, cu_tok, lse, compact);
+    N = sg.N;
+    nq = sg.nq;
+    const int64_t roff = (int64_t)nr * sg.tok0;                  // this sequence's (nr, N) block in r_in / r_out / a workspace slice
+    const int k0 = kt * AT_KT + wave * 32;
+    const int t_begin = s * tps, t_end = min(t_begin + tps, (int)cdiv(nq, AT_QT));
     if (t_begin >= t_end || k0 >= N) return;                     // (also N <= 0) wave-uniform; the kernel has no barrier
 
     const int r32 = lane & 31, half = lane >> 5;
     const int krow = min(k0 + r32, N - 1);
     const bool klive = k0 + r32 < N;
-    const double sl2d = (double)scale * R_LOG2E_D;                // scale * log2 e as hi + lo floats (used when q is not pre-scaled)
-    const float sl2 = (float)sl2d, sl2_lo = (float)(sl2d - (double)sl2);
-    const int D = H * R_HD;
+    float sl2, sl2_lo;
+    scale_log2e(scale, sl2, sl2_lo);
+    const int D = H * AT_HD;
 
     float part[R_MAX_NR];
 #pragma unroll
     for (int j = 0; j < R_MAX_NR; ++j) part[j] = 0.f;
 
     for (int qt = t_begin; qt < t_end; ++qt) {
-        const int q0 = qt * R_QT;
+        const int q0 = qt * AT_QT;
         const int qrow = min(q0 + r32, nq - 1);
-        int qr[16];                                              // the (clamped) query row of every accumulator register
-#pragma unroll
-        for (int i = 0; i < 16; ++i) qr[i] = min(q0 + acc_row(i, lane), nq - 1);
+        int qr[16];
+        tile_query_rows(qr, q0, nq, lane);
 
         f32x16 acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
         for (int h = 0; h < H; ++h) {
-            const T* base = qkv + tok0 * ldqkv + h * R_HD;       // q of token 0 of this (sequence, head)
-            // the probabilities of this tile, operation for operation those of attn_probs_kernel
-            const float* lse_h = lse_b + (int64_t)h * lse_pitch;
+            const T* base = qkv + sg.tok0 * ldqkv + h * AT_HD;    // q of token 0 of this (sequence, head)
             f32x16 p;
-            {
-                F qf[NF], kf[NF];
-#pragma unroll
-                for (int f = 0; f < NF; ++f) {
-                    const int off = (f * 2 + half) * EPC;
-                    qf[f] = *(const F*)(base + (int64_t)qrow * ldqkv + off);
-                    kf[f] = *(const F*)(base + D + (int64_t)krow * ldqkv + off);
-                }
-                f32x16 c, cl;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float nl = -lse_h[qr[i]];
-                    c[i] = nl * R_LOG2E;
-                    cl[i] = fmaf(nl, R_LOG2E, -c[i]) + nl * R_LOG2E_LO;
-                }
-                f32x16 sc[NC];
-#pragma unroll
-                for (int j = 0; j < NC; ++j) {
-                    mma32_first<T>(sc[j], qf[j * (NF / NC)], kf[j * (NF / NC)]);
-#pragma unroll
-                    for (int st = 1; st < NF / NC; ++st) mma32<T>(sc[j], qf[j * (NF / NC) + st], kf[j * (NF / NC) + st]);
-                }
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    float sv = sc[0][i];
-                    if constexpr (NC == 4) sv = (sc[0][i] + sc[1][i]) + (sc[2][i] + sc[3][i]);
-                    float e = PRE ? (sv + c[i]) + cl[i] : fmaf(sv, sl2, c[i]) + fmaf(sv, sl2_lo, cl[i]);
-                    e = klive ? e : -INFINITY;
-                    p[i] = __builtin_amdgcn_exp2f(e);
-                }
-            }
+            tile_probs<T, PRE>(p, base + (int64_t)qrow * ldqkv, base + D + (int64_t)krow * ldqkv, sg.lse_b + (int64_t)h * sg.lse_pitch,
+                               qr, klive, sl2, sl2_lo, half);
             if constexpr (CAM) {
-                // g = d_o v^T of this head, the chains of attn_probs_grad_kernel
-                const T* do_row = d_o + (compact ? do0 + qrow : tok0 + qrow) * (int64_t)ldo;
-                F df[NF], vf[NF];
+                f32x16 g;
+                tile_grad<T>(g, d_o + (sg.do0 + qrow) * (int64_t)ldo + h * AT_HD, base + 2 * D + (int64_t)krow * ldqkv, half);
 #pragma unroll
-                for (int f = 0; f < NF; ++f) {
-                    const int off = (f * 2 + half) * EPC;
-                    df[f] = *(const F*)(do_row + h * R_HD + off);
-                    vf[f] = *(const F*)(base + 2 * D + (int64_t)krow * ldqkv + off);
-                }
-                f32x16 gc[NC];
-#pragma unroll
-                for (int j = 0; j < NC; ++j) {
-                    mma32_first<T>(gc[j], df[j * (NF / NC)], vf[j * (NF / NC)]);
-#pragma unroll
-                    for (int st = 1; st < NF / NC; ++st) mma32<T>(gc[j], df[j * (NF / NC) + st], vf[j * (NF / NC) + st]);
-                }
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    float g = gc[0][i];
-                    if constexpr (NC == 4) g = (gc[0][i] + gc[1][i]) + (gc[2][i] + gc[3][i]);
-                    acc[i] += fmaxf(p[i] * (g * g_scale), 0.f);
-                }
+                for (int i = 0; i < 16; ++i) acc[i] += fmaxf(p[i] * (g[i] * g_scale), 0.f);
             } else {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc[i] += p[i];
@@ -180,7 +104,7 @@ __global__ __launch_bounds__(256) void attn_rollout_kernel(const T* __restrict__
                 float t = 0.f;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const float rv = q0 + acc_row(i, lane) < nq ? rj[qr[i]] : 0.f;
+                    const float rv = acc_row(i, lane) < nq - q0 ? rj[qr[i]] : 0.f;
                     t = fmaf(acc[i], rv, t);
                 }
                 t += __shfl_xor(t, 32, 64);
@@ -208,16 +132,12 @@ __global__ __launch_bounds__(256) void attn_rollout_finish_kernel(const float* _
                                                                   int H, int N, int nq, int nr, int tps, int64_t ws_pitch, float a,
                                                                   float b_) {
     const int b = blockIdx.z, j = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
-    int64_t tok0 = (int64_t)b * N;
-    if constexpr (VL) {
-        const int t0 = cu_tok[b], t1 = cu_tok[b + 1];
-        N = t1 - t0;
-        tok0 = t0;
-        nq = min(nq, N);
-    }
+    const SeqGeom sg = seq_geom<VL, false>(b, 0, H, N, nq, cu_tok, nullptr, 0);
+    N = sg.N;
+    nq = sg.nq;
     if (k >= N) return;
-    const int Sb = (int)cdiv(cdiv(nq, R_QT), tps);               // the slices this sequence has
-    const int64_t e = (int64_t)nr * tok0 + (int64_t)j * N + k;
+    const int Sb = (int)cdiv(cdiv(nq, AT_QT), tps);               // the slices this sequence has
+    const int64_t e = (int64_t)nr * sg.tok0 + (int64_t)j * N + k;
     float sum = ws[e];
     for (int s = 1; s < Sb; ++s) sum += ws[(int64_t)s * ws_pitch + e];
     r_out[e] = fmaf(b_, sum * (1.0f / (float)H), a * r_in[e]);
@@ -238,7 +158,7 @@ static int current_device_cus() {
 // never more slices than tiles, the tiles spread evenly.  Returns S, *tps = query tiles per slice.
 static int rollout_slices(int B, int N, int nqk, int slices, int* tps) {
     const int cus = slices > 0 ? 0 : current_device_cus();
-    const int64_t nqt = cdiv(nqk, R_QT);
+    const int64_t nqt = cdiv(nqk, AT_QT);
     int64_t S = slices;
     if (S <= 0) S = ((int64_t)cus * 8) / ((int64_t)B * cdiv(N, 32));
     S = S < 1 ? 1 : (S > nqt ? nqt : S);
@@ -254,7 +174,7 @@ static int attention_rollout_t(const void* qkv, int ldqkv, const float* lse, con
     int tps = 1;
     const int S = rollout_slices(B, N, nqk, slices, &tps);
     if (S > 1 && !ws) return PA_EINVAL;
-    const int nkt = (int)cdiv(N, R_KT);
+    const int nkt = (int)cdiv(N, AT_KT);
     const int64_t items = (int64_t)nkt * S * B;
     if (items >= (int64_t)1 << 31 || B > 65535) return PA_EUNSUPPORTED;
     const dim3 grid((unsigned)items), block(256);
@@ -316,7 +236,7 @@ extern "C" int pa_attention_rollout(const void* qkv, int ldqkv, const float* lse
     if (mode == PA_ATTN_ROLLOUT_CAM ? !d_o : (d_o != nullptr || do_compact)) return PA_EINVAL;
     if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
     if (cu_tok ? total_tok < N : (nq > N || total_tok != (int64_t)B * N)) return PA_EINVAL;
-    if (ldqkv < 3 * H * R_HD || (d_o && ldo < H * R_HD)) return PA_EINVAL;
+    if (ldqkv < 3 * H * AT_HD || (d_o && ldo < H * AT_HD)) return PA_EINVAL;
     const int es = dtype == PA_BF16 ? 2 : 4;
     if ((ldqkv * es) % 16 != 0 || (d_o && (ldo * es) % 16 != 0)) return PA_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;

@@ -839,6 +839,37 @@ def attention_fwd_varlen(qkv, cu_tok, B, H, max_N, scale, nq=None, flags=0):
     return o, lse
 
 
+def _f32_out(name, out, shape, device):
+    """``out``, which must hold as many elements as ``shape``, or a fresh f32 tensor of that shape"""
+    n = int(np.prod(shape))
+    if out is None:
+        return torch.empty(shape, device=device, dtype=torch.float32)
+    if out.numel() != n:
+        raise _lib.PasstAmdError(f"{name}: out has {out.numel()} elements, expected {n}")
+    return out
+
+
+def _packed_ok(qkv, cu_tok, B, H, max_N):
+    """the shapes every packed attention entry asks of qkv [total][3*H*64], cu_tok [B + 1] and max_N"""
+    return qkv.dim() == 2 and qkv.shape[1] == 3 * H * 64 and cu_tok.dim() == 1 and cu_tok.numel() == B + 1 and 1 <= max_N <= qkv.shape[0]
+
+
+def _packed_nq(name, nq, lse, B, H, max_N, total, do_compact=False, lse_optional=False):
+    """The nq a packed entry hands to the library: max_N stands for every query (lse [H][total]), a smaller one for the compact
+    prefix form (lse [(b*H+h)*nq+q], the only one a compact d_o goes with).  Checks lse's size against it."""
+    if nq is None or nq >= max_N:
+        nq, nlse = max_N, H * total
+        if do_compact:
+            raise _lib.PasstAmdError(f"{name}: do_compact needs nq < max_N")
+    else:
+        if nq < 1:
+            raise _lib.PasstAmdError(f"{name}: nq must be >= 1")
+        nlse = B * H * nq
+    if not (lse is None and lse_optional) and lse.numel() != nlse:
+        raise _lib.PasstAmdError(f"{name}: lse has {lse.numel()} elements, expected {nlse}")
+    return nq
+
+
 def attention_probs(qkv, lse, B, H, N, scale, nq=None, head_mean=False, flags=0, out=None):
     """The attention probabilities softmax(q k^T * scale) of the attention_fwd call that made ``lse`` (same qkv, nq, flags): f32
     (B, H, nq, N), or (B, 1, nq, N) = the mean over heads with ``head_mean``.  out: an f32 tensor of that many elements to write
@@ -848,10 +879,7 @@ def attention_probs(qkv, lse, B, H, N, scale, nq=None, head_mean=False, flags=0,
     Ho = 1 if head_mean else H
     if qkv.dim() != 2 or qkv.shape[0] != B * N or qkv.shape[1] != 3 * H * 64 or lse.numel() != B * H * nq or not 1 <= nq <= N:
         raise _lib.PasstAmdError(f"attention_probs: qkv {tuple(qkv.shape)}, lse {tuple(lse.shape)}, B={B}, H={H}, N={N}, nq={nq}")
-    if out is None:
-        out = torch.empty((B, Ho, nq, N), device=qkv.device, dtype=torch.float32)
-    elif out.numel() != B * Ho * nq * N:
-        raise _lib.PasstAmdError(f"attention_probs: out has {out.numel()} elements, expected {B * Ho * nq * N}")
+    out = _f32_out("attention_probs", out, (B, Ho, nq, N), qkv.device)
     _timed("attn_probs", 4.0 * out.numel(),
            lambda: check(_lib.load().pa_attention_probs(_p(qkv, None, True), qkv.stride(0), _p(lse, torch.float32), _p(out, torch.float32),
                                                         None, None, B, H, N, nq, int(bool(head_mean)), scale, dtype, flags, _stream()),
@@ -877,22 +905,11 @@ def attention_probs_varlen(qkv, lse, cu_tok, out_off, total_out, B, H, max_N, sc
     sequence b dense at out_off[b] as [H or 1][min(nq, N_b)][N_b] (out_off: B int64 on the device, attention_probs_offsets)."""
     dtype = PA_DTYPE[qkv.dtype]
     total = qkv.shape[0]
-    if qkv.dim() != 2 or qkv.shape[1] != 3 * H * 64 or cu_tok.dim() != 1 or cu_tok.numel() != B + 1 or not 1 <= max_N <= total or \
-            out_off.dim() != 1 or out_off.numel() != B:
+    if not _packed_ok(qkv, cu_tok, B, H, max_N) or out_off.dim() != 1 or out_off.numel() != B:
         raise _lib.PasstAmdError(f"attention_probs_varlen: qkv {tuple(qkv.shape)}, cu_tok {tuple(cu_tok.shape)}, out_off "
                                  f"{tuple(out_off.shape)}, B={B}, H={H}, max_N={max_N}")
-    if nq is None or nq >= max_N:
-        nq, nlse = max_N, H * total
-    else:
-        if nq < 1:
-            raise _lib.PasstAmdError("attention_probs_varlen: nq must be >= 1")
-        nlse = B * H * nq
-    if lse.numel() != nlse:
-        raise _lib.PasstAmdError(f"attention_probs_varlen: lse has {lse.numel()} elements, expected {nlse}")
-    if out is None:
-        out = torch.empty((total_out,), device=qkv.device, dtype=torch.float32)
-    elif out.numel() != total_out:
-        raise _lib.PasstAmdError(f"attention_probs_varlen: out has {out.numel()} elements, expected {total_out}")
+    nq = _packed_nq("attention_probs_varlen", nq, lse, B, H, max_N, total)
+    out = _f32_out("attention_probs_varlen", out, (total_out,), qkv.device)
     _timed("attn_probs", 4.0 * total_out,
            lambda: check(_lib.load().pa_attention_probs(_p(qkv, None, True), qkv.stride(0), _p(lse, torch.float32), _p(out, torch.float32),
                                                         _p(cu_tok, torch.int32), _p(out_off, torch.int64), B, H, max_N, nq,
@@ -926,10 +943,7 @@ def attention_probs_grad(qkv, lse, d_o, B, H, N, scale, nq=None, head_mean=False
         raise _lib.PasstAmdError(f"attention_probs_grad: qkv {tuple(qkv.shape)}, lse {None if lse is None else tuple(lse.shape)}, "
                                  f"B={B}, H={H}, N={N}, nq={nq}, mode={mode}, head_mean={head_mean}")
     _pgrad_d_o("attention_probs_grad", d_o, qkv, H, B * N, B * nq, do_compact)
-    if out is None:
-        out = torch.empty((B, Ho, nq, N), device=qkv.device, dtype=torch.float32)
-    elif out.numel() != B * Ho * nq * N:
-        raise _lib.PasstAmdError(f"attention_probs_grad: out has {out.numel()} elements, expected {B * Ho * nq * N}")
+    out = _f32_out("attention_probs_grad", out, (B, Ho, nq, N), qkv.device)
     _timed("attn_probs_grad", 4.0 * out.numel(),
            lambda: check(_lib.load().pa_attention_probs_grad(_p(qkv, None, True), qkv.stride(0), None if lse is None else _p(lse, torch.float32),
                                                              _p(d_o, qkv.dtype, True), d_o.stride(0), int(bool(do_compact)),
@@ -946,25 +960,12 @@ def attention_probs_grad_varlen(qkv, lse, d_o, cu_tok, out_off, total_out, B, H,
     dtype = PA_DTYPE[qkv.dtype]
     total = qkv.shape[0]
     cam = mode == ATTN_PGRAD_CAM
-    if qkv.dim() != 2 or qkv.shape[1] != 3 * H * 64 or cu_tok.dim() != 1 or cu_tok.numel() != B + 1 or not 1 <= max_N <= total or \
-            out_off.dim() != 1 or out_off.numel() != B or (lse is None if cam else head_mean):
+    if not _packed_ok(qkv, cu_tok, B, H, max_N) or out_off.dim() != 1 or out_off.numel() != B or (lse is None if cam else head_mean):
         raise _lib.PasstAmdError(f"attention_probs_grad_varlen: qkv {tuple(qkv.shape)}, cu_tok {tuple(cu_tok.shape)}, out_off "
                                  f"{tuple(out_off.shape)}, B={B}, H={H}, max_N={max_N}, mode={mode}, head_mean={head_mean}")
-    if nq is None or nq >= max_N:
-        nq, nlse = max_N, H * total
-        if do_compact:
-            raise _lib.PasstAmdError("attention_probs_grad_varlen: do_compact needs nq < max_N")
-    else:
-        if nq < 1:
-            raise _lib.PasstAmdError("attention_probs_grad_varlen: nq must be >= 1")
-        nlse = B * H * nq
-    if lse is not None and lse.numel() != nlse:
-        raise _lib.PasstAmdError(f"attention_probs_grad_varlen: lse has {lse.numel()} elements, expected {nlse}")
+    nq = _packed_nq("attention_probs_grad_varlen", nq, lse, B, H, max_N, total, do_compact, lse_optional=True)
     _pgrad_d_o("attention_probs_grad_varlen", d_o, qkv, H, total, B * nq, do_compact)
-    if out is None:
-        out = torch.empty((total_out,), device=qkv.device, dtype=torch.float32)
-    elif out.numel() != total_out:
-        raise _lib.PasstAmdError(f"attention_probs_grad_varlen: out has {out.numel()} elements, expected {total_out}")
+    out = _f32_out("attention_probs_grad_varlen", out, (total_out,), qkv.device)
     _timed("attn_probs_grad", 4.0 * total_out,
            lambda: check(_lib.load().pa_attention_probs_grad(_p(qkv, None, True), qkv.stride(0), None if lse is None else _p(lse, torch.float32),
                                                              _p(d_o, qkv.dtype, True), d_o.stride(0), int(bool(do_compact)),
@@ -1028,21 +1029,11 @@ def attention_rollout_varlen(qkv, lse, r_in, cu_tok, B, H, max_N, scale, a, b, n
     query tiles per slice."""
     total = qkv.shape[0]
     cam = mode == ATTN_ROLLOUT_CAM
-    if qkv.dim() != 2 or qkv.shape[1] != 3 * H * 64 or cu_tok.dim() != 1 or cu_tok.numel() != B + 1 or not 1 <= max_N <= total or \
-            r_in.dim() != 2 or r_in.shape[1] != total or not 1 <= r_in.shape[0] <= ATTN_ROLLOUT_MAX_ROWS or (d_o is None) == cam or \
-            (do_compact and not cam):
+    if not _packed_ok(qkv, cu_tok, B, H, max_N) or r_in.dim() != 2 or r_in.shape[1] != total or \
+            not 1 <= r_in.shape[0] <= ATTN_ROLLOUT_MAX_ROWS or (d_o is None) == cam or (do_compact and not cam):
         raise _lib.PasstAmdError(f"attention_rollout_varlen: qkv {tuple(qkv.shape)}, cu_tok {tuple(cu_tok.shape)}, r_in {tuple(r_in.shape)}, "
                                  f"B={B}, H={H}, max_N={max_N}, mode={mode}, d_o {'given' if d_o is not None else 'missing'}")
-    if nq is None or nq >= max_N:
-        nq, nlse = max_N, H * total
-        if do_compact:
-            raise _lib.PasstAmdError("attention_rollout_varlen: do_compact needs nq < max_N")
-    else:
-        if nq < 1:
-            raise _lib.PasstAmdError("attention_rollout_varlen: nq must be >= 1")
-        nlse = B * H * nq
-    if lse.numel() != nlse:
-        raise _lib.PasstAmdError(f"attention_rollout_varlen: lse has {lse.numel()} elements, expected {nlse}")
+    nq = _packed_nq("attention_rollout_varlen", nq, lse, B, H, max_N, total, do_compact)
     if cam:
         _pgrad_d_o("attention_rollout_varlen", d_o, qkv, H, total, B * nq, do_compact)
     return _rollout_launch("attention_rollout_varlen", qkv, lse, d_o, r_in, out, cu_tok, total, B, H, max_N, nq, r_in.shape[0], mode, slices,

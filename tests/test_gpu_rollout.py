@@ -3,7 +3,8 @@ repeatability, the packed form against the fixed one, the model against its own 
 (tests/golden/rollout.npz), ragged batches, the invariants of the interface and two ranks under passt_amd.ddp.attach.
 
 Kernel bound.  out = a r + b_ sum_{q < nq} r[q] M[q][k] with every term non-negative, so nothing cancels and the bound is elementwise
-and relative: the kernel forms the same tiles as pa_attention_probs / pa_attention_probs_grad (head_mean), whose f32 output M is the
+and relative: the kernel forms the same tiles as pa_attention_probs / pa_attention_probs_grad (head_mean) -- all three take them
+from passt_amd/csrc/pa_attn_tile.h, and the one-hot identity test below pins that bit for bit --, whose f32 output M is the
 reference's matrix and differs from the registers by the one rounding of (sum over heads) / H; the fused sum over nq products carries
 at most nq roundings (fma: the products are exact), the scaling by 1 / H, b_ and the addition of a r a few more:
     |out - ref| <= (nq + 16) * 2^-24 * ref + 1e-37.
@@ -18,7 +19,8 @@ slices, which the kernel bound covers.
 Every measured value is recorded through test_gpu_kernels.record() / test_gpu_model.record() ("attn_rollout[...]" / "rollout." names,
 filed as profiles/rollout_parity_metrics.json).
 
-Every test fails on the parent commit: the kernel tests on the missing ops, the others with a TypeError on the ``rollout=`` keyword."""
+Every test but the two one-hot identity tests failed on the commit before ``rollout=``: the kernel tests on the missing ops, the others
+with a TypeError on the keyword."""
 import os
 import socket
 import subprocess
@@ -208,6 +210,77 @@ def test_attention_rollout_packed_equals_fixed_per_clip(dt, nq, mode):
                 alone = ops.attention_rollout(q1, lse1, rs[i], 1, H, N, 0.125, 1.0, 0.5, nq=nq1, d_o=d1, mode=mode, g_scale=2.0,
                                               do_compact=compact, flags=1, slices=slices)
                 assert torch.equal(view, alone[0]), (i, N, compact, slices)
+
+
+def _one_hot_rows(qs, N):
+    r = torch.zeros(len(qs), N)
+    r[torch.arange(len(qs)), torch.tensor(qs)] = 1.0
+    return r
+
+
+def _identity_maps(qkv, lse, d_in, B, H, N, nq, mode, pre, compact):
+    """the sibling kernel's head-mean map (B, nq, N) for g_scale = 1; for another power of two the map is that multiple, exactly"""
+    return _matrix(qkv, lse, d_in, B, H, N, nq, mode, pre, 1.0, compact)
+
+
+@pytest.mark.parametrize("pre", [0, 1])
+@pytest.mark.parametrize("mode", [ATTN, CAM], ids=["attn", "cam"])
+@pytest.mark.parametrize("dt", [PA_F32, PA_BF16])
+@pytest.mark.parametrize("prefix", [False, True], ids=["all", "nq2"])
+def test_rollout_of_a_one_hot_row_is_a_row_of_the_sibling_map_bit_for_bit(prefix, dt, mode, pre):
+    """What sharing passt_amd/csrc/pa_attn_tile.h promises: with a = 0, b = 1 and r_in[b, j] = e_q the rollout returns row q of the
+    head-mean map that pa_attention_probs (ATTN) / pa_attention_probs_grad (CAM) writes -- torch.equal, not a bound.  Exact because
+    fma(acc, 1, 0) = acc and fma(acc, 0, t) = t for finite acc, the other lane half and every slice without q add 0, and
+    fma(1, part / H, 0 * r) is the map kernel's acc * (1 / H); g_scale = 2 doubles every term exactly.  So a single differing
+    operation in the tile of either kernel shows as a differing bit.
+    B = 2, H = 2, N = 45: two query tiles (the second a 13-row tail), two key waves (the second with 19 dead lanes); the one-hots sit
+    in both lane halves (rows 3 / 5), the last row of the full tile (31) and the last live row of the tail (44); 1 and 2 slices.
+    nq = 2: rows 0 and 1, CAM from the compact d_o."""
+    B, H, N = 2, 2, 45
+    D = H * 64
+    qkv, _ = _attn_inputs(rnd(B * N, 3 * D, seed=19, scale=1.5), dt, D, pre)
+    d_o = rnd(B * N, D, seed=33).to(TD[dt]).to(DEV)
+    nq, qs, slices_list = (2, (0, 1), (1,)) if prefix else (N, (3, 5, 31, 44), (1, 2))
+    r = _one_hot_rows(qs, N).expand(B, len(qs), N).contiguous().to(DEV)
+    lse = ops.attention_fwd(qkv, B, H, N, 0.125, nq=nq, flags=pre)[1]
+    compact = mode == CAM and prefix
+    d_in = None if mode == ATTN else (_compact(d_o, B, N, nq) if compact else d_o)
+    M = _identity_maps(qkv, lse, d_in, B, H, N, nq, mode, pre, compact)
+    assert M.shape == (B, nq, N) and float(M.max()) > 0
+    for g_scale in ((1.0,) if mode == ATTN else (1.0, 2.0)):
+        want = M[:, list(qs), :] * g_scale
+        for slices in slices_list:
+            assert _slices(B * N, B, N, nq, len(qs), slices) == slices
+            out = ops.attention_rollout(qkv, lse, r, B, H, N, 0.125, 0.0, 1.0, nq=nq, d_o=d_in, mode=mode, g_scale=g_scale,
+                                        do_compact=compact, flags=pre, slices=slices)
+            assert out.shape == want.shape and torch.equal(out, want), (g_scale, slices, float((out - want).abs().max()))
+
+
+def test_packed_rollout_of_one_hot_rows_is_the_fixed_map_of_every_clip_bit_for_bit():
+    """The same identity through the packed entry, clips of 45 and 5 tokens: clip i's block against the map rows the fixed-layout
+    sibling kernel gives the clip alone at B = 1 (both types, both modes, all queries, 1 and 2 slices)."""
+    lens, H = [45, 5], 2
+    D, B, total = H * 64, len(lens), sum(lens)
+    qs = [(3, 5, 31, 44), (0, 1, 3, 4)]
+    cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    cu_dev = torch.from_numpy(cu).to(DEV)
+    r = torch.cat([_one_hot_rows(q, n).reshape(-1) for q, n in zip(qs, lens)]).view(4, total).contiguous().to(DEV)
+    for dt in (PA_F32, PA_BF16):
+        qkv, _ = _attn_inputs(rnd(total, 3 * D, seed=21, scale=1.5), dt, D, 1)
+        d_tok = rnd(total, D, seed=35).to(TD[dt]).to(DEV)
+        lse = ops.attention_fwd_varlen(qkv, cu_dev, B, H, max(lens), 0.125, flags=1)[1]
+        for mode in (ATTN, CAM):
+            maps = []
+            for i, N in enumerate(lens):
+                q1 = qkv[cu[i]:cu[i + 1]].contiguous()
+                lse1 = ops.attention_fwd(q1, 1, H, N, 0.125, flags=1)[1]
+                d1 = None if mode == ATTN else d_tok[cu[i]:cu[i + 1]].contiguous()
+                maps.append(_identity_maps(q1, lse1, d1, 1, H, N, N, mode, 1, False)[0][list(qs[i])])
+            for slices in (1, 2):
+                got = ops.attention_rollout_varlen(qkv, lse, r, cu_dev, B, H, max(lens), 0.125, 0.0, 1.0, d_o=None if mode == ATTN else d_tok,
+                                                   mode=mode, flags=1, slices=slices)
+                for i, view in enumerate(ops.rollout_views(got, lens)):
+                    assert torch.equal(view, maps[i]), (dt, mode, slices, i)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -154,6 +154,20 @@ def test_header_declares_the_entries_and_the_binding_lists_them():
     assert "attention_rollout.hip" in mk and "build/attention_rollout.o" in mk.split("EXTRA = -mllvm -amdgpu-mfma-vgpr-form")[0]
 
 
+def test_the_three_map_kernels_take_their_tile_from_one_header():
+    """passt_amd/csrc/pa_attn_tile.h holds the only copy of the tile arithmetic: the three translation units include it, none of them
+    issues an MFMA or an exponential itself, and editing the header rebuilds every object."""
+    csrc = os.path.join(ROOT, "passt_amd", "csrc")
+    tile = open(os.path.join(csrc, "pa_attn_tile.h")).read()
+    assert "mma32_first<T>(" in tile and "mma32<T>(" in tile and tile.count("__builtin_amdgcn_exp2f(") == 1
+    for name in ("attention_probs.hip", "attention_probs_grad.hip", "attention_rollout.hip"):
+        text = open(os.path.join(csrc, name)).read()
+        assert '#include "pa_attn_tile.h"' in text and '#include "pa_mma.h"' not in text, name
+        assert "mma32" not in text and "__builtin_amdgcn_exp2f" not in text and "mfma" not in text.replace("amdgpu-mfma-vgpr-form", ""), name
+    rules = [ln for ln in open(os.path.join(csrc, "Makefile")).read().splitlines() if ln.startswith("build/") and ".hip" in ln]
+    assert len(rules) == 3 and rules[0].startswith("build/%.o: %.hip") and all("pa_attn_tile.h" in ln.split(":", 1)[1] for ln in rules)
+
+
 def test_packed_start_rows_and_views():
     """The packed buffer: clip b's dense (2, N_b) block at float 2 * cu_tok[b], one-hot at cls / dist."""
     with pytest.MonkeyPatch.context() as mp:
