@@ -321,6 +321,16 @@ int pa_gemm_tn(const pa_gemm_args* a, void* stream);
 #endif
 int pa_gemm_tn_step_rows(void);    /* the value the library was built with */
 int pa_gemm_tn_batched(const pa_gemm_args* a, int n, void* stream);
+/* The same launch with UNEQUAL token slices (problems that all have the same token count a->K): every 256 x 256 tile's
+ * steps = ceil(K / PA_TN_STEP_ROWS) token steps are cut into n_long slices of long_steps steps (slabs 0 .. n_long - 1) and
+ * one short slice of the steps - n_long * long_steps >= 1 that are left (slab n_long).  split_k of every problem must be
+ * n_long + 1, the number of slabs out_f32 (and colsum_ws) hold; finish with pa_reduce_partials(_batched) as before.  The
+ * long items of all tiles are launched first, slice-major with every XCD owning a contiguous run; the short items follow in
+ * an XCD-contiguous order of their own and fill the CUs the first dispatch wave left free.  Results differ from
+ * pa_gemm_tn_batched only in the grouping of the f32 partial sums.
+ * PA_EINVAL: n_long < 1, long_steps < 1, n_long * long_steps >= steps (the short slice is never empty), split_k != n_long + 1.
+ * PA_EUNSUPPORTED: token counts that differ between the problems (and whatever pa_gemm_tn_batched does not support). */
+int pa_gemm_tn_batched_plan(const pa_gemm_args* a, int n, int n_long, int long_steps, void* stream);
 /* Row gather / scatter and strided zero fill (prefix-token path of the last block):
  * gather: out[i] = in[idx[i]]; scatter: out[idx[i]] = in[i]; rows of row_bytes bytes (multiple of 4). */
 int pa_gather_rows(const void* in, const int32_t* idx, int n_idx, int64_t row_bytes, void* out, void* stream);

@@ -1970,6 +1970,43 @@ __global__ __launch_bounds__(512) void gemm_tn_stagger_batched_kernel(const TnBa
     gemm_tn_stagger_item(b.a[p], b.tiles_n[p], t, split, b.per[p]);
 }
 
+// Long/short plan (pa_gemm_tn_batched_plan): every tile's token steps are cut into n_long slices of long_steps steps and one
+// short slice of what is left, instead of split_k equal slices.  The n_long * tiles long items come first in the grid, so the
+// first dispatch wave puts one on a CU each, and the CUs left over work through the short items as they free up: the launch
+// lasts about one long item, with n_long + 1 slabs, prologues and epilogues per tile instead of split_k.  A sibling of the
+// batched kernel (one item per workgroup through the same gemm_tn_stagger_range; only one of the kernels runs at a time, so
+// the copy costs no instruction cache): the uniform launch stays the code it was.
+struct TnPlan {
+    pa_gemm_args a[PA_TN_BATCH_MAX];
+    int32_t tiles_n[PA_TN_BATCH_MAX];
+    int32_t tfirst[PA_TN_BATCH_MAX + 1];     // first tile of problem p in the order over all tiles; tfirst[n] = tiles of the batch
+    int32_t n, n_long, long_steps, steps;
+};
+__global__ __launch_bounds__(512) void gemm_tn_stagger_plan_kernel(const TnPlan b) {
+    // Long items: slice-major over the whole batch, every XCD owning a contiguous run of that order, as in the uniform launch --
+    // an XCD's resident long items walk ONE token range at the same time and share its dY / X panel stages in their L2.
+    // Short items: an XCD-contiguous order of their own.  (One swizzle over all items would hand an XCD 1/8 of ALL items as
+    // its contiguous run: 40 long items of the passt_s block on an XCD with 32 CUs.)
+    const int tiles_all = b.tfirst[b.n], nlong = tiles_all * b.n_long;
+    int g, t;
+    if ((int)blockIdx.x < nlong) {
+        const int logical = xcd_swizzle(blockIdx.x, nlong);
+        g = logical / tiles_all;
+        t = logical - g * tiles_all;
+    } else {
+        g = b.n_long;
+        t = xcd_swizzle(blockIdx.x - nlong, tiles_all);
+    }
+    int p = 0;
+    while (p + 1 < b.n && t >= b.tfirst[p + 1]) ++p;
+    t -= b.tfirst[p];
+    const pa_gemm_args& a = b.a[p];
+    const int st_begin = g * b.long_steps;                                     // the short slice starts where the long ones end
+    const int nsteps = g < b.n_long ? b.long_steps : b.steps - st_begin;       // >= 1: checked by the entry point
+    gemm_tn_stagger_range(a, b.tiles_n[p], t, st_begin, nsteps, a.out_f32 + (int64_t)g * a.M * a.ldo32, a.ldo32,
+                          a.colsum_ws ? a.colsum_ws + (int64_t)g * a.M : nullptr);
+}
+
 // (r03: a stream-K form of the batched launch -- ONE sequence of tiles x token steps cut into 256 equal contiguous runs,
 // one per CU, 364 partial tiles instead of 756, no round quantisation -- measured 504 us + 23 us fix-up against 382 + 36:
 // in tile-major runs the CUs working at the same time sit at different token offsets, nobody shares a dY / X panel stage and
@@ -2487,6 +2524,41 @@ extern "C" int pa_gemm_tn_batched(const pa_gemm_args* a, int n, void* stream) {
     static signed char lds_attr[64] = {0};
     (void)lds_attr_on_this_device((const void*)gemm_tn_stagger_batched_kernel, LDS, lds_attr);
     hipLaunchKernelGGL(gemm_tn_stagger_batched_kernel, dim3(total), dim3(512), LDS, (hipStream_t)stream, batch);
+    return check_launch();
+}
+
+extern "C" int pa_gemm_tn_batched_plan(const pa_gemm_args* a, int n, int n_long, int long_steps, void* stream) {
+    if (!a || n < 1 || n > PA_TN_BATCH_MAX || n_long < 1 || long_steps < 1) return PA_EINVAL;
+    TnPlan plan;
+    TnPlan* pb = &plan;
+    int64_t tiles = 0;
+    for (int p = 0; p < n; ++p) {
+        const pa_gemm_args& x = a[p];
+        if (!x.A || !x.B || !x.out_f32 || x.M <= 0 || x.N <= 0 || x.K <= 0 || x.split_k != n_long + 1) return PA_EINVAL;
+        if (x.dtype != PA_BF16 || x.epilogue != PA_EPI_PARTIAL) return PA_EUNSUPPORTED;
+        if ((x.lda * 2) % 16 || (x.ldb * 2) % 16 || x.ldo32 % 4 || x.M < 8 || x.N < 8 || x.N % 8 || x.M % 8) return PA_EUNSUPPORTED;
+        if (x.K != a[0].K) return PA_EUNSUPPORTED;             // one token axis, one plan
+        pb->a[p] = x;
+        pb->tiles_n[p] = (int)cdiv(x.N, 256);
+        pb->tfirst[p] = (int)tiles;
+        tiles += cdiv(x.M, 256) * pb->tiles_n[p];
+    }
+    const int steps = (int)cdiv(a[0].K, TN_ROWS);
+    if ((int64_t)n_long * long_steps >= steps) return PA_EINVAL;               // an empty short slice is never launched
+    if (tiles * (n_long + 1) > INT32_MAX) return PA_EUNSUPPORTED;
+    pb->tfirst[n] = (int)tiles;
+    pb->n = n;
+    pb->n_long = n_long;
+    pb->long_steps = long_steps;
+    pb->steps = steps;
+#ifdef PA_PROBE
+    constexpr int LDS = TN_LDS + 2 * PROBE_SLOTS * 8;
+#else
+    constexpr int LDS = TN_LDS;
+#endif
+    static signed char lds_attr[64] = {0};
+    (void)lds_attr_on_this_device((const void*)gemm_tn_stagger_plan_kernel, LDS, lds_attr);
+    hipLaunchKernelGGL(gemm_tn_stagger_plan_kernel, dim3((unsigned)(tiles * (n_long + 1))), dim3(512), LDS, (hipStream_t)stream, plan);
     return check_launch();
 }
 

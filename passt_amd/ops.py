@@ -650,6 +650,85 @@ def _pick_batched_splits(probs, slots=256):
     return best if best is not None else [1] * len(probs)
 
 
+_PLAN_CACHE = {}
+# A/B switch of the long/short plan (profiles/r07_wgrad_long_short.txt), read once: PASST_AMD_WGRAD_PLAN=uniform cuts equal
+# token slices everywhere, as _pick_batched_splits does; =long_short lets the planner below decide.  A forced slice count
+# (PASST_AMD_WGRAD_SLICES) is a uniform plan too.
+WGRAD_PLAN_DEFAULT = "long_short"       # in the step at batch 64: 21.38 -> 21.07 ms, weight gradients 377 -> 357 us per block
+_SHORT_ITEM_COST = 1.25       # modelled cost of a short item's steps relative to a long item's (see _long_short_cost)
+_PLAN_MIN_GAIN = 0.04         # modelled gain below which the long/short plan is not taken
+_FORCE_UNIFORM = os.environ.get("PASST_AMD_WGRAD_PLAN", WGRAD_PLAN_DEFAULT) == "uniform" or _FORCE_SLICES > 0
+
+
+def pick_batched_plan(probs, slots=256):
+    """Memoised front of _pick_batched_plan: (n_long, long_steps, splits).  n_long = 0: the uniform plan, splits[p] equal
+    slices of problem p (pa_gemm_tn_batched).  n_long >= 1: every tile is cut into n_long slices of long_steps token steps and
+    one short slice of the rest (pa_gemm_tn_batched_plan); splits[p] = n_long + 1 slabs."""
+    if _FORCE_UNIFORM:
+        return 0, 0, pick_batched_splits(probs, slots)
+    key = (tuple(probs), slots)
+    hit = _PLAN_CACHE.get(key)
+    if hit is None:
+        hit = _PLAN_CACHE[key] = _pick_batched_plan(list(probs), slots)
+    return hit
+
+
+def _uniform_cost(probs, S, slots=256):
+    """Modelled us of the uniform plan S (slices per problem): the cost _pick_batched_splits minimises."""
+    items = sum(t * s_ for (t, _), s_ in zip(probs, S))
+    per = max(-(-st // s_) for (_, st), s_ in zip(probs, S))
+    return -(-items // slots) * (per + 4) * 1.2 + items * 0.05
+
+
+def _long_short_cost(tiles, steps, a, L, slots=256):
+    """Modelled us of `a` long slices of L steps + one short slice of steps - a * L per tile, with the constants of
+    _pick_batched_splits (1.2 us per step, 4 steps' worth fixed per item, 0.05 per slab).  The makespan comes from dealing the
+    items in launch order -- all long items, then all short ones -- each onto the CU that frees first.  A short item is
+    charged _SHORT_ITEM_COST times its steps (re-fitted on MI355X, profiles/r07_wgrad_long_short.txt: with the short items'
+    three rounds as long as one long item, the model's optimum, the launch ran 90 us over the model; it met the model once the
+    short rounds were 0.8 of a long item or less; supposed cause: a freed CU waits for the next item in launch order that is
+    bound to ITS XCD, so the short rounds slip)."""
+    import heapq
+    free = [0.0] * slots
+    end = 0.0
+    for steps_item, count, k in ((L, a * tiles, 1.0), (steps - a * L, tiles, _SHORT_ITEM_COST)):
+        dur = (steps_item + 4) * 1.2 * k
+        for _ in range(count):
+            t = free[0] + dur
+            heapq.heapreplace(free, t)
+            end = max(end, t)
+    return end + tiles * (a + 1) * 0.05
+
+
+def _pick_batched_plan(probs, slots=256):
+    """The cheaper of the best uniform split and the best long/short plan (a = 1 or 2 long slices of L steps, a short slice
+    of R = steps - a * L, 1 <= R <= L) under one cost model.  With equal slices tiles x slices has to land just under a
+    multiple of the CU count or the last round runs partly empty, which is what keeps the passt_s block at 7 slices (756
+    items, 2.95 rounds); two long slices on 216 CUs with the short third dealt onto the other 40 last the same 3/7 of the
+    token axis with 324 prologues, epilogues and slabs.  Problems with different token counts keep the uniform plan, and so
+    does a launch whose equal slices already fit one round (the ESC-50 block: 2 x 108 items): there is no partly empty round
+    to win back, and the model's constants are not fine enough to rank plans half a microsecond apart."""
+    S = _pick_batched_splits(probs, slots)
+    steps = probs[0][1]
+    tiles = sum(t for t, _ in probs)
+    if any(st != steps for _, st in probs) or sum(t * s_ for (t, _), s_ in zip(probs, S)) <= slots:
+        return 0, 0, S
+    best, best_cost = (0, 0, S), _uniform_cost(probs, S, slots)
+    for a in (1, 2):
+        for L in range((steps - 1) // a, -(-steps // (a + 1)) - 1, -1):        # 1 <= R <= L; on a tie the shorter short slice
+            cost = _long_short_cost(tiles, steps, a, L, slots)
+            if cost < best_cost - 1e-9:
+                best, best_cost = (a, L, [a + 1] * len(probs)), cost
+    # the model is within a few per cent of the measured launches, not better: a smaller modelled gain keeps the uniform plan
+    return best if best_cost < (1.0 - _PLAN_MIN_GAIN) * _uniform_cost(probs, S, slots) else (0, 0, S)
+
+
+def wgrad_batched_ws_floats(splits, shapes):
+    """f32 elements of the partial workspace of wgrad_tn_batched: splits[p] slabs of problem p's N x K gradient, and of its N
+    column sums where it has a bias gradient.  shapes: [(N, K, has_db)]."""
+    return sum(S * N * (K + (1 if has_db else 0)) for S, (N, K, has_db) in zip(splits, shapes))
+
+
 def wgrad_tn(dY, X, out_f32, dtype, accumulate=False, partial_ws=None, db=None):
     """out[N][K] (+)= dY[M][N]^T X[M][K], operands read in place (pa_gemm_tn), deterministic split-K.  db [N] f32 (bf16
     role-split kernel only, see wgrad_tn_fuses_bias): (+)= column sums of dY out of the same launch."""
@@ -698,12 +777,13 @@ def wgrad_tn_fuses_bias(dtype):
     return dtype == PA_BF16 and GEMM_TUNE != 1
 
 
-def wgrad_tn_batched(problems, dtype, partial_ws=None, row_jobs=None):
+def wgrad_tn_batched(problems, dtype, partial_ws=None, row_jobs=None, plan=None):
     """problems: up to 4 of (dY [M][N], X [M][K], out [N][K] f32, accumulate[, db [N] f32 or None]): all weight gradients of a
     block in ONE pa_gemm_tn_batched launch + ONE batched finishing reduction.  A problem with db also gets its bias gradient
     (column sums of dY) out of the same launch.  row_jobs: (partial, rows, pitch, n, out) reductions of many short partial rows
     (deferred LayerNorm / GELU' parameter gradients of the block, see layernorm_bwd / dgelu_gemm) that ride in the same finishing
-    launch.  Returns the (possibly grown) partial workspace."""
+    launch.  plan=(n_long, long_steps) forces that long/short plan (pick_batched_plan; tests), plan=(0, 0) the uniform one.
+    Returns the (possibly grown) partial workspace."""
     from ._lib import ReduceDesc
     assert dtype == PA_BF16 and 1 <= len(problems) <= 4
     problems = [tuple(p) + (None,) * (5 - len(p)) for p in problems]
@@ -711,9 +791,15 @@ def wgrad_tn_batched(problems, dtype, partial_ws=None, row_jobs=None):
     for dY, X, out, acc, db in problems:
         Mtok, N = dY.shape
         metas.append((Mtok, N, X.shape[1]))
-    splits = pick_batched_splits([(((N + 255) // 256) * ((K + 255) // 256), (Mtok + tn_step_rows() - 1) // tn_step_rows())
-                                  for Mtok, N, K in metas])
-    need = sum(S * m[1] * (m[2] + (1 if p[4] is not None else 0)) for S, m, p in zip(splits, metas, problems))
+    shapes = [(((N + 255) // 256) * ((K + 255) // 256), (Mtok + tn_step_rows() - 1) // tn_step_rows()) for Mtok, N, K in metas]
+    if plan is None:
+        n_long, long_steps, splits = pick_batched_plan(shapes)
+    elif plan[0] == 0:
+        n_long, long_steps, splits = 0, 0, pick_batched_splits(shapes)
+    else:
+        n_long, long_steps = plan
+        splits = [n_long + 1] * len(problems)
+    need = wgrad_batched_ws_floats(splits, [(m[1], m[2], p[4] is not None) for m, p in zip(metas, problems)])
     if partial_ws is None or partial_ws.numel() < need:
         partial_ws = torch.empty(need, device=problems[0][0].device, dtype=torch.float32)
     row_jobs = row_jobs or []
@@ -749,7 +835,10 @@ def wgrad_tn_batched(problems, dtype, partial_ws=None, row_jobs=None):
     if GEMM_PROFILE is not None:        # the bracket covers the batched split-K reduction too
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-    check(lib.pa_gemm_tn_batched(args, len(problems), _stream()), "pa_gemm_tn_batched")
+    if n_long:
+        check(lib.pa_gemm_tn_batched_plan(args, len(problems), n_long, long_steps, _stream()), "pa_gemm_tn_batched_plan")
+    else:
+        check(lib.pa_gemm_tn_batched(args, len(problems), _stream()), "pa_gemm_tn_batched")
     # a normal block fills the launch exactly (4 weight gradients + qkv.bias + 2 x 3 LayerNorm rows + fc1.bias = 12 =
     # PA_REDUCE_BATCH_MAX); anything beyond goes out as a second launch instead of failing in the middle of a backward
     for lo in range(0, nred, REDUCE_BATCH_MAX):
