@@ -310,11 +310,23 @@ static int ln_bwd_launch(const void* dy, int dtype, const float* x, const float*
     const int nblk = ln_bwd_blocks(M);
     const size_t lds = (size_t)12 * D * sizeof(float);
     const int nvl = (int)cdiv(D, 256);
-    // both forms are instantiated: without a second addend the launch is the kernel pa_layernorm_bwd always ran
+    // both forms are instantiated: without a second addend the launch is the kernel pa_layernorm_bwd always ran.
+    // [4][3][D] floats of dynamic LDS pass 64 KiB from D = 1368 on (96 KiB at D = 2048): such a launch asks for the kernel's
+    // per-device attribute first, like every other large-LDS launch of the library (the MI355X runtime the tests ran on accepts
+    // it without: profiles/row_kernel_parity.txt; another device or runtime need not).  The attribute is decided once per device
+    // and instantiation (one state array each), so it is asked for with the most that instantiation ever requests (D = 256 V),
+    // which covers every later width; a device that refuses it cannot run these widths
 #define PA_LN_BWD_T(T, V)                                                                                         \
     do {                                                                                                          \
-        if (dres2) hipLaunchKernelGGL((ln_bwd2_kernel<T, V>), dim3(nblk), dim3(256), lds, st, (const T*)dy, x, gamma, mean, rstd, dres, dres2, dx, (T*)dx_lp, ws, M, D); \
-        else hipLaunchKernelGGL((ln_bwd_kernel<T, V>), dim3(nblk), dim3(256), lds, st, (const T*)dy, x, gamma, mean, rstd, dres, dx, (T*)dx_lp, ws, M, D); \
+        if (dres2) {                                                                                              \
+            static signed char lds_attr2[64] = {0};                                                               \
+            if (lds > 64 * 1024 && !lds_attr_on_this_device((const void*)ln_bwd2_kernel<T, V>, 12 * 256 * V * (int)sizeof(float), lds_attr2)) return PA_EUNSUPPORTED; \
+            hipLaunchKernelGGL((ln_bwd2_kernel<T, V>), dim3(nblk), dim3(256), lds, st, (const T*)dy, x, gamma, mean, rstd, dres, dres2, dx, (T*)dx_lp, ws, M, D); \
+        } else {                                                                                                  \
+            static signed char lds_attr[64] = {0};                                                                \
+            if (lds > 64 * 1024 && !lds_attr_on_this_device((const void*)ln_bwd_kernel<T, V>, 12 * 256 * V * (int)sizeof(float), lds_attr)) return PA_EUNSUPPORTED; \
+            hipLaunchKernelGGL((ln_bwd_kernel<T, V>), dim3(nblk), dim3(256), lds, st, (const T*)dy, x, gamma, mean, rstd, dres, dx, (T*)dx_lp, ws, M, D); \
+        }                                                                                                         \
     } while (0)
 #define PA_LN_BWD(V)                                                                                              \
     do {                                                                                                          \
