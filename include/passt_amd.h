@@ -678,6 +678,34 @@ int pa_sgd(float* p, const float* g, int64_t n, float lr, void* stream);
 int pa_swa_update(float* avg, const float* p, int64_t n, int num_averaged, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Validation metrics (ex_audioset.py:245-291, ex_openmic.py:228-270): per-class average precision and ROC-AUC on the device,
+ * sort-free, as exact integer rank counts per positive sample.  For one class, over the valid samples (P positives, Nn
+ * negatives), with GEp_i / GEn_i = the positives / negatives whose score is >= that of positive i and GTn_i = the negatives
+ * whose score is greater:
+ *   AP  = (1 / P) sum_i GEp_i / (GEp_i + GEn_i)
+ *   AUC = sum_i (2 (Nn - GEn_i) + (GEn_i - GTn_i)) / (2 P Nn)
+ * which is what scikit-learn's average_precision_score / roc_auc_score return, ties included.
+ *
+ * pa_eval_append: one batch scores[B][C], target[B][C] (positive when > 0.5), mask[B][C] (valid when > 0.5; NULL = all valid)
+ *   goes, transposed, into columns n0 .. n0 + B of the class-major buffers keys[C][capacity] (u32) and state[C][capacity] (u8).
+ *   mode PA_EVAL_SIGMOID ranks the f32 1 / (1 + exp(-z)) of the logits, PA_EVAL_RAW the values as given.  The key is the score's
+ *   bit pattern made order-preserving (-0 equals +0); the state is 0 excluded, 1 negative, 2 positive, 3 a valid sample whose
+ *   score is NaN.  Any B, C >= 1 and any n0 with n0 + B <= capacity; columns outside n0 .. n0 + B are not touched.
+ * pa_eval_rank: the first n columns of every class -> n_pos[C], n_neg[C], auc_num[C] (the AUC numerator above) as int64 and
+ *   ap[C], auc[C] as f64.  P = 0: ap 0.0; P = 0 or Nn = 0: auc NaN; a class with a NaN-scored valid sample: ap and auc NaN
+ *   (that sample is in neither count).  n = 0 is allowed.  The integers are exact; the f64 sum of the AP terms runs in a fixed order
+ *   (sample order inside a run of 256 positives, the runs in order), so equal inputs give equal bits.  ws: pa_eval_ws_bytes(C, capacity) bytes, 16-byte aligned; 0 from the query = a
+ *   shape the entry refuses (capacity >= 2^31, or C * ceil(capacity / 256) >= 2^31).  Nothing is read at or behind column n.
+ * PA_EINVAL: NULL pointers (mask excepted), B or C < 1, n0 < 0, n < 0, n0 + B or n > capacity, an unknown mode. */
+#define PA_EVAL_SIGMOID 0
+#define PA_EVAL_RAW 1
+int pa_eval_append(const float* scores, const float* target, const float* mask, int B, int C, int64_t n0, int64_t capacity, int mode,
+                   uint32_t* keys, uint8_t* state, void* stream);
+int64_t pa_eval_ws_bytes(int C, int64_t capacity);
+int pa_eval_rank(const uint32_t* keys, const uint8_t* state, int C, int64_t n, int64_t capacity, void* ws, int64_t* n_pos,
+                 int64_t* n_neg, int64_t* auc_num, double* ap, double* auc, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Data-parallel exchange step: gradient all-reduce over RCCL / xGMI, one communicator per process (= per GPU).
  * Replaces Lightning's DDP plugin (ex_audioset.py:488-489 -> torch DDP: NCCL all-reduce of gradient buckets from
  * autograd hooks; mean of the per-rank gradients).  Here the caller owns the buckets: contiguous slices of its flat

@@ -8,5 +8,6 @@ gradient reducer (passt_amd.ddp).  All compute goes through libpasst_amd.so (inc
 """
 from .passt import PaSST, get_model, get_model_passt, get_ensemble_model, EnsembelerModel  # noqa: F401
 from .preprocess import AugmentMelSTFT  # noqa: F401
+from . import metrics  # noqa: F401     (passt_amd.metrics.EvalAccumulator: validation mAP / ROC-AUC on the device)
 
 __version__ = "0.1.0"

@@ -133,6 +133,9 @@ SIGNATURES = {
     "pa_sgd": (i32, [vp, vp, i64, f32, vp]),
     "pa_swa_update": (i32, [vp, vp, i64, i32, vp]),
     "pa_wave_augment": (i32, [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "pa_eval_append": (i32, [vp, vp, vp, i32, i32, i64, i64, i32, vp, vp, vp]),
+    "pa_eval_ws_bytes": (i64, [i32, i64]),
+    "pa_eval_rank": (i32, [vp, vp, i32, i64, i64, vp, vp, vp, vp, vp, vp, vp]),
     "pa_comm_unique_id": (i32, [vp]),
     "pa_comm_init": (i32, [vp, i32, i32, C.POINTER(vp)]),
     "pa_allreduce_bucket": (i32, [vp, vp, i64, i32, vp]),
@@ -146,6 +149,8 @@ GEMM_COLSUM_DEFER = 0x2000    # PA_EPI_DGELU column sums stay as partial rows fo
 REDUCE_SLABS, REDUCE_ROWS = 0, 1    # pa_reduce_desc.mode
 GEMM_EPILOGUE_V3 = 0x1000     # run a pa_gemm_nt call with the LDS-free epilogue (A/B, equality test; slower: opt-in)
 COMM_ID_BYTES = 128
+EVAL_SIGMOID, EVAL_RAW = 0, 1       # pa_eval_append mode
+EVAL_EXCLUDED, EVAL_NEG, EVAL_POS, EVAL_NAN = 0, 1, 2, 3      # its one-byte sample state
 
 _lib = None
 

@@ -1392,11 +1392,17 @@ def linear_f32_bwd(dy, x, W, dW, db, accumulate=False):
     return dx
 
 
-def bce_fwd_bwd(logits, target, grad_scale=1.0):
+def bce_fwd_bwd(logits, target, grad_scale=1.0, out=None):
+    """out: (loss [1], dlogits [>= B * C], ws [>= 1 + ceil(B * C / 256)]) f32 buffers to reuse instead of allocating"""
     B, Cc = logits.shape
-    loss = torch.empty(1, device=logits.device, dtype=torch.float32)
-    dlogits = torch.empty_like(logits)
-    ws = torch.empty(1 + (B * Cc + 255) // 256, device=logits.device, dtype=torch.float32)
+    if out is not None:
+        loss, dlogits, ws = out
+        if loss.numel() < 1 or dlogits.numel() < B * Cc or ws.numel() < 1 + (B * Cc + 255) // 256:
+            raise _lib.PasstAmdError("bce_fwd_bwd: the buffers in `out` are too small")
+    else:
+        loss = torch.empty(1, device=logits.device, dtype=torch.float32)
+        dlogits = torch.empty_like(logits)
+        ws = torch.empty(1 + (B * Cc + 255) // 256, device=logits.device, dtype=torch.float32)
     check(_lib.load().pa_bce_fwd_bwd(_p(logits, torch.float32), _p(target, torch.float32), B, Cc, grad_scale, _p(loss), _p(dlogits), _p(ws),
                                      _stream()), "pa_bce_fwd_bwd")
     return loss, dlogits
@@ -1455,3 +1461,38 @@ def swa_update(avg, p, num_averaged):
 
 def sgd(p, g, lr):
     check(_lib.load().pa_sgd(_p(p, torch.float32), _p(g, torch.float32), p.numel(), lr, _stream()), "pa_sgd")
+
+
+# ---- validation metrics ----------------------------------------------------------------------
+def eval_append(scores, target, keys, state, n0, mask=None, mode=_lib.EVAL_SIGMOID):
+    """One validation batch [B][C] (f32 logits or scores, targets, optional 0/1 mask) into columns n0 .. n0 + B of the
+    class-major buffers keys [C][capacity] int32 (the u32 rank keys) and state [C][capacity] uint8 (pa_eval_append)."""
+    B, Cc = scores.shape
+    if target.shape != scores.shape or (mask is not None and mask.shape != scores.shape):
+        raise _lib.PasstAmdError(f"eval_append: scores {tuple(scores.shape)}, target {tuple(target.shape)}"
+                                 f"{'' if mask is None else f', mask {tuple(mask.shape)}'} must have one shape")
+    if keys.dim() != 2 or keys.shape[0] != Cc or state.shape != keys.shape:
+        raise _lib.PasstAmdError(f"eval_append: keys {tuple(keys.shape)} / state {tuple(state.shape)} are not [{Cc}][capacity]")
+    check(_lib.load().pa_eval_append(_p(scores, torch.float32), _p(target, torch.float32), _p(mask, torch.float32), B, Cc, int(n0),
+                                     keys.shape[1], int(mode), _p(keys, torch.int32), _p(state, torch.uint8), _stream()), "pa_eval_append")
+
+
+def eval_rank(keys, state, n, ws=None):
+    """Per-class metrics of the first n columns: (n_pos, n_neg, auc_num) int64 [C] and (ap, auc) float64 [C] (pa_eval_rank).
+    ws: a uint8 workspace of at least pa_eval_ws_bytes(C, capacity) bytes to reuse, else one is allocated."""
+    if keys.dim() != 2 or state.shape != keys.shape:
+        raise _lib.PasstAmdError(f"eval_rank: keys {tuple(keys.shape)} / state {tuple(state.shape)} are not [C][capacity]")
+    Cc, cap = keys.shape
+    lib = _lib.load()
+    need = lib.pa_eval_ws_bytes(Cc, cap)
+    if need <= 0:
+        raise _lib.PasstAmdError(f"eval_rank: unsupported shape [{Cc}][{cap}]")
+    if ws is None:
+        ws = torch.empty(need, device=keys.device, dtype=torch.uint8)
+    elif ws.numel() < need:
+        raise _lib.PasstAmdError(f"eval_rank: workspace of {ws.numel()} bytes, {need} needed")
+    ints = torch.empty((3, Cc), device=keys.device, dtype=torch.int64)
+    flt = torch.empty((2, Cc), device=keys.device, dtype=torch.float64)
+    check(lib.pa_eval_rank(_p(keys, torch.int32), _p(state, torch.uint8), Cc, int(n), cap, _p(ws, torch.uint8), _p(ints[0]), _p(ints[1]),
+                           _p(ints[2]), _p(flt[0]), _p(flt[1]), _stream()), "pa_eval_rank")
+    return ints[0], ints[1], ints[2], flt[0], flt[1]
