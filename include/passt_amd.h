@@ -146,6 +146,11 @@ int pa_mel_frontend_bwd_varlen_aug(const float* wave, int B, int ldw, const int3
  * ------------------------------------------------------------------------------------------ */
 /* out[i] = (dtype) in[i] */
 int pa_convert_f32(const float* in, void* out, int64_t n, int dtype, void* stream);
+/* out[m][d] = (dtype)(rowscale[m] * in[m][d]), in [M][D] f32, D % 4 == 0: the copy of a gradient that enters a branch carrying a
+ * stochastic-depth row factor (DropPath, models/helpers/vit_helpers.py:203-222 as Block applies it to the MLP branch,
+ * models/passt.py:378-379) -- where the head's gradient enters the last block.  With dtype PA_F32 `out` is a second f32 buffer.
+ * rowscale NULL: pa_convert_f32 over M * D elements. */
+int pa_convert_f32_rowscale(const float* in, const float* rowscale, void* out, int M, int D, int dtype, void* stream);
 /* out[i] = (float) in[i], in of `dtype` (the bf16 gradient wire of the data-parallel reducer, passt_amd/ddp.py) */
 int pa_convert_to_f32(const void* in, int dtype, float* out, int64_t n, void* stream);
 /* Batched form of the two calls below, for refreshing every GEMM-ready weight copy after an optimizer
@@ -203,6 +208,20 @@ int pa_layernorm_bwd2(const void* dy, int dtype, const float* x, const float* ga
 int pa_layernorm_bwd2_partial(const void* dy, int dtype, const float* x, const float* gamma,
                               const float* mean, const float* rstd, const float* dres, const float* dres2, float* dx,
                               void* dx_lp, float* ws, int M, int D, void* stream);
+
+/* The four calls above with a per-row factor on the branch the gradient enters (stochastic depth: DropPath,
+ * models/helpers/vit_helpers.py:203-233, applied to both branches of a Block, models/passt.py:372, 378-379): rowscale[M] f32 is
+ * keep / (1 - p) of the clip the row belongs to.  dx (f32) stays the residual gradient, unscaled; the copy is
+ * dx_lp[m][:] = (dtype)(rowscale[m] * dx[m][:]) -- with dtype PA_F32 a second f32 buffer, which must not be dx -- and the third
+ * column sum (dcolsum: the branch's bias gradient) is the sum of the scaled rows.  dres2 may be NULL (the one-addend forms).
+ * dx, dgamma and dbeta are bit-identical to the call without a factor; rowscale NULL IS that call. */
+int pa_layernorm_bwd_rowscale(const void* dy, int dtype, const float* x, const float* gamma, const float* mean,
+                              const float* rstd, const float* dres, const float* dres2, const float* rowscale, float* dx,
+                              void* dx_lp, float* dgamma, float* dbeta, float* dcolsum, int accumulate, float* ws, int M,
+                              int D, void* stream);
+int pa_layernorm_bwd_partial_rowscale(const void* dy, int dtype, const float* x, const float* gamma, const float* mean,
+                                      const float* rstd, const float* dres, const float* dres2, const float* rowscale,
+                                      float* dx, void* dx_lp, float* ws, int M, int D, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * GEMM  C[M][N] = A[M][K] * B[N][K]^T  (both operands K-contiguous), MFMA, f32 accumulation.
@@ -299,6 +318,15 @@ int pa_gemm_nt(const pa_gemm_args* a, void* stream);
 int pa_gemm_nt_splitk_plan(int M, int N, int K, int epilogue, int dtype);
 int64_t pa_gemm_nt_splitk_ws_floats(int M, int N, int K, int epilogue, int dtype);
 int pa_gemm_nt_splitk(const pa_gemm_args* a, float* ws, int64_t ws_floats, void* stream);
+/* PA_EPI_RESID (row_mod == 0) with a per-row factor on the product: out_f32[m][n] = resid[m][n] + rowscale[m] * (acc + bias[n]),
+ * rowscale[M] f32 -- the branch of a Block under stochastic depth, x + drop_path(branch) (DropPath, models/helpers/vit_helpers.py:
+ * 203-233; models/passt.py:378-379), with rowscale[m] = keep / (1 - p) of row m's clip.  Kernel instantiations of their own (the
+ * generic epilogue in bf16 and f32, the role-split epilogues v2 and v3, PA_GEMM_NO_PERSIST, the split-K finishing pass): a row
+ * whose factor is 0 leaves resid as it is, a factor of 1 gives pa_gemm_nt's result bit for bit, and out_f32 may be resid.
+ * a->tune other than 1 / 6 / 7 / 8 / 17 / 18 is ignored.  rowscale NULL IS pa_gemm_nt / pa_gemm_nt_splitk.
+ * PA_EINVAL: another epilogue or the row remap with a factor. */
+int pa_gemm_nt_rowscale(const pa_gemm_args* a, const float* rowscale, void* stream);
+int pa_gemm_nt_splitk_rowscale(const pa_gemm_args* a, const float* rowscale, float* ws, int64_t ws_floats, void* stream);
 /* Weight gradient  C[a->M][a->N] = sum_{m < a->K} A[m][a->M]^T B[m][a->N]  (A = dY, B = X, both row-major
  * [tokens][features] read IN PLACE, no transposed copies).  epilogue must be PA_EPI_PARTIAL: split-K over
  * the token axis, out_f32[split_k][M][N] partial slabs, finished by pa_reduce_partials (deterministic).

@@ -65,6 +65,7 @@ SIGNATURES = {
     "pa_mel_frontend_fwd_varlen_aug": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i32, f32, C.POINTER(MelParams), vp, vp]),
     "pa_mel_frontend_bwd_varlen_aug": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, i64, C.POINTER(MelParams), vp, vp]),
     "pa_convert_f32": (i32, [vp, vp, i64, i32, vp]),
+    "pa_convert_f32_rowscale": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "pa_convert_to_f32": (i32, [vp, i32, vp, i64, vp]),
     "pa_transpose": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp]),
     "pa_stage_weights": (i32, [vp, i32, i32, i32, vp]),
@@ -75,6 +76,8 @@ SIGNATURES = {
     "pa_layernorm_bwd_partial": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "pa_layernorm_bwd2": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp]),
     "pa_layernorm_bwd2_partial": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "pa_layernorm_bwd_rowscale": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp]),
+    "pa_layernorm_bwd_partial_rowscale": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "pa_tail_inject": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp]),
     "pa_gemm_last_colsum_rows": (i32, []),
     "pa_gemm_colsum_ws_floats": (i64, [i32, i32]),
@@ -84,6 +87,8 @@ SIGNATURES = {
     "pa_gemm_nt_splitk_plan": (i32, [i32, i32, i32, i32, i32]),
     "pa_gemm_nt_splitk_ws_floats": (i64, [i32, i32, i32, i32, i32]),
     "pa_gemm_nt_splitk": (i32, [C.POINTER(GemmArgs), vp, i64, vp]),
+    "pa_gemm_nt_rowscale": (i32, [C.POINTER(GemmArgs), vp, vp]),
+    "pa_gemm_nt_splitk_rowscale": (i32, [C.POINTER(GemmArgs), vp, vp, i64, vp]),
     "pa_gemm_tn": (i32, [C.POINTER(GemmArgs), vp]),
     "pa_gemm_tn_batched": (i32, [C.POINTER(GemmArgs), i32, vp]),
     "pa_gemm_tn_batched_plan": (i32, [C.POINTER(GemmArgs), i32, i32, i32, vp]),

@@ -88,10 +88,15 @@ __device__ __forceinline__ void load_bias8(const pa_gemm_args& a, int n0, int wc
     }
 }
 
-template <typename T, int EPI, int TM = 2>
+// RS (PA_EPI_RESID without the row remap only; pa_gemm_nt_rowscale): out[m][n] = resid[m][n] + rowscale[m] * (acc + bias[n]), one f32
+// factor per output row -- the keep / (1 - p) factor of stochastic depth (DropPath, models/helpers/vit_helpers.py:203-222) on
+// the branch this GEMM adds to the residual stream.  A template instantiation of its own in every epilogue below: RS = false is
+// the code as it always was.
+template <typename T, int EPI, int TM = 2, bool RS = false>
 __device__ __forceinline__ void gemm_epilogue(const pa_gemm_args& a, f32x16 (&acc)[TM][2], float* slab, int m0,
                                               int n0, int split, int wr, int wc, int lane, const float (&bias8)[8],
-                                              int colsum_row = 0) {
+                                              int colsum_row = 0, const float* rowscale = nullptr) {
+    static_assert(!RS || EPI == PA_EPI_RESID, "row factors: the residual epilogue only");
     const int erow = lane >> 3, ecol = (lane & 7) * 8;
     const int ncol = n0 + wc * 64 + ecol;
     const bool colok = ncol < a.N;               // N % 8 == 0: the lane's 8-vector is all in or all out
@@ -164,7 +169,12 @@ __device__ __forceinline__ void gemm_epilogue(const pa_gemm_args& a, f32x16 (&ac
             for (int it = 0; it < 4; ++it) {
                 float x[8];
                 aux_val(i % P, it, x);
-                if constexpr (EPI == PA_EPI_RESID) {
+                if constexpr (EPI == PA_EPI_RESID && RS) {
+                    const int m = pass_row(i, it);
+                    const float rs = m >= 0 ? rowscale[m] : 0.f;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[it][e] = fmaf(rs, v[it][e], x[e]);
+                } else if constexpr (EPI == PA_EPI_RESID) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[it][e] += x[e];
                 } else {
@@ -343,6 +353,18 @@ static constexpr int AUX_DEPTH_R = 1;               // RESID: 32-row passes of r
 // not cover)
 __host__ __device__ __forceinline__ int64_t blocked_pre_rows(int M) { return ((int64_t)M + 767) / 768 * 768; }
 
+// (an empty base without factors: the auxiliary-row structs of the kernels without them keep the members they always had)
+template <int N> struct RowFactors { float rsv[N]; };
+template <> struct RowFactors<0> {};
+// the (TM + 1) / 2 factor loads of a wave tile whose first row is mb (V2Aux / V3Aux with RS): always emitted, like the auxiliary rows
+template <int TM>
+__device__ __forceinline__ void issue_rowscale(float (&rsv)[(TM + 1) / 2], const pa_gemm_args& a, const float* rowscale, int mb, int nb, int lane) {
+    const auto rrs = tile_rsrc(rowscale + (mb < a.M ? mb : 0), (mb < a.M && nb < a.N) ? (int64_t)(a.M - mb) * 4 : 0);
+#pragma unroll
+    for (int k = 0; k < (TM + 1) / 2; ++k)
+        rsv[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrs, (uint32_t)(k * 64 + lane) * 4u, 0, 0));
+}
+
 // Auxiliary rows of an item's epilogue (DGELU: pre-activation, RESID: residual): descriptor + the row vectors requested
 // ahead of their use.  The kernel calls issue() DURING the last K-tile of the item (the first rows come from HBM, not from
 // a cache: requested at the start of the epilogue their ~2-3k-cycle latency was exposed once per item), the epilogue
@@ -354,18 +376,24 @@ __host__ __device__ __forceinline__ int64_t blocked_pre_rows(int M) { return ((i
 // 32 j + (lane & 31) for j = q >> 1, k = 4 (q & 1) + dword).  fc1's epilogue stores it and the dgrad-fc2 epilogue loads it
 // with four 1 KiB-contiguous 16-byte-per-lane accesses per pass and NO LDS transposition on either side (nobody else
 // reads the pre-activation; both GEMMs have the same M x N and pass geometry whatever their tile height).
-template <int EPI, int TM, bool BLK = false> struct V2Aux {
+// RS: the row factors of the wave tile ride along, lane l <- rowscale[mb + 64 k + l] in rsv[k] (rows past M read as 0); the epilogue
+// hands a row's factor to the lanes that hold the row with a wave shuffle.
+template <int EPI, int TM, bool BLK = false, bool RS = false> struct V2Aux : RowFactors<RS ? (TM + 1) / 2 : 0> {
     static constexpr bool X = EPI == PA_EPI_DGELU, R = EPI == PA_EPI_RESID;
+    static_assert(!RS || R, "row factors: the residual epilogue only");
+    static constexpr int NRS = RS ? (TM + 1) / 2 : 0;
     uint32_t blk_base = 0, blk_pitch = 0;                 // BLK: byte offset of pass 0's block, bytes between passes
     static constexpr int PASSES = X ? (AUX_DEPTH_X < TM ? AUX_DEPTH_X : TM) : 0;                    // DGELU: 32-row passes in flight
     static constexpr int HALVES = R ? (AUX_DEPTH_R < TM ? 2 * AUX_DEPTH_R : 2 * TM) : 0;        // RESID: 16-row half passes
-    static constexpr int N = X ? PASSES * 4 : HALVES * 4;                                           // loads per wave in issue()
-    u32x4 v[N > 0 ? N : 1];
+    static constexpr int NV = X ? PASSES * 4 : HALVES * 4;
+    static constexpr int N = NV + NRS;                                                              // loads per wave in issue()
+    u32x4 v[NV > 0 ? NV : 1];
     decltype(tile_rsrc(nullptr, 0)) rs;
     uint32_t vofs, ld;
 
-    __device__ __forceinline__ void issue(const pa_gemm_args& a, int m0, int n0, int wr, int wc, int lane) {
-        if constexpr (N > 0) {
+    __device__ __forceinline__ void issue(const pa_gemm_args& a, int m0, int n0, int wr, int wc, int lane, const float* rowscale = nullptr) {
+        if constexpr (RS) issue_rowscale<TM>(this->rsv, a, rowscale, m0 + wr * (TM * 32), n0 + wc * 64, lane);
+        if constexpr (NV > 0) {
             const int mb = m0 + wr * (TM * 32), nb = n0 + wc * 64;
             const bool exists = mb < a.M && nb < a.N;
             if constexpr (X && BLK) {
@@ -565,9 +593,10 @@ __device__ __forceinline__ void gemm_epilogue_v2_bf16(const pa_gemm_args& a, f32
 }
 
 // f32 residual epilogue through LDS: out[m][n] = acc + bias[n] + resid[m][n]
-template <int TM>
+// RS: out[m][n] = resid[m][n] + rowscale[m] * (acc + bias[n]); the factor of a lane's row comes out of aux.rsv by a wave shuffle
+template <int TM, bool RS = false>
 __device__ __forceinline__ void gemm_epilogue_v2_resid(const pa_gemm_args& a, f32x16 (&acc)[TM][2], char* slab, const float* bias_row,
-                                                       int m0, int n0, int wr, int wc, int lane, V2Aux<PA_EPI_RESID, TM>& aux) {
+                                                       int m0, int n0, int wr, int wc, int lane, V2Aux<PA_EPI_RESID, TM, false, RS>& aux) {
     const int h = lane >> 5, c = lane & 31;
     const int mb = m0 + wr * (TM * 32), nb = n0 + wc * 64;
     if (mb >= a.M || nb >= a.N) return;
@@ -581,7 +610,7 @@ __device__ __forceinline__ void gemm_epilogue_v2_resid(const pa_gemm_args& a, f3
     const auto ors = tile_rsrc((const char*)a.out_f32 + ((int64_t)mb * a.ldo32 + nb) * 4, ((int64_t)(a.M - mb - 1) * a.ldo32 + (a.N - nb)) * 4);
     const uint32_t vo = colok ? (uint32_t)er * ldo4 + (uint32_t)sl * 16u : V2_OOB;
     // residual rows: DEPTH half passes (16 rows = 4 vectors per lane) were requested during the last K-tile (V2Aux)
-    constexpr int NH = 2 * TM, DEPTH = V2Aux<PA_EPI_RESID, TM>::HALVES;
+    constexpr int NH = 2 * TM, DEPTH = V2Aux<PA_EPI_RESID, TM, false, RS>::HALVES;
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         __builtin_amdgcn_sched_barrier(0);       // keep the passes apart (register pressure)
@@ -595,8 +624,15 @@ __device__ __forceinline__ void gemm_epilogue_v2_resid(const pa_gemm_args& a, f3
             const int hp = 2 * i + hh;
             f32x4 o[4];
 #pragma unroll
-            for (int it = 0; it < 4; ++it)
-                o[it] = *(const f32x4*)(rdbase + (hh * 4 + it) * 1024) + __builtin_bit_cast(f32x4, aux.v[(hp % DEPTH) * 4 + it]);
+            for (int it = 0; it < 4; ++it) {
+                if constexpr (RS) {              // row (i * 32 + hh * 16 + it * 4 + er) of the wave tile: lane (row & 63) of rsv[row >> 6]
+                    const float f = __shfl(aux.rsv[i >> 1], (i & 1) * 32 + hh * 16 + it * 4 + er, 64);
+                    o[it] = __builtin_elementwise_fma(f32x4{f, f, f, f}, *(const f32x4*)(rdbase + (hh * 4 + it) * 1024),
+                                                      __builtin_bit_cast(f32x4, aux.v[(hp % DEPTH) * 4 + it]));
+                } else {
+                    o[it] = *(const f32x4*)(rdbase + (hh * 4 + it) * 1024) + __builtin_bit_cast(f32x4, aux.v[(hp % DEPTH) * 4 + it]);
+                }
+            }
             __builtin_amdgcn_sched_barrier(0);   // the refill must not be hoisted above the adds (it would get fresh registers)
             if (hp + DEPTH < NH) aux.load_half(hp % DEPTH, hp + DEPTH);
 #pragma unroll
@@ -627,17 +663,21 @@ __device__ __forceinline__ void gemm_epilogue_v2_resid(const pa_gemm_args& a, f3
 // MEASURED SLOWER THAN v2 and therefore opt-in (see epilogue_v3_enabled): every store instruction covers 32 rows x 32 bytes
 // (two lanes per row) -- four partial-line requests per row where v2 sends one full line.
 // ------------------------------------------------------------------------------------------------
-template <int EPI, int TM> struct V3Aux {
+template <int EPI, int TM, bool RS = false> struct V3Aux : RowFactors<RS ? (TM + 1) / 2 : 0> {
     static constexpr bool X = EPI == PA_EPI_DGELU, R = EPI == PA_EPI_RESID;
+    static_assert(!RS || R, "row factors: the residual epilogue only");
+    static constexpr int NRS = RS ? (TM + 1) / 2 : 0;       // as V2Aux: lane l <- rowscale[mb + 64 k + l]
     static constexpr int PASSES = X ? (AUX_DEPTH_X < TM ? AUX_DEPTH_X : TM) : 0;              // DGELU: 32-row passes in flight
     static constexpr int HALVES = R ? (AUX_DEPTH_R < TM ? 2 * AUX_DEPTH_R : 2 * TM) : 0;  // RESID: 32-row x 32-column blocks in flight
-    static constexpr int N = X ? PASSES * 4 : HALVES * 4;        // loads per wave in issue(): the K loop's counted vmcnt wait relies on it
-    u32x4 v[N > 0 ? N : 1];
+    static constexpr int NV = X ? PASSES * 4 : HALVES * 4;
+    static constexpr int N = NV + NRS;        // loads per wave in issue(): the K loop's counted vmcnt wait relies on it
+    u32x4 v[NV > 0 ? NV : 1];
     decltype(tile_rsrc(nullptr, 0)) rs;
     uint32_t vofs[4], ld;       // DGELU: lane offset of chunk (j, gp) = vofs[2j + gp]; RESID: of group g = vofs[g] (block j: + 128 bytes)
 
-    __device__ __forceinline__ void issue(const pa_gemm_args& a, int m0, int n0, int wr, int wc, int lane) {
-        if constexpr (N > 0) {
+    __device__ __forceinline__ void issue(const pa_gemm_args& a, int m0, int n0, int wr, int wc, int lane, const float* rowscale = nullptr) {
+        if constexpr (RS) issue_rowscale<TM>(this->rsv, a, rowscale, m0 + wr * (TM * 32), n0 + wc * 64, lane);
+        if constexpr (NV > 0) {
             const int mb = m0 + wr * (TM * 32), nb = n0 + wc * 64;
             const bool exists = mb < a.M && nb < a.N;
             const int q = lane & 31, h = lane >> 5;
@@ -786,9 +826,10 @@ __device__ __forceinline__ void gemm_epilogue_v3_bf16(const pa_gemm_args& a, f32
 }
 
 // out[m][n] = acc + bias[n] + resid[m][n], f32, straight from / to the registers
-template <int TM>
+// RS: out[m][n] = resid[m][n] + rowscale[m] * (acc + bias[n]); lane = token, so one factor per lane per 32-row block
+template <int TM, bool RS = false>
 __device__ __forceinline__ void gemm_epilogue_v3_resid(const pa_gemm_args& a, f32x16 (&acc)[TM][2], const float* bias_row,
-                                                       int m0, int n0, int wr, int wc, int lane, V3Aux<PA_EPI_RESID, TM>& aux) {
+                                                       int m0, int n0, int wr, int wc, int lane, V3Aux<PA_EPI_RESID, TM, RS>& aux) {
     const int h = lane >> 5, q = lane & 31;
     const int mb = m0 + wr * (TM * 32), nb = n0 + wc * 64;
     if (mb >= a.M || nb >= a.N) return;
@@ -798,18 +839,22 @@ __device__ __forceinline__ void gemm_epilogue_v3_resid(const pa_gemm_args& a, f3
     uint32_t vo[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) vo[g] = (uint32_t)q * ldo4 + (uint32_t)(8 * g + 4 * h) * 4u;
-    constexpr int NH = 2 * TM, DEPTH = V3Aux<PA_EPI_RESID, TM>::HALVES;
+    constexpr int NH = 2 * TM, DEPTH = V3Aux<PA_EPI_RESID, TM, RS>::HALVES;
 #pragma unroll
     for (int hp = 0; hp < NH; ++hp) {
         const int i = hp >> 1, j = hp & 1;
         __builtin_amdgcn_sched_barrier(0);       // keep the blocks apart (register pressure: 256-row tiles spilled otherwise)
         f32x4 o[4];
+        float f = 1.f;                           // RS: row i * 32 + q of the wave tile
+        if constexpr (RS) f = __shfl(aux.rsv[i >> 1], (i & 1) * 32 + q, 64);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             // the bias of this lane's four columns: an LDS broadcast read per group, not 32 registers held across the epilogue
             const f32x4 b = bias_row ? *(const f32x4*)(bias_row + wc * 64 + j * 32 + 8 * g + 4 * h) : f32x4{0.f, 0.f, 0.f, 0.f};
             const f32x4 r = __builtin_bit_cast(f32x4, aux.v[(hp % DEPTH) * 4 + g]);
-            o[g] = f32x4{acc[i][j][4 * g] + b[0], acc[i][j][4 * g + 1] + b[1], acc[i][j][4 * g + 2] + b[2], acc[i][j][4 * g + 3] + b[3]} + r;
+            const f32x4 ab = f32x4{acc[i][j][4 * g] + b[0], acc[i][j][4 * g + 1] + b[1], acc[i][j][4 * g + 2] + b[2], acc[i][j][4 * g + 3] + b[3]};
+            if constexpr (RS) o[g] = __builtin_elementwise_fma(f32x4{f, f, f, f}, ab, r);
+            else o[g] = ab + r;
         }
         __builtin_amdgcn_sched_barrier(0);       // the refill must not be hoisted above the adds (it would get fresh registers)
         if (hp + DEPTH < NH) aux.load_half(hp % DEPTH, hp + DEPTH, ncols);
@@ -857,13 +902,31 @@ template <int KBT> __device__ __forceinline__ int swz_rows(int row) {
     else return (row >> 2) & 3;
 }
 
+// the launch arguments of a kernel instantiated with row factors (RS): pa_gemm_args itself gets no new field
+struct pa_gemm_args_rs : pa_gemm_args {
+    const float* rowscale;
+};
+template <bool RS> using gemm_kargs = std::conditional_t<RS, pa_gemm_args_rs, pa_gemm_args>;
+// A kernel with row factors is the PA_EPI_RESID kernel instantiated under an epilogue number of its own (library-internal, never in
+// pa_gemm_args.epilogue): every other instantiation keeps its template arguments, and with them its name.
+static constexpr int EPI_RESID_ROWSCALE = 5;
+__host__ __device__ constexpr bool epi_rs(int epix) { return epix == EPI_RESID_ROWSCALE; }
+__host__ __device__ constexpr int epi_base(int epix) { return epix == EPI_RESID_ROWSCALE ? (int)PA_EPI_RESID : epix; }
+template <bool RS> __device__ __forceinline__ const float* rowscale_of(const gemm_kargs<RS>& a) {
+    if constexpr (RS) return a.rowscale;
+    else return nullptr;
+}
+
 // BLK (r06): the epilogue is the role-split kernels' v2 epilogue (accumulator-layout math, packed row-pair slab, buffer
 // instructions) with the MLP pre-activation in the library's blocked layout -- what makes the blocked pre-activation reachable
 // from the tiles that fit TWO workgroups per CU (tunes 3 / 9: one workgroup's transposition + store burst under the other's K loop)
 // EPV (r06): 0 = the first-generation epilogue; 1 = epilogue v2 (row-major outputs); 2 = epilogue v2 with the blocked pre-activation
-template <typename T, int EPI, int WM, int WN, int TM, int STAGES, int KBT = KB, int EPV = 0>
-__global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu((KBT == 64 || EPV) ? 2 : 1))) void gemm_nt_kernel(const pa_gemm_args a, const int tiles_m, const int tiles_n,
+template <typename T, int EPIX, int WM, int WN, int TM, int STAGES, int KBT = KB, int EPV = 0>
+__global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu((KBT == 64 || EPV) ? 2 : 1))) void gemm_nt_kernel(const gemm_kargs<epi_rs(EPIX)> a, const int tiles_m, const int tiles_n,
                                                                const int nwg, const int ksteps_per_split) {
+    constexpr bool RS = epi_rs(EPIX);
+    constexpr int EPI = epi_base(EPIX);
+    static_assert(!RS || EPV == 0, "row factors: the first-generation epilogue");
     constexpr int TBM = WM * TM * 32, TBN = WN * 64;
     constexpr int A_BYTES = TBM * KBT, B_BYTES = TBN * KBT, STAGE_BYTES = A_BYTES + B_BYTES;
     constexpr int CPR = KBT / 16, NSUB = KBT / 32;       // 16-byte chunks per row, 16-wide k-substeps per stage
@@ -989,12 +1052,12 @@ __global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu((K
         else gemm_epilogue_v2_bf16<EPI, TM, BLKX>(a, acc, smem + wave * 8192, brow, m0, n0, wr, wc, lane, tm * WM + wr, aux);
     } else {
         __syncthreads();  // every wave is done reading the operand tiles; LDS is reused by the slabs
-        gemm_epilogue<T, EPI, TM>(a, acc, (float*)(smem + wave * SLAB_BYTES), m0, n0, blockIdx.y, wr, wc, lane, bias8, tm * WM + wr);
+        gemm_epilogue<T, EPI, TM, RS>(a, acc, (float*)(smem + wave * SLAB_BYTES), m0, n0, blockIdx.y, wr, wc, lane, bias8, tm * WM + wr, rowscale_of<RS>(a));
     }
 }
 
-template <typename T, int EPI, int WM, int WN, int TM, int STAGES, int KBT = KB, int EPV = 0>
-static int launch_gemm_v(const pa_gemm_args& a, hipStream_t st) {
+template <typename T, int EPI, int WM, int WN, int TM, int STAGES, int KBT = KB, int EPV = 0, bool RS = false>
+static int launch_gemm_v(const gemm_kargs<RS>& a, hipStream_t st) {
     constexpr int TBM = WM * TM * 32, TBN = WN * 64;
     constexpr int LDS = STAGES * (TBM + TBN) * KBT;
     static_assert(LDS <= 160 * 1024, "LDS ring too large");
@@ -1011,8 +1074,10 @@ static int launch_gemm_v(const pa_gemm_args& a, hipStream_t st) {
     const int splits = EPI == PA_EPI_PARTIAL ? a.split_k : 1;
     const int per = (int)cdiv(ksteps, splits);
     static signed char lds_attr[64] = {0};
-    (void)lds_attr_on_this_device((const void*)gemm_nt_kernel<T, EPI, WM, WN, TM, STAGES, KBT, EPV>, LDS, lds_attr);
-    hipLaunchKernelGGL((gemm_nt_kernel<T, EPI, WM, WN, TM, STAGES, KBT, EPV>), dim3(nwg, splits), dim3(WM * WN * 64), LDS, st, a,
+    static_assert(!RS || EPI == PA_EPI_RESID, "row factors: the residual epilogue only");
+    constexpr int EPIX = RS ? EPI_RESID_ROWSCALE : EPI;
+    (void)lds_attr_on_this_device((const void*)gemm_nt_kernel<T, EPIX, WM, WN, TM, STAGES, KBT, EPV>, LDS, lds_attr);
+    hipLaunchKernelGGL((gemm_nt_kernel<T, EPIX, WM, WN, TM, STAGES, KBT, EPV>), dim3(nwg, splits), dim3(WM * WN * 64), LDS, st, a,
                        tiles_m, tiles_n, nwg, per);
     const int rc = check_launch();
     if (rc == PA_OK && EPI == PA_EPI_DGELU && a.colsum_out) return finish_gemm_colsum(a, tiles_m * WM, st);
@@ -1064,10 +1129,13 @@ template <int TM, bool A3> struct StaggerGeom {
 };
 
 // TR (r04): MFMA operands swapped -> transposed accumulators (lane = token row) and the LDS-free epilogue v3 (see there)
-template <typename T, int EPI, int TM, bool A3 = false, bool BLK = false, bool TR = false>
-__global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const pa_gemm_args a, const int tiles_m, const int tiles_n,
+template <typename T, int EPIX, int TM, bool A3 = false, bool BLK = false, bool TR = false>
+__global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const gemm_kargs<epi_rs(EPIX)> a, const int tiles_m, const int tiles_n,
                                                               const int nwg, const int ksteps_per_split, const int total) {
+    constexpr bool RS = epi_rs(EPIX);
+    constexpr int EPI = epi_base(EPIX);
     using G = StaggerGeom<TM, A3>;
+    static_assert(!RS || (sizeof(T) == 2 && EPI == PA_EPI_RESID && !BLK), "row factors: the bf16 residual epilogues (v2 / v3)");
     static_assert(!TR || (sizeof(T) == 2 && EPI != PA_EPI_PARTIAL && !BLK), "v3: bf16 operands, fused epilogues, row-major pre-activation");
     constexpr int WN = 4;
     constexpr int TBM = G::TBM, TBN = G::TBN;         // TM = 2/3/4 -> 128/192/256-row tiles (tile quantisation)
@@ -1190,9 +1258,9 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const pa_gemm_args
         // saves TM x 32 v_mov per wave and item in the seam between two items
         f32x16 acc[TM][2];
         constexpr int AUX_EPI = USE_V2 ? EPI : PA_EPI_STORE;
-        std::conditional_t<TR, V3Aux<AUX_EPI, TM>, V2Aux<AUX_EPI, TM, BLK>> aux;
+        std::conditional_t<TR, V3Aux<AUX_EPI, TM, RS>, V2Aux<AUX_EPI, TM, BLK, RS>> aux;
         constexpr int AUXN = decltype(aux)::N;
-        static_assert(V3Aux<AUX_EPI, TM>::N == V2Aux<AUX_EPI, TM, false>::N, "both epilogues leave the same number of loads in flight");
+        static_assert(V3Aux<AUX_EPI, TM, RS>::N == V2Aux<AUX_EPI, TM, false, RS>::N, "both epilogues leave the same number of loads in flight");
         const int cur_m0 = m0, cur_n0 = n0, cur_split = split;
         if (wr == 1) __builtin_amdgcn_s_barrier();         // group 1 runs one barrier behind
         PA_PROBE_STAMP(round < 24, round * 16);
@@ -1244,7 +1312,7 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const pa_gemm_args
                 // last K-tile of the item: request the first auxiliary rows of its epilogue now, AFTER this tile's LDS-DMA:
                 // they land under the remaining MFMAs
                 if constexpr (USE_V2 && AUXN > 0) {
-                    if (last && ph == NPH / 2) aux.issue(a, cur_m0, cur_n0, wr, wc, lane);
+                    if (last && ph == NPH / 2) aux.issue(a, cur_m0, cur_n0, wr, wc, lane, rowscale_of<RS>(a));
                 }
                 if (ph == NPH - 1 && wr == 1) wait_tile();
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1302,9 +1370,9 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const pa_gemm_args
             const float* brow = HAS_BIAS && a.bias ? (const float*)(smem + G::BIAS_OFF) : nullptr;
             if constexpr (TR) {
                 (void)slab;
-                if constexpr (EPI == PA_EPI_RESID) gemm_epilogue_v3_resid<TM>(a, acc, brow, cur_m0, cur_n0, wr, wc, lane, aux);
+                if constexpr (EPI == PA_EPI_RESID) gemm_epilogue_v3_resid<TM, RS>(a, acc, brow, cur_m0, cur_n0, wr, wc, lane, aux);
                 else gemm_epilogue_v3_bf16<EPI, TM>(a, acc, brow, cur_m0, cur_n0, wr, wc, lane, aux);
-            } else if constexpr (EPI == PA_EPI_RESID) gemm_epilogue_v2_resid<TM>(a, acc, (char*)slab, brow, cur_m0, cur_n0, wr, wc, lane, aux);
+            } else if constexpr (EPI == PA_EPI_RESID) gemm_epilogue_v2_resid<TM, RS>(a, acc, (char*)slab, brow, cur_m0, cur_n0, wr, wc, lane, aux);
             else gemm_epilogue_v2_bf16<EPI, TM, BLK>(a, acc, (char*)slab, brow, cur_m0, cur_n0, wr, wc, lane, (cur_m0 / TBM) * 2 + wr, aux);
         } else if constexpr (EPI == PA_EPI_RESID || EPI == PA_EPI_PARTIAL) {
             (void)slab;
@@ -1353,8 +1421,8 @@ static bool epilogue_v3_enabled() {
     return on;
 }
 
-template <typename T, int EPI, int TM, bool A3 = false, bool BLK = false, bool TR = false>
-static int launch_gemm_stagger(const pa_gemm_args& a, hipStream_t st) {
+template <typename T, int EPI, int TM, bool A3 = false, bool BLK = false, bool TR = false, bool RS = false>
+static int launch_gemm_stagger(const gemm_kargs<RS>& a, hipStream_t st) {
     using G = StaggerGeom<TM, A3>;
     // the LDS-free epilogue (transposed accumulators) wherever it applies: bf16 operands, a fused epilogue, row-major
     // pre-activation, no column sums asked of the DGELU epilogue (they are lane-local only in the v2 orientation)
@@ -1362,7 +1430,7 @@ static int launch_gemm_stagger(const pa_gemm_args& a, hipStream_t st) {
     if constexpr (!TR && !BLK && sizeof(T) == 2 && EPI != PA_EPI_PARTIAL && !(EPI == PA_EPI_RESID && TM == 4)) {
         if ((epilogue_v3_enabled() || (a.reserved & PA_GEMM_EPILOGUE_V3)) && !(EPI == PA_EPI_DGELU && a.colsum_out) &&
             !(EPI == PA_EPI_RESID && a.row_mod > 0))
-            return launch_gemm_stagger<T, EPI, TM, A3, false, true>(a, st);
+            return launch_gemm_stagger<T, EPI, TM, A3, false, true, RS>(a, st);
     }
     static_assert(G::LDS <= 160 * 1024, "LDS budget");
     const int tiles_m = (int)cdiv(a.M, 64 * TM), tiles_n = (int)cdiv(a.N, 256);
@@ -1379,11 +1447,11 @@ static int launch_gemm_stagger(const pa_gemm_args& a, hipStream_t st) {
                      (int64_t)a.M * a.ldr * 4 >= lim || (int64_t)a.M * a.ldo32 * 4 >= lim;
     if (ksteps < 1 || (int64_t)(splits - 1) * per >= ksteps ||
         (sizeof(T) == 2 && EPI != PA_EPI_PARTIAL && (big || (EPI == PA_EPI_RESID && a.row_mod > 0))))
-        return BLK ? PA_EUNSUPPORTED : launch_gemm_v<T, EPI, 2, 2, 2, 2>(a, st);     // (the generic kernel has no blocked form)
+        return BLK ? PA_EUNSUPPORTED : launch_gemm_v<T, EPI, 2, 2, 2, 2, KB, 0, RS>(a, st);     // (the generic kernel has no blocked form)
     if constexpr (A3) {      // two K-tiles of lead need two K-tiles in every item; the short item table bounds the rounds
-        if (ksteps - (splits - 1) * per < 2 || per < 2 || cdiv(total, 256) > G::MAX_ROUNDS) return launch_gemm_stagger<T, EPI, TM, false, BLK, TR>(a, st);
+        if (ksteps - (splits - 1) * per < 2 || per < 2 || cdiv(total, 256) > G::MAX_ROUNDS) return launch_gemm_stagger<T, EPI, TM, false, BLK, TR, RS>(a, st);
     } else {
-        if (cdiv(total, 256) > G::MAX_ROUNDS) return BLK ? PA_EUNSUPPORTED : launch_gemm_v<T, EPI, 2, 2, 2, 2>(a, st);
+        if (cdiv(total, 256) > G::MAX_ROUNDS) return BLK ? PA_EUNSUPPORTED : launch_gemm_v<T, EPI, 2, 2, 2, 2, KB, 0, RS>(a, st);
     }
 #ifdef PA_PROBE
     constexpr int LDS_BYTES = G::LDS + 2 * PROBE_SLOTS * 8;
@@ -1392,14 +1460,16 @@ static int launch_gemm_stagger(const pa_gemm_args& a, hipStream_t st) {
 #endif
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget (probe build)");
     static signed char lds_attr[64] = {0};
-    (void)lds_attr_on_this_device((const void*)gemm_nt_stagger_kernel<T, EPI, TM, A3, BLK, TR>, LDS_BYTES, lds_attr);
+    static_assert(!RS || EPI == PA_EPI_RESID, "row factors: the residual epilogue only");
+    constexpr int EPIX = RS ? EPI_RESID_ROWSCALE : EPI;
+    (void)lds_attr_on_this_device((const void*)gemm_nt_stagger_kernel<T, EPIX, TM, A3, BLK, TR>, LDS_BYTES, lds_attr);
     // PA_GEMM_NO_PERSIST (a.reserved) / PA_NT_PERSISTENT=0: one work item per workgroup, handed out by the hardware as CUs free
     // up, instead of 256 resident workgroups walking their item lists.  The persistent form assumes it owns every CU: when
     // another kernel (an RCCL all-reduce on the communication stream) holds R of them, R of its workgroups only start after the
     // others have finished ALL their items and the launch takes twice as long; one item per workgroup degrades by R / 256.
     static const bool persist_env = [] { const char* e = getenv("PA_NT_PERSISTENT"); return !e || atoi(e) != 0; }();
     const bool persistent = persist_env && !(a.reserved & PA_GEMM_NO_PERSIST);
-    hipLaunchKernelGGL((gemm_nt_stagger_kernel<T, EPI, TM, A3, BLK, TR>), dim3(persistent ? std::min(total, 256) : total), dim3(512), LDS_BYTES, st, a,
+    hipLaunchKernelGGL((gemm_nt_stagger_kernel<T, EPIX, TM, A3, BLK, TR>), dim3(persistent ? std::min(total, 256) : total), dim3(512), LDS_BYTES, st, a,
                        tiles_m, tiles_n, nwg, per, total);
     const int rc = check_launch();
     if (rc == PA_OK && EPI == PA_EPI_DGELU && a.colsum_out) return finish_gemm_colsum(a, tiles_m * 2, st);
@@ -1492,6 +1562,31 @@ static int launch_gemm(const pa_gemm_args& a, hipStream_t st) {
             case 8: return launch_gemm_stagger<T, EPI, 2>(a, st);      // 128x256 role-split
             case 17: return launch_gemm_stagger<T, EPI, 3, true>(a, st);   // 192x256 role-split, A two K-tiles ahead (3 A slots)
             case 18: return launch_gemm_stagger<T, EPI, 2, true>(a, st);   // 128x256 role-split, A two K-tiles ahead
+        }
+        return PA_EINVAL;
+    }
+}
+
+// PA_EPI_RESID with row factors (pa_gemm_nt_rowscale): the variants the heuristic picks for a residual GEMM -- the generic kernel
+// (f32: always) and the role-split tiles with epilogue v2 or, opted in, v3 -- each as an instantiation of its own.  A forced tune
+// of another variant runs the heuristic's choice: the factor is not an A/B knob.
+template <typename T>
+static int launch_gemm_rs(const pa_gemm_args_rs& a, hipStream_t st) {
+    if constexpr (sizeof(T) == 4) return launch_gemm_v<T, PA_EPI_RESID, 2, 2, 2, 2, KB, 0, true>(a, st);
+    else {
+        int v = a.tune;
+        if (v != 1 && v != 6 && v != 7 && v != 8 && v != 17 && v != 18) {
+            v = pick_nt_variant(a.M, a.N, a.K);
+            static const bool a3 = [] { const char* e = getenv("PA_NT_A3"); return !e || atoi(e) != 0; }();
+            if (a3 && (v == 7 || v == 8)) v += 10;
+        }
+        switch (v) {
+            case 1: return launch_gemm_v<T, PA_EPI_RESID, 2, 2, 2, 2, KB, 0, true>(a, st);
+            case 6: return launch_gemm_stagger<T, PA_EPI_RESID, 4, false, false, false, true>(a, st);
+            case 7: return launch_gemm_stagger<T, PA_EPI_RESID, 3, false, false, false, true>(a, st);
+            case 8: return launch_gemm_stagger<T, PA_EPI_RESID, 2, false, false, false, true>(a, st);
+            case 17: return launch_gemm_stagger<T, PA_EPI_RESID, 3, true, false, false, true>(a, st);
+            case 18: return launch_gemm_stagger<T, PA_EPI_RESID, 2, true, false, false, true>(a, st);
         }
         return PA_EINVAL;
     }
@@ -2264,11 +2359,29 @@ __global__ void gather_rows_kernel(const char* __restrict__ in, const int32_t* _
     }
 }
 
+// out[m][:] = (T)(rowscale[m] * in[m][:]): the 16-bit (f32 mode: f32) copy of a gradient that enters a branch carrying a row factor
+// (pa_convert_f32_rowscale).  Four columns per thread and step; D % 4 == 0.
+template <typename T>
+__global__ __launch_bounds__(256) void convert_rowscale_kernel(const float* __restrict__ in, const float* __restrict__ rowscale,
+                                                               T* __restrict__ out, int M, int D) {
+    const int nv = D >> 2;
+    const int64_t total = (int64_t)M * nv;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const float f = rowscale[i / nv];
+        const f32x4 v = *(const f32x4*)(in + i * 4) * f;
+        if constexpr (sizeof(T) == 4) *(f32x4*)(out + i * 4) = v;
+        else *(uint2*)(out + i * 4) = uint2{cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3])};
+    }
+}
+
 // Finish of a split-K NT GEMM (pa_gemm_nt_splitk): out = epilogue(sum_z ws[z][m][n]) for the two epilogues whose output is
 // a plain function of the accumulator -- STORE: (acc + bias) * colscale -> bf16, RESID: acc + bias + resid -> f32.
 // One 16-byte vector of 4 columns per thread and step; N % 8 == 0.
-template <int EPI>
-__global__ void nt_splitk_finish_kernel(pa_gemm_args a, const float* __restrict__ ws, int splits) {
+// EPI_RESID_ROWSCALE: out = resid + rowscale[m] * (sum + bias), the multiply-add of the fused epilogues (pa_gemm_nt_splitk_rowscale)
+template <int EPIX>
+__global__ void nt_splitk_finish_kernel(gemm_kargs<epi_rs(EPIX)> a, const float* __restrict__ ws, int splits) {
+    constexpr bool RS = epi_rs(EPIX);
+    constexpr int EPI = epi_base(EPIX);
     const int nv = a.N >> 2;
     const int64_t total = (int64_t)a.M * nv, slab = (int64_t)a.M * a.N;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -2287,7 +2400,12 @@ __global__ void nt_splitk_finish_kernel(pa_gemm_args a, const float* __restrict_
             *(uint2*)((bf16*)a.out_lp + (int64_t)m * a.ldolp + n) = uint2{o[0], o[1]};
         } else {
             const f32x4 r = *(const f32x4*)(a.resid + (int64_t)m * a.ldr + n);
-            *(f32x4*)(a.out_f32 + (int64_t)m * a.ldo32 + n) = (v + b) + r;
+            if constexpr (RS) {
+                const float f = a.rowscale[m];
+                *(f32x4*)(a.out_f32 + (int64_t)m * a.ldo32 + n) = __builtin_elementwise_fma(f32x4{f, f, f, f}, v + b, r);
+            } else {
+                *(f32x4*)(a.out_f32 + (int64_t)m * a.ldo32 + n) = (v + b) + r;
+            }
         }
     }
 }
@@ -2296,7 +2414,8 @@ __global__ void nt_splitk_finish_kernel(pa_gemm_args a, const float* __restrict_
 
 using namespace pa;
 
-extern "C" int pa_gemm_nt(const pa_gemm_args* a, void* stream) {
+// the argument checks of pa_gemm_nt (everything but the dispatch)
+static int check_gemm_nt_args(const pa_gemm_args* a) {
     if (!a || !a->A || !a->B || a->M <= 0 || a->N <= 0 || a->K <= 0) return PA_EINVAL;
     const size_t es = a->dtype == PA_BF16 ? 2 : 4;
     if ((a->K * es) % KB) return PA_EUNSUPPORTED;
@@ -2312,6 +2431,25 @@ extern "C" int pa_gemm_nt(const pa_gemm_args* a, void* stream) {
     if (a->aux && a->ldaux % 8) return PA_EUNSUPPORTED;
     if (a->colsum_out && (a->epilogue != PA_EPI_DGELU || !a->colsum_ws)) return PA_EINVAL;
     if (a->colscale_n && (a->epilogue != PA_EPI_STORE || a->colscale_n < 0 || a->colscale_n % 64)) return PA_EINVAL;
+    return PA_OK;
+}
+
+extern "C" int pa_gemm_nt_rowscale(const pa_gemm_args* a, const float* rowscale, void* stream) {
+    if (!rowscale) return pa_gemm_nt(a, stream);
+    const int rc = check_gemm_nt_args(a);
+    if (rc != PA_OK) return rc;
+    if (a->epilogue != PA_EPI_RESID || a->row_mod > 0 || !a->out_f32 || !a->resid) return PA_EINVAL;
+    pa_gemm_args_rs r;
+    static_cast<pa_gemm_args&>(r) = *a;
+    r.rowscale = rowscale;
+    if (a->dtype == PA_BF16) return launch_gemm_rs<bf16>(r, (hipStream_t)stream);
+    if (a->dtype == PA_F32) return launch_gemm_rs<float>(r, (hipStream_t)stream);
+    return PA_EINVAL;
+}
+
+extern "C" int pa_gemm_nt(const pa_gemm_args* a, void* stream) {
+    const int rc = check_gemm_nt_args(a);
+    if (rc != PA_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (a->dtype == PA_BF16) return dispatch_gemm<bf16>(*a, st);
     if (a->dtype == PA_F32) return dispatch_gemm<float>(*a, st);
@@ -2347,10 +2485,22 @@ extern "C" int64_t pa_gemm_nt_splitk_ws_floats(int M, int N, int K, int epilogue
     return s > 1 ? (int64_t)s * M * N : 0;
 }
 
+static int gemm_nt_splitk(const pa_gemm_args* a, const float* rowscale, float* ws, int64_t ws_floats, void* stream);
+
 extern "C" int pa_gemm_nt_splitk(const pa_gemm_args* a, float* ws, int64_t ws_floats, void* stream) {
+    return gemm_nt_splitk(a, nullptr, ws, ws_floats, stream);
+}
+
+extern "C" int pa_gemm_nt_splitk_rowscale(const pa_gemm_args* a, const float* rowscale, float* ws, int64_t ws_floats, void* stream) {
+    if (rowscale && (!a || a->epilogue != PA_EPI_RESID || a->row_mod > 0)) return PA_EINVAL;
+    return gemm_nt_splitk(a, rowscale, ws, ws_floats, stream);
+}
+
+// rowscale (PA_EPI_RESID only, checked by the caller): NULL is pa_gemm_nt_splitk as it always was
+static int gemm_nt_splitk(const pa_gemm_args* a, const float* rowscale, float* ws, int64_t ws_floats, void* stream) {
     if (!a) return PA_EINVAL;
     const int s = (a->row_mod > 0 || a->split_k > 1 || a->tune) ? 1 : pa_gemm_nt_splitk_plan(a->M, a->N, a->K, a->epilogue, a->dtype);
-    if (s <= 1 || !ws || ws_floats < (int64_t)s * a->M * a->N) return pa_gemm_nt(a, stream);
+    if (s <= 1 || !ws || ws_floats < (int64_t)s * a->M * a->N) return rowscale ? pa_gemm_nt_rowscale(a, rowscale, stream) : pa_gemm_nt(a, stream);
     if (a->epilogue == PA_EPI_STORE ? !a->out_lp || a->ldolp % 8 : (!a->out_f32 || !a->resid || a->ldo32 % 4 || a->ldr % 4)) return PA_EINVAL;
     if (a->colscale_n && (a->epilogue != PA_EPI_STORE || a->colscale_n < 0 || a->colscale_n % 64)) return PA_EINVAL;
     pa_gemm_args p = *a;
@@ -2365,11 +2515,16 @@ extern "C" int pa_gemm_nt_splitk(const pa_gemm_args* a, float* ws, int64_t ws_fl
     p.tune = v == 6 ? 6 : v + 10;            // the 192- / 128-row tiles with A two K-tiles ahead where a slice allows it
     int rc = pa_gemm_nt(&p, stream);
     // drop-in for pa_gemm_nt: a shape the partial form does not cover runs unsplit instead of failing
-    if (rc == PA_EUNSUPPORTED || rc == PA_EINVAL) return pa_gemm_nt(a, stream);
+    if (rc == PA_EUNSUPPORTED || rc == PA_EINVAL) return rowscale ? pa_gemm_nt_rowscale(a, rowscale, stream) : pa_gemm_nt(a, stream);
     if (rc != PA_OK) return rc;
     const int64_t vecs = (int64_t)a->M * (a->N / 4);
     const int blocks = (int)std::min<int64_t>(cdiv(vecs, 256), 2048);
-    if (a->epilogue == PA_EPI_STORE)
+    if (rowscale) {
+        pa_gemm_args_rs r;
+        static_cast<pa_gemm_args&>(r) = *a;
+        r.rowscale = rowscale;
+        hipLaunchKernelGGL(nt_splitk_finish_kernel<EPI_RESID_ROWSCALE>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, r, ws, s);
+    } else if (a->epilogue == PA_EPI_STORE)
         hipLaunchKernelGGL(nt_splitk_finish_kernel<PA_EPI_STORE>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a, ws, s);
     else
         hipLaunchKernelGGL(nt_splitk_finish_kernel<PA_EPI_RESID>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a, ws, s);
@@ -2382,6 +2537,18 @@ extern "C" int pa_convert_f32(const float* in, void* out, int64_t n, int dtype, 
     const int blocks = (int)std::min<int64_t>(cdiv(n, 1024), 4096);
     if (dtype == PA_BF16) hipLaunchKernelGGL(convert_kernel<bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, (bf16*)out, n);
     else if (dtype == PA_F32) hipLaunchKernelGGL(convert_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, (float*)out, n);
+    else return PA_EINVAL;
+    return check_launch();
+}
+
+extern "C" int pa_convert_f32_rowscale(const float* in, const float* rowscale, void* out, int M, int D, int dtype, void* stream) {
+    if (!rowscale) return (M < 0 || D < 0) ? PA_EINVAL : pa_convert_f32(in, out, (int64_t)M * D, dtype, stream);
+    if (!in || !out || M < 0 || D <= 0) return PA_EINVAL;
+    if (D % 4) return PA_EUNSUPPORTED;
+    if (M == 0) return PA_OK;
+    const int blocks = (int)std::min<int64_t>(cdiv((int64_t)M * (D / 4), 256), 4096);
+    if (dtype == PA_BF16) hipLaunchKernelGGL(convert_rowscale_kernel<bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, rowscale, (bf16*)out, M, D);
+    else if (dtype == PA_F32) hipLaunchKernelGGL(convert_rowscale_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, rowscale, (float*)out, M, D);
     else return PA_EINVAL;
     return check_launch();
 }

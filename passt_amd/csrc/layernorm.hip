@@ -83,13 +83,17 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 // column sums of dy*xhat (dgamma) and dy (dbeta) go to ws[block][2][D].
 // ADD2: a second addend dres2 (the gradient a caller injects into the residual stream at this block boundary) joins dx before
 // the 16-bit copy and the column sums are taken, so both see it.  ADD2 = false is the kernel as it always was (dres2 is not read).
-template <typename T, int MAXV, bool ADD2>
+// RS: a row factor rowscale[row] (stochastic depth's keep / (1 - p) of the branch this gradient enters, DropPath,
+// models/helpers/vit_helpers.py:203-222) scales the COPY dx_lp and the third column sum (that branch's bias gradient); dx itself stays
+// the residual gradient, unscaled.  With T = float the copy is a second f32 buffer.  RS = false is the kernel as it always was.
+template <typename T, int MAXV, bool ADD2, bool RS = false>
 __device__ __forceinline__ void ln_bwd_body(const T* __restrict__ dy, const float* __restrict__ x,
                                                      const float* __restrict__ gamma, const float* __restrict__ mean,
                                                      const float* __restrict__ rstd, const float* __restrict__ dres,
                                                      const float* __restrict__ dres2,
                                                      float* __restrict__ dx, T* __restrict__ dx_lp,
-                                                     float* __restrict__ ws, int M, int D, float* red) {
+                                                     float* __restrict__ ws, int M, int D, float* red,
+                                                     const float* __restrict__ rowscale = nullptr) {
     // ws[block][3][D]: partial column sums of dy*xhat (dgamma), dy (dbeta) and of the OUTPUT dx (the bias gradient
     // of the Linear that produced this LayerNorm's input: proj for norm2, the previous block's fc2 for norm1)
     // red: dynamic LDS [4][3][D]
@@ -106,6 +110,8 @@ __device__ __forceinline__ void ln_bwd_body(const T* __restrict__ dy, const floa
     }
     for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
         const float mu = mean[row], r = rstd[row];
+        float f = 1.f;
+        if constexpr (RS) f = rowscale[row];
         const int64_t base = (int64_t)row * D;
         float4 xh[MAXV], gy[MAXV];
         float s1 = 0.f, s2 = 0.f;
@@ -142,6 +148,7 @@ __device__ __forceinline__ void ln_bwd_body(const T* __restrict__ dy, const floa
                 {
                     *(float4*)(dx + base + 4 * c) = o;
                 }
+                if constexpr (RS) { o.x *= f; o.y *= f; o.z *= f; o.w *= f; }     // dx is stored: from here on the scaled copy
                 if (dx_lp) store4<T>(dx_lp + base + 4 * c, o);
                 ac[i].x += o.x; ac[i].y += o.y; ac[i].z += o.z; ac[i].w += o.w;
             }
@@ -187,6 +194,18 @@ __global__ __launch_bounds__(256) void ln_bwd2_kernel(const T* __restrict__ dy, 
                                                       float* __restrict__ ws, int M, int D) {
     extern __shared__ __attribute__((aligned(16))) float red[];   // [4][3][D]
     ln_bwd_body<T, MAXV, true>(dy, x, gamma, mean, rstd, dres, dres2, dx, dx_lp, ws, M, D, red);
+}
+
+// the forms with a row factor (pa_layernorm_bwd*_rowscale), with and without the second addend: kernels of their own
+template <typename T, int MAXV, bool ADD2>
+__global__ __launch_bounds__(256) void ln_bwd_rs_kernel(const T* __restrict__ dy, const float* __restrict__ x,
+                                                        const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                        const float* __restrict__ rstd, const float* __restrict__ dres,
+                                                        const float* __restrict__ dres2, const float* __restrict__ rowscale,
+                                                        float* __restrict__ dx, T* __restrict__ dx_lp,
+                                                        float* __restrict__ ws, int M, int D) {
+    extern __shared__ __attribute__((aligned(16))) float red[];   // [4][3][D]
+    ln_bwd_body<T, MAXV, ADD2, true>(dy, x, gamma, mean, rstd, dres, dres2, dx, dx_lp, ws, M, D, red, rowscale);
 }
 
 // out[which][c] (+)= sum_b ws[b][which][c], which = dgamma | dbeta | dcol(optional);  block = 16 columns x 16 row
@@ -258,7 +277,8 @@ extern "C" int64_t pa_layernorm_bwd_ws_floats(int M, int D) { return (int64_t)ln
 extern "C" int pa_layernorm_bwd_rows(int M) { return M > 0 ? ln_bwd_blocks(M) : 0; }
 
 static int ln_bwd_launch(const void* dy, int dtype, const float* x, const float* gamma, const float* mean, const float* rstd,
-                         const float* dres, const float* dres2, float* dx, void* dx_lp, float* ws, int M, int D, hipStream_t st);
+                         const float* dres, const float* dres2, float* dx, void* dx_lp, float* ws, int M, int D, hipStream_t st,
+                         const float* rowscale = nullptr);
 
 extern "C" int pa_layernorm_bwd_partial(const void* dy, int dtype, const float* x, const float* gamma,
                                         const float* mean, const float* rstd, const float* dres, float* dx,
@@ -280,12 +300,12 @@ extern "C" int pa_layernorm_bwd2_partial(const void* dy, int dtype, const float*
 
 static int ln_bwd_finish(const void* dy, int dtype, const float* x, const float* gamma, const float* mean, const float* rstd,
                          const float* dres, const float* dres2, float* dx, void* dx_lp, float* dgamma, float* dbeta, float* dcolsum,
-                         int accumulate, float* ws, int M, int D, void* stream) {
+                         int accumulate, float* ws, int M, int D, void* stream, const float* rowscale = nullptr) {
     if (!dy || !x || !gamma || !mean || !rstd || !dx || !dgamma || !dbeta || !ws || M <= 0 || D <= 0) return PA_EINVAL;
     if (D % 4 || D > LN_MAXV * 256) return PA_EUNSUPPORTED;
     if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    int rc = ln_bwd_launch(dy, dtype, x, gamma, mean, rstd, dres, dres2, dx, dx_lp, ws, M, D, st);
+    int rc = ln_bwd_launch(dy, dtype, x, gamma, mean, rstd, dres, dres2, dx, dx_lp, ws, M, D, st, rowscale);
     if (rc) return rc;
     hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((unsigned)cdiv(3 * D, 16)), dim3(256), 0, st, ws, ln_bwd_blocks(M), D, dgamma, dbeta, dcolsum, accumulate);
     return check_launch();
@@ -305,8 +325,27 @@ extern "C" int pa_layernorm_bwd(const void* dy, int dtype, const float* x, const
     return ln_bwd_finish(dy, dtype, x, gamma, mean, rstd, dres, nullptr, dx, dx_lp, dgamma, dbeta, dcolsum, accumulate, ws, M, D, stream);
 }
 
+extern "C" int pa_layernorm_bwd_rowscale(const void* dy, int dtype, const float* x, const float* gamma, const float* mean,
+                                         const float* rstd, const float* dres, const float* dres2, const float* rowscale, float* dx,
+                                         void* dx_lp, float* dgamma, float* dbeta, float* dcolsum, int accumulate, float* ws, int M,
+                                         int D, void* stream) {
+    if (rowscale && dx_lp == (void*)dx) return PA_EINVAL;       // the scaled copy needs a buffer of its own (f32 mode too)
+    return ln_bwd_finish(dy, dtype, x, gamma, mean, rstd, dres, dres2, dx, dx_lp, dgamma, dbeta, dcolsum, accumulate, ws, M, D, stream, rowscale);
+}
+
+extern "C" int pa_layernorm_bwd_partial_rowscale(const void* dy, int dtype, const float* x, const float* gamma, const float* mean,
+                                                 const float* rstd, const float* dres, const float* dres2, const float* rowscale,
+                                                 float* dx, void* dx_lp, float* ws, int M, int D, void* stream) {
+    if (!dy || !x || !gamma || !mean || !rstd || !dx || !ws || M <= 0 || D <= 0) return PA_EINVAL;
+    if (D % 4 || D > LN_MAXV * 256) return PA_EUNSUPPORTED;
+    if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
+    if (rowscale && dx_lp == (void*)dx) return PA_EINVAL;
+    return ln_bwd_launch(dy, dtype, x, gamma, mean, rstd, dres, dres2, dx, dx_lp, ws, M, D, (hipStream_t)stream, rowscale);
+}
+
 static int ln_bwd_launch(const void* dy, int dtype, const float* x, const float* gamma, const float* mean, const float* rstd,
-                         const float* dres, const float* dres2, float* dx, void* dx_lp, float* ws, int M, int D, hipStream_t st) {
+                         const float* dres, const float* dres2, float* dx, void* dx_lp, float* ws, int M, int D, hipStream_t st,
+                         const float* rowscale) {
     const int nblk = ln_bwd_blocks(M);
     const size_t lds = (size_t)12 * D * sizeof(float);
     const int nvl = (int)cdiv(D, 256);
@@ -316,9 +355,17 @@ static int ln_bwd_launch(const void* dy, int dtype, const float* x, const float*
     // it without: profiles/row_kernel_parity.txt; another device or runtime need not).  The attribute is decided once per device
     // and instantiation (one state array each), so it is asked for with the most that instantiation ever requests (D = 256 V),
     // which covers every later width; a device that refuses it cannot run these widths
+#define PA_LN_BWD_RS(T, V, ADD2)                                                                                  \
+    do {                                                                                                          \
+        static signed char lds_attr_rs[64] = {0};                                                                 \
+        if (lds > 64 * 1024 && !lds_attr_on_this_device((const void*)ln_bwd_rs_kernel<T, V, ADD2>, 12 * 256 * V * (int)sizeof(float), lds_attr_rs)) return PA_EUNSUPPORTED; \
+        hipLaunchKernelGGL((ln_bwd_rs_kernel<T, V, ADD2>), dim3(nblk), dim3(256), lds, st, (const T*)dy, x, gamma, mean, rstd, dres, dres2, rowscale, dx, (T*)dx_lp, ws, M, D); \
+    } while (0)
 #define PA_LN_BWD_T(T, V)                                                                                         \
     do {                                                                                                          \
-        if (dres2) {                                                                                              \
+        if (rowscale) {                                                                                           \
+            if (dres2) PA_LN_BWD_RS(T, V, true); else PA_LN_BWD_RS(T, V, false);                                  \
+        } else if (dres2) {                                                                                              \
             static signed char lds_attr2[64] = {0};                                                               \
             if (lds > 64 * 1024 && !lds_attr_on_this_device((const void*)ln_bwd2_kernel<T, V>, 12 * 256 * V * (int)sizeof(float), lds_attr2)) return PA_EUNSUPPORTED; \
             hipLaunchKernelGGL((ln_bwd2_kernel<T, V>), dim3(nblk), dim3(256), lds, st, (const T*)dy, x, gamma, mean, rstd, dres, dres2, dx, (T*)dx_lp, ws, M, D); \
@@ -336,5 +383,6 @@ static int ln_bwd_launch(const void* dy, int dtype, const float* x, const float*
     else if (nvl == 4) PA_LN_BWD(4); else PA_LN_BWD(8);
 #undef PA_LN_BWD
 #undef PA_LN_BWD_T
+#undef PA_LN_BWD_RS
     return check_launch();
 }

@@ -277,7 +277,22 @@ def mel_frontend_bwd_varlen_aug(wave, lens_dev, clip_dev, window, bin_mel, twidd
 
 
 # ---- staging ---------------------------------------------------------------------------------
-def convert(x_f32, dtype):
+def _rowscale(rowscale, M, what):
+    """A row-factor argument: None, or one f32 per row, contiguous."""
+    if rowscale is not None and (rowscale.dtype != torch.float32 or rowscale.shape != (M,) or not rowscale.is_contiguous()):
+        raise _lib.PasstAmdError(f"{what}: rowscale must be a contiguous f32 [{M}] tensor, got {rowscale.dtype} {tuple(rowscale.shape)}")
+    return rowscale
+
+
+def convert(x_f32, dtype, rowscale=None):
+    """The copy of ``x_f32`` the next GEMM reads.  ``rowscale`` ([M] f32, x_f32 [M][D]): out[m] = rowscale[m] * x_f32[m] -- the gradient
+    entering a branch that carries a stochastic-depth row factor; always a fresh buffer, in f32 mode too."""
+    if rowscale is not None:
+        M, D = x_f32.shape
+        out = torch.empty((M, D), device=x_f32.device, dtype=TORCH_DTYPE[dtype])
+        check(_lib.load().pa_convert_f32_rowscale(_p(x_f32, torch.float32), _p(_rowscale(rowscale, M, "convert"), torch.float32), _p(out), M, D,
+                                                  dtype, _stream()), "pa_convert_f32_rowscale")
+        return out
     if dtype == PA_F32:
         return x_f32
     out = torch.empty(x_f32.shape, device=x_f32.device, dtype=TORCH_DTYPE[dtype])
@@ -361,10 +376,38 @@ def layernorm_fwd(x, gamma, beta, eps, dtype, save_stats=True):
     return y, mean, rstd
 
 
-def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, want_lp, accumulate=False, dcolsum=None, defer=None):
+def _layernorm_bwd_rowscale(dy, x, gamma, mean, rstd, dres, dres2, rowscale, dgamma, dbeta, want_lp, accumulate, dcolsum, defer):
+    """layernorm_bwd / layernorm_bwd2 with a row factor: dx stays unscaled, the copy (a second f32 buffer in f32 mode) and dcolsum are
+    those of rowscale[m] * dx[m]."""
+    M, D = x.shape
+    dtype = PA_DTYPE[dy.dtype]
+    lib = _lib.load()
+    _rowscale(rowscale, M, "layernorm_bwd")
+    dx = torch.empty((M, D), device=x.device, dtype=torch.float32)
+    dx_lp = torch.empty((M, D), device=x.device, dtype=dy.dtype) if (want_lp or dtype == PA_F32) else None
+    ws = torch.empty(lib.pa_layernorm_bwd_ws_floats(M, D), device=x.device, dtype=torch.float32)
+    lead = (_p(dy), dtype, _p(x, torch.float32), _p(gamma, torch.float32), _p(mean, torch.float32), _p(rstd, torch.float32),
+            _p(dres, torch.float32), _p(dres2, torch.float32), _p(rowscale, torch.float32), _p(dx), _p(dx_lp))
+    if defer is not None and not accumulate:
+        check(lib.pa_layernorm_bwd_partial_rowscale(*lead, _p(ws), M, D, _stream()), "pa_layernorm_bwd_partial_rowscale")
+        rows = lib.pa_layernorm_bwd_rows(M)
+        for j, out in enumerate((dgamma, dbeta, dcolsum)):
+            if out is not None:
+                defer.append((ws[j * D:], rows, 3 * D, D, out))
+        return dx, dx_lp
+    check(lib.pa_layernorm_bwd_rowscale(*lead, _p(dgamma), _p(dbeta), _p(dcolsum), int(accumulate), _p(ws), M, D, _stream()),
+          "pa_layernorm_bwd_rowscale")
+    return dx, dx_lp
+
+
+def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, want_lp, accumulate=False, dcolsum=None, defer=None, rowscale=None):
     """Returns (dx f32, dx_lp or None).  dgamma/dbeta (and dcolsum = column sums of dx, if given) are written in place.
     defer: a list -- the parameter gradients stay as partial rows and (partial, rows, pitch, n, out) jobs are appended to it for
-    the block's ONE finishing launch (wgrad_tn_batched(..., row_jobs=defer)) instead of a reduction launch per LayerNorm."""
+    the block's ONE finishing launch (wgrad_tn_batched(..., row_jobs=defer)) instead of a reduction launch per LayerNorm.
+    rowscale ([M] f32): the factor of the branch the gradient enters (stochastic depth); dx stays the residual gradient, dx_lp --
+    in f32 mode a second f32 buffer -- and dcolsum are those of rowscale[m] * dx[m]."""
+    if rowscale is not None:
+        return _layernorm_bwd_rowscale(dy, x, gamma, mean, rstd, dres, None, rowscale, dgamma, dbeta, want_lp, accumulate, dcolsum, defer)
     M, D = x.shape
     dtype = PA_DTYPE[dy.dtype]
     lib = _lib.load()
@@ -386,14 +429,18 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, want_lp, accumu
     return dx, (dx if dtype == PA_F32 else dx_lp)
 
 
-def layernorm_bwd2(dy, x, gamma, mean, rstd, dres, dres2, dgamma, dbeta, want_lp, accumulate=False, dcolsum=None, defer=None):
+def layernorm_bwd2(dy, x, gamma, mean, rstd, dres, dres2, dgamma, dbeta, want_lp, accumulate=False, dcolsum=None, defer=None,
+                   rowscale=None):
     """layernorm_bwd with a second addend: dx = dres + dres2 + LN'(dy) -- ``dres2`` [M][D] f32 is a gradient injected into the
-    residual stream at this LayerNorm's input; the 16-bit copy and ``dcolsum`` include it.  Same returns and ``defer`` contract."""
+    residual stream at this LayerNorm's input; the 16-bit copy and ``dcolsum`` include it.  Same returns, ``defer`` and ``rowscale``
+    contract (the injected gradient joins dx before the scaling)."""
     M, D = x.shape
     dtype = PA_DTYPE[dy.dtype]
     lib = _lib.load()
     if dres2 is None or dres2.shape != (M, D):
         raise _lib.PasstAmdError(f"layernorm_bwd2: dres2 must be an f32 [{M}][{D}] tensor")
+    if rowscale is not None:
+        return _layernorm_bwd_rowscale(dy, x, gamma, mean, rstd, dres, dres2, rowscale, dgamma, dbeta, want_lp, accumulate, dcolsum, defer)
     dx = torch.empty((M, D), device=x.device, dtype=torch.float32)
     dx_lp = torch.empty((M, D), device=x.device, dtype=dy.dtype) if (want_lp and dtype != PA_F32) else None
     ws = torch.empty(lib.pa_layernorm_bwd_ws_floats(M, D), device=x.device, dtype=torch.float32)
@@ -420,9 +467,10 @@ _TUNE_BY_EPI = {EPI_STORE: int(os.environ.get("PASST_AMD_TUNE_STORE", "0")), EPI
 
 def gemm_nt(A, B, dtype, epilogue=EPI_STORE, bias=None, resid=None, aux=None, out_f32=None, out_lp=None,
             out_lp2=None, row_mod=0, out_batch_rows=0, out_row_off=0, split_k=1, M=None, N=None, K=None,
-            colsum_out=None, colsum_ws=None, colsum_accumulate=False, flags=0, colscale_n=0, colscale=1.0, tune=None):
+            colsum_out=None, colsum_ws=None, colsum_accumulate=False, flags=0, colscale_n=0, colscale=1.0, tune=None, rowscale=None):
     """C[M][N] = A[M][K] B[N][K]^T with the fused epilogues of include/passt_amd.h.  EPI_DGELU can also return the
-    column sums of its output (colsum_out [N] f32; colsum_ws from gemm_colsum_ws)."""
+    column sums of its output (colsum_out [N] f32; colsum_ws from gemm_colsum_ws).  rowscale ([M] f32, EPI_RESID without the row
+    remap): out_f32[m] = resid[m] + rowscale[m] * (A B^T + bias)[m] (pa_gemm_nt_rowscale / pa_gemm_nt_splitk_rowscale)."""
     a = GemmArgs()
     a.dtype, a.epilogue = dtype, epilogue
     a.M = A.shape[0] if M is None else M
@@ -454,8 +502,20 @@ def gemm_nt(A, B, dtype, epilogue=EPI_STORE, bias=None, resid=None, aux=None, ou
     if epilogue in (EPI_STORE, EPI_RESID) and dtype == PA_BF16 and row_mod == 0 and split_k == 1 and not tune:
         ws_n = _splitk_ws_floats(a.M, a.N, a.K, epilogue, dtype)
 
+    if rowscale is not None:
+        if epilogue != EPI_RESID or row_mod:
+            raise _lib.PasstAmdError("gemm_nt: rowscale goes with EPI_RESID without the row remap")
+        _rowscale(rowscale, a.M, "gemm_nt")
+
     def launch():
-        if ws_n:
+        if rowscale is not None:
+            rs = _p(rowscale, torch.float32)
+            if ws_n:
+                ws = _splitk_ws(A.device, ws_n)
+                check(_lib.load().pa_gemm_nt_splitk_rowscale(C.byref(a), rs, ws.data_ptr(), ws_n, _stream()), "pa_gemm_nt_splitk_rowscale")
+            else:
+                check(_lib.load().pa_gemm_nt_rowscale(C.byref(a), rs, _stream()), "pa_gemm_nt_rowscale")
+        elif ws_n:
             ws = _splitk_ws(A.device, ws_n)
             check(_lib.load().pa_gemm_nt_splitk(C.byref(a), ws.data_ptr(), ws_n, _stream()), "pa_gemm_nt_splitk")
         else:
@@ -468,7 +528,9 @@ def gemm_nt(A, B, dtype, epilogue=EPI_STORE, bias=None, resid=None, aux=None, ou
     ev0.record()
     launch()
     ev1.record()
-    kind = _EPI_NAME[epilogue] if not PROFILE_BY_SHAPE else f"{_EPI_NAME[epilogue]}_M{a.M}_N{a.N}_K{a.K}"
+    kind = _EPI_NAME[epilogue] + ("_rowscale" if rowscale is not None else "")
+    if PROFILE_BY_SHAPE:
+        kind = f"{kind}_M{a.M}_N{a.N}_K{a.K}"
     GEMM_PROFILE.setdefault(kind, []).append((ev0, ev1, 2.0 * a.M * a.N * a.K))
 
 
@@ -566,11 +628,14 @@ def dgelu_gemm(dy_lp, Wt_lp, pre, dtype, colsum_out=None, colsum_ws=None, defer=
     return d_pre
 
 
-def linear_resid(x_lp, W_lp, bias, resid_f32, dtype, out=None):
-    """out_f32[M][N] = resid + x W^T + b"""
+def linear_resid(x_lp, W_lp, bias, resid_f32, dtype, out=None, rowscale=None):
+    """out_f32[M][N] = resid + x W^T + b; with rowscale ([M] f32): resid[m] + rowscale[m] * (x W^T + b)[m]"""
     if out is None:
         out = torch.empty_like(resid_f32)
-    gemm_nt(x_lp, W_lp, dtype, EPI_RESID, bias=bias, resid=resid_f32, out_f32=out)
+    if rowscale is None:
+        gemm_nt(x_lp, W_lp, dtype, EPI_RESID, bias=bias, resid=resid_f32, out_f32=out)
+    else:
+        gemm_nt(x_lp, W_lp, dtype, EPI_RESID, bias=bias, resid=resid_f32, out_f32=out, rowscale=rowscale)
     return out
 
 

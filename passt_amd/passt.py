@@ -84,13 +84,33 @@ class Mlp(nn.Module):
         self.drop = nn.Dropout(drop)
 
 
+class DropPath(nn.Module):
+    """Stochastic depth per sample (models/helpers/vit_helpers.py:203-233): holds the rate.  The kernel sequence reads ``drop_prob`` and
+    never calls ``forward`` -- the factor rides in the residual GEMM's epilogue (drop_path_draws, _forward_trunk); ``forward`` is the
+    reference's own arithmetic in plain torch, for hooks and CPU use.  No parameters, no buffers."""
+
+    def __init__(self, drop_prob=None):
+        super().__init__()
+        self.drop_prob = drop_prob
+
+    def forward(self, x):
+        if not self.drop_prob or not self.training:
+            return x
+        keep = 1 - self.drop_prob
+        mask = (keep + torch.rand((x.shape[0],) + (1,) * (x.ndim - 1), dtype=x.dtype, device=x.device)).floor_()
+        return x.div(keep) * mask
+
+    def extra_repr(self):
+        return f"drop_prob={self.drop_prob}"
+
+
 class Block(nn.Module):
     def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, drop=0., attn_drop=0., drop_path=0.,
                  act_layer=nn.GELU, norm_layer=nn.LayerNorm):
         super().__init__()
         self.norm1 = norm_layer(dim)
         self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop)
-        self.drop_path = nn.Identity()
+        self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()      # one module for both branches (:372)
         self.norm2 = norm_layer(dim)
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
 
@@ -562,7 +582,73 @@ class _Fwd(NamedTuple):
         return cls(logits, feat, None, hidden, maps, next(it, None), roll)
 
 
-def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, rollout=None):
+# --------------------------------------------------------------------------------------------
+# stochastic depth (DropPath, models/helpers/vit_helpers.py:203-233; models/passt.py:372, 378-379, 444-448)
+# --------------------------------------------------------------------------------------------
+def drop_path_rates(model):
+    """Per block: the drop probability of its DropPath in training mode, 0.0 for an Identity, a rate of 0 and in eval mode."""
+    if not model.training:
+        return [0.0] * len(model.blocks)
+    return [float(getattr(blk.drop_path, "drop_prob", 0.0) or 0.0) for blk in model.blocks]
+
+
+def drop_path_draws(model, B, device):
+    """The factors of one training forward, (depth, 2, B) f32 on ``device``: [i, 0] the attention branch of block i, [i, 1] its MLP
+    branch, entry b = floor(keep + u) / keep of clip b -- 1 / keep (kept) or 0 (dropped) -- and 1 for a block without an active
+    DropPath.  u is drawn as the reference's modules draw it: one ``torch.rand((B, 1, 1), dtype=torch.float32, device=device)`` call
+    per active module call, blocks ascending, attention branch then MLP branch, so ``device``'s generator is consumed exactly as the
+    reference consumes it in fp32.  (Under autocast the reference's branch output is 16-bit and it draws in that type; this path
+    always draws f32: the masks then differ from the reference's under the same seed, their distribution does not.)  Eval mode or
+    no active module: all ones, nothing drawn."""
+    rates = drop_path_rates(model)
+    out = torch.ones((len(rates), 2, B), dtype=torch.float32, device=device)
+    for i, p in enumerate(rates):
+        if p > 0.0:
+            keep = 1 - p
+            for j in range(2):
+                u = torch.rand((B, 1, 1), dtype=torch.float32, device=device)
+                out[i, j] = ((keep + u).floor_() / keep).view(B)
+    return out
+
+
+def drop_path_scales(model, masks, B, device):
+    """``drop_path_masks`` -- (depth, 2, B) keep flags, 1 keep / 0 drop, any dtype or device -- as drop_path_draws' factors: flag / keep
+    for an active module, 1 elsewhere (entries of inactive modules are ignored).  Nothing is drawn."""
+    rates = drop_path_rates(model)
+    m = torch.as_tensor(masks)
+    if tuple(m.shape) != (len(rates), 2, B):
+        raise ValueError(f"drop_path_masks must have shape (depth, 2, B) = {(len(rates), 2, B)}, got {tuple(m.shape)}")
+    m = m.to(device=device, dtype=torch.float32)
+    active = torch.tensor([p > 0.0 for p in rates], device=device).view(-1, 1, 1)
+    keep = torch.tensor([1 - p for p in rates], dtype=torch.float32, device=device).view(-1, 1, 1)
+    return torch.where(active, m, torch.ones_like(m)) / keep
+
+
+class _DropRows:
+    """A forward's drop-path factors per ROW, expanded once: ``full`` (depth, 2, M) for launches over all token rows (``ntok`` rows per
+    clip), ``tail`` (2, 2 B) for the last block on the compact prefix rows (2 per clip); ``active``: the blocks with a factor."""
+
+    def __init__(self, scales, rates, ntok):
+        self.active = [p > 0.0 for p in rates]
+        self.full = scales.repeat_interleave(ntok, dim=2).contiguous()
+        self.tail = scales[-1].repeat_interleave(2, dim=1).contiguous()
+
+    def rows(self, i, branch, compact=False):
+        """block i's factor rows for its attention (0) / MLP (1) branch, or None when the block has none"""
+        if i < 0 or not self.active[i]:
+            return None
+        return self.tail[branch] if compact else self.full[i, branch]
+
+
+def _drop_rows(model, lay, scales):
+    """_DropRows of a fixed-layout forward from its (depth, 2, B) factors, or None when no DropPath is active (rate 0, eval)."""
+    rates = drop_path_rates(model)
+    if scales is None or not any(p > 0.0 for p in rates):
+        return None
+    return _DropRows(scales, rates, lay.Ntok)
+
+
+def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, rollout=None, drop=None):
     """Token matrix xs [M][D] f32 in layout ``lay`` -> blocks -> tail -> head.  Returns a _Fwd (tok_offsets left to the caller); ctx
     (``save`` only) is what _backward_trunk needs plus ``patch``, the entry path's own state for its patch-stage backward.
     ``hidden`` (parse_hidden's tuple or None): the token outputs to hand out, in that order -- a block's output is the f32
@@ -576,7 +662,9 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, roll
     duration of the call and, behind the last block, runs the chain r <- 0.5 r + 0.5 r A_l from the one-hot cls / dist rows, last block
     first, one pa_attention_rollout step per block; the prefix-only tail's block enters with its two query rows and its own two-row
     lse, which is exact because the start rows are one-hot in the prefix.  A _RolloutRequest ("cam") only gets its start rows here: the
-    chain rides with the backward (_backward_trunk)."""
+    chain rides with the backward (_backward_trunk).
+    ``drop`` (a _DropRows or None): stochastic depth -- both residual GEMMs of a block with a factor add rowscale[m] * branch[m]; a
+    block without one, and every block when ``drop`` is None, makes exactly the calls it always made."""
     st = model._staged
     D, H = model.embed_dim, model.num_heads
     scale = (D // H) ** -0.5
@@ -614,10 +702,14 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, roll
                 maps[bi] = lay.attention_probs(qkv, lse, H, scale, 2, amean, aflags)
         if bi >= roll_first:
             roll_keep.append((qkv, lse, None if (not last or full_tail) else 2))
-        x_mid = ops.linear_resid(att, st.get(blk.attn.proj.weight, dt, False), blk.attn.proj.bias, x_res, dt)
+        compact = last and not full_tail
+        # stochastic depth: the keyword goes only to a block that has a factor
+        kw_a = {} if drop is None or drop.rows(bi, 0) is None else dict(rowscale=drop.rows(bi, 0, compact))
+        kw_m = {} if drop is None or drop.rows(bi, 1) is None else dict(rowscale=drop.rows(bi, 1, compact))
+        x_mid = ops.linear_resid(att, st.get(blk.attn.proj.weight, dt, False), blk.attn.proj.bias, x_res, dt, **kw_a)
         ln2, mean2, rstd2 = ops.layernorm_fwd(x_mid, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, save)
         h_pre, h_act = ops.linear_gelu(ln2, st.get(blk.mlp.fc1.weight, dt, False), blk.mlp.fc1.bias, dt)
-        x_out = ops.linear_resid(h_act, st.get(blk.mlp.fc2.weight, dt, False), blk.mlp.fc2.bias, x_mid, dt)
+        x_out = ops.linear_resid(h_act, st.get(blk.mlp.fc2.weight, dt, False), blk.mlp.fc2.bias, x_mid, dt, **kw_m)
         if save:
             saved.append((xs, ln1, mean1, rstd1, qkv, att, lse, x_mid, ln2, mean2, rstd2, h_pre, h_act))
         if bi in want:
@@ -647,6 +739,8 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, roll
             roll = lay.attention_rollout(qkv, lse, roll, H, scale, 0.5, 0.5, nq, aflags)
     # tail: None = the prefix-only tail; else the full tail's own state (the last block's output, the final norm's row statistics)
     ctx = dict(dt=dt, lay=lay, scale=scale, saved=saved, xl=xl, feat=feat, hn=hn, stats=stats, patch=patch, tail=tail) if save else None
+    if save and drop is not None:
+        ctx["drop"] = drop
     return _Fwd(logits, feat, ctx, tuple(lay.hidden_view(outs[k]) for k in want), tuple(maps[k] for k in amaps), roll=roll)
 
 
@@ -666,28 +760,34 @@ def patchout_draws(model, x_shape):
     return dict(pf=pf_np, pt=pt_np, toff=toff, Np=pf_np.size)
 
 
-def passt_forward(model, x, save, draws=None, hidden=None, attn=None):
+def passt_forward(model, x, save, draws=None, hidden=None, attn=None, drop_path_masks=None):
     """Kernel sequence of PaSST.forward (:576-595).  Returns (logits, features, ctx).  ``draws``: device-resident Patchout
-    draws {pf, pt, pt_pos (= pt + time offset), Np} prepared by the caller (captured-graph mode); None = draw here.
+    draws {pf, pt, pt_pos (= pt + time offset), Np} prepared by the caller (captured-graph mode) -- with an active DropPath also
+    ``dp``, drop_path_draws' (depth, 2, B) factors; None = draw here.
     ``hidden`` (parse_hidden's tuple): returns (logits, features, ctx, hs), hs = the (B, Ntok, D) f32 token outputs asked for.
-    ``attn`` (parse_attn's triple): returns (logits, features, ctx, hs, maps), maps = the attention maps asked for."""
-    r = _run_forward(model, x, None, save, draws, hidden, attn)
+    ``attn`` (parse_attn's triple): returns (logits, features, ctx, hs, maps), maps = the attention maps asked for.
+    ``drop_path_masks`` ((depth, 2, B) keep flags): used in place of the stochastic-depth draws (PaSST.forward)."""
+    r = _run_forward(model, x, None, save, draws, hidden, attn, drop_path_masks=drop_path_masks)
     out = (r.logits, r.feat, r.ctx)
     if hidden is not None or attn is not None:
         out += (list(r.hidden),)
     return out if attn is None else out + (list(r.maps),)
 
 
-def _run_forward(model, x, lengths=None, save=False, draws=None, hidden=None, attn=None, rollout=None):
+def _run_forward(model, x, lengths=None, save=False, draws=None, hidden=None, attn=None, rollout=None, drop_path_masks=None):
     """The one way into the kernel sequence of a forward: the fixed path, or with ``lengths`` the packed one, under this model's GEMM
     flags.  Returns the _Fwd."""
+    if lengths is not None and any(p > 0.0 for p in drop_path_rates(model)):
+        raise NotImplementedError("PaSST.forward(x, lengths=...) in training mode with drop_path_rate > 0 is not supported: the draw "
+                                  "order that gives every clip the masks it would get alone at batch size 1 is not decided yet "
+                                  "(train with equal-length batches, or with drop_path_rate = 0 on ragged ones)")
     with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
         if lengths is None:
-            return _passt_forward(model, x, save, draws, hidden, attn, rollout)
+            return _passt_forward(model, x, save, draws, hidden, attn, rollout, drop_path_masks)
         return _passt_forward_varlen(model, x, lengths, save, hidden, attn, rollout)
 
 
-def _passt_forward(model, x, save, draws=None, hidden=None, attn=None, rollout=None):
+def _passt_forward(model, x, save, draws=None, hidden=None, attn=None, rollout=None, drop_path_masks=None):
     x, dt = _checked_input(model, x, True)
     B, Cin, F, T = x.shape
     P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
@@ -699,6 +799,15 @@ def _passt_forward(model, x, save, draws=None, hidden=None, attn=None, rollout=N
     else:
         pf, pt, pt_pos, toff, Np = draws["pf"], draws["pt"], draws["pt_pos"], 0, draws["Np"]
     D, Ntok = model.embed_dim, Np + 2
+    # stochastic depth: behind the Patchout draws, as the reference's blocks run behind its patch stage
+    scales = None
+    if any(p > 0.0 for p in drop_path_rates(model)):
+        if drop_path_masks is not None:
+            scales = drop_path_scales(model, drop_path_masks, B, x.device)
+        elif draws is not None and draws.get("dp") is not None:
+            scales = draws["dp"]
+        else:
+            scales = drop_path_draws(model, B, x.device)
 
     # patch embedding: gather-first im2col GEMM, epilogue adds bias + time/freq positional rows and
     # scatters to token rows 2.. ; rows 0,1 = cls/dist + new_pos_embed                 (:323,:527-564)
@@ -710,7 +819,11 @@ def _passt_forward(model, x, save, draws=None, hidden=None, attn=None, rollout=N
                 row_mod=Np, out_batch_rows=Ntok, out_row_off=2)
     # pt_grid: the kept patches' own grid columns (pt may carry the time-positional offset); F, T: the input gradient's shape
     patch = dict(Np=Np, pf=pf, pt=pt_pos, pt_grid=pt, toff=toff, F=F, T=T, cols=cols) if save else None
-    return _forward_trunk(model, _FixedLayout(model, B, Ntok), tok.view(B * Ntok, D), dt, save, patch, hidden, attn, rollout)
+    lay = _FixedLayout(model, B, Ntok)
+    drop = _drop_rows(model, lay, scales)
+    if drop is None:
+        return _forward_trunk(model, lay, tok.view(B * Ntok, D), dt, save, patch, hidden, attn, rollout)
+    return _forward_trunk(model, lay, tok.view(B * Ntok, D), dt, save, patch, hidden, attn, rollout, drop=drop)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1000,8 +1113,18 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
     forward handed out that fed the loss; an output that did not is simply absent.  A
     block's enters the residual stream where that block's output gradient is formed: inside the next block's norm1 backward (its
     second addend; the 16-bit copy and the column sums = this block's fc2.bias gradient see it), or, for the last block of a full
-    tail, in pa_tail_inject together with the final norm's backward and the head's prefix-row gradient."""
+    tail, in pa_tail_inject together with the final norm's backward and the head's prefix-row gradient.
+    ``ctx["drop"]`` (a _DropRows, put there by a forward with an active DropPath): the gradient that enters a branch carries that
+    branch's row factor -- block i's norm2 backward scales its copy and column sums (proj) by block i's attention factor, block i's
+    norm1 backward by block i - 1's MLP factor (fc2 of block i - 1), the head's gradient enters the last block's MLP branch through a
+    scaled copy; dx, the residual gradient, is never scaled.  Everything downstream of a copy (d_pre, d_att, the attention backward,
+    the maps' gradients, the weight and bias gradients) sees the scaled gradient by construction."""
     dt, lay, st, scratch = ctx["dt"], ctx["lay"], model._staged, model._scratch
+    drop = ctx.get("drop")
+
+    def factor(i, branch, compact=False):       # the keyword goes only to a launch whose branch has a factor
+        rows = None if drop is None else drop.rows(i, branch, compact)
+        return {} if rows is None else dict(rowscale=rows)
     B, D, H = lay.B, model.embed_dim, model.num_heads
     g, rowjobs = wg.g, wg.rowjobs
     # head: logits = hn W^T + b ; hn = LN_1e-5(feat) ; feat = mean of the two normed prefix tokens
@@ -1027,10 +1150,12 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
     wg.report(nblk)
     if tail is None:
         dx = dxl.view(2 * B, D)             # gradient w.r.t. the compact (prefix-rows) output of the last block
-        dx_lp = ops.convert(dx, dt)
+        dx_lp = ops.convert(dx, dt, **factor(nblk - 1, 1, True))
     else:
         # FULL TAIL: gradient w.r.t. all M rows of the last block's output, f32 and 16-bit, in one pass
         dx, dx_lp = ops.tail_inject(dxl.view(2 * B, D), lay.prefix_rows(dxl.device), lay.M, dh.get(nblk - 1), d_norm, dt)
+        if factor(nblk - 1, 1):             # the copy that enters the last block's MLP branch carries that branch's factor
+            dx_lp = ops.convert(dx, dt, **factor(nblk - 1, 1))
     for i in range(nblk - 1, -1, -1):
         blk = model.blocks[i]
         last = i == nblk - 1
@@ -1054,7 +1179,8 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
         ops.gemm_nt(d_pre, st.get(blk.mlp.fc1.weight, dt, True), dt, EPI_STORE, out_lp=d_ln2)
         del d_pre
         dx, dx_lp = ops.layernorm_bwd(d_ln2, x_mid, blk.norm2.weight, mean2, rstd2, dx, g[pfx + "norm2.weight"],
-                                      g[pfx + "norm2.bias"], True, dcolsum=g[pfx + "attn.proj.bias"], defer=rowjobs)
+                                      g[pfx + "norm2.bias"], True, dcolsum=g[pfx + "attn.proj.bias"], defer=rowjobs,
+                                      **factor(i, 0, prefix_tail))
         # ---- attention:  x_mid = x_in + proj(attn(qkv(LN1(x_in))))      (proj.bias gradient came out of LN2' above)
         wg.launch(dx_lp, att, g[pfx + "attn.proj.weight"], None)
         d_att = torch.empty_like(att)
@@ -1082,10 +1208,12 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
         if inject is None:
             dx, dx_lp = ops.layernorm_bwd(d_ln1, xs, blk.norm1.weight, mean1, rstd1, dres, g[pfx + "norm1.weight"],
                                           g[pfx + "norm1.bias"], i > 0 or lay.dx0_lp,
-                                          dcolsum=g[f"blocks.{i - 1}.mlp.fc2.bias"] if i > 0 else None, defer=rowjobs)
+                                          dcolsum=g[f"blocks.{i - 1}.mlp.fc2.bias"] if i > 0 else None, defer=rowjobs,
+                                          **factor(i - 1, 1))
         else:
             dx, dx_lp = ops.layernorm_bwd2(d_ln1, xs, blk.norm1.weight, mean1, rstd1, dres, inject, g[pfx + "norm1.weight"],
-                                           g[pfx + "norm1.bias"], True, dcolsum=g[f"blocks.{i - 1}.mlp.fc2.bias"], defer=rowjobs)
+                                           g[pfx + "norm1.bias"], True, dcolsum=g[f"blocks.{i - 1}.mlp.fc2.bias"], defer=rowjobs,
+                                           **factor(i - 1, 1))
         # last weight gradient of the block; the side stream (ordered after the LayerNorm gradients above)
         # then reports the block complete, so its all-reduce bucket starts without stalling the main stream
         wg.launch(d_qkv, ln1, g[pfx + "attn.qkv.weight"], g[pfx + "attn.qkv.bias"], done=i)
@@ -1212,9 +1340,10 @@ class _PasstFunction(torch.autograd.Function):
     non-differentiable (on the packed path one flat buffer per map); the backward ignores their (None) gradients."""
 
     @staticmethod
-    def forward(ctx, model, lengths, hidden, attn, rollout, x, *params):
+    def forward(ctx, model, lengths, hidden, attn, rollout, drop_path_masks, x, *params):
         req = attn if isinstance(attn, _AttnGradRequest) else None        # the maps' gradients were asked for as well
-        r = _run_forward(model, x, lengths, True, hidden=hidden, attn=attn if req is None else req.triple, rollout=rollout)
+        r = _run_forward(model, x, lengths, True, hidden=hidden, attn=attn if req is None else req.triple, rollout=rollout,
+                         drop_path_masks=drop_path_masks)
         # the integer row offsets of the packed path are non-differentiable as they are
         ctx.mark_non_differentiable(*r.maps, *(() if r.roll is None else (r.roll,)))
         ctx.rollout = rollout if isinstance(rollout, _RolloutRequest) else None   # "cam": the backward runs the chain
@@ -1222,8 +1351,8 @@ class _PasstFunction(torch.autograd.Function):
         ctx.attn_grad = req
         # the input spectrogram's gradient is computed only when asked for; a graph none of whose parameters requires a gradient
         # (a frozen loss network) runs the backward without any weight-gradient work
-        ctx.want_dx = bool(ctx.needs_input_grad[5])
-        ctx.frozen = not any(ctx.needs_input_grad[6:])
+        ctx.want_dx = bool(ctx.needs_input_grad[6])
+        ctx.frozen = not any(ctx.needs_input_grad[7:])
         ctx.named, ctx.total = model._graph_params(validate=False)     # the list forward() just handed to apply()
         # bound to a passt_amd.optim.AdamW (PaSST.bind_flat_grads): the only input is a token; the backward writes the gradients
         # straight into the optimizer's persistent flat buffer -- p.grad are views of it -- and hands autograd nothing
@@ -1238,7 +1367,8 @@ class _PasstFunction(torch.autograd.Function):
             raise RuntimeError("passt_amd.PaSST: the saved activations of this forward were already consumed by a backward "
                                "pass (retain_graph / double backward are not supported: run the forward again)")
         run_backward = passt_backward_varlen if ctx.varlen else passt_backward
-        lead = (None, None, None, None, None)   # the model, the lengths, the hidden request, the attention-map request, the rollout request
+        # the model, the lengths, the hidden request, the attention-map request, the rollout request, the drop-path masks
+        lead = (None, None, None, None, None, None)
         dev = c["feat"].device
         # gradients of the token outputs that fed the loss, as [M][D] rows (an unused one arrives as None and costs nothing)
         dhidden = {k: d.contiguous().view(c["lay"].M, -1) for k, d in zip(ctx.hidden or (), dhs) if d is not None}
@@ -1357,9 +1487,9 @@ class PaSST(nn.Module):
         if not distilled:
             raise NotImplementedError("passt_amd covers the distilled (cls+dist token) PaSST archs -- every "
                                       "arch get_model() can return (models/passt.py:963-1008)")
-        if in_chans != 1 or drop_rate or attn_drop_rate or drop_path_rate or mlp_ratio != 4. or not qkv_bias \
-                or representation_size:
-            raise NotImplementedError("passt_amd hot path: in_chans=1, no dropout/drop-path, mlp_ratio=4, qkv_bias")
+        if in_chans != 1 or drop_rate or attn_drop_rate or mlp_ratio != 4. or not qkv_bias or representation_size:
+            raise NotImplementedError("passt_amd hot path: in_chans=1, no dropout (drop_rate / attn_drop_rate; stochastic depth, "
+                                      "drop_path_rate, is covered), mlp_ratio=4, qkv_bias")
         if embed_dim % num_heads or embed_dim // num_heads != 64:
             raise NotImplementedError("attention kernels are built for head_dim 64 (768/12, 1024/16, 384/6 ...)")
         self.num_classes = num_classes
@@ -1377,9 +1507,10 @@ class PaSST(nn.Module):
         self.freq_new_pos_embed = nn.Parameter(torch.zeros(1, embed_dim, self.patch_embed.grid_size[0], 1))
         self.time_new_pos_embed = nn.Parameter(torch.zeros(1, embed_dim, 1, self.patch_embed.grid_size[1]))
         self.pos_drop = nn.Dropout(p=drop_rate)
+        dpr = [r.item() for r in torch.linspace(0, drop_path_rate, depth)]      # stochastic depth decay rule (:444)
         self.blocks = nn.Sequential(*[
-            Block(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, norm_layer=norm_layer,
-                  act_layer=act_layer) for _ in range(depth)])
+            Block(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, drop_path=dpr[i], norm_layer=norm_layer,
+                  act_layer=act_layer) for i in range(depth)])
         self.norm = norm_layer(embed_dim)
         self.pre_logits = nn.Identity()
         self.head = nn.Sequential(nn.LayerNorm(self.num_features),
@@ -1545,7 +1676,7 @@ class PaSST(nn.Module):
 
     @compile_opaque
     def forward(self, x, lengths=None, hidden=None, attn=None, attn_rows="all", attn_heads="each", attn_grad=None, rollout=None,
-                rollout_from=0):
+                rollout_from=0, drop_path_masks=None):
         """x: (B,1,F,T) -> (logits (B,C), features (B,D)); always a tuple (models/passt.py:588,595).  With the keywords below:
         ``(logits, features[, hidden][, attn][, roll][, tok_offsets])``, tok_offsets whenever ``lengths`` comes with ``hidden``, ``attn``
         or ``rollout``.
@@ -1610,6 +1741,17 @@ class PaSST(nn.Module):
         of ``attn`` / ``attn_grad``; everything else the call returns or accumulates is bit for bit what it is without ``rollout``.
         Any other value, a ``rollout_from`` that is no int or out of range, or one without ``rollout`` raises ValueError before
         anything is launched or drawn.  Not taken by TrainStep or captured graphs.
+
+        Stochastic depth (``drop_path_rate > 0`` at construction): in training mode every clip keeps or drops each branch of each
+        block with an active ``DropPath`` -- kept: scaled by 1 / (1 - p), dropped: contributes nothing, forward and backward, that
+        branch's weight and bias gradients included.  The draws are the reference's: per active module call one
+        ``torch.rand((B, 1, 1), dtype=torch.float32, device=x.device)``, blocks ascending, attention branch then MLP branch, behind
+        the Patchout draws (``drop_path_draws``); under autocast the reference would draw in the 16-bit type, this path always
+        draws f32.  ``drop_path_masks`` (a (depth, 2, B) tensor of keep flags, 1 keep / 0 drop, [i, 0] the attention branch of block
+        i, [i, 1] its MLP branch): used in place of the draws -- nothing is drawn; entries of blocks without an active ``DropPath``
+        are ignored -- which is how a recorded run is replayed.  Ignored in eval mode, where, as at rate 0, the network launches
+        exactly what it launches without stochastic depth.  With ``lengths`` in training mode an active ``DropPath`` raises
+        NotImplementedError.  ``drop_rate`` / ``attn_drop_rate`` (element-wise dropout) are not covered: the constructor raises.
 
         An ``x`` that requires a gradient gets one (``x.grad`` / ``torch.autograd.grad``), as in the reference: PaSST as a
         differentiable loss network.  With every parameter frozen (``net.requires_grad_(False)``) this needs no switch and the backward
@@ -1706,14 +1848,17 @@ class PaSST(nn.Module):
                 fl = None
             # bound (same validated parameter list as at bind time): the single token stands for every parameter
             params = (fl["token"],) if fl is not None else [p for _, p in named]
-            r = _Fwd.from_flat(_PasstFunction.apply(self, lengths, hid, amap if agrad is None else req, roll, x, *params), len(hid or ()),
+            r = _Fwd.from_flat(_PasstFunction.apply(self, lengths, hid, amap if agrad is None else req, roll, drop_path_masks, x, *params), len(hid or ()),
                                len(amap[0]) if amap else 0, roll is not None)
         elif lengths is None and hid is None and amap is None and roll is None:
+            if drop_path_masks is not None:
+                return passt_forward(self, x, save=False, drop_path_masks=drop_path_masks)[:2]
             return passt_forward(self, x, save=False)[:2]       # the plain call stays on the public entry (callers stand in for it)
         else:
             # the ragged forward records nothing unless asked to; the fixed one leaves that to the caller's own grad mode
             with torch.no_grad() if lengths is not None else contextlib.nullcontext():
-                r = _run_forward(self, x, lengths, hidden=hid, attn=amap, rollout=roll)
+                r = _run_forward(self, x, lengths, hidden=hid, attn=amap, rollout=roll,
+                                 **({} if drop_path_masks is None else dict(drop_path_masks=drop_path_masks)))
         res = self._outputs(r, hid, amap)
         if agrad is not None:
             req.targets = list(res[2 if hid is None else 3])      # the tensors the caller holds: the backward fills their .grad

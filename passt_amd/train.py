@@ -14,7 +14,7 @@ import torch
 
 from . import ops
 from .ddp import GradReducer
-from .passt import _precision, passt_backward, passt_forward, patchout_draws
+from .passt import _precision, drop_path_draws, drop_path_rates, passt_backward, passt_forward, patchout_draws
 
 
 class TrainStep:
@@ -24,7 +24,9 @@ class TrainStep:
         per-bucket optimizer launches (~290 of the step's ~300 launches) are captured once as a hipGraph (torch.cuda.CUDAGraph)
         and replayed; only the front end, mixup and the uploads of the step's host-drawn arrays stay eager.  Same kernels, same
         arguments, bit-identical parameters (tests/test_gpu_model.py::test_train_step_graph_equals_eager); what changes is the
-        host: one replay instead of ~290 ctypes launches -- it matters where the step is short (ESC-50 at batch 12)."""
+        host: one replay instead of ~290 ctypes launches -- it matters where the step is short (ESC-50 at batch 12).
+        Stochastic depth (a net built with drop_path_rate > 0): the step's factors are drawn on the device ahead of the replay
+        (passt.drop_path_draws, where the eager forward draws them) into a buffer of fixed address next to the Patchout indices."""
         self.net, self.mel = net, mel
         self.lr, self.wd, self.betas, self.eps, self.optimizer = lr, weight_decay, betas, eps, optimizer
         self.mixup_alpha, self.use_mixup = mixup_alpha, use_mixup
@@ -155,6 +157,8 @@ class TrainStep:
         g["pf"].copy_(ops.upload_small(d["pf"], x.device))
         g["pt"].copy_(ops.upload_small(d["pt"], x.device))
         g["pt_pos"].copy_(ops.upload_small(d["pt"] + np.int32(d["toff"]), x.device))
+        if g["dp"] is not None:
+            g["dp"].copy_(d["dp"])          # stochastic depth: the step's factors, drawn on the device ahead of the replay
         # (through the pinned ring like the index arrays: a fixed host buffer could be rewritten for step k + 1 before the
         # asynchronous copy of step k has read it)
         ops.adamw_hyper(self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self._t_now, g["hyper_host"])
@@ -251,6 +255,8 @@ class TrainStep:
             lam_d = None
         self._t_now = self.t + 1
         d = patchout_draws(net, x.shape)                     # the Patchout draws of this step, where passt_forward would draw them
+        if any(p > 0.0 for p in drop_path_rates(net)):       # ... and behind them the stochastic-depth draws, as passt_forward orders them
+            d["dp"] = drop_path_draws(net, x.shape[0], x.device)
         g = self._g
         if g is None or "graph" not in g:
             if g is None:
@@ -258,7 +264,8 @@ class TrainStep:
                          pf=torch.empty(d["Np"], device=x.device, dtype=torch.int32), pt=torch.empty(d["Np"], device=x.device, dtype=torch.int32),
                          pt_pos=torch.empty(d["Np"], device=x.device, dtype=torch.int32), y=torch.empty_like(y),
                          y2=None if y2 is None else torch.empty_like(y2), lam=None if lam_d is None else torch.empty_like(lam_d),
-                         hyper=torch.empty(7, device=x.device, dtype=torch.float32), hyper_host=torch.empty(7, dtype=torch.float32))
+                         hyper=torch.empty(7, device=x.device, dtype=torch.float32), hyper_host=torch.empty(7, dtype=torch.float32),
+                         dp=torch.empty_like(d["dp"]) if "dp" in d else None)
                 self._g = g
             self._graph_fill(g, d, x, y, y2, lam_d)
             net.mark_params_updated()                        # the staged weight copies are stale: their refresh launch is captured too
