@@ -699,6 +699,19 @@ typedef struct pa_adamw_stage_desc {
 int pa_adamw_stage(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, int n_desc, int total_items,
                    int dtype, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                    const float* hyper_dev, void* stream);
+/* Parameter groups (torch.optim.AdamW param_groups: layer-wise learning-rate decay, no weight decay on biases / norms / position
+ * tables) in the same one launch per bucket.  `scales` (DEVICE memory, 8-byte aligned, n_desc pairs of floats, parallel to `descs`):
+ * entry i is updated with lr * scales[2 i] and weight_decay * scales[2 i + 1], lr and weight_decay being the launch's own -- by value
+ * or, with hyper_dev, the device row's, so a captured launch keeps following the schedule.  A pair of ones is bit-identical to
+ * pa_adamw_stage; lr_scale = 0 leaves the parameter (and its copies' values) unchanged while its moments still advance.
+ * pa_adamw_stage_groups: pa_adamw_stage with `scales`.  pa_adamw_groups: the plain form -- the same table, no copies written (dst /
+ * dst_t are not looked at: every entry counts ceil(rows * cols / 4096) work items in tile_begin / total_items). */
+int pa_adamw_stage_groups(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, const float* scales,
+                          int n_desc, int total_items, int dtype, float lr, float beta1, float beta2, float eps, float weight_decay,
+                          int step, const float* hyper_dev, void* stream);
+int pa_adamw_groups(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, const float* scales, int n_desc,
+                    int total_items, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                    const float* hyper_dev, void* stream);
 /* torch.optim.SGD lr only (ex_audioset.py:392 model_speed_test) */
 int pa_sgd(float* p, const float* g, int64_t n, float lr, void* stream);
 /* Stochastic weight averaging step on flat buffers (helpers/swa_callback.py:246-268, update_parameters + avg_fn):

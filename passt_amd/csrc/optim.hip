@@ -106,25 +106,71 @@ template <typename TO> __device__ __forceinline__ void st_bf16x4(TO* p, const f3
     *(bf16x4*)p = bf16x4{(bf16)w[0], (bf16)w[1], (bf16)w[2], (bf16)w[3]};
 }
 
-template <typename TO>
-__global__ __launch_bounds__(256) void adamw_stage_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                          float* __restrict__ v, const pa_adamw_stage_desc* __restrict__ descs,
-                                                          int n_desc, const float* __restrict__ hy_dev, AdamwHyper hv) {
-    __shared__ float tile[64][65];
-    __shared__ int s_entry;
-    const int bid = blockIdx.x, tid = threadIdx.x;
-    if (tid < 64) {                // one wave scans the (short) table: the last entry with tile_begin <= bid
+// the last table entry with tile_begin <= bid, found by one wave (the table is short) and handed to the block through LDS
+__device__ __forceinline__ int adamw_find_entry(const pa_adamw_stage_desc* __restrict__ descs, int n_desc, int bid, int* s_entry) {
+    const int tid = threadIdx.x;
+    if (tid < 64) {
         int found = -1;
         for (int e = tid; e < n_desc; e += 64)
             if (descs[e].tile_begin <= bid) found = e;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) found = max(found, __shfl_xor(found, o, 64));
-        if (tid == 0) s_entry = found;
+        if (tid == 0) *s_entry = found;
     }
     __syncthreads();
-    const pa_adamw_stage_desc d = descs[s_entry];
+    return *s_entry;
+}
+// a parameter without copies (biases, LayerNorm, positional tables, the f32 head): work item t is a run of 4096 consecutive elements
+__device__ __forceinline__ void adamw_run(float* pp, const float* gp, float* mp, float* vp, int64_t n, int t, bool aligned,
+                                          const AdamwHyper& h) {
+    const int tid = threadIdx.x;
+    const int64_t i0 = (int64_t)t * 4096, i1 = min(i0 + 4096, n);
+    if (aligned) {
+        for (int64_t i = i0 + tid * 4; i < i1; i += 1024) {
+            if (i + 4 <= i1) {
+                f32x4 pv = *(f32x4*)(pp + i), mv = *(f32x4*)(mp + i), vv = *(f32x4*)(vp + i);
+                const f32x4 gv = *(const f32x4*)(gp + i);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float pe = pv[e], me = mv[e], ve = vv[e];
+                    adamw_one(pe, gv[e], me, ve, h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
+                    pv[e] = pe; mv[e] = me; vv[e] = ve;
+                }
+                *(f32x4*)(pp + i) = pv; *(f32x4*)(mp + i) = mv; *(f32x4*)(vp + i) = vv;
+            } else {
+                for (int64_t k = i; k < i1; ++k) adamw_one(pp[k], gp[k], mp[k], vp[k], h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
+            }
+        }
+    } else {
+        for (int64_t i = i0 + tid; i < i1; i += 256) adamw_one(pp[i], gp[i], mp[i], vp[i], h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
+    }
+}
+// the hyper-parameters of one launch (by value, or the 7-float row in device memory) for table entry ``entry``: with parameter groups
+// (``scales``: one (lr_scale, wd_scale) pair per descriptor) lr and weight decay are those of the launch times the entry's pair, so a
+// captured launch follows the schedule through the device row while every parameter keeps its own factor
+template <bool GROUPS>
+__device__ __forceinline__ AdamwHyper adamw_hyper_of(const AdamwHyper& hv, const float* __restrict__ hy_dev, const float2* __restrict__ scales,
+                                                     int entry) {
     AdamwHyper h = hv;
     if (hy_dev) { h.lr = hy_dev[0]; h.b1 = hy_dev[1]; h.b2 = hy_dev[2]; h.eps = hy_dev[3]; h.wd = hy_dev[4]; h.bc1 = hy_dev[5]; h.bc2_sqrt = hy_dev[6]; }
+    if constexpr (GROUPS) {
+        const float2 s = scales[entry];
+        h.lr *= s.x;
+        h.wd *= s.y;
+    }
+    return h;
+}
+
+template <typename TO, bool GROUPS>
+__device__ __forceinline__ void adamw_stage_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                 float* __restrict__ v, const pa_adamw_stage_desc* __restrict__ descs, int n_desc,
+                                                 const float* __restrict__ hy_dev, const AdamwHyper& hv, const float2* __restrict__ scales) {
+    __shared__ float tile[64][65];
+    __shared__ int s_entry;
+    const int bid = blockIdx.x, tid = threadIdx.x;
+    const int entry = adamw_find_entry(descs, n_desc, bid, &s_entry);
+    const pa_adamw_stage_desc d = descs[entry];
+    const AdamwHyper h = adamw_hyper_of<GROUPS>(hv, hy_dev, scales, entry);
     float* pp = p + d.offset;
     const float* gp = g + d.offset;
     float* mp = m + d.offset;
@@ -132,27 +178,7 @@ __global__ __launch_bounds__(256) void adamw_stage_kernel(float* __restrict__ p,
     const int t = bid - d.tile_begin;
     const bool aligned = ((((uintptr_t)pp | (uintptr_t)gp | (uintptr_t)mp | (uintptr_t)vp) & 15) == 0);
     if (!d.dst && !d.dst_t) {
-        // a parameter without copies (biases, LayerNorm, positional tables, the f32 head): a run of 4096 consecutive elements
-        const int64_t n = (int64_t)d.rows * d.cols, i0 = (int64_t)t * 4096, i1 = min(i0 + 4096, n);
-        if (aligned) {
-            for (int64_t i = i0 + tid * 4; i < i1; i += 1024) {
-                if (i + 4 <= i1) {
-                    f32x4 pv = *(f32x4*)(pp + i), mv = *(f32x4*)(mp + i), vv = *(f32x4*)(vp + i);
-                    const f32x4 gv = *(const f32x4*)(gp + i);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float pe = pv[e], me = mv[e], ve = vv[e];
-                        adamw_one(pe, gv[e], me, ve, h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
-                        pv[e] = pe; mv[e] = me; vv[e] = ve;
-                    }
-                    *(f32x4*)(pp + i) = pv; *(f32x4*)(mp + i) = mv; *(f32x4*)(vp + i) = vv;
-                } else {
-                    for (int64_t k = i; k < i1; ++k) adamw_one(pp[k], gp[k], mp[k], vp[k], h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
-                }
-            }
-        } else {
-            for (int64_t i = i0 + tid; i < i1; i += 256) adamw_one(pp[i], gp[i], mp[i], vp[i], h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
-        }
+        adamw_run(pp, gp, mp, vp, (int64_t)d.rows * d.cols, t, aligned, h);
         return;
     }
     const int tiles_c = (d.cols + 63) >> 6;
@@ -227,6 +253,39 @@ __global__ __launch_bounds__(256) void adamw_stage_kernel(float* __restrict__ p,
         const int c = c0 + i, r = r0 + tx;
         if (c < d.cols && r < d.rows) dst_t[(int64_t)c * d.rows + r] = from_f32<TO>(tile[tx][i]);
     }
+}
+
+// parameter groups without staging: the same table (dst / dst_t are not looked at), every entry as runs of 4096 elements
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, const pa_adamw_stage_desc* __restrict__ descs,
+                                                           int n_desc, const float* __restrict__ hy_dev, AdamwHyper hv,
+                                                           const float2* __restrict__ scales) {
+    __shared__ int s_entry;
+    const int bid = blockIdx.x;
+    const int entry = adamw_find_entry(descs, n_desc, bid, &s_entry);
+    const pa_adamw_stage_desc d = descs[entry];
+    const AdamwHyper h = adamw_hyper_of<true>(hv, hy_dev, scales, entry);
+    float* pp = p + d.offset;
+    const float* gp = g + d.offset;
+    float* mp = m + d.offset;
+    float* vp = v + d.offset;
+    const bool aligned = ((((uintptr_t)pp | (uintptr_t)gp | (uintptr_t)mp | (uintptr_t)vp) & 15) == 0);
+    adamw_run(pp, gp, mp, vp, (int64_t)d.rows * d.cols, bid - d.tile_begin, aligned, h);
+}
+
+template <typename TO>
+__global__ __launch_bounds__(256) void adamw_stage_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, const pa_adamw_stage_desc* __restrict__ descs,
+                                                          int n_desc, const float* __restrict__ hy_dev, AdamwHyper hv) {
+    adamw_stage_body<TO, false>(p, g, m, v, descs, n_desc, hy_dev, hv, nullptr);
+}
+// ... with parameter groups (pa_adamw_stage_groups)
+template <typename TO>
+__global__ __launch_bounds__(256) void adamw_stage_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                 float* __restrict__ v, const pa_adamw_stage_desc* __restrict__ descs,
+                                                                 int n_desc, const float* __restrict__ hy_dev, AdamwHyper hv,
+                                                                 const float2* __restrict__ scales) {
+    adamw_stage_body<TO, true>(p, g, m, v, descs, n_desc, hy_dev, hv, scales);
 }
 
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, int64_t n, float lr) {
@@ -327,9 +386,9 @@ extern "C" int pa_adamw_dev(float* p, const float* g, float* m, float* v, int64_
     return check_launch();
 }
 
-extern "C" int pa_adamw_stage(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, int n_desc,
-                              int total_items, int dtype, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                              const float* hyper_dev, void* stream) {
+static int adamw_stage_launch(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, const float* scales,
+                              int n_desc, int total_items, int dtype, float lr, float beta1, float beta2, float eps, float weight_decay,
+                              int step, const float* hyper_dev, void* stream) {
     if (!p || !g || !m || !v || !descs || n_desc < 1 || total_items < 1 || (!hyper_dev && step < 1)) return PA_EINVAL;
     if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
     AdamwHyper h{lr, beta1, beta2, eps, weight_decay, 1.f, 1.f};
@@ -337,10 +396,46 @@ extern "C" int pa_adamw_stage(float* p, const float* g, float* m, float* v, cons
         h.bc1 = 1.f - powf(beta1, (float)step);
         h.bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
     }
-    if (dtype == PA_BF16)
-        hipLaunchKernelGGL(adamw_stage_kernel<bf16>, dim3(total_items), dim3(256), 0, (hipStream_t)stream, p, g, m, v, descs, n_desc, hyper_dev, h);
+    const float2* sc = (const float2*)scales;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PA_BF16 && !sc)
+        hipLaunchKernelGGL(adamw_stage_kernel<bf16>, dim3(total_items), dim3(256), 0, st, p, g, m, v, descs, n_desc, hyper_dev, h);
+    else if (dtype == PA_BF16)
+        hipLaunchKernelGGL(adamw_stage_groups_kernel<bf16>, dim3(total_items), dim3(256), 0, st, p, g, m, v, descs, n_desc, hyper_dev, h, sc);
+    else if (!sc)
+        hipLaunchKernelGGL(adamw_stage_kernel<float>, dim3(total_items), dim3(256), 0, st, p, g, m, v, descs, n_desc, hyper_dev, h);
     else
-        hipLaunchKernelGGL(adamw_stage_kernel<float>, dim3(total_items), dim3(256), 0, (hipStream_t)stream, p, g, m, v, descs, n_desc, hyper_dev, h);
+        hipLaunchKernelGGL(adamw_stage_groups_kernel<float>, dim3(total_items), dim3(256), 0, st, p, g, m, v, descs, n_desc, hyper_dev, h, sc);
+    return check_launch();
+}
+
+extern "C" int pa_adamw_stage(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, int n_desc,
+                              int total_items, int dtype, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                              const float* hyper_dev, void* stream) {
+    return adamw_stage_launch(p, g, m, v, descs, nullptr, n_desc, total_items, dtype, lr, beta1, beta2, eps, weight_decay, step, hyper_dev,
+                              stream);
+}
+
+extern "C" int pa_adamw_stage_groups(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, const float* scales,
+                                     int n_desc, int total_items, int dtype, float lr, float beta1, float beta2, float eps,
+                                     float weight_decay, int step, const float* hyper_dev, void* stream) {
+    if (!scales || ((uintptr_t)scales & 7)) return PA_EINVAL;
+    return adamw_stage_launch(p, g, m, v, descs, scales, n_desc, total_items, dtype, lr, beta1, beta2, eps, weight_decay, step, hyper_dev,
+                              stream);
+}
+
+extern "C" int pa_adamw_groups(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, const float* scales,
+                               int n_desc, int total_items, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                               const float* hyper_dev, void* stream) {
+    if (!p || !g || !m || !v || !descs || !scales || ((uintptr_t)scales & 7) || n_desc < 1 || total_items < 1 || (!hyper_dev && step < 1))
+        return PA_EINVAL;
+    AdamwHyper h{lr, beta1, beta2, eps, weight_decay, 1.f, 1.f};
+    if (!hyper_dev) {
+        h.bc1 = 1.f - powf(beta1, (float)step);
+        h.bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
+    }
+    hipLaunchKernelGGL(adamw_groups_kernel, dim3(total_items), dim3(256), 0, (hipStream_t)stream, p, g, m, v, descs, n_desc, hyper_dev, h,
+                       (const float2*)scales);
     return check_launch();
 }
 

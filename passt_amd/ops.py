@@ -361,6 +361,30 @@ def adamw_stage(p, g, m, v, table, n, items, dtype, lr, beta1, beta2, eps, weigh
                                      _p(hyper_dev), _stream()), "pa_adamw_stage")
 
 
+def make_adamw_scales(pairs, device):
+    """pairs: [(lr_scale, wd_scale)], one per table entry in table order -> the f32 [n][2] device array of adamw_stage_groups /
+    adamw_groups."""
+    import numpy as np
+    return torch.from_numpy(np.asarray(pairs, dtype=np.float32).reshape(-1, 2)).to(device)
+
+
+def adamw_stage_groups(p, g, m, v, table, scales, n, items, dtype, lr, beta1, beta2, eps, weight_decay, step, hyper_dev=None):
+    """adamw_stage with parameter groups: table entry i is updated with lr * scales[i, 0] and weight_decay * scales[i, 1]."""
+    assert scales.dtype == torch.float32 and scales.numel() == 2 * n and scales.is_contiguous()
+    check(_lib.load().pa_adamw_stage_groups(_p(p, torch.float32), _p(g, torch.float32), _p(m, torch.float32), _p(v, torch.float32), _p(table),
+                                            _p(scales), n, items, dtype, float(lr), float(beta1), float(beta2), float(eps),
+                                            float(weight_decay), int(step), _p(hyper_dev), _stream()), "pa_adamw_stage_groups")
+
+
+def adamw_groups(p, g, m, v, table, scales, n, items, lr, beta1, beta2, eps, weight_decay, step, hyper_dev=None):
+    """The plain form: AdamW with parameter groups over a table without copies (every entry in runs of 4096 elements); hyper_dev
+    (7 device floats, see adamw_hyper) in place of the by-value scalars makes the launch capturable."""
+    assert scales.dtype == torch.float32 and scales.numel() == 2 * n and scales.is_contiguous()
+    check(_lib.load().pa_adamw_groups(_p(p, torch.float32), _p(g, torch.float32), _p(m, torch.float32), _p(v, torch.float32), _p(table),
+                                      _p(scales), n, items, float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                                      int(step), _p(hyper_dev), _stream()), "pa_adamw_groups")
+
+
 def stage_weights(table, n, tiles, dtype):
     check(_lib.load().pa_stage_weights(_p(table), n, tiles, dtype, _stream()), "pa_stage_weights")
 

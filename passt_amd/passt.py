@@ -585,6 +585,58 @@ class _Fwd(NamedTuple):
 # --------------------------------------------------------------------------------------------
 # stochastic depth (DropPath, models/helpers/vit_helpers.py:203-233; models/passt.py:372, 378-379, 444-448)
 # --------------------------------------------------------------------------------------------
+def param_stage(name, depth):
+    """The stage a parameter belongs to: -1 the patch embedding, cls / dist tokens and position tables, 0 .. depth-1 the blocks,
+    ``depth`` the final norm + head (the buckets of ddp.bucket_layout and of passt_backward's ``on_block_done``)."""
+    if name.startswith("blocks."):
+        return int(name.split(".")[1])
+    return depth if name.startswith(("norm.", "head.")) else -1
+
+
+# the weights whose gradient is a weight-gradient GEMM of its own: frozen, the problem is left out of the launch.  Every other
+# gradient falls out of a kernel that runs anyway (head.1.weight leaves pa_linear_f32_bwd together with its bias)
+_WGRAD_MATRICES = ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight", "patch_embed.proj.weight")
+
+
+class _Plan(NamedTuple):
+    """What one forward / backward pair of a partly frozen network does, decided when the forward starts (trainable_plan)."""
+    stop: int               # the lowest stage the backward reaches; the forward keeps nothing of the blocks below it
+    wanted: frozenset       # names of the parameters that get a gradient
+    live: frozenset         # stages holding one
+    mats: frozenset         # stages holding a wanted weight-gradient GEMM
+    dump: tuple             # (name, numel) of the unwanted small parameters of live stages: their reductions land in a scratch buffer
+    idx: tuple              # positions of the wanted parameters in the list the plan was made from
+    total: int              # their element count
+
+
+def trainable_plan(model, want_dx=False, low_block=None, named=None, flags=None):
+    """The _Plan of ``model`` as its ``requires_grad`` flags stand (``flags``: one bool per entry of ``named``, in place of them).
+    ``stop`` is the lowest stage with a trainable parameter (``depth`` when there is none), -1 when the input's gradient is wanted
+    (``want_dx``), and at most ``low_block`` when the backward has other work at that block (``attn_grad=``, ``rollout="cam"``)."""
+    if named is None:
+        named = model._graph_params()[0]
+    if flags is None:
+        flags = tuple(p.requires_grad for _, p in named)
+    key = (flags, bool(want_dx), low_block)
+    plans = model._scratch.get("plans")
+    if plans is None or plans[0] is not named:
+        plans = model._scratch["plans"] = (named, {})
+    plan = plans[1].get(key)
+    if plan is None:
+        depth = len(model.blocks)
+        idx = tuple(i for i, f in enumerate(flags) if f)
+        wanted = frozenset(named[i][0] for i in idx)
+        live = frozenset(param_stage(n, depth) for n in wanted)
+        mats = frozenset(param_stage(n, depth) for n in wanted if n.endswith(_WGRAD_MATRICES))
+        dump = tuple((n, p.numel()) for n, p in named
+                     if n not in wanted and param_stage(n, depth) in live and not n.endswith(_WGRAD_MATRICES))
+        stop = -1 if want_dx else min(live, default=depth)
+        if low_block is not None:
+            stop = min(stop, low_block)
+        plan = plans[1][key] = _Plan(stop, wanted, live, mats, dump, idx, sum(named[i][1].numel() for i in idx))
+    return plan
+
+
 def drop_path_rates(model):
     """Per block: the drop probability of its DropPath in training mode, 0.0 for an Identity, a rate of 0 and in eval mode."""
     if not model.training:
@@ -664,8 +716,11 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, roll
     lse, which is exact because the start rows are one-hot in the prefix.  A _RolloutRequest ("cam") only gets its start rows here: the
     chain rides with the backward (_backward_trunk).
     ``drop`` (a _DropRows or None): stochastic depth -- both residual GEMMs of a block with a factor add rowscale[m] * branch[m]; a
-    block without one, and every block when ``drop`` is None, makes exactly the calls it always made."""
+    block without one, and every block when ``drop`` is None, makes exactly the calls it always made.
+    ``save``: False, True (keep what a backward down to the patch stage needs) or a _Plan: the blocks below ``plan.stop`` launch what
+    they always launch and keep nothing -- their entry of ``ctx["saved"]`` is None and their LayerNorms write no row statistics."""
     st = model._staged
+    plan = save if isinstance(save, _Plan) else None
     D, H = model.embed_dim, model.num_heads
     scale = (D // H) ** -0.5
     aflags = ops.ATTN_Q_PRESCALED
@@ -679,7 +734,8 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, roll
     roll_keep = []                          # (qkv, lse, query rows) of the blocks an "attn" rollout multiplies through
     for bi, blk in enumerate(model.blocks):
         last = bi == nblk - 1
-        ln1, mean1, rstd1 = ops.layernorm_fwd(xs, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt, save)
+        keep = bool(save) and (plan is None or bi >= plan.stop)
+        ln1, mean1, rstd1 = ops.layernorm_fwd(xs, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt, keep)
         # the q third leaves the GEMM as q * scale * log2(e) (one rounding): attention takes "score - row reference"
         # straight from the matrix pipe (ATTN_Q_PRESCALED); every gradient stays the gradient of the unscaled Linear
         qkv = ops.linear(ln1, st.get(blk.attn.qkv.weight, dt, False), blk.attn.qkv.bias, dt,
@@ -707,11 +763,11 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, roll
         kw_a = {} if drop is None or drop.rows(bi, 0) is None else dict(rowscale=drop.rows(bi, 0, compact))
         kw_m = {} if drop is None or drop.rows(bi, 1) is None else dict(rowscale=drop.rows(bi, 1, compact))
         x_mid = ops.linear_resid(att, st.get(blk.attn.proj.weight, dt, False), blk.attn.proj.bias, x_res, dt, **kw_a)
-        ln2, mean2, rstd2 = ops.layernorm_fwd(x_mid, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, save)
+        ln2, mean2, rstd2 = ops.layernorm_fwd(x_mid, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, keep)
         h_pre, h_act = ops.linear_gelu(ln2, st.get(blk.mlp.fc1.weight, dt, False), blk.mlp.fc1.bias, dt)
         x_out = ops.linear_resid(h_act, st.get(blk.mlp.fc2.weight, dt, False), blk.mlp.fc2.bias, x_mid, dt, **kw_m)
         if save:
-            saved.append((xs, ln1, mean1, rstd1, qkv, att, lse, x_mid, ln2, mean2, rstd2, h_pre, h_act))
+            saved.append((xs, ln1, mean1, rstd1, qkv, att, lse, x_mid, ln2, mean2, rstd2, h_pre, h_act) if keep else None)
         if bi in want:
             outs[bi] = x_out
         xs = x_out
@@ -721,7 +777,7 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, roll
         xl = ops.gather_rows(xs, lay.prefix_rows(xs.device)).view(lay.B, 2, D)
         stats_n = None
         if "norm" in want:
-            outs["norm"], mean_n, rstd_n = ops.layernorm_fwd(xs, model.norm.weight, model.norm.bias, model.norm.eps, PA_F32, save)
+            outs["norm"], mean_n, rstd_n = ops.layernorm_fwd(xs, model.norm.weight, model.norm.bias, model.norm.eps, PA_F32, bool(save))
             stats_n = (mean_n, rstd_n)
         tail = dict(x_last=xs, norm=stats_n)
     else:
@@ -741,7 +797,14 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, roll
     ctx = dict(dt=dt, lay=lay, scale=scale, saved=saved, xl=xl, feat=feat, hn=hn, stats=stats, patch=patch, tail=tail) if save else None
     if save and drop is not None:
         ctx["drop"] = drop
+    if plan is not None:
+        ctx["plan"] = plan
     return _Fwd(logits, feat, ctx, tuple(lay.hidden_view(outs[k]) for k in want), tuple(maps[k] for k in amaps), roll=roll)
+
+
+def _saves_patch(save):
+    """Does a forward called with ``save`` (False / True / a _Plan) keep the patch stage's state?  Only a backward that reaches it needs it."""
+    return bool(save) and (not isinstance(save, _Plan) or save.stop < 0)
 
 
 def patchout_draws(model, x_shape):
@@ -761,7 +824,8 @@ def patchout_draws(model, x_shape):
 
 
 def passt_forward(model, x, save, draws=None, hidden=None, attn=None, drop_path_masks=None):
-    """Kernel sequence of PaSST.forward (:576-595).  Returns (logits, features, ctx).  ``draws``: device-resident Patchout
+    """Kernel sequence of PaSST.forward (:576-595).  Returns (logits, features, ctx).  ``save``: False, True (everything a full
+    backward needs) or a trainable_plan (what the backward of a partly frozen network needs, see _forward_trunk).  ``draws``: device-resident Patchout
     draws {pf, pt, pt_pos (= pt + time offset), Np} prepared by the caller (captured-graph mode) -- with an active DropPath also
     ``dp``, drop_path_draws' (depth, 2, B) factors; None = draw here.
     ``hidden`` (parse_hidden's tuple): returns (logits, features, ctx, hs), hs = the (B, Ntok, D) f32 token outputs asked for.
@@ -818,7 +882,7 @@ def _passt_forward(model, x, save, draws=None, hidden=None, attn=None, rollout=N
     ops.gemm_nt(cols, model._staged.get(model.patch_embed.proj.weight, dt, False), dt, EPI_RESID, resid=table, out_f32=tok,
                 row_mod=Np, out_batch_rows=Ntok, out_row_off=2)
     # pt_grid: the kept patches' own grid columns (pt may carry the time-positional offset); F, T: the input gradient's shape
-    patch = dict(Np=Np, pf=pf, pt=pt_pos, pt_grid=pt, toff=toff, F=F, T=T, cols=cols) if save else None
+    patch = dict(Np=Np, pf=pf, pt=pt_pos, pt_grid=pt, toff=toff, F=F, T=T, cols=cols) if _saves_patch(save) else None
     lay = _FixedLayout(model, B, Ntok)
     drop = _drop_rows(model, lay, scales)
     if drop is None:
@@ -986,8 +1050,8 @@ def _passt_forward_varlen(model, x, lengths, save=False, hidden=None, attn=None,
                                        d["row_tpos" if train else "row_t"], model.cls_token, model.dist_token, model.new_pos_embed)
     xs = torch.empty((M, model.embed_dim), device=x.device, dtype=torch.float32)
     ops.gemm_nt(cols, model._staged.get(model.patch_embed.proj.weight, dt, False), dt, EPI_RESID, resid=table, out_f32=xs)
-    patch = dict(F=F, T=T, cols=cols) if save else None
-    if save and train:
+    patch = dict(F=F, T=T, cols=cols) if _saves_patch(save) else None
+    if patch is not None and train:
         patch.update(slot=d["slot"], toff=d["toff"])   # Patchout: the patch-stage backward finds a row's grid position through the table
     tok_offsets = torch.from_numpy(cu.astype(np.int64)) if (hidden is not None or attn is not None or rollout is not None) else None
     lay = _PackedLayout(B, M, g["max_N"], d["cu_tok"], d["pidx"], ntok=np.diff(cu))
@@ -1032,16 +1096,46 @@ class _NoGrads(dict):
         return None
 
 
+class _PlanGrads(dict):
+    """``grads`` of a partly frozen backward: a wanted parameter's output buffer; for an unwanted small parameter of a live stage a
+    piece of a scratch buffer (its reduction falls out of a kernel that runs anyway, and those kernels take all their outputs or
+    none); None for everything else -- the frozen weight matrices, and every parameter of a stage without a trainable one."""
+
+    def __init__(self, grads, dump):
+        super().__init__(grads)
+        self.dump = dump
+
+    def __missing__(self, name):
+        return self.dump.get(name)
+
+
+def _dump_views(model, plan, device):
+    """name -> f32 view for ``plan.dump``, cut from one scratch buffer (kept per model and plan)."""
+    hit = model._scratch.get("grad_dump")
+    if hit is None or hit[0] is not plan or hit[1].device != device:
+        buf = torch.empty(sum(n for _, n in plan.dump), device=device, dtype=torch.float32)
+        views = dict(zip((name for name, _ in plan.dump), buf.split([n for _, n in plan.dump]))) if plan.dump else {}
+        hit = model._scratch["grad_dump"] = (plan, buf, views)
+    return hit[2]
+
+
 class _WgradSchedule:
     """Where and when the parameter gradients of ONE backward go out -- the side stream, the per-block batching, the deferred row
     reductions, who produces which bias gradient, the ``on_block_done`` reports -- decided here, once per call, for both token
     layouts.  Every A/B switch of the backward is read here, per call (a test toggles one between two models of one process).
-    ``g``: the parameter-name -> output-buffer dict, all None when ``grads`` is None (frozen: no weight-gradient work at all)."""
+    ``g``: the parameter-name -> output-buffer dict, all None when ``grads`` is None (frozen: no weight-gradient work at all).
+    ``plan`` (the forward's _Plan, or None: every stage as ``grads`` says): the backward ends behind stage ``stop``, and ``enter(s)``
+    makes stage s the current one -- ``frozen`` (no weight-gradient work, deferred reductions dropped, no report) when it holds no
+    trainable parameter."""
 
-    def __init__(self, model, dt, grads, on_block_done, device):
+    def __init__(self, model, dt, grads, on_block_done, device, plan=None):
         self.dt, self.scratch = dt, model._scratch
         self.frozen = frozen = grads is None
-        self.g = _NoGrads() if frozen else grads
+        self.plan, self.stop = plan, -1 if plan is None else plan.stop
+        if frozen:
+            self.g = _NoGrads()
+        else:
+            self.g = grads if plan is None else _PlanGrads(grads, _dump_views(model, plan, device))
         self.on_block_done = None if frozen else on_block_done
         overlap = getattr(model, "overlap_wgrad", False)
         side = self.scratch.get("side")
@@ -1063,9 +1157,29 @@ class _WgradSchedule:
         # GELU' epilogue's lane-local column sums
         self.bias_from_wgrad = (dt == PA_BF16 and ops.wgrad_tn_fuses_bias(dt) and self.fused_bias
                                 and (env("PASST_AMD_BIAS_FROM_WGRAD") == "1" or env("PA_EPILOGUE_V3") == "1"))
+        self._all_frozen, self._rowjobs = frozen, self.rowjobs
+
+    def is_frozen(self, s):
+        """does stage s run without any parameter-gradient work?"""
+        return self._all_frozen or (self.plan is not None and s not in self.plan.live)
+
+    def wants(self, name):
+        """does parameter ``name`` get a gradient from this backward?"""
+        return not self._all_frozen and (self.plan is None or name in self.plan.wanted)
+
+    def enter(self, s):
+        """Stage s begins.  A stage whose weight matrices are all frozen has no finishing launch for deferred rows to ride in:
+        its small reductions go out right behind their producers."""
+        self.frozen = self.is_frozen(s)
+        if self.frozen:
+            self.rowjobs = _NoRowJobs()
+        elif self.plan is not None and s not in self.plan.mats:
+            self.rowjobs = None
+        else:
+            self.rowjobs = self._rowjobs
 
     def report(self, i):
-        if self.on_block_done:
+        if self.on_block_done and not self.frozen:
             self.on_block_done(i)
 
     def launch_async(self, dY, X, dW, db, done=None):
@@ -1075,9 +1189,10 @@ class _WgradSchedule:
         if self.frozen:
             return
         with self.side.fork(dY, X):
-            fused = db is not None and ops.wgrad_tn_fuses_bias(self.dt) and self.fused_bias
-            self.scratch["part"] = ops.wgrad_tn(dY, X, dW.view(dY.shape[1], -1), self.dt, False, self.scratch.get("part"),
-                                                db=db if fused else None)
+            fused = dW is not None and db is not None and ops.wgrad_tn_fuses_bias(self.dt) and self.fused_bias
+            if dW is not None:          # None: a frozen matrix in a stage that has trainable parameters
+                self.scratch["part"] = ops.wgrad_tn(dY, X, dW.view(dY.shape[1], -1), self.dt, False, self.scratch.get("part"),
+                                                    db=db if fused else None)
             if db is not None and not fused:
                 ops.colsum(dY, db, accumulate=False)
             if done is not None:
@@ -1094,12 +1209,15 @@ class _WgradSchedule:
         # the block's last problem (qkv) -- and fc1, `fuse` -- get their bias gradient out of the batched launch itself (a
         # ninth MFMA per phase in the tiles of the first X-column block); the compact fc2 of the last block uses the
         # column-sum kernel right away
-        fused_bias = (done is not None or fuse) and db is not None and self.fused_bias
-        pending.append((dY, X, dW.view(dY.shape[1], -1), False, db if fused_bias else None))
+        # a frozen matrix (dW None) is no problem of the launch; a bias gradient it would have carried is summed on its own
+        fused_bias = dW is not None and (done is not None or fuse) and db is not None and self.fused_bias
+        if dW is not None:
+            pending.append((dY, X, dW.view(dY.shape[1], -1), False, db if fused_bias else None))
         if db is not None and not fused_bias:
             ops.colsum(dY, db)
         if done is not None:
-            self.scratch["part"] = ops.wgrad_tn_batched(pending, self.dt, self.scratch.get("part"), row_jobs=self.rowjobs)
+            if pending:
+                self.scratch["part"] = ops.wgrad_tn_batched(pending, self.dt, self.scratch.get("part"), row_jobs=self.rowjobs)
             pending.clear()
             if self.rowjobs is not None:
                 self.rowjobs.clear()
@@ -1126,7 +1244,10 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
         rows = None if drop is None else drop.rows(i, branch, compact)
         return {} if rows is None else dict(rowscale=rows)
     B, D, H = lay.B, model.embed_dim, model.num_heads
-    g, rowjobs = wg.g, wg.rowjobs
+    nblk = len(model.blocks)
+    g = wg.g
+    wg.enter(nblk)
+    rowjobs = wg.rowjobs
     # head: logits = hn W^T + b ; hn = LN_1e-5(feat) ; feat = mean of the two normed prefix tokens
     dhn = ops.linear_f32_bwd(dlogits.contiguous(), ctx["hn"], model.head[1].weight, g["head.1.weight"],
                              g["head.1.bias"])
@@ -1136,7 +1257,6 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
     for j, name in enumerate(("head.0.weight", "head.0.bias", "norm.weight", "norm.bias")):
         if not wg.frozen:
             ops.colsum_f32(part4[:, j, :], g[name])
-    nblk = len(model.blocks)
     dh, tail = ctx.get("dhidden") or {}, ctx["tail"]
     ag = ctx.get("attn_grad")               # the _AttnGradRequest of a forward run with attn_grad=, put there by the caller
     rr = ctx.get("rollout")                 # the _RolloutRequest of a forward run with rollout="cam", put there by the caller
@@ -1148,6 +1268,9 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
         d_norm, _ = ops.layernorm_bwd(dh["norm"], tail["x_last"], model.norm.weight, mean_n, rstd_n, None, g["norm.weight"],
                                       g["norm.bias"], False, **(dict(defer=rowjobs) if wg.frozen else dict(accumulate=True)))
     wg.report(nblk)
+    stop = wg.stop
+    if stop >= nblk:                        # only the final norm and the head are trainable: the backward ends here
+        return None, None
     if tail is None:
         dx = dxl.view(2 * B, D)             # gradient w.r.t. the compact (prefix-rows) output of the last block
         dx_lp = ops.convert(dx, dt, **factor(nblk - 1, 1, True))
@@ -1156,16 +1279,20 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
         dx, dx_lp = ops.tail_inject(dxl.view(2 * B, D), lay.prefix_rows(dxl.device), lay.M, dh.get(nblk - 1), d_norm, dt)
         if factor(nblk - 1, 1):             # the copy that enters the last block's MLP branch carries that branch's factor
             dx_lp = ops.convert(dx, dt, **factor(nblk - 1, 1))
-    for i in range(nblk - 1, -1, -1):
+    for i in range(nblk - 1, max(stop, 0) - 1, -1):
         blk = model.blocks[i]
         last = i == nblk - 1
         prefix_tail = last and tail is None
         pfx = f"blocks.{i}."
+        wg.enter(i)
+        rowjobs = wg.rowjobs
         xs, ln1, mean1, rstd1, qkv, att, lse, x_mid, ln2, mean2, rstd2, h_pre, h_act = ctx["saved"][i]
         # ---- MLP:  x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))      (on [2B, D] rows for the last block of a prefix-only tail)
         # fc2.bias gradient = column sums of dx: already produced by the LayerNorm backward that made dx (the next
         # block's norm1) -- except for the last block, whose dx comes from the head
-        wg.launch(dx_lp, h_act, g[pfx + "mlp.fc2.weight"], g[pfx + "mlp.fc2.bias"] if last else None)
+        # (or the block above is frozen while this one wants it: a frozen stage reduces nothing)
+        fc2_bias_here = last or (wg.is_frozen(i + 1) and wg.wants(pfx + "mlp.fc2.bias"))
+        wg.launch(dx_lp, h_act, g[pfx + "mlp.fc2.weight"], g[pfx + "mlp.fc2.bias"] if fc2_bias_here else None)
         # the fc1.bias gradient (column sums of d_pre) comes out of the GELU' epilogue -- unless it rides in the weight-gradient
         # launch, like qkv.bias (the LDS-free GELU' epilogue -- transposed accumulators, lane = token -- has no lane-local column
         # sums to offer), or nobody wants it
@@ -1192,7 +1319,6 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
                 _map_grad(lay, ag, ag.triple[0].index(i), qkv, lse, d_att, H, ctx["scale"], False)
             if rr is not None and i >= rr.first:
                 roll = _rollout_cam_step(lay, rr, roll, qkv, lse, d_att, H, ctx["scale"], False)
-            dres = dx
         else:
             # only 2 queries per sequence carry a gradient (the Q third of d_qkv is zero elsewhere); the residual gradient lives
             # on the prefix rows only
@@ -1201,10 +1327,15 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
                 _map_grad(lay, ag, ag.triple[0].index(i), qkv, lse, d_att, H, ctx["scale"], True)
             if rr is not None and i >= rr.first:
                 roll = _rollout_cam_step(lay, rr, roll, qkv, lse, d_att, H, ctx["scale"], True)
-            dres = ops.scatter_rows_into_zeros(dx, lay.prefix_rows(dx.device), lay.M)
+        if i == stop and not (wg.wants(pfx + "norm1.weight") or wg.wants(pfx + "norm1.bias")):
+            # the backward ends behind this block and its norm1 is frozen: nobody reads the gradient of the block's input
+            wg.launch(d_qkv, ln1, g[pfx + "attn.qkv.weight"], g[pfx + "attn.qkv.bias"], done=i)
+            break
+        dres = dx if not prefix_tail else ops.scatter_rows_into_zeros(dx, lay.prefix_rows(dx.device), lay.M)
         d_ln1 = torch.empty_like(ln1)
         ops.gemm_nt(d_qkv, st.get(blk.attn.qkv.weight, dt, True), dt, EPI_STORE, out_lp=d_ln1)
-        inject = dh.get(i - 1) if i > 0 else None       # a loss on the previous block's output: this LayerNorm's input
+        # a loss on the previous block's output: this LayerNorm's input (dropped where the backward ends: it reaches nothing trainable)
+        inject = dh.get(i - 1) if i > max(stop, 0) else None
         if inject is None:
             dx, dx_lp = ops.layernorm_bwd(d_ln1, xs, blk.norm1.weight, mean1, rstd1, dres, g[pfx + "norm1.weight"],
                                           g[pfx + "norm1.bias"], i > 0 or lay.dx0_lp,
@@ -1296,15 +1427,23 @@ def _patch_backward_varlen(model, ctx, wg, dx, dx_lp, want_dx):
 
 def _backward(model, ctx, dlogits, dfeat, grads, on_block_done, want_dx, patch_stage):
     with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
-        wg = _WgradSchedule(model, ctx["dt"], grads, on_block_done, dlogits.device)
+        wg = _WgradSchedule(model, ctx["dt"], grads, on_block_done, dlogits.device, ctx.get("plan"))
+        if want_dx and wg.stop >= 0:
+            raise ValueError("passt_backward(want_dx=True): this forward's plan ends the backward at stage "
+                             f"{wg.stop} (make the plan with want_dx=True)")
         dx, dx_lp = _backward_trunk(model, ctx, dlogits, dfeat, wg)
-        dx_in = patch_stage(model, ctx, wg, dx, dx_lp, want_dx)
+        dx_in = None
+        if wg.stop < 0:
+            wg.enter(-1)
+            dx_in = patch_stage(model, ctx, wg, dx, dx_lp, want_dx)
         wg.side.join()
     return dx_in
 
 
 def passt_backward(model, ctx, dlogits, dfeat, grads, on_block_done=None, want_dx=False):
-    """Backward of passt_forward.  ``grads``: dict param-name -> f32 tensor to OVERWRITE.
+    """Backward of passt_forward.  ``grads``: dict param-name -> f32 tensor to OVERWRITE -- of a forward run with ``save=`` a
+    trainable_plan: the plan's wanted parameters only; the backward then ends behind the plan's lowest stage, a stage without a
+    trainable parameter runs its activation gradients only, and ``on_block_done`` fires for the stages that have one.
     ``on_block_done(i)`` is called after block i's parameter gradients are enqueued (i = depth for the
     head, then depth-1 .. 0, then -1 for the patch embedding) -- the hook the data-parallel reducer
     uses to start all-reducing finished buckets while the rest of the backward runs.
@@ -1342,7 +1481,19 @@ class _PasstFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, lengths, hidden, attn, rollout, drop_path_masks, x, *params):
         req = attn if isinstance(attn, _AttnGradRequest) else None        # the maps' gradients were asked for as well
-        r = _run_forward(model, x, lengths, True, hidden=hidden, attn=attn if req is None else req.triple, rollout=rollout,
+        named, total = model._graph_params(validate=False)            # the list forward() just handed to apply()
+        flat = model._flat if (len(params) == 1 and model._flat is not None and params[0] is model._flat["token"]) else None
+        # what the backward will have to reach is known now: the parameters and the input that ask for a gradient, and the lowest
+        # block whose map gradient or rollout step rides with it.  The forward keeps nothing below that
+        low = [min(req.triple[0])] if req is not None else []
+        if isinstance(rollout, _RolloutRequest):
+            low.append(rollout.first)
+        # (under ddp.attach on several ranks the reducer's buckets are laid out over every parameter: all of them are produced)
+        red = getattr(model, "_ddp", None)
+        every = flat is not None or (red is not None and red.world > 1)
+        plan = trainable_plan(model, bool(ctx.needs_input_grad[6]), min(low) if low else None, named,
+                              (True,) * len(named) if every else tuple(ctx.needs_input_grad[7:]))
+        r = _run_forward(model, x, lengths, plan, hidden=hidden, attn=attn if req is None else req.triple, rollout=rollout,
                          drop_path_masks=drop_path_masks)
         # the integer row offsets of the packed path are non-differentiable as they are
         ctx.mark_non_differentiable(*r.maps, *(() if r.roll is None else (r.roll,)))
@@ -1353,10 +1504,10 @@ class _PasstFunction(torch.autograd.Function):
         # (a frozen loss network) runs the backward without any weight-gradient work
         ctx.want_dx = bool(ctx.needs_input_grad[6])
         ctx.frozen = not any(ctx.needs_input_grad[7:])
-        ctx.named, ctx.total = model._graph_params(validate=False)     # the list forward() just handed to apply()
+        ctx.named, ctx.total, ctx.plan = named, total, plan
         # bound to a passt_amd.optim.AdamW (PaSST.bind_flat_grads): the only input is a token; the backward writes the gradients
         # straight into the optimizer's persistent flat buffer -- p.grad are views of it -- and hands autograd nothing
-        ctx.flat = model._flat if (len(params) == 1 and model._flat is not None and params[0] is model._flat["token"]) else None
+        ctx.flat = flat
         ctx.set_materialize_grads(False)        # an unused `features` output arrives as None, not as a zero tensor
         return r.flat()
 
@@ -1382,9 +1533,9 @@ class _PasstFunction(torch.autograd.Function):
             red = getattr(model, "_ddp", None)
             rr.g_scale = float(red.world) if (red is not None and red.world > 1 and not ctx.frozen) else 1.0
             c["rollout"] = rr
-        # gradient buffers for EVERY parameter the backward writes (all but head_dist.*): the kernel sequence produces
-        # them all; parameters with requires_grad=False are simply not handed back to autograd (frozen backbone, ...)
-        named, total = ctx.named, ctx.total
+        # gradient buffers for the parameters that asked for one (ctx.plan; head_dist.* is never among them): a frozen
+        # parameter has no buffer and its gradient is not computed where that is a launch of its own (frozen backbone, ...)
+        named, plan = ctx.named, ctx.plan
         fl = ctx.flat
         B = c["lay"].B
         if dlogits is not None:
@@ -1400,11 +1551,12 @@ class _PasstFunction(torch.autograd.Function):
         if fl is not None and fl["fresh"]:
             flat, grads = fl["flat_g"], fl["grads"]     # overwritten in place: the caller zeroed (optimizer.zero_grad()) since the last backward
         else:
-            flat = torch.empty(total, device=dev, dtype=torch.float32)
+            flat = torch.empty(plan.total, device=dev, dtype=torch.float32)
             # one C++ call makes the 159 views (a Python loop of slice + view costs 1.3 ms of host time in front of the first
             # backward kernel: exposed whenever the caller synchronised in this step, and the reference's mixup does)
-            views = torch._C._nn.unflatten_dense_tensors(flat, [p for _, p in named])
-            grads = {n: v for (n, _), v in zip(named, views)}
+            wanted = [named[i] for i in plan.idx]
+            views = torch._C._nn.unflatten_dense_tensors(flat, [p for _, p in wanted])
+            grads = {n: v for (n, _), v in zip(wanted, views)}
         # a fresh flat buffer per backward: autograd may keep (not copy) the views as .grad
         if dlogits is None:                     # only `features` fed the loss
             dlogits = torch.zeros((B, model.num_classes), device=flat.device, dtype=torch.float32)
@@ -1445,9 +1597,10 @@ class _PasstFunction(torch.autograd.Function):
                 fl["flat_g"].add_(flat)
             fl["fresh"] = False
             return lead + (dx, None)
-        out = list(lead) + [dx]
-        for n, p in named:                      # the same list, in the same order, as PaSST.forward handed to apply()
-            out.append(grads[n] if p.requires_grad else None)
+        out = list(lead) + [dx] + [None] * len(named)      # the same list, in the same order, as PaSST.forward handed to apply()
+        for i in plan.idx:
+            if ctx.needs_input_grad[7 + i]:
+                out[7 + i] = grads[named[i][0]]
         return tuple(out)
 
 

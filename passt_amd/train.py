@@ -14,13 +14,42 @@ import torch
 
 from . import ops
 from .ddp import GradReducer
-from .passt import _precision, drop_path_draws, drop_path_rates, passt_backward, passt_forward, patchout_draws
+from .passt import (_precision, drop_path_draws, drop_path_rates, param_stage, passt_backward, passt_forward, patchout_draws,
+                    trainable_plan)
+
+
+def group_scales(named_dims, depth, layer_decay=None, no_weight_decay=(), model_no_weight_decay=()):
+    """The parameter groups of a fine-tuning recipe as one (lr_scale, wd_scale) pair per parameter, or None when there are none (every
+    pair would be (1, 1)).  ``named_dims``: [(name, p.dim())] in flat-buffer order.
+    ``layer_decay`` = d: the learning rate of stage s (passt.param_stage) is scaled by d ** (depth - s) -- the head by 1, block i by
+    d ** (depth - i), the patch stage by d ** (depth + 1).
+    ``no_weight_decay``: the names whose weight decay is 0, or "bias_norm": every 1-D parameter plus ``model_no_weight_decay``
+    (net.no_weight_decay(): the tokens and position tables)."""
+    if isinstance(no_weight_decay, str):
+        if no_weight_decay != "bias_norm":
+            raise ValueError(f'no_weight_decay: a collection of parameter names or "bias_norm", got {no_weight_decay!r}')
+        nwd = {n for n, dim in named_dims if dim <= 1} | set(model_no_weight_decay)
+    else:
+        nwd = set(no_weight_decay)
+        unknown = nwd - {n for n, _ in named_dims} - set(model_no_weight_decay)
+        if unknown:
+            raise ValueError(f"no_weight_decay names no trainable parameter: {sorted(unknown)[:3]}")
+    if layer_decay is None and not any(n in nwd for n, _ in named_dims):
+        return None
+    d = 1.0 if layer_decay is None else float(layer_decay)
+    return [(d ** (depth - param_stage(n, depth)), 0.0 if n in nwd else 1.0) for n, _ in named_dims]
 
 
 class TrainStep:
     def __init__(self, net, mel=None, lr=2e-5, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, optimizer="adamw",
-                 mixup_alpha=0.3, use_mixup=True, process_group=None, loss="bce", comm_dtype="fp32", transport="torch", graph=False):
-        """graph=True (single GPU): after ``graph_warmup`` eager steps the network's forward, the loss, the backward and the
+                 mixup_alpha=0.3, use_mixup=True, process_group=None, loss="bce", comm_dtype="fp32", transport="torch", graph=False,
+                 layer_decay=None, no_weight_decay=()):
+        """A partly frozen network (``requires_grad`` as it stands at construction) is trained as it is: the flat buffers, the moments
+        and the all-reduce buckets span the trainable parameters only, the frozen ones keep their storage and are never written, the
+        forward keeps nothing of the blocks below the lowest trainable stage and the backward ends behind it (passt.trainable_plan).
+        ``layer_decay`` / ``no_weight_decay`` (AdamW): parameter groups, see group_scales -- one fused launch per bucket as without
+        them (pa_adamw_stage_groups), in graph mode too: the groups' factors multiply the learning rate the schedule sets.
+        graph=True (single GPU): after ``graph_warmup`` eager steps the network's forward, the loss, the backward and the
         per-bucket optimizer launches (~290 of the step's ~300 launches) are captured once as a hipGraph (torch.cuda.CUDAGraph)
         and replayed; only the front end, mixup and the uploads of the step's host-drawn arrays stay eager.  Same kernels, same
         arguments, bit-identical parameters (tests/test_gpu_model.py::test_train_step_graph_equals_eager); what changes is the
@@ -33,13 +62,17 @@ class TrainStep:
         assert loss in ("bce", "ce")      # bce: ex_audioset.py:181-186 ; ce: ex_esc50.py:159-165 (class-index targets)
         self.loss = loss
         dev = next(net.parameters()).device
-        frozen = [n for n, p in net.named_parameters() if not p.requires_grad and not n.startswith("head_dist.")]
-        if frozen:
-            raise NotImplementedError("TrainStep updates every PaSST parameter through one flat buffer (the reference trains all of "
-                                      f"them, ex_audioset.py:104-109); frozen parameters are not supported here: {frozen[:3]} ... "
-                                      "use the autograd path (net(x); loss.backward()) with your own optimizer instead")
-        names = net._grad_names
+        self.plan = trainable_plan(net)
+        if not self.plan.wanted:
+            raise ValueError("TrainStep: no PaSST parameter requires a gradient (head_dist.* is never trained): nothing to update")
+        names = self.plan.wanted
         self.named = [(n, p) for n, p in net.named_parameters() if n in names]
+        self._frozen_ids = {id(p) for p in net.parameters()} - {id(p) for _, p in self.named}
+        self.groups = group_scales([(n, p.dim()) for n, p in self.named], len(net.blocks), layer_decay, no_weight_decay,
+                                   net.no_weight_decay())
+        if self.groups is not None and optimizer != "adamw":
+            raise ValueError("TrainStep: layer_decay / no_weight_decay are parameter groups of AdamW; optimizer='sgd' has none")
+        self._group_tabs = {}
         total = sum(p.numel() for _, p in self.named)
         # flat parameter buffer: every nn.Parameter becomes a view (state_dict / load_state_dict keep working)
         self.flat_p = torch.empty(total, device=dev, dtype=torch.float32)
@@ -91,6 +124,10 @@ class TrainStep:
             # inside the capture: the step's scalars come from device memory (launch arguments must not change between replays)
             if self.optimizer != "adamw":
                 raise NotImplementedError("graph mode: AdamW only")
+            if self.groups is not None:
+                tab, n, items, scales = self._group_table(s, e)
+                return ops.adamw_groups(self.flat_p[s:e], self.flat_g[s:e], self.m[s:e], self.v[s:e], tab, scales, n, items, 0.0, 0.0, 0.0,
+                                        0.0, 0.0, 0, hyper_dev=self._g["hyper"])
             return ops.adamw_dev(self.flat_p[s:e], self.flat_g[s:e], self.m[s:e], self.v[s:e], self._g["hyper"])
         if self.optimizer == "adamw" and self.fused_stage:
             # no kernel enqueued after this point reads this bucket's copies before the next forward: the bucket's own input-
@@ -98,14 +135,34 @@ class TrainStep:
             st, dt = self.net._staged, _precision(self.net)
             lo, hi = self._span_params(s, e)
             tab, n, items, keys = st.adamw_table((s, e), [(self.named[i][1], self._offsets[i] - s) for i in range(lo, hi)], dt)
-            ops.adamw_stage(self.flat_p[s:e], self.flat_g[s:e], self.m[s:e], self.v[s:e], tab, n, items, dt, self.lr, self.betas[0],
-                            self.betas[1], self.eps, self.wd, self._t_now)
+            if self.groups is None:
+                ops.adamw_stage(self.flat_p[s:e], self.flat_g[s:e], self.m[s:e], self.v[s:e], tab, n, items, dt, self.lr, self.betas[0],
+                                self.betas[1], self.eps, self.wd, self._t_now)
+            else:
+                ops.adamw_stage_groups(self.flat_p[s:e], self.flat_g[s:e], self.m[s:e], self.v[s:e], tab, self._group_table(s, e)[3], n,
+                                       items, dt, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self._t_now)
             self._fresh += keys
+        elif self.optimizer == "adamw" and self.groups is not None:
+            tab, n, items, scales = self._group_table(s, e)
+            ops.adamw_groups(self.flat_p[s:e], self.flat_g[s:e], self.m[s:e], self.v[s:e], tab, scales, n, items, self.lr, self.betas[0],
+                             self.betas[1], self.eps, self.wd, self._t_now)
         elif self.optimizer == "adamw":
             ops.adamw(self.flat_p[s:e], self.flat_g[s:e], self.m[s:e], self.v[s:e], self.lr, self.betas[0], self.betas[1],
                       self.eps, self.wd, self._t_now)
         else:
             ops.sgd(self.flat_p[s:e], self.flat_g[s:e], self.lr)
+
+    def _group_table(self, s, e):
+        """(plain descriptor table, n, work items, scales) of flat span [s, e) for the launches with parameter groups: one entry per
+        parameter, no copies (pa_adamw_groups); the scales alone serve pa_adamw_stage_groups, whose table lists the same parameters
+        in the same order.  Uploaded once per span (graph mode: ahead of the capture)."""
+        hit = self._group_tabs.get((s, e))
+        if hit is None:
+            lo, hi = self._span_params(s, e)
+            dev = self.flat_p.device
+            tab = ops.make_adamw_stage_table([(self._offsets[i] - s, 1, self.named[i][1].numel(), None, None) for i in range(lo, hi)], dev)
+            hit = self._group_tabs[(s, e)] = tab + (ops.make_adamw_scales(self.groups[lo:hi], dev),)
+        return hit
 
     def _span_params(self, s, e):
         """indices [lo, hi) into self.named of the parameters that make up flat span [s, e) (spans are unions of whole parameters)"""
@@ -118,8 +175,13 @@ class TrainStep:
         """End of a step: every parameter changed (epoch bump: all staged copies stale) -- except that the copies the fused
         optimizer launches of this step rewrote are current."""
         self.net.mark_params_updated()
+        st = self.net._staged
+        if self._frozen_ids:
+            # ... and so are the copies of the frozen weights: nothing wrote those parameters (one stale copy would make the next
+            # forward refresh every copy, the frozen ones included)
+            self._fresh += [k for k in st.cache if k[0] in self._frozen_ids]
         if self._fresh:
-            self.net._staged.mark_fresh(self._fresh)
+            st.mark_fresh(self._fresh)
             self._fresh = []
 
     def _block_done(self, i):
@@ -166,7 +228,7 @@ class TrainStep:
 
     def _graph_body(self, g):
         net = self.net
-        logits, feat, ctx = passt_forward(net, g["x"], save=True, draws=g)
+        logits, feat, ctx = passt_forward(net, g["x"], save=self.plan, draws=g)
         if self.loss == "bce":
             loss, dlogits = ops.bce_fwd_bwd(logits, g["y"], grad_scale=1.0)
         elif g["y2"] is not None:
@@ -203,7 +265,7 @@ class TrainStep:
                 y = ops.mixup(y, perm_d, lam_d)
         if self.graph and self.t >= self.graph_warmup and self._graph_fits(x):
             return self._graph_step(x, y, perm_d if self.use_mixup else None, lam_d if self.use_mixup else None)
-        logits, feat, ctx = passt_forward(net, x, save=True)
+        logits, feat, ctx = passt_forward(net, x, save=self.plan)
         gs = 1.0 / self.reducer.world
         if self.loss == "bce":
             loss, dlogits = ops.bce_fwd_bwd(logits, y, grad_scale=gs)
@@ -270,6 +332,10 @@ class TrainStep:
             self._graph_fill(g, d, x, y, y2, lam_d)
             net.mark_params_updated()                        # the staged weight copies are stale: their refresh launch is captured too
             net._staged.stage_table(_precision(net))         # (its descriptor table is uploaded here: no copies inside a capture)
+            if self.groups is not None:                      # ... and so are the tables and factors of the parameter groups
+                for s_, e_ in list(self.reducer.spans.values()) + [(0, self.flat_p.numel())]:
+                    if e_ > s_:
+                        self._group_table(s_, e_)
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             g["capturing"] = True
