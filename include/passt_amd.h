@@ -236,6 +236,9 @@ enum {
     PA_EPI_DGELU = 3,      /* out_lp = acc * gelu_erf'(aux)                         */
     PA_EPI_PARTIAL = 4     /* split-K: out_f32[z][M][N] = partial sums (no bias)    */
 };
+/* PA_EPI_PARTIAL, pa_gemm_nt: slab z starts at out_f32 + z * M * ldo32 and holds the product over K steps [z * per, (z + 1) * per),
+ * per = ceil(steps / split_k), a step being 128 bytes of K (64 bytes for tune 9); a slab whose range is empty (ceil-divided slices:
+ * e.g. 4 steps in 3 slices of 2) is written as zeros.  tune 13 / 19 have the fused epilogues only: PA_EPI_PARTIAL is PA_EINVAL. */
 typedef struct {
     int32_t dtype;         /* PA_F32 / PA_BF16: type of A, B, aux, out_lp, out_lp2 */
     int32_t epilogue;
@@ -334,7 +337,11 @@ int pa_gemm_nt_splitk_rowscale(const pa_gemm_args* a, const float* rowscale, flo
  * colsum_ws[split_k][a->M] partial sums over each slice's tokens (the bias gradient of the Linear whose output
  * gradient is A: nn.Linear, models/passt.py:345), computed by one extra MFMA per phase in the tiles of the first
  * B-column block instead of a separate pass over A; finish with pa_reduce_partials(colsum_ws, split_k, a->M, ...).
- * colsum_out / colsum_accumulate are ignored here. */
+ * colsum_out / colsum_accumulate are ignored here.
+ * Slab z starts at out_f32 + z * a->M * ldo32 and holds the tokens of steps [z * per, (z + 1) * per), per = ceil(steps / split_k), a
+ * step being PA_TN_STEP_ROWS tokens in the bf16 role-split kernel, 64 with bf16 tune = 1 and 32 in f32; an empty range gives zeros.
+ * PA_EUNSUPPORTED: another epilogue, lda / ldb off 16 bytes, ldo32 % 4, a->N % 8, a->M not a multiple of one 16-byte vector of
+ * `dtype` (8 bf16 / 4 f32) or either below it, colsum_ws with f32 or tune = 1. */
 int pa_gemm_tn(const pa_gemm_args* a, void* stream);
 /* Up to PA_TN_BATCH_MAX bf16 weight-gradient problems in ONE launch (e.g. the four Linears of a transformer block,
  * once all their operands exist): the work items of all problems share one grid, so there is no drain / prologue

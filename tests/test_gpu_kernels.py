@@ -2,6 +2,9 @@
 of the same op.  Tolerances: PA_F32 path ~1e-5..1e-4 relative (exact-f32 MFMA, different summation
 order); PA_BF16 path checked against a reference computed from the SAME bf16-rounded inputs, so only
 f32-accumulation order and the final bf16 rounding (2^-8 relative) remain.
+
+One max-over-max figure per call cannot see a dropped K element, a shifted bias group or a misattributed row: the GEMM family is
+checked for those with exact integer operands in guarded buffers by tests/test_gpu_gemm_exact.py (cases: tests/gemm_cases.py).
 """
 import json
 import math
@@ -914,6 +917,7 @@ def test_blocked_pre_buffer_holds_every_pass_of_every_tile_height():
         for hgt in (128, 192, 256):
             assert rows >= (M + hgt - 1) // hgt * hgt, (M, hgt, rows)
     M, N, K = 474 * 7, 3072, 768
+    record(f"blocked_pre_buffer_ran[{M},{N},{K}]", ran=int(bool(ops.blocked_pre_ok(M, N, K))))
     if not ops.blocked_pre_ok(M, N, K):
         pytest.skip("the library runs this shape on a kernel without the blocked form")
     n = lib.pa_gemm_blocked_pre_elems(M, N)
@@ -935,6 +939,7 @@ def test_blocked_pre_activation_equals_row_major(M, N, K):
     epilogue of the input-gradient GEMM reads it back: activation, d_pre and the fused fc1.bias column sums are
     BIT-identical to the row-major path (same arithmetic, only the storage of one intermediate differs)."""
     dt = PA_BF16
+    record(f"blocked_pre_equals_row_major_ran[{M},{N},{K}]", ran=int(bool(ops.blocked_pre_ok(M, N, K))))
     if not ops.blocked_pre_ok(M, N, K):
         pytest.skip("the library runs this shape on a kernel without the blocked form")
     x = rnd(M, K, seed=31).to(TD[dt]).to(DEV)
