@@ -428,6 +428,10 @@ int pa_colsum_f32(const float* in, int R, int C, int ld, float* out, int accumul
  * pa_gemm_args.colscale_n / colscale, one rounding).  The kernels then take "score - row reference" straight from the
  * matrix pipe (no multiply-add per score); o, lse and every gradient are the same quantities as without the flag
  * (dqkv's q third is the gradient with respect to the UNSCALED q).  The same flag must be given to fwd and bwd.
+ *
+ * Leading dimensions are in elements.  Every entry of this section refuses one below its row width with PA_EINVAL before anything is
+ * launched -- ldqkv, lddqkv < 3*H*64, ldo < H*64 (o and d_o share ldo) -- and one whose rows are not 16-byte aligned with
+ * PA_EUNSUPPORTED.  Gap columns of a padded leading dimension are neither read nor written.
  * ------------------------------------------------------------------------------------------ */
 #define PA_ATTN_Q_PRESCALED 1
 /* pa_attention_bwd only (ABI 5).  bf16 + PA_ATTN_Q_PRESCALED + nq == N <= 512 can run as ONE kernel (one workgroup per
@@ -441,6 +445,7 @@ int pa_colsum_f32(const float* in, int R, int C, int ld, float* out, int accumul
 #define PA_ATTN_BWD_TWO_PASS 2
 #define PA_ATTN_BWD_SINGLE_PASS 4
 #define PA_ATTN_BWD_SINGLE_PASS_W16 8
+/* PA_EINVAL: ldqkv < 3*H*64 or ldo < H*64 (as well as a NULL pointer, a size <= 0, nq > N, an unknown flag or dtype). */
 int pa_attention_fwd(const void* qkv, int ldqkv, void* o, int ldo, float* lse, int B, int H, int N, int nq,
                      float scale, int dtype, int flags, void* stream);
 /* Forward over PACKED sequences of different lengths (ragged batches; backward: pa_attention_bwd_varlen).  The B sequences lie back to back
@@ -454,7 +459,7 @@ int pa_attention_fwd(const void* qkv, int ldqkv, void* o, int ldo, float* lse, i
  *                lse[h * cu_tok[B] + cu_tok[b] + q]  (H * cu_tok[B] floats).
  *   nq <  max_N: the first min(nq, N_b) queries of every sequence, COMPACT as in pa_attention_fwd: o[(b*nq + q)][H*64],
  *                lse[(b*H + h)*nq + q]  (nq = 2: the last block's prefix rows); rows q >= N_b are not written.
- * flags as pa_attention_fwd.  qkv, o, lse, cu_tok are device memory. */
+ * flags as pa_attention_fwd.  qkv, o, lse, cu_tok are device memory.  PA_EINVAL: ldqkv < 3*H*64 or ldo < H*64. */
 int pa_attention_fwd_varlen(const void* qkv, int ldqkv, void* o, int ldo, float* lse, const int32_t* cu_tok, int B, int H,
                             int max_N, int nq, float scale, int dtype, int flags, void* stream);
 /* The attention probabilities themselves, softmax((Q K^T) * scale), f32: what the fused forward never writes (a forward hook on the
@@ -469,7 +474,8 @@ int pa_attention_fwd_varlen(const void* qkv, int ldqkv, void* o, int ldo, float*
  *     [Ho][min(nq, N_b)][N_b]; out_off: B int64 offsets in device memory.  Tail tiles are clamped to the sequence's own last row (no
  *     row of a neighbour and none at or behind cu_tok[B] is read) and every sequence gets bit for bit what the fixed form gives it
  *     alone at B = 1.
- * Every element of the output is written and nothing else.  Key lanes at or behind N_b are masked before the exponential. */
+ * Every element of the output is written and nothing else.  Key lanes at or behind N_b are masked before the exponential.
+ * PA_EINVAL: ldqkv < 3*H*64. */
 int pa_attention_probs(const void* qkv, int ldqkv, const float* lse, float* out, const int32_t* cu_tok, const int64_t* out_off,
                        int B, int H, int N /* max_N when cu_tok != NULL */, int nq, int head_mean, float scale, int dtype, int flags,
                        void* stream);
@@ -483,7 +489,8 @@ int pa_attention_probs(const void* qkv, int ldqkv, const float* lse, float* out,
  * read; do_compact = 1: the compact prefix form d_o[(b*nq + q)][H*64].
  *   mode PA_ATTN_PGRAD_GRAD: out = g.  head_mean must be 0; lse is not read and may be NULL.
  *   mode PA_ATTN_PGRAD_CAM:  out = max(p * g, 0) with p formed exactly as pa_attention_probs forms it from qkv and lse; with
- *     head_mean = 1 the mean over the heads of that, added in f32 registers in head order. */
+ *     head_mean = 1 the mean over the heads of that, added in f32 registers in head order.
+ * PA_EINVAL: ldqkv < 3*H*64 or ldo < H*64. */
 #define PA_ATTN_PGRAD_GRAD 0
 #define PA_ATTN_PGRAD_CAM 1
 int pa_attention_probs_grad(const void* qkv, int ldqkv, const float* lse, const void* d_o, int ldo, int do_compact, float* out,
@@ -507,7 +514,8 @@ int pa_attention_probs_grad(const void* qkv, int ldqkv, const float* lse, const 
  *     number of query tiles; tests, A/B).  Each slice's partial rows go to `ws` and a finishing kernel adds them in slice order; S = 1
  *     (always so for nq <= 32) finishes in the one launch.  ws: pa_attention_rollout_ws_floats(same arguments) floats, may be NULL
  *     when that is 0.  No atomics: launches on the same inputs are bit-identical, and a sequence's result depends on its own inputs
- *     and the number of query tiles per slice only. */
+ *     and the number of query tiles per slice only.
+ *   PA_EINVAL: ldqkv < 3*H*64, or (with d_o) ldo < H*64. */
 #define PA_ATTN_ROLLOUT_ATTN 0
 #define PA_ATTN_ROLLOUT_CAM 1
 #define PA_ATTN_ROLLOUT_MAX_ROWS 4
@@ -520,7 +528,8 @@ int pa_attention_rollout(const void* qkv, int ldqkv, const float* lse, const voi
 int64_t pa_attention_bwd_ws_floats(int B, int H, int nq);
 /* dqkv[B*N][3*H*64] from d_o[B*nq][H*64]; lse from the forward; delta: f32 workspace of pa_attention_bwd_ws_floats()
  * (per-query scalars the dQ kernel hands to the dK/dV kernel: -rowsum(dO*O), then -lse*log2 e).  The K and V thirds
- * of dqkv are written for all N tokens, the Q third only for rows q < nq (the caller zeroes the rest: pa_zero2d). */
+ * of dqkv are written for all N tokens, the Q third only for rows q < nq (the caller zeroes the rest: pa_zero2d).
+ * PA_EINVAL: ldqkv or lddqkv < 3*H*64, ldo < H*64. */
 int pa_attention_bwd(const void* qkv, int ldqkv, const void* o, const void* d_o, int ldo,
                      const float* lse, float* delta, void* dqkv, int lddqkv, int B, int H, int N, int nq,
                      float scale, int dtype, int flags, void* stream);
@@ -534,7 +543,7 @@ int pa_attention_bwd(const void* qkv, int ldqkv, const void* o, const void* d_o,
  * N <= 512 for the whole launch; the PA_ATTN_BWD_* flags are accepted and ignored.  cdiv(nq, 128) query blocks and cdiv(max_N, 128)
  * key blocks are launched per (sequence, head); those a short sequence does not have return before their first memory access, and
  * tail tiles (K / V as well as Q / dO) are clamped to the sequence's own last row: no row of a neighbour is read.  Equal lengths
- * reproduce pa_attention_bwd(..., PA_ATTN_BWD_TWO_PASS) bit for bit. */
+ * reproduce pa_attention_bwd(..., PA_ATTN_BWD_TWO_PASS) bit for bit.  PA_EINVAL: ldqkv or lddqkv < 3*H*64, ldo < H*64. */
 int64_t pa_attention_bwd_varlen_ws_floats(int64_t total_tokens, int B, int H, int nq);
 int pa_attention_bwd_varlen(const void* qkv, int ldqkv, const void* o, const void* d_o, int ldo, const float* lse, float* ws,
                             void* dqkv, int lddqkv, const int32_t* cu_tok, int B, int H, int max_N, int nq, float scale, int dtype,

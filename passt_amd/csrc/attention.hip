@@ -502,7 +502,16 @@ __device__ __forceinline__ void attn_fwd_body(const T* __restrict__ qkv, int ldq
         // only the first nq queries of every sequence are produced; o / lse are compact (nq rows per sequence)
         l_run += other_half(l_run);
         if (lane < 32 && q0 + lane < nq) lse_row[q0 + lane] = (m_run + __builtin_amdgcn_logf(l_run)) * LN2;   // natural log units
-        store_rows_direct<T>(oacc, __builtin_amdgcn_rcpf(l_run), o + orow0 * ldo + h * HD, ldo, q0, min(32, nq - q0), lane);
+        if constexpr (sizeof(T) == 4) {
+            // f32 rows get the quotient itself: v_rcp_f32 is good to 1 ulp and the product rounds once more, up to 1.5 ulp off
+            // O / l (with q = 0 and integer v, where O and l are exact, 5 % of the elements were not a neighbour of the exact mean);
+            // a lane's 32 accumulators belong to ONE query, so this is 32 divisions per lane and workgroup.  bf16 rounds it away.
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { oacc[0][r] /= l_run; oacc[1][r] /= l_run; }
+            store_rows_direct<T>(oacc, 1.0f, o + orow0 * ldo + h * HD, ldo, q0, min(32, nq - q0), lane);
+        } else {
+            store_rows_direct<T>(oacc, __builtin_amdgcn_rcpf(l_run), o + orow0 * ldo + h * HD, ldo, q0, min(32, nq - q0), lane);
+        }
     }
 }
 
@@ -1434,6 +1443,7 @@ extern "C" int pa_attention_fwd(const void* qkv, int ldqkv, void* o, int ldo, fl
                                 float scale, int dtype, int flags, void* stream) {
     if (!qkv || !o || !lse || B <= 0 || H <= 0 || N <= 0 || nq <= 0 || nq > N || (flags & ~PA_ATTN_Q_PRESCALED)) return PA_EINVAL;
     if (!attn_args_ok(ldqkv, dtype) || !attn_args_ok(ldo, dtype)) return PA_EUNSUPPORTED;
+    if (ldqkv < 3 * H * HD || ldo < H * HD) return PA_EINVAL;      // a leading dimension below the row width
     if (dtype == PA_BF16) return attention_fwd_t<bf16>(qkv, ldqkv, o, ldo, lse, B, H, N, nq, scale, flags, (hipStream_t)stream);
     if (dtype == PA_F32) return attention_fwd_t<float>(qkv, ldqkv, o, ldo, lse, B, H, N, nq, scale, flags, (hipStream_t)stream);
     return PA_EINVAL;
@@ -1443,6 +1453,7 @@ extern "C" int pa_attention_fwd_varlen(const void* qkv, int ldqkv, void* o, int 
                                        int max_N, int nq, float scale, int dtype, int flags, void* stream) {
     if (!qkv || !o || !lse || !cu_tok || B <= 0 || H <= 0 || max_N <= 0 || nq <= 0 || (flags & ~PA_ATTN_Q_PRESCALED)) return PA_EINVAL;
     if (!attn_args_ok(ldqkv, dtype) || !attn_args_ok(ldo, dtype)) return PA_EUNSUPPORTED;
+    if (ldqkv < 3 * H * HD || ldo < H * HD) return PA_EINVAL;      // a leading dimension below the row width
     if (dtype == PA_BF16) return attention_fwd_varlen_t<bf16>(qkv, ldqkv, o, ldo, lse, cu_tok, B, H, max_N, nq, scale, flags, (hipStream_t)stream);
     if (dtype == PA_F32) return attention_fwd_varlen_t<float>(qkv, ldqkv, o, ldo, lse, cu_tok, B, H, max_N, nq, scale, flags, (hipStream_t)stream);
     return PA_EINVAL;
@@ -1455,6 +1466,7 @@ extern "C" int pa_attention_bwd(const void* qkv, int ldqkv, const void* o, const
         (flags & ~(PA_ATTN_Q_PRESCALED | PA_ATTN_BWD_TWO_PASS | PA_ATTN_BWD_SINGLE_PASS | PA_ATTN_BWD_SINGLE_PASS_W16)))
         return PA_EINVAL;
     if (!attn_args_ok(ldqkv, dtype) || !attn_args_ok(ldo, dtype) || !attn_args_ok(lddqkv, dtype)) return PA_EUNSUPPORTED;
+    if (ldqkv < 3 * H * HD || lddqkv < 3 * H * HD || ldo < H * HD) return PA_EINVAL;      // a leading dimension below the row width
     const bool pre = flags & PA_ATTN_Q_PRESCALED;
     hipStream_t st = (hipStream_t)stream;
     // single pass where it applies and fills the chip: one workgroup per (sequence, head) takes a whole CU (148 KiB of LDS), so B * H

@@ -4,7 +4,9 @@ order); PA_BF16 path checked against a reference computed from the SAME bf16-rou
 f32-accumulation order and the final bf16 rounding (2^-8 relative) remain.
 
 One max-over-max figure per call cannot see a dropped K element, a shifted bias group or a misattributed row: the GEMM family is
-checked for those with exact integer operands in guarded buffers by tests/test_gpu_gemm_exact.py (cases: tests/gemm_cases.py).
+checked for those with exact integer operands in guarded buffers by tests/test_gpu_gemm_exact.py (cases: tests/gemm_cases.py), the
+attention family with exact operand families, padded leading dimensions and per-element bounds by tests/test_gpu_attention_exact.py
+(cases: tests/attention_cases.py).
 """
 import json
 import math
