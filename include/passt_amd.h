@@ -57,8 +57,8 @@ const char* pa_last_hip_error(void);
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
     int32_t n_fft;        /* must be 1024 */
-    int32_t hop;          /* 320 */
-    int32_t n_mels;       /* <= 128 */
+    int32_t hop;          /* 320; any value in [1, 1024] */
+    int32_t n_mels;       /* 4 .. 128 */
     int32_t n_frames;     /* T = 1 + (L-1-1+... ) see pa_mel_num_frames */
     float preemph;        /* 0.97: y[n] = x[n+1] - preemph*x[n]  (:46,:59) */
     float mel_low;        /* mel(fmin) = 1127 ln(1+fmin/700) */
@@ -75,7 +75,16 @@ int pa_mel_num_frames(int L, int hop);
 /* wave[B][L] f32 -> out[B][n_mels][n_frames] f32.
  * window[n_fft]  : analysis window already zero-padded/centred to n_fft (:38-40 + torch.stft rule)
  * bin_mel[n_fft/2]: mel value of FFT bin k, 1127 ln(1 + k*sr/n_fft/700) (kaldi.get_mel_banks)
- * twiddle[n_fft/2][2]: (cos, -sin)(2 pi k / n_fft), k = 0..n_fft/2-1 */
+ * twiddle[n_fft/2][2]: (cos, -sin)(2 pi k / n_fft), k = 0..n_fft/2-1
+ * Alignment: `wave` must be 16-byte aligned, in all six front-end entry points.  The forward moves the span of an interior tile as
+ * 16-byte pieces (vector loads, LDS-DMA in the persistent form) and the backward reads an interior frame as 8-byte pairs; both decide
+ * from the element index b * L + i0 (b * ldw + i0 in the packed forms), i.e. relative to `wave`, whether a piece is aligned.  Rows
+ * need no alignment of their own: with L (ldw) not a multiple of 4 the tiles of the misaligned rows are staged sample by sample.
+ * The tables, out, dout, dwave, lens and clip need their natural 4-byte alignment only.
+ * Argument checks, in this order, nothing is launched when one fails: PA_EINVAL for a null pointer or B <= 0 (the packed forms:
+ * T_max <= 0, lens == NULL) and for a `wave` off 16-byte alignment; PA_EUNSUPPORTED for n_fft != 1024, n_mels outside [4, 128], hop
+ * outside [1, 1024] and L - 1 <= n_fft/2 (the packed forms: ldw - 1 <= n_fft/2); PA_EINVAL for p->n_frames != pa_mel_num_frames(L, hop)
+ * (the packed forms: p->n_frames != T_max, or T_max > pa_mel_num_frames(ldw, hop)). */
 int pa_mel_frontend_fwd(const float* wave, int B, int L, const float* window, const float* bin_mel,
                         const float* twiddle, float* out, const pa_mel_params* p, void* stream);
 /* The same for a batch of clips of different lengths (inference on ragged input; the reference runs such clips one at a time,

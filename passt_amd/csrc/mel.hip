@@ -127,6 +127,19 @@ __device__ __forceinline__ cf tw1024(const float2* __restrict__ tw, int j) {
     return (j & 512) ? cf{-t.x, -t.y} : cf{t.x, t.y};
 }
 
+// Filterbank geometry of one bin: t = (bin_mel - mel_low) * inv_mel_delta as TWO rounded operations, j = floor(t) (clamped), u = t - floor(t),
+// which is exact.  Contraction is switched off in here: left on, the compiler fuses the product into the last subtraction
+// (u = fma(bin_mel - mel_low, inv_mel_delta, -floor(t))) -- a weight that no longer belongs to the rounded t whose floor chose the
+// triangle: up to half an ulp of t away from it (1.5e-4 of a band that gets 2 % of a bin at t = 68), and NEGATIVE when the exact product
+// lies just under the integer that t rounds to.  tests/mel_cases.py evaluates exactly these three operations.
+__device__ __forceinline__ void band_of_bin(float bm, float mel_low, float inv_mel_delta, int& j, float& u) {
+#pragma clang fp contract(off)
+    const float t = (bm - mel_low) * inv_mel_delta;
+    const float fl = floorf(t);
+    j = (int)fmaxf(fminf(fl, 100000.f), -1.f);
+    u = t - fl;
+}
+
 // PERSIST (round 6): the workgroup walks tiles of FR_PER_WG frames (tile = blockIdx.x, + gridDim.x, ...).  The per-lane constants and
 // the filterbank geometry are worked out ONCE per workgroup; the signal span of tile k + 1 is requested by LDS-DMA (global_load_lds: no
 // registers, raw samples) into the second span buffer while tile k is transformed, so neither the HBM latency of the span nor the ~40
@@ -299,10 +312,7 @@ __device__ __forceinline__ void mel_frontend_body(const float* __restrict__ wave
     // ---- filterbank geometry for this call's (fmin, fmax): bin k -> triangle j_k, weight u_k ----
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const float t = ((h ? bm1 : bm0) - mel_low) * inv_mel_delta;
-        const float fl = floorf(t);
-        sJ[tid + h * NT] = (int)fmaxf(fminf(fl, 100000.f), -1.f);
-        sU[tid + h * NT] = t - fl;
+        band_of_bin(h ? bm1 : bm0, mel_low, inv_mel_delta, sJ[tid + h * NT], sU[tid + h * NT]);
     }
     __syncthreads();
     cf* scr = (cf*)(sScr + wv * WAVE_SCRATCH);
@@ -607,10 +617,7 @@ __device__ __forceinline__ void mel_frontend_bwd_body(const float* __restrict__ 
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {                                      // filterbank geometry: the forward's expressions
-        const float t = (bin_mel[tid + h * NT] - mel_low) * inv_mel_delta;
-        const float fl = floorf(t);
-        sJ[tid + h * NT] = (int)fmaxf(fminf(fl, 100000.f), -1.f);
-        sU[tid + h * NT] = t - fl;
+        band_of_bin(bin_mel[tid + h * NT], mel_low, inv_mel_delta, sJ[tid + h * NT], sU[tid + h * NT]);
     }
     __syncthreads();
     cf* scr = (cf*)(sScr + wv * WAVE_SCRATCH);
@@ -875,9 +882,14 @@ using namespace pa;
 
 extern "C" int pa_mel_num_frames(int L, int hop) { return (L < 2 || hop <= 0) ? 0 : 1 + (L - 1) / hop; }
 
+// The 16-byte loads and LDS-DMA pieces of the forward's interior tiles and the 8-byte loads of the backward's interior frames take their
+// alignment from the element index (b * ldw + i0), i.e. relative to `wave`: the base itself has to be 16-byte aligned (include/passt_amd.h)
+static bool wave_misaligned(const float* wave) { return ((uintptr_t)wave & 15) != 0; }
+
 extern "C" int pa_mel_frontend_fwd(const float* wave, int B, int L, const float* window, const float* bin_mel,
                                    const float* twiddle, float* out, const pa_mel_params* p, void* stream) {
     if (!wave || !window || !bin_mel || !twiddle || !out || !p || B <= 0) return PA_EINVAL;
+    if (wave_misaligned(wave)) return PA_EINVAL;
     if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
     if (L - 1 <= NFFT / 2) return PA_EUNSUPPORTED;          // reflect padding needs L-1 > n_fft/2 (torch.stft rule)
     if (p->n_frames != pa_mel_num_frames(L, p->hop)) return PA_EINVAL;
@@ -937,6 +949,7 @@ extern "C" int pa_mel_frontend_fwd(const float* wave, int B, int L, const float*
 extern "C" int pa_mel_frontend_fwd_varlen(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
                                           const float* twiddle, float* out, int T_max, float fill, const pa_mel_params* p, void* stream) {
     if (!wave || !lens || !window || !bin_mel || !twiddle || !out || !p || B <= 0 || T_max <= 0) return PA_EINVAL;
+    if (wave_misaligned(wave)) return PA_EINVAL;
     if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
     if (ldw - 1 <= NFFT / 2) return PA_EUNSUPPORTED;        // no row can hold a clip long enough for the reflect padding
     if (p->n_frames != T_max || T_max > pa_mel_num_frames(ldw, p->hop)) return PA_EINVAL;
@@ -957,6 +970,7 @@ extern "C" int pa_mel_frontend_fwd_varlen_aug(const float* wave, int B, int ldw,
                                               const float* twiddle, float* out, int T_max, float fill, const pa_mel_params* p,
                                               const pa_mel_clip_params* clip, void* stream) {
     if (!wave || !lens || !window || !bin_mel || !twiddle || !out || !p || !clip || B <= 0 || T_max <= 0) return PA_EINVAL;
+    if (wave_misaligned(wave)) return PA_EINVAL;
     if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
     if (ldw - 1 <= NFFT / 2) return PA_EUNSUPPORTED;
     if (p->n_frames != T_max || T_max > pa_mel_num_frames(ldw, p->hop)) return PA_EINVAL;
@@ -995,6 +1009,7 @@ extern "C" int pa_mel_frontend_bwd(const float* wave, int B, int L, const float*
                                    const float* dout, float* dwave, void* workspace, int64_t workspace_bytes, const pa_mel_params* p, void* stream) {
     (void)workspace; (void)workspace_bytes;
     if (!wave || !window || !bin_mel || !twiddle || !dout || !dwave || !p || B <= 0) return PA_EINVAL;
+    if (wave_misaligned(wave)) return PA_EINVAL;
     if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
     if (L - 1 <= NFFT / 2) return PA_EUNSUPPORTED;
     if (p->n_frames != pa_mel_num_frames(L, p->hop)) return PA_EINVAL;
@@ -1006,6 +1021,7 @@ extern "C" int pa_mel_frontend_bwd_varlen(const float* wave, int B, int ldw, con
                                           int64_t workspace_bytes, const pa_mel_params* p, void* stream) {
     (void)workspace; (void)workspace_bytes;
     if (!wave || !lens || !window || !bin_mel || !twiddle || !dout || !dwave || !p || B <= 0 || T_max <= 0) return PA_EINVAL;
+    if (wave_misaligned(wave)) return PA_EINVAL;
     if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
     if (ldw - 1 <= NFFT / 2) return PA_EUNSUPPORTED;
     if (p->n_frames != T_max || T_max > pa_mel_num_frames(ldw, p->hop)) return PA_EINVAL;
@@ -1017,6 +1033,7 @@ extern "C" int pa_mel_frontend_bwd_varlen_aug(const float* wave, int B, int ldw,
                                               int64_t workspace_bytes, const pa_mel_params* p, const pa_mel_clip_params* clip, void* stream) {
     (void)workspace; (void)workspace_bytes;
     if (!wave || !lens || !window || !bin_mel || !twiddle || !dout || !dwave || !p || !clip || B <= 0 || T_max <= 0) return PA_EINVAL;
+    if (wave_misaligned(wave)) return PA_EINVAL;
     if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
     if (ldw - 1 <= NFFT / 2) return PA_EUNSUPPORTED;
     if (p->n_frames != T_max || T_max > pa_mel_num_frames(ldw, p->hop)) return PA_EINVAL;

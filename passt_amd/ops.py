@@ -163,7 +163,14 @@ def round_up(a, b):
 
 
 # ---- front end -----------------------------------------------------------------------------
+def _mel_wave(wave):
+    """The front end takes the alignment of its 16-byte and 8-byte loads from the element index, so the waveform's base pointer must be
+    16-byte aligned (include/passt_amd.h); an offset view gets a copy."""
+    return wave.clone() if wave.is_cuda and wave.is_contiguous() and wave.data_ptr() % 16 else wave
+
+
 def mel_frontend(wave, window, bin_mel, twiddle, params: MelParams):
+    wave = _mel_wave(wave)
     B, L = wave.shape
     out = torch.empty((B, params.n_mels, params.n_frames), device=wave.device, dtype=torch.float32)
     _timed("mel", 4.0 * (B * L + out.numel()),
@@ -177,6 +184,7 @@ def mel_frontend_varlen(wave, lens_dev, window, bin_mel, twiddle, params: MelPar
     """Ragged batch: wave (B, L_max) f32 with clips left-aligned, lens_dev (B,) int32 on the device (valid samples per row; the
     caller has checked 1 + n_fft/2 < len <= L_max on the host).  Returns (B, n_mels, params.n_frames); the frames behind a clip's
     own end hold ``fill``."""
+    wave = _mel_wave(wave)
     if wave.dim() != 2 or lens_dev.dim() != 1 or lens_dev.numel() != wave.shape[0]:
         raise _lib.PasstAmdError(f"mel_frontend_varlen: wave {tuple(wave.shape)} needs one length per row, got {tuple(lens_dev.shape)}")
     B, L = wave.shape
@@ -192,6 +200,7 @@ def mel_frontend_varlen(wave, lens_dev, window, bin_mel, twiddle, params: MelPar
 def mel_frontend_bwd(wave, window, bin_mel, twiddle, params: MelParams, dout):
     """Gradient of mel_frontend w.r.t. ``wave`` (B, L) f32 for the upstream gradient ``dout`` (B, n_mels, n_frames) f32; ``params`` is
     the forward call's (mask ranges included).  Nothing was saved: the spectrum is recomputed from the wave.  Deterministic."""
+    wave = _mel_wave(wave)
     B, L = wave.shape
     if tuple(dout.shape) != (B, params.n_mels, params.n_frames):
         raise _lib.PasstAmdError(f"mel_frontend_bwd: dout {tuple(dout.shape)} for a ({B}, {params.n_mels}, {params.n_frames}) output")
@@ -207,6 +216,7 @@ def mel_frontend_bwd(wave, window, bin_mel, twiddle, params: MelParams, dout):
 def mel_frontend_bwd_varlen(wave, lens_dev, window, bin_mel, twiddle, params: MelParams, dout):
     """Gradient of mel_frontend_varlen w.r.t. ``wave`` (B, L_max): row i equals the clip's own gradient in its first lens[i] samples and
     is exactly 0 behind them; ``dout`` behind a clip's frames is not used."""
+    wave = _mel_wave(wave)
     if wave.dim() != 2 or lens_dev.dim() != 1 or lens_dev.numel() != wave.shape[0]:
         raise _lib.PasstAmdError(f"mel_frontend_bwd_varlen: wave {tuple(wave.shape)} needs one length per row, got {tuple(lens_dev.shape)}")
     B, L = wave.shape
@@ -244,6 +254,7 @@ def mel_frontend_varlen_aug(wave, lens_dev, clip_dev, window, bin_mel, twiddle, 
     """mel_frontend_varlen with every clip's own filterbank edges and SpecAugment bands: ``clip_dev`` is ops.upload_mel_clips' table
     (its six values replace params.mel_low / inv_mel_delta / fmask_* / tmask_*, which are not read; the caller guarantees finite
     mel_low and inv_mel_delta > 0).  The frames behind a clip's own end hold ``fill``, never the mask constant."""
+    wave = _mel_wave(wave)
     if wave.dim() != 2 or lens_dev.dim() != 1 or lens_dev.numel() != wave.shape[0]:
         raise _lib.PasstAmdError(f"mel_frontend_varlen_aug: wave {tuple(wave.shape)} needs one length per row, got {tuple(lens_dev.shape)}")
     B, L = wave.shape
@@ -260,6 +271,7 @@ def mel_frontend_varlen_aug(wave, lens_dev, clip_dev, window, bin_mel, twiddle, 
 
 def mel_frontend_bwd_varlen_aug(wave, lens_dev, clip_dev, window, bin_mel, twiddle, params: MelParams, dout):
     """Gradient of mel_frontend_varlen_aug w.r.t. ``wave``; ``clip_dev`` is the forward call's table."""
+    wave = _mel_wave(wave)
     if wave.dim() != 2 or lens_dev.dim() != 1 or lens_dev.numel() != wave.shape[0]:
         raise _lib.PasstAmdError(f"mel_frontend_bwd_varlen_aug: wave {tuple(wave.shape)} needs one length per row, got {tuple(lens_dev.shape)}")
     B, L = wave.shape
