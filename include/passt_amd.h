@@ -737,6 +737,39 @@ int pa_adamw_stage_groups(float* p, const float* g, float* m, float* v, const pa
 int pa_adamw_groups(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, const float* scales, int n_desc,
                     int total_items, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                     const float* hyper_dev, void* stream);
+/* Global-norm gradient clipping and gradient accumulation (Lightning's trainer.gradient_clip_val / trainer.accumulate_grad_batches,
+ * ex_audioset.py:36; torch.nn.utils.clip_grad_norm_) without a host sync.  Additive to ABI 6.
+ *
+ * pa_grad_norm_partials(n): host only; the number of f32 partial sums a span of n elements produces: ceil(n / 4096), a function of n
+ *   alone (not of the grid, the CU count or the alignment); 0 for n <= 0.
+ * pa_grad_accum_sumsq: ONE streaming pass over a span of n gradients.
+ *   acc != NULL:      acc[i] = first ? g[i] : acc[i] + g[i] (one f32 addition; with `first` acc is never read: it may hold NaN)
+ *   partials != NULL: partials[k] = sum of the squares of elements [4096 k, min(4096 (k + 1), n)) of the RESULT (acc, or g when acc is
+ *                     NULL), pa_grad_norm_partials(n) floats.
+ *   One workgroup per chunk, the order of the additions a function of the element's index in the chunk only: the same bits from run to
+ *   run and for the same data at another address or alignment; no atomics, no finishing launch.  Every addend is >= 0, so a partial's
+ *   relative error is at most gamma_24 = 24 u / (1 - 24 u), u = 2^-24.  16-byte accesses where g (and acc, which must then
+ *   share g's misalignment) allow, a scalar head and tail otherwise; nothing outside [0, n) is read or written.
+ *   PA_EINVAL: g NULL, n <= 0, acc and partials both NULL.
+ * pa_clip_coef: one workgroup; out[0] = (float)sqrt(sum of the n_partials partials, in f64, fixed order) -- the total L2 norm;
+ *   out[1] = the clip factor in f32 exactly as torch forms it: c = reciprocal(out[0] + 1e-6f) * max_norm (torch evaluates
+ *   max_norm / tensor as tensor.reciprocal() * max_norm), factor = c > 1 ? 1 : c.  A NaN norm gives a NaN factor
+ *   (clip_grad_norm_(error_if_nonfinite=False)); max_norm = +inf gives exactly 1.  PA_EINVAL: max_norm <= 0 or NaN, n_partials < 1.
+ * pa_adamw_clip: pa_adamw (hyper_dev == NULL: scalars by value) / pa_adamw_dev (hyper_dev: the 7 device floats) with the factor.
+ * pa_adamw_stage_clip: pa_adamw_stage / pa_adamw_stage_groups / pa_adamw_groups with the factor: `scales` may be NULL (no groups),
+ *   table entries may omit their copies.
+ *   gscale_dev: ONE device float; the gradient entering the update is g * *gscale_dev (one f32 multiplication).  The gradient buffer
+ *   itself is NOT written: after a clipped step g (p.grad, TrainStep.flat_g) still holds the UNCLIPPED values -- on purpose, unlike
+ *   torch's in-place clip_grad_norm_: it saves a 345 MB write per step.  gscale_dev == NULL and a factor of exactly 1.0f are
+ *   bit-identical to the entries without it (parameters, both moments, both copies). */
+int64_t pa_grad_norm_partials(int64_t n);
+int pa_grad_accum_sumsq(const float* g, float* acc, int first, int64_t n, float* partials, void* stream);
+int pa_clip_coef(const float* partials, int n_partials, float max_norm, float* out, void* stream);
+int pa_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                  float weight_decay, int step, const float* hyper_dev, const float* gscale_dev, void* stream);
+int pa_adamw_stage_clip(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, const float* scales,
+                        int n_desc, int total_items, int dtype, float lr, float beta1, float beta2, float eps, float weight_decay,
+                        int step, const float* hyper_dev, const float* gscale_dev, void* stream);
 /* torch.optim.SGD lr only (ex_audioset.py:392 model_speed_test) */
 int pa_sgd(float* p, const float* g, int64_t n, float lr, void* stream);
 /* Stochastic weight averaging step on flat buffers (helpers/swa_callback.py:246-268, update_parameters + avg_fn):

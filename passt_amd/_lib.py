@@ -136,6 +136,11 @@ SIGNATURES = {
     "pa_adamw_stage": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, i32, vp, vp]),
     "pa_adamw_stage_groups": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, i32, vp, vp]),
     "pa_adamw_groups": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, i32, vp, vp]),
+    "pa_grad_norm_partials": (i64, [i64]),
+    "pa_grad_accum_sumsq": (i32, [vp, vp, i32, i64, vp, vp]),
+    "pa_clip_coef": (i32, [vp, i32, f32, vp, vp]),
+    "pa_adamw_clip": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp, vp, vp]),
+    "pa_adamw_stage_clip": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, i32, vp, vp, vp]),
     "pa_adamw_hyper": (None, [f32, f32, f32, f32, f32, i32, C.POINTER(f32)]),
     "pa_sgd": (i32, [vp, vp, i64, f32, vp]),
     "pa_swa_update": (i32, [vp, vp, i64, i32, vp]),

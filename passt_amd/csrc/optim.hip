@@ -45,6 +45,14 @@ __device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v,
     const float step = (lr / bc1) * (m / denom);
     p = pi - step;
 }
+// Global-norm clipping (pa_adamw_clip / pa_adamw_stage_clip): the gradient entering adamw_one is g * factor, ONE f32 multiplication,
+// the factor being a device float (pa_clip_coef writes it: no host sync).  The gradient buffer is not written.  x * 1.0f == x bit for
+// bit, so a factor of exactly 1 -- and CLIP = false, which is what every other entry instantiates -- leave today's bits.
+template <bool CLIP> __device__ __forceinline__ float clip_g(float g, float gs) {
+#pragma clang fp contract(off)
+    if constexpr (CLIP) return g * gs;
+    else return g;
+}
 // 16-byte accesses (n4 = n / 4 when all four pointers are 16-byte aligned, else 0) + scalar tail
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t n4, int64_t n, float lr, float b1, float b2,
@@ -121,8 +129,9 @@ __device__ __forceinline__ int adamw_find_entry(const pa_adamw_stage_desc* __res
     return *s_entry;
 }
 // a parameter without copies (biases, LayerNorm, positional tables, the f32 head): work item t is a run of 4096 consecutive elements
+template <bool CLIP = false>
 __device__ __forceinline__ void adamw_run(float* pp, const float* gp, float* mp, float* vp, int64_t n, int t, bool aligned,
-                                          const AdamwHyper& h) {
+                                          const AdamwHyper& h, float gs = 1.f) {
     const int tid = threadIdx.x;
     const int64_t i0 = (int64_t)t * 4096, i1 = min(i0 + 4096, n);
     if (aligned) {
@@ -133,16 +142,18 @@ __device__ __forceinline__ void adamw_run(float* pp, const float* gp, float* mp,
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float pe = pv[e], me = mv[e], ve = vv[e];
-                    adamw_one(pe, gv[e], me, ve, h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
+                    adamw_one(pe, clip_g<CLIP>(gv[e], gs), me, ve, h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
                     pv[e] = pe; mv[e] = me; vv[e] = ve;
                 }
                 *(f32x4*)(pp + i) = pv; *(f32x4*)(mp + i) = mv; *(f32x4*)(vp + i) = vv;
             } else {
-                for (int64_t k = i; k < i1; ++k) adamw_one(pp[k], gp[k], mp[k], vp[k], h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
+                for (int64_t k = i; k < i1; ++k)
+                    adamw_one(pp[k], clip_g<CLIP>(gp[k], gs), mp[k], vp[k], h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
             }
         }
     } else {
-        for (int64_t i = i0 + tid; i < i1; i += 256) adamw_one(pp[i], gp[i], mp[i], vp[i], h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
+        for (int64_t i = i0 + tid; i < i1; i += 256)
+            adamw_one(pp[i], clip_g<CLIP>(gp[i], gs), mp[i], vp[i], h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
     }
 }
 // the hyper-parameters of one launch (by value, or the 7-float row in device memory) for table entry ``entry``: with parameter groups
@@ -161,10 +172,11 @@ __device__ __forceinline__ AdamwHyper adamw_hyper_of(const AdamwHyper& hv, const
     return h;
 }
 
-template <typename TO, bool GROUPS>
+template <typename TO, bool GROUPS, bool CLIP = false>
 __device__ __forceinline__ void adamw_stage_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                  float* __restrict__ v, const pa_adamw_stage_desc* __restrict__ descs, int n_desc,
-                                                 const float* __restrict__ hy_dev, const AdamwHyper& hv, const float2* __restrict__ scales) {
+                                                 const float* __restrict__ hy_dev, const AdamwHyper& hv, const float2* __restrict__ scales,
+                                                 float gs = 1.f) {
     __shared__ float tile[64][65];
     __shared__ int s_entry;
     const int bid = blockIdx.x, tid = threadIdx.x;
@@ -178,7 +190,7 @@ __device__ __forceinline__ void adamw_stage_body(float* __restrict__ p, const fl
     const int t = bid - d.tile_begin;
     const bool aligned = ((((uintptr_t)pp | (uintptr_t)gp | (uintptr_t)mp | (uintptr_t)vp) & 15) == 0);
     if (!d.dst && !d.dst_t) {
-        adamw_run(pp, gp, mp, vp, (int64_t)d.rows * d.cols, t, aligned, h);
+        adamw_run<CLIP>(pp, gp, mp, vp, (int64_t)d.rows * d.cols, t, aligned, h, gs);
         return;
     }
     const int tiles_c = (d.cols + 63) >> 6;
@@ -207,7 +219,7 @@ __device__ __forceinline__ void adamw_stage_body(float* __restrict__ p, const fl
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float pe = pv[i][e], me = mv[i][e], ve = vv[i][e];
-                    adamw_one(pe, gv[i][e], me, ve, h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
+                    adamw_one(pe, clip_g<CLIP>(gv[i][e], gs), me, ve, h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
                     pv[i][e] = pe; mv[i][e] = me; vv[i][e] = ve;
                 }
                 opt_st((f32x4*)(pp + at), pv[i]); opt_st((f32x4*)(mp + at), mv[i]); opt_st((f32x4*)(vp + at), vv[i]);
@@ -241,7 +253,7 @@ __device__ __forceinline__ void adamw_stage_body(float* __restrict__ p, const fl
         float w = 0.f;
         if (ok) {
             const int64_t at = (int64_t)r * d.cols + c;
-            adamw_one(pp[at], gp[at], mp[at], vp[at], h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
+            adamw_one(pp[at], clip_g<CLIP>(gp[at], gs), mp[at], vp[at], h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
             w = pp[at];
             if (dst) dst[at] = from_f32<TO>(w);
         }
@@ -286,6 +298,151 @@ __global__ __launch_bounds__(256) void adamw_stage_groups_kernel(float* __restri
                                                                  int n_desc, const float* __restrict__ hy_dev, AdamwHyper hv,
                                                                  const float2* __restrict__ scales) {
     adamw_stage_body<TO, true>(p, g, m, v, descs, n_desc, hy_dev, hv, scales);
+}
+
+// ... with the clip factor of the step read from device memory (pa_adamw_stage_clip): the same body, g * factor entering adamw_one
+template <typename TO, bool GROUPS>
+__global__ __launch_bounds__(256) void adamw_stage_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, const pa_adamw_stage_desc* __restrict__ descs,
+                                                               int n_desc, const float* __restrict__ hy_dev, AdamwHyper hv,
+                                                               const float2* __restrict__ scales, const float* __restrict__ gscale) {
+    adamw_stage_body<TO, GROUPS, true>(p, g, m, v, descs, n_desc, hy_dev, hv, scales, gscale ? *gscale : 1.f);
+}
+// the flat form (pa_adamw_clip): adamw_kernel / adamw_dev_kernel with the factor; scalars by value or from the device row
+__global__ __launch_bounds__(256) void adamw_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, int64_t n4, int64_t n, AdamwHyper hv,
+                                                         const float* __restrict__ hy_dev, const float* __restrict__ gscale) {
+    const AdamwHyper h = adamw_hyper_of<false>(hv, hy_dev, nullptr, 0);
+    const float gs = gscale ? *gscale : 1.f;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t i = t0; i < n4; i += stride) {
+        f32x4 pv = ((f32x4*)p)[i], mv = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+        const f32x4 gv = ((const f32x4*)g)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float pe = pv[e], me = mv[e], ve = vv[e];
+            adamw_one(pe, clip_g<true>(gv[e], gs), me, ve, h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
+            pv[e] = pe; mv[e] = me; vv[e] = ve;
+        }
+        ((f32x4*)p)[i] = pv; ((f32x4*)m)[i] = mv; ((f32x4*)v)[i] = vv;
+    }
+    for (int64_t i = n4 * 4 + t0; i < n; i += stride)
+        adamw_one(p[i], clip_g<true>(g[i], gs), m[i], v[i], h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
+}
+
+// ---- Global gradient norm + gradient accumulation: ONE streaming pass per span of the flat gradient buffer ---------------------
+// Partition: a span of n elements is cut into chunks of GN_CHUNK = 4096 consecutive elements counted from the span's first element
+// (pa_grad_norm_partials(n) = ceil(n / 4096): a function of n alone); one workgroup of 256 threads owns one chunk and writes one
+// partial.  The order of additions inside a chunk depends on the element's index in the chunk only: the chunk's values go through an
+// LDS image (element j at buf[shift + j], shift = the chunk's misalignment in elements, so 16-byte global accesses land on 16-byte
+// LDS slots; a scalar head and tail), then thread t sums the squares of elements 4 (t + 256 k) + e in the order k = 0..3, e = 0..3
+// (elements past the span count as +0: x + 0 == x), the 64 lanes of a wave combine by the xor butterfly (wave_sum), the 4 waves
+// as (w0 + w1) + (w2 + w3).  No atomics, no finishing launch: bit-identical from run to run and for the same data at any address.
+// Longest chain of roundings per partial: 1 (square) + 15 + 6 + 2 = 24 (DESIGN: the bound tests/test_gpu_grad_clip.py asserts).
+// The gradient read is non-temporal although AdamW reads the same bytes again: measured (profiles/grad_clip.txt), not assumed -- the
+// pass alone runs at 6.4 against 5.8 TB/s, the pair norm pass + AdamW over 340 MB takes 0.568 against 0.584 ms, and in the step the
+// cost of clipping is 0.02 - 0.04 ms lower; a 345 MB gradient buffer does not stay in the 256 MiB Infinity Cache until the optimizer
+// comes back to it.  -DPA_GRADNORM_PLAIN builds the plain load for the A/B (tools/bench_grad_clip.py --ab-lib).
+constexpr int GN_CHUNK = 4096;
+#ifdef PA_GRADNORM_PLAIN
+static constexpr bool CP_NT_GRADNORM = false;
+#else
+static constexpr bool CP_NT_GRADNORM = PA_CP(1);
+#endif
+template <typename V> __device__ __forceinline__ V gn_ld(const V* p) {
+    if constexpr (CP_NT_GRADNORM) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+__global__ __launch_bounds__(256) void grad_accum_sumsq_kernel(const float* __restrict__ g, float* __restrict__ acc, int first, int64_t n,
+                                                               float* __restrict__ partials) {
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) float buf[GN_CHUNK + 4];
+    __shared__ float wsum[4];
+    const int tid = threadIdx.x;
+    const int64_t c0 = (int64_t)blockIdx.x * GN_CHUNK;
+    const int len = (int)min((int64_t)GN_CHUNK, n - c0);
+    const float* gp = g + c0;
+    float* ap = acc ? acc + c0 : nullptr;
+    const bool rd_acc = ap && !first;
+    const int sg = (int)(((uintptr_t)gp >> 2) & 3);
+    const bool vec = !ap || (int)(((uintptr_t)ap >> 2) & 3) == sg;       // 16-byte accesses need g and acc equally (mis)aligned
+    const int shift = vec ? sg : 0;
+    auto one = [&](int j) {
+        float r = gn_ld(gp + j);
+        if (rd_acc) r = ap[j] + r;
+        if (ap) ap[j] = r;
+        if (partials) buf[shift + j] = r;
+    };
+    if (!vec) {
+        for (int j = tid; j < len; j += 256) one(j);
+    } else {
+        const int head = min((4 - shift) & 3, len), nv = (len - head) >> 2;
+        if (tid < head) one(tid);
+        for (int i = tid; i < nv; i += 256) {
+            const int j = head + 4 * i;
+            f32x4 r = gn_ld((const f32x4*)(gp + j));
+            if (rd_acc) {
+                const f32x4 a = *(const f32x4*)(ap + j);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) r[e] = a[e] + r[e];
+            }
+            if (ap) *(f32x4*)(ap + j) = r;
+            if (partials) *(f32x4*)(buf + shift + j) = r;
+        }
+        const int j = head + 4 * nv + tid;
+        if (j < len) one(j);
+    }
+    if (!partials) return;
+    __syncthreads();
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = 4 * (tid + 256 * k);
+        float x[4];
+        if (shift == 0) {
+            const f32x4 q = *(const f32x4*)(buf + j);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x[e] = q[e];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x[e] = buf[shift + j + e];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float xe = j + e < len ? x[e] : 0.f;      // what lies behind the chunk's end in LDS was never written
+            const float sq = xe * xe;
+            s = s + sq;
+        }
+    }
+    s = wave_sum(s);
+    if ((tid & 63) == 0) wsum[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+// total norm and clip factor of one update: one workgroup, fixed order, the partials summed in f64 (thread t takes partials t, t + 256,
+// ... in order, then a binary tree over the 256 sums).  The factor is what torch.nn.utils.clip_grad_norm_ computes in f32:
+// max_norm / (norm + 1e-6) evaluated as reciprocal(norm + 1e-6f) * max_norm (Tensor.__rdiv__), clamped from above by a comparison, not
+// fminf: a NaN norm gives a NaN factor (error_if_nonfinite=False); max_norm = +inf gives exactly 1.
+__global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict__ partials, int n, float max_norm, float* __restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    for (int i = tid; i < n; i += 256) s = s + (double)partials[i];
+    red[tid] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] = red[tid] + red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float norm = (float)sqrt(red[0]);
+        const float r = 1.0f / (norm + 1e-6f);
+        const float c = r * max_norm;
+        out[0] = norm;
+        out[1] = c > 1.0f ? 1.0f : c;
+    }
 }
 
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, int64_t n, float lr) {
@@ -436,6 +593,61 @@ extern "C" int pa_adamw_groups(float* p, const float* g, float* m, float* v, con
     }
     hipLaunchKernelGGL(adamw_groups_kernel, dim3(total_items), dim3(256), 0, (hipStream_t)stream, p, g, m, v, descs, n_desc, hyper_dev, h,
                        (const float2*)scales);
+    return check_launch();
+}
+
+extern "C" int pa_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                             float weight_decay, int step, const float* hyper_dev, const float* gscale_dev, void* stream) {
+    if (!p || !g || !m || !v || n <= 0 || (!hyper_dev && step < 1)) return PA_EINVAL;
+    AdamwHyper h{lr, beta1, beta2, eps, weight_decay, 1.f, 1.f};
+    if (!hyper_dev) {
+        h.bc1 = 1.f - powf(beta1, (float)step);
+        h.bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
+    }
+    const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+    const int64_t n4 = vec ? n / 4 : 0;
+    const int blocks = (int)std::min<int64_t>(cdiv(std::max<int64_t>(n4, 1), 256), 8192);
+    hipLaunchKernelGGL(adamw_clip_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, n, h, hyper_dev, gscale_dev);
+    return check_launch();
+}
+
+extern "C" int pa_adamw_stage_clip(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, const float* scales,
+                                   int n_desc, int total_items, int dtype, float lr, float beta1, float beta2, float eps,
+                                   float weight_decay, int step, const float* hyper_dev, const float* gscale_dev, void* stream) {
+    if (!p || !g || !m || !v || !descs || n_desc < 1 || total_items < 1 || (!hyper_dev && step < 1)) return PA_EINVAL;
+    if ((dtype != PA_BF16 && dtype != PA_F32) || ((uintptr_t)scales & 7)) return PA_EINVAL;
+    AdamwHyper h{lr, beta1, beta2, eps, weight_decay, 1.f, 1.f};
+    if (!hyper_dev) {
+        h.bc1 = 1.f - powf(beta1, (float)step);
+        h.bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
+    }
+    const float2* sc = (const float2*)scales;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(total_items), block(256);
+    if (dtype == PA_BF16 && !sc)
+        hipLaunchKernelGGL((adamw_stage_clip_kernel<bf16, false>), grid, block, 0, st, p, g, m, v, descs, n_desc, hyper_dev, h, sc, gscale_dev);
+    else if (dtype == PA_BF16)
+        hipLaunchKernelGGL((adamw_stage_clip_kernel<bf16, true>), grid, block, 0, st, p, g, m, v, descs, n_desc, hyper_dev, h, sc, gscale_dev);
+    else if (!sc)
+        hipLaunchKernelGGL((adamw_stage_clip_kernel<float, false>), grid, block, 0, st, p, g, m, v, descs, n_desc, hyper_dev, h, sc, gscale_dev);
+    else
+        hipLaunchKernelGGL((adamw_stage_clip_kernel<float, true>), grid, block, 0, st, p, g, m, v, descs, n_desc, hyper_dev, h, sc, gscale_dev);
+    return check_launch();
+}
+
+extern "C" int64_t pa_grad_norm_partials(int64_t n) { return n <= 0 ? 0 : cdiv(n, GN_CHUNK); }
+
+extern "C" int pa_grad_accum_sumsq(const float* g, float* acc, int first, int64_t n, float* partials, void* stream) {
+    if (!g || n <= 0 || (!acc && !partials)) return PA_EINVAL;
+    const int64_t chunks = cdiv(n, GN_CHUNK);
+    if (chunks > 0x7fffffff) return PA_EINVAL;
+    hipLaunchKernelGGL(grad_accum_sumsq_kernel, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream, g, acc, first, n, partials);
+    return check_launch();
+}
+
+extern "C" int pa_clip_coef(const float* partials, int n_partials, float max_norm, float* out, void* stream) {
+    if (!partials || !out || n_partials < 1 || !(max_norm > 0.f)) return PA_EINVAL;
+    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n_partials, max_norm, out);
     return check_launch();
 }
 

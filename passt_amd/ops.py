@@ -1549,6 +1549,47 @@ def adamw_dev(p, g, m, v, hyper_dev):
                                    _p(hyper_dev, torch.float32), _stream()), "pa_adamw_dev")
 
 
+def grad_norm_partials(n):
+    """how many f32 partial sums pa_grad_accum_sumsq writes for a span of n elements (host only: a function of n alone)"""
+    return int(_lib.load().pa_grad_norm_partials(int(n)))
+
+
+def grad_accum_sumsq(g, acc=None, first=False, partials=None):
+    """One pass over the flat f32 gradients ``g``: ``acc = g if first else acc + g`` (when given) and/or ``partials[k]`` = the sum of
+    squares of chunk k of the result (acc, or g without acc); deterministic, see pa_grad_accum_sumsq."""
+    n = g.numel()
+    if acc is not None and acc.numel() != n:
+        raise _lib.PasstAmdError(f"grad_accum_sumsq: acc holds {acc.numel()} elements, g {n}")
+    if partials is not None and partials.numel() != grad_norm_partials(n):
+        raise _lib.PasstAmdError(f"grad_accum_sumsq: {partials.numel()} partial slots for {n} elements, {grad_norm_partials(n)} needed")
+    check(_lib.load().pa_grad_accum_sumsq(_p(g, torch.float32), _p(acc, torch.float32), int(bool(first)), n, _p(partials, torch.float32),
+                                          _stream()), "pa_grad_accum_sumsq")
+
+
+def clip_coef(partials, max_norm, out):
+    """out[0] = the total L2 norm behind ``partials``, out[1] = clip_grad_norm_'s factor for ``max_norm`` (2 device floats, no sync)"""
+    if out.numel() != 2:
+        raise _lib.PasstAmdError("clip_coef: out holds 2 floats (norm, factor)")
+    check(_lib.load().pa_clip_coef(_p(partials, torch.float32), partials.numel(), float(max_norm), _p(out, torch.float32), _stream()),
+          "pa_clip_coef")
+
+
+def adamw_clip(p, g, m, v, lr, beta1, beta2, eps, wd, step, hyper_dev=None, gscale=None):
+    """adamw / adamw_dev (hyper_dev: 7 device floats) on g * gscale, gscale one device float (None: 1); g itself is not written"""
+    check(_lib.load().pa_adamw_clip(_p(p, torch.float32), _p(g, torch.float32), _p(m, torch.float32), _p(v, torch.float32), p.numel(),
+                                    float(lr), float(beta1), float(beta2), float(eps), float(wd), int(step), _p(hyper_dev, torch.float32),
+                                    _p(gscale, torch.float32), _stream()), "pa_adamw_clip")
+
+
+def adamw_stage_clip(p, g, m, v, table, scales, n, items, dtype, lr, beta1, beta2, eps, weight_decay, step, hyper_dev=None, gscale=None):
+    """adamw_stage / adamw_stage_groups / adamw_groups (scales may be None, table entries may omit their copies) on g * gscale"""
+    assert scales is None or (scales.dtype == torch.float32 and scales.numel() == 2 * n and scales.is_contiguous())
+    check(_lib.load().pa_adamw_stage_clip(_p(p, torch.float32), _p(g, torch.float32), _p(m, torch.float32), _p(v, torch.float32), _p(table),
+                                          _p(scales), n, items, dtype, float(lr), float(beta1), float(beta2), float(eps),
+                                          float(weight_decay), int(step), _p(hyper_dev), _p(gscale, torch.float32), _stream()),
+          "pa_adamw_stage_clip")
+
+
 def adamw_hyper(lr, beta1, beta2, eps, wd, step, out_host):
     """fill the 7-float HOST tensor `out_host` with [lr, beta1, beta2, eps, wd, 1 - beta1^step, sqrt(1 - beta2^step)]"""
     assert out_host.dtype == torch.float32 and out_host.numel() == 7 and not out_host.is_cuda

@@ -23,6 +23,12 @@ the model's backward writes into it in place and ``p.grad`` are standing views o
 launch (update + the bf16 weight copies of the next forward) and O(1) Python: no 159 AccumulateGrad nodes, no per-parameter
 ``state["step"]`` / version bumps (the parameters of a bound model share one step tensor), ``zero_grad()`` marks the buffer fresh
 instead of dropping 159 ``.grad`` tensors.  ``PASST_AMD_NO_FLAT_GRADS=1`` keeps the unbound behaviour (A/B).
+
+``max_grad_norm=c`` (keyword-only): global-norm clipping inside the step, ``torch.nn.utils.clip_grad_norm_(params, c)``'s arithmetic
+without its foreach passes and without a host sync: one ``pa_grad_accum_sumsq`` per run of gradients (a bound model: one over its flat
+gradient buffer), one ``pa_clip_coef``, then the runs' updates with the factor read from device memory (``pa_adamw_stage_clip`` /
+``pa_adamw_clip``).  The norm covers every parameter of this optimizer that has a gradient.  ``p.grad`` keep the UNCLIPPED values
+(torch clips in place); ``opt.grad_norm`` is the last step's pre-clip norm, a 1-element device tensor.
 """
 import os
 
@@ -33,13 +39,18 @@ from . import ops
 
 class AdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
-                 foreach=None, capturable=False, differentiable=False, fused=None):
+                 foreach=None, capturable=False, differentiable=False, fused=None, max_grad_norm=None):
         if amsgrad or maximize or capturable or differentiable:
             raise NotImplementedError("passt_amd.optim.AdamW: amsgrad / maximize / capturable / differentiable are not supported "
                                       "(the reference uses none of them, ex_audioset.py:108)")
         if lr < 0.0 or eps < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or weight_decay < 0.0:
             raise ValueError("invalid AdamW hyper-parameter")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"passt_amd.optim.AdamW: max_grad_norm must be positive (or None: no clipping), got {max_grad_norm!r}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.grad_norm = None      # max_grad_norm: the last step's pre-clip global norm (1-element device tensor, no sync)
+        self._clip_buf = None
         self._flat = {}            # group index -> dict(ids, flat_p, m, v, offs)
         self._bound = {}           # group index -> dict(net (weakref), i0, i1, s, e, fl (the model's binding), step)
 
@@ -166,7 +177,7 @@ class AdamW(torch.optim.Optimizer):
             st["step"] = torch.tensor(float(step))
         return st
 
-    def _step_bound(self, b, fl, ps, lr, b1, b2, eps, wd):
+    def _step_bound(self, b, fl, ps, lr, b1, b2, eps, wd, jobs=None):
         """The bound model's parameters: ONE pa_adamw_stage launch on (flat parameters, the model's flat gradient buffer, flat
         moments) that also rewrites the GEMM-ready weight copies of the dtype the model last ran in.  False: the binding is gone
         (model moved / re-built / its .grad replaced by the caller) -- the per-parameter path takes over and re-binds later."""
@@ -189,7 +200,11 @@ class AdamW(torch.optim.Optimizer):
         st = net._staged
         dt = net._last_dt if net._last_dt is not None else PA_BF16
         tab, n, items, keys = st.adamw_table(("optim", id(self), s, e), [(ps[k], fl["offs"][k] - s) for k in range(i0, i1)], dt)
-        ops.adamw_stage(fl["flat_p"][s:e], b["flat_g"], fl["m"][s:e], fl["v"][s:e], tab, n, items, dt, lr, b1, b2, eps, wd, t)
+        if jobs is None:
+            ops.adamw_stage(fl["flat_p"][s:e], b["flat_g"], fl["m"][s:e], fl["v"][s:e], tab, n, items, dt, lr, b1, b2, eps, wd, t)
+        else:       # clipping: launched behind the factor (_clip_and_launch), still inside this step()
+            jobs.append((b["flat_g"], lambda gs: ops.adamw_stage_clip(fl["flat_p"][s:e], b["flat_g"], fl["m"][s:e], fl["v"][s:e], tab, None,
+                                                                      n, items, dt, lr, b1, b2, eps, wd, t, gscale=gs)))
         b["step"].fill_(float(t))
         for k in range(i0, i1):
             fl["steps"][k] = t
@@ -200,12 +215,30 @@ class AdamW(torch.optim.Optimizer):
     def _launch(self, p, g, m, v, lr, b1, b2, eps, wd, step):
         ops.adamw(p, g, m, v, lr, b1, b2, eps, wd, step)
 
+    def _clip_and_launch(self, jobs):
+        """jobs: [(flat gradients of a run, launch(gscale))] of the whole step.  Partial sums of squares per run, ONE factor over all
+        of them, then every run's update with it."""
+        counts = [ops.grad_norm_partials(g.numel()) for g, _ in jobs]
+        dev, total = jobs[0][0].device, sum(counts)
+        buf = self._clip_buf
+        if buf is None or buf.device != dev or buf.numel() != total + 2:
+            buf = self._clip_buf = torch.zeros(total + 2, device=dev, dtype=torch.float32)
+        off = 0
+        for (g, _), k in zip(jobs, counts):
+            ops.grad_accum_sumsq(g, partials=buf[off:off + k])
+            off += k
+        ops.clip_coef(buf[:total], self.max_grad_norm, buf[total:])
+        self.grad_norm = buf[total:total + 1]
+        for _, launch in jobs:
+            launch(buf[total + 1:])
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        jobs = [] if self.max_grad_norm is not None else None
         for gi, group in enumerate(self.param_groups):
             if not any(p.requires_grad for p in group["params"]):
                 continue
@@ -215,7 +248,7 @@ class AdamW(torch.optim.Optimizer):
             # runs of consecutive parameters whose gradients are dense f32 and adjacent in memory: one launch each
             i, n_p = 0, len(ps)
             bound = self._bound.get(gi)
-            if bound is not None and not self._step_bound(bound, fl, ps, lr, b1, b2, eps, wd):
+            if bound is not None and not self._step_bound(bound, fl, ps, lr, b1, b2, eps, wd, jobs):
                 bound = None
             while i < n_p:
                 if bound is not None and i == bound["i0"]:
@@ -245,7 +278,11 @@ class AdamW(torch.optim.Optimizer):
                 t = steps[i] + 1
                 # one flat view over the run's gradients (adjacent views of one allocation: as_strided from the first)
                 gflat = g.as_strided((n,), (1,)) if j > i + 1 else g.reshape(-1)
-                self._launch(fl["flat_p"][start:end], gflat, fl["m"][start:end], fl["v"][start:end], lr, b1, b2, eps, wd, t)
+                args = (fl["flat_p"][start:end], gflat, fl["m"][start:end], fl["v"][start:end], lr, b1, b2, eps, wd, t)
+                if jobs is None:
+                    self._launch(*args)
+                else:
+                    jobs.append((gflat, lambda gs, a=args: ops.adamw_clip(*a, gscale=gs)))
                 for k in range(i, j):
                     st = self.state[ps[k]]
                     if "exp_avg" not in st:
@@ -254,4 +291,6 @@ class AdamW(torch.optim.Optimizer):
                     steps[k] = t
                     torch.autograd.graph.increment_version(ps[k])      # raw-pointer update: consumers key on _version
                 i = j
+        if jobs:
+            self._clip_and_launch(jobs)
         return loss

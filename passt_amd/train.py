@@ -43,7 +43,7 @@ def group_scales(named_dims, depth, layer_decay=None, no_weight_decay=(), model_
 class TrainStep:
     def __init__(self, net, mel=None, lr=2e-5, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, optimizer="adamw",
                  mixup_alpha=0.3, use_mixup=True, process_group=None, loss="bce", comm_dtype="fp32", transport="torch", graph=False,
-                 layer_decay=None, no_weight_decay=()):
+                 layer_decay=None, no_weight_decay=(), clip_grad_norm=None, accumulate=1):
         """A partly frozen network (``requires_grad`` as it stands at construction) is trained as it is: the flat buffers, the moments
         and the all-reduce buckets span the trainable parameters only, the frozen ones keep their storage and are never written, the
         forward keeps nothing of the blocks below the lowest trainable stage and the backward ends behind it (passt.trainable_plan).
@@ -55,12 +55,32 @@ class TrainStep:
         arguments, bit-identical parameters (tests/test_gpu_model.py::test_train_step_graph_equals_eager); what changes is the
         host: one replay instead of ~290 ctypes launches -- it matters where the step is short (ESC-50 at batch 12).
         Stochastic depth (a net built with drop_path_rate > 0): the step's factors are drawn on the device ahead of the replay
-        (passt.drop_path_draws, where the eager forward draws them) into a buffer of fixed address next to the Patchout indices."""
+        (passt.drop_path_draws, where the eager forward draws them) into a buffer of fixed address next to the Patchout indices.
+        ``clip_grad_norm`` = c (AdamW; Lightning's trainer.gradient_clip_val): the update uses g * min(1, c / (norm + 1e-6)), norm
+        being the global L2 norm over the flat gradient buffer (the trainable parameters; torch.nn.utils.clip_grad_norm_'s
+        arithmetic).  Every bucket's partial sums of squares go out from the backward (pa_grad_accum_sumsq), the factor is formed
+        on the device (pa_clip_coef) and the per-bucket AdamW launches read it from there (pa_adamw_stage_clip / pa_adamw_clip),
+        after the backward: no host sync, capturable.  ``flat_g`` / ``p.grad`` keep the UNCLIPPED gradients (torch clips in
+        place; not writing them saves a pass over the buffer).  ``grad_norm``: the last update's pre-clip norm, a 1-element
+        device tensor.
+        ``accumulate`` = k (trainer.accumulate_grad_batches): ``step()`` is called once per micro-batch and returns its loss; the
+        loss gradient carries 1 / (world k); micro-steps 1 .. k - 1 fold their finished buckets into a second flat buffer
+        (``flat_acc``) and touch nothing else -- no all-reduce (Lightning's no_sync), no optimizer launch, ``t`` stands still; the
+        k-th folds, all-reduces, and updates from the accumulated buffer.  ``flush()`` applies a partial accumulation (the end
+        of an epoch whose batch count is no multiple of k)."""
         self.net, self.mel = net, mel
         self.lr, self.wd, self.betas, self.eps, self.optimizer = lr, weight_decay, betas, eps, optimizer
         self.mixup_alpha, self.use_mixup = mixup_alpha, use_mixup
         assert loss in ("bce", "ce")      # bce: ex_audioset.py:181-186 ; ce: ex_esc50.py:159-165 (class-index targets)
         self.loss = loss
+        if clip_grad_norm is not None and not float(clip_grad_norm) > 0.0:
+            raise ValueError(f"TrainStep: clip_grad_norm must be positive (or None: no clipping), got {clip_grad_norm!r}")
+        if clip_grad_norm is not None and optimizer != "adamw":
+            raise ValueError("TrainStep: clip_grad_norm rides on the AdamW launches (pa_adamw_stage_clip); optimizer='sgd' has no such form")
+        if int(accumulate) != accumulate or accumulate < 1:
+            raise ValueError(f"TrainStep: accumulate is a count of micro-batches >= 1, got {accumulate!r}")
+        self.clip = None if clip_grad_norm is None else float(clip_grad_norm)
+        self.accumulate, self._micro, self._last = int(accumulate), 0, True
         dev = next(net.parameters()).device
         self.plan = trainable_plan(net)
         if not self.plan.wanted:
@@ -87,7 +107,10 @@ class TrainStep:
             off += k
         self.m = torch.zeros_like(self.flat_p) if optimizer == "adamw" else None
         self.v = torch.zeros_like(self.flat_p) if optimizer == "adamw" else None
-        self.reducer = GradReducer(self.flat_g, [(n, p.numel()) for n, p in self.named], len(net.blocks), process_group,
+        # accumulate > 1: the buffer the micro-batches' gradients are summed in; the all-reduce and the optimizer read THIS one
+        self.flat_acc = torch.zeros_like(self.flat_g) if self.accumulate > 1 else None
+        self._gbuf = self.flat_g if self.flat_acc is None else self.flat_acc
+        self.reducer = GradReducer(self._gbuf, [(n, p.numel()) for n, p in self.named], len(net.blocks), process_group,
                                    comm_dtype=comm_dtype, transport=transport)
         # identical replicas: rank 0's parameters everywhere (what Lightning's DDP wrapper does at construction,
         # ex_audioset.py:488-489); a caller that seeded per rank or loaded different state must not train diverging copies
@@ -99,6 +122,9 @@ class TrainStep:
             # Per model (net._gemm_flags rides on every pa_gemm_nt call of this net's forward / backward); close() undoes it.
             object.__setattr__(net, "_gemm_flags", getattr(net, "_gemm_flags", 0) | ops._lib.GEMM_NO_PERSIST)
             self._set_no_persist = True
+        if graph and self.accumulate > 1:
+            raise NotImplementedError("TrainStep(graph=True) with accumulate > 1 is not supported: the folding micro-steps and the "
+                                      "updating one are two different launch sequences, i.e. two captured graphs; use graph=False")
         self.graph = bool(graph) and self.reducer.world == 1
         if self.graph and optimizer != "adamw":
             raise NotImplementedError("TrainStep(graph=True) captures the per-bucket AdamW launches (pa_adamw_dev reads its scalars "
@@ -117,18 +143,66 @@ class TrainStep:
             self._offsets.append(off)
             off += p.numel()
         self._fresh = []
+        # clipping: one run of partial slots per bucket (pa_grad_norm_partials of its span) in ONE array, [norm, factor] behind it
+        self._part, self.grad_norm = {}, None
+        if self.clip is not None:
+            n_part = 0
+            for s_, e_ in self._spans():
+                k = ops.grad_norm_partials(e_ - s_)
+                self._part[(s_, e_)] = (n_part, n_part + k)
+                n_part += k
+            self._partials = torch.zeros(n_part, device=dev, dtype=torch.float32)
+            self._clip_out = torch.zeros(2, device=dev, dtype=torch.float32)
+            self.grad_norm = self._clip_out[:1]
         net.mark_params_updated()
 
+    def _spans(self):
+        """the non-empty buckets' flat spans in the order the backward completes them"""
+        return [se for se in (self.reducer.spans[b] for b in self.reducer.launch_order()) if se[1] > se[0]]
+
+    def _norm_partials(self, s, e, fold=False):
+        """bucket [s, e): its partial sums of squares -- of the gradients as they stand, or (fold) of the accumulated buffer in the
+        pass that adds this micro-batch to it"""
+        a, b = self._part[(s, e)]
+        if fold:
+            ops.grad_accum_sumsq(self.flat_g[s:e], self.flat_acc[s:e], first=self._micro == 0, partials=self._partials[a:b])
+        else:
+            ops.grad_accum_sumsq(self._gbuf[s:e], partials=self._partials[a:b])
+
+    def _optimizer_clip(self, s, e):
+        """_optimizer with the clip factor (device memory: self._clip_out[1]) on the gradients: the same launch per case"""
+        fp, g, m, v, gs = self.flat_p[s:e], self._gbuf[s:e], self.m[s:e], self.v[s:e], self._clip_out[1:]
+        hy = (self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self._t_now)
+        if self._g is not None and self._g.get("capturing"):
+            if self.groups is not None:
+                tab, n, items, scales = self._group_table(s, e)
+                return ops.adamw_stage_clip(fp, g, m, v, tab, scales, n, items, _precision(self.net), 0.0, 0.0, 0.0, 0.0, 0.0, 0,
+                                            hyper_dev=self._g["hyper"], gscale=gs)
+            return ops.adamw_clip(fp, g, m, v, 0.0, 0.0, 0.0, 0.0, 0.0, 0, hyper_dev=self._g["hyper"], gscale=gs)
+        if self.fused_stage:
+            st, dt = self.net._staged, _precision(self.net)
+            lo, hi = self._span_params(s, e)
+            tab, n, items, keys = st.adamw_table((s, e), [(self.named[i][1], self._offsets[i] - s) for i in range(lo, hi)], dt)
+            ops.adamw_stage_clip(fp, g, m, v, tab, None if self.groups is None else self._group_table(s, e)[3], n, items, dt, *hy, gscale=gs)
+            self._fresh += keys
+        elif self.groups is not None:
+            tab, n, items, scales = self._group_table(s, e)
+            ops.adamw_stage_clip(fp, g, m, v, tab, scales, n, items, _precision(self.net), *hy, gscale=gs)
+        else:
+            ops.adamw_clip(fp, g, m, v, *hy, gscale=gs)
+
     def _optimizer(self, s, e):
+        if self.clip is not None:
+            return self._optimizer_clip(s, e)
         if self._g is not None and self._g.get("capturing"):
             # inside the capture: the step's scalars come from device memory (launch arguments must not change between replays)
             if self.optimizer != "adamw":
                 raise NotImplementedError("graph mode: AdamW only")
             if self.groups is not None:
                 tab, n, items, scales = self._group_table(s, e)
-                return ops.adamw_groups(self.flat_p[s:e], self.flat_g[s:e], self.m[s:e], self.v[s:e], tab, scales, n, items, 0.0, 0.0, 0.0,
+                return ops.adamw_groups(self.flat_p[s:e], self._gbuf[s:e], self.m[s:e], self.v[s:e], tab, scales, n, items, 0.0, 0.0, 0.0,
                                         0.0, 0.0, 0, hyper_dev=self._g["hyper"])
-            return ops.adamw_dev(self.flat_p[s:e], self.flat_g[s:e], self.m[s:e], self.v[s:e], self._g["hyper"])
+            return ops.adamw_dev(self.flat_p[s:e], self._gbuf[s:e], self.m[s:e], self.v[s:e], self._g["hyper"])
         if self.optimizer == "adamw" and self.fused_stage:
             # no kernel enqueued after this point reads this bucket's copies before the next forward: the bucket's own input-
             # gradient GEMMs (the readers of W^T) are already on the stream, earlier blocks read their own weights
@@ -136,21 +210,21 @@ class TrainStep:
             lo, hi = self._span_params(s, e)
             tab, n, items, keys = st.adamw_table((s, e), [(self.named[i][1], self._offsets[i] - s) for i in range(lo, hi)], dt)
             if self.groups is None:
-                ops.adamw_stage(self.flat_p[s:e], self.flat_g[s:e], self.m[s:e], self.v[s:e], tab, n, items, dt, self.lr, self.betas[0],
+                ops.adamw_stage(self.flat_p[s:e], self._gbuf[s:e], self.m[s:e], self.v[s:e], tab, n, items, dt, self.lr, self.betas[0],
                                 self.betas[1], self.eps, self.wd, self._t_now)
             else:
-                ops.adamw_stage_groups(self.flat_p[s:e], self.flat_g[s:e], self.m[s:e], self.v[s:e], tab, self._group_table(s, e)[3], n,
+                ops.adamw_stage_groups(self.flat_p[s:e], self._gbuf[s:e], self.m[s:e], self.v[s:e], tab, self._group_table(s, e)[3], n,
                                        items, dt, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self._t_now)
             self._fresh += keys
         elif self.optimizer == "adamw" and self.groups is not None:
             tab, n, items, scales = self._group_table(s, e)
-            ops.adamw_groups(self.flat_p[s:e], self.flat_g[s:e], self.m[s:e], self.v[s:e], tab, scales, n, items, self.lr, self.betas[0],
+            ops.adamw_groups(self.flat_p[s:e], self._gbuf[s:e], self.m[s:e], self.v[s:e], tab, scales, n, items, self.lr, self.betas[0],
                              self.betas[1], self.eps, self.wd, self._t_now)
         elif self.optimizer == "adamw":
-            ops.adamw(self.flat_p[s:e], self.flat_g[s:e], self.m[s:e], self.v[s:e], self.lr, self.betas[0], self.betas[1],
+            ops.adamw(self.flat_p[s:e], self._gbuf[s:e], self.m[s:e], self.v[s:e], self.lr, self.betas[0], self.betas[1],
                       self.eps, self.wd, self._t_now)
         else:
-            ops.sgd(self.flat_p[s:e], self.flat_g[s:e], self.lr)
+            ops.sgd(self.flat_p[s:e], self._gbuf[s:e], self.lr)
 
     def _group_table(self, s, e):
         """(plain descriptor table, n, work items, scales) of flat span [s, e) for the launches with parameter groups: one entry per
@@ -189,12 +263,70 @@ class TrainStep:
         patch embedding).  One GPU: update that bucket's parameters right away -- no later kernel of this backward reads
         them (input gradients use the bf16 copies staged before the step), so the bandwidth-bound optimizer pass runs next
         to the remaining blocks' GEMMs instead of after them.  Several GPUs: start the bucket's all-reduce."""
-        if self.reducer.world > 1:
+        s, e = self.reducer.spans[i]
+        one_gpu = self.reducer.world == 1
+        if self.flat_acc is not None and e > s:
+            # gradient accumulation: fold this micro-batch's bucket into the accumulated buffer -- and, on the updating micro-step of
+            # one GPU with clipping, take the partial sums of squares of the result in the same pass
+            if self._last and one_gpu and self.clip is not None:
+                self._norm_partials(s, e, fold=True)
+            else:
+                ops.grad_accum_sumsq(self.flat_g[s:e], self.flat_acc[s:e], first=self._micro == 0)
+        if not self._last:
+            return                  # no all-reduce (Lightning's no_sync), no update
+        if not one_gpu:
             return self.reducer.on_block_done(i)
-        if self.block_optimizer:
-            s, e = self.reducer.spans[i]
-            if e > s:
-                self._optimizer(s, e)
+        if self.clip is not None:
+            # the norm needs every bucket: the extra read overlaps the rest of the backward, the updates go out behind it (_apply)
+            if self.flat_acc is None and e > s:
+                self._norm_partials(s, e)
+        elif self.block_optimizer and e > s:
+            self._optimizer(s, e)
+
+    def _apply(self, flush=False):
+        """The launches that end an update, behind the backward (or from flush()): all-reduce waits, the clip factor, and every
+        optimizer launch _block_done could not issue."""
+        total = self.flat_p.numel()
+        if self.reducer.world > 1:
+            if flush:                                       # the folding micro-steps reduced nothing
+                for b in self.reducer.launch_order():
+                    self.reducer.on_block_done(b)
+            # one optimizer launch per all-reduce bucket, in the order the buckets were launched: the update of bucket k runs
+            # while buckets k+1.. are still on the wire, so the LAST bucket (block 0 + patch embedding, released only when
+            # the backward ends) is covered by ~0.4 ms of optimizer work instead of being exposed in front of one big launch.
+            # With clipping a bucket's partial sums take the update's place here; the updates follow the factor.
+            for s_, e_ in self.reducer.drain():
+                if self.clip is None:
+                    self._optimizer(s_, e_)
+                else:
+                    self._norm_partials(s_, e_)
+        elif flush and self.clip is not None:
+            for s_, e_ in self._spans():
+                self._norm_partials(s_, e_)
+        if self.clip is not None:
+            ops.clip_coef(self._partials, self.clip, self._clip_out)
+            if self.reducer.world == 1 and not self.block_optimizer:
+                self._optimizer(0, total)
+            else:
+                for s_, e_ in self._spans():
+                    self._optimizer(s_, e_)
+        elif self.reducer.world == 1:
+            if not self.block_optimizer:
+                self._optimizer(0, total)
+            elif flush:
+                for s_, e_ in self._spans():
+                    self._optimizer(s_, e_)
+
+    def flush(self):
+        """Apply what has accumulated since the last update (accumulate > 1: fewer than k micro-steps; the gradients keep their
+        1 / k scale, as Lightning's last update of an epoch does).  Nothing pending: nothing happens."""
+        if self._micro == 0:
+            return
+        self._t_now = self.t + 1
+        self._apply(flush=True)
+        self.t = self._t_now
+        self._micro = 0
+        self._params_updated()
 
     def close(self):
         """Release the reducer's communicator (C-ABI RCCL transport); torch.distributed groups belong to the caller."""
@@ -236,8 +368,7 @@ class TrainStep:
         else:
             loss, dlogits = ops.ce_mixup_fwd_bwd(logits, g["y"], grad_scale=1.0)
         passt_backward(net, ctx, dlogits, None, self.grads, on_block_done=self._block_done)
-        if not self.block_optimizer:
-            self._optimizer(0, self.flat_p.numel())
+        self._apply()
         return loss
 
     def step(self, wave_or_spec, target):
@@ -266,7 +397,7 @@ class TrainStep:
         if self.graph and self.t >= self.graph_warmup and self._graph_fits(x):
             return self._graph_step(x, y, perm_d if self.use_mixup else None, lam_d if self.use_mixup else None)
         logits, feat, ctx = passt_forward(net, x, save=self.plan)
-        gs = 1.0 / self.reducer.world
+        gs = 1.0 / (self.reducer.world * self.accumulate)
         if self.loss == "bce":
             loss, dlogits = ops.bce_fwd_bwd(logits, y, grad_scale=gs)
         else:
@@ -281,16 +412,14 @@ class TrainStep:
         # a failed step is not atomic; recover from a checkpoint (or run with PASST_AMD_BLOCK_OPT=0, where nothing is
         # touched before the backward has finished).
         self._t_now = self.t + 1
+        self._last = self._micro + 1 >= self.accumulate         # does this micro-step end with the update?
         passt_backward(net, ctx, dlogits, None, self.grads, on_block_done=self._block_done)
-        if self.reducer.world == 1 and not self.block_optimizer:
-            self._optimizer(0, self.flat_p.numel())
-        if self.reducer.world > 1:
-            # one optimizer launch per all-reduce bucket, in the order the buckets were launched: the update of bucket k runs
-            # while buckets k+1.. are still on the wire, so the LAST bucket (block 0 + patch embedding, released only when
-            # the backward ends) is covered by ~0.4 ms of optimizer work instead of being exposed in front of one big launch
-            for s_, e_ in self.reducer.drain():
-                self._optimizer(s_, e_)
+        self._micro += 1
+        if not self._last:
+            return loss             # parameters, moments, staged copies and t untouched
+        self._apply()
         self.t = self._t_now
+        self._micro = 0
         self._params_updated()
         return loss
 
