@@ -153,20 +153,28 @@ int pa_mel_frontend_bwd_varlen_aug(const float* wave, int B, int ldw, const int3
 /* ------------------------------------------------------------------------------------------
  * Parameter staging (no reference counterpart: AMP autocast casts weights per op)
  * ------------------------------------------------------------------------------------------ */
-/* out[i] = (dtype) in[i] */
+/* Casts to bf16 everywhere in this library round to nearest even; NaN stays NaN, the largest finite f32 rounds to inf, f32 subnormals
+ * round like any other value (to +-0 or a bf16 subnormal) -- bit for bit what torch's CPU cast gives (tests/patch_cases.py, tie family).
+ * out[i] = (dtype) in[i].  `in` needs only its natural 4-byte alignment: a pointer off 16 bytes (a parameter at an arbitrary offset of a
+ * flat buffer) is read with scalar loads instead of 16-byte vectors; `out` is written element by element. */
 int pa_convert_f32(const float* in, void* out, int64_t n, int dtype, void* stream);
 /* out[m][d] = (dtype)(rowscale[m] * in[m][d]), in [M][D] f32, D % 4 == 0: the copy of a gradient that enters a branch carrying a
  * stochastic-depth row factor (DropPath, models/helpers/vit_helpers.py:203-222 as Block applies it to the MLP branch,
  * models/passt.py:378-379) -- where the head's gradient enters the last block.  With dtype PA_F32 `out` is a second f32 buffer.
- * rowscale NULL: pa_convert_f32 over M * D elements. */
+ * rowscale NULL: pa_convert_f32 over M * D elements.  With a rowscale, `in` and `out` must be 16-byte aligned (four columns per access;
+ * PA_EINVAL otherwise, nothing launched); rowscale itself is read one float per row. */
 int pa_convert_f32_rowscale(const float* in, const float* rowscale, void* out, int M, int D, int dtype, void* stream);
-/* out[i] = (float) in[i], in of `dtype` (the bf16 gradient wire of the data-parallel reducer, passt_amd/ddp.py) */
+/* out[i] = (float) in[i], in of `dtype` (the bf16 gradient wire of the data-parallel reducer, passt_amd/ddp.py).  Either pointer off
+ * 16 bytes: scalar accesses instead of vectors. */
 int pa_convert_to_f32(const void* in, int dtype, float* out, int64_t n, void* stream);
 /* Batched form of the two calls below, for refreshing every GEMM-ready weight copy after an optimizer
  * step in ONE launch: entry e reads src[rows][cols] (f32, contiguous) and writes, where non-NULL,
  * dst[rows][cols] (straight cast) and dst_t[cols][rows] (transposed), both of `dtype` and contiguous.
  * `descs` is an array of n_desc entries in DEVICE memory; tile_begin is the running count of 64x64 tiles
- * (ceil(rows/64)*ceil(cols/64) per entry, in order); total_tiles is their sum. */
+ * (ceil(rows/64)*ceil(cols/64) per entry, in order); total_tiles is their sum.
+ * Alignment: none required beyond the element's own.  An entry takes the vector path (16-byte loads, 4-element stores) when rows and
+ * cols are multiples of 4, src is 16-byte aligned and dst / dst_t (where given) are aligned to 4 elements (8 bytes in bf16, 16 in
+ * f32); any other entry is moved element by element -- the table lives in device memory, so the kernel decides, per entry. */
 typedef struct pa_stage_desc {
     const float* src;
     void* dst;
@@ -177,7 +185,8 @@ typedef struct pa_stage_desc {
 } pa_stage_desc;
 int pa_stage_weights(const pa_stage_desc* descs, int n_desc, int total_tiles, int dtype, void* stream);
 /* in[R][C] (ld = ldi) of dtype in_dtype -> out[C][ldo] of dtype out_dtype, out[c][r] = in[r][c];
- * columns r in [R, ldo) of out are zero-filled (K-padding for the weight-gradient GEMM). */
+ * columns r in [R, ldo) of out are zero-filled (K-padding for the weight-gradient GEMM), whole 64-column tiles behind R included.
+ * Element accesses only: no alignment beyond the element's own. */
 int pa_transpose(const void* in, int in_dtype, int R, int C, int ldi, void* out, int out_dtype,
                  int ldo, void* stream);
 
@@ -376,15 +385,20 @@ int pa_gemm_tn_batched(const pa_gemm_args* a, int n, void* stream);
  * PA_EUNSUPPORTED: token counts that differ between the problems (and whatever pa_gemm_tn_batched does not support). */
 int pa_gemm_tn_batched_plan(const pa_gemm_args* a, int n, int n_long, int long_steps, void* stream);
 /* Row gather / scatter and strided zero fill (prefix-token path of the last block):
- * gather: out[i] = in[idx[i]]; scatter: out[idx[i]] = in[i]; rows of row_bytes bytes (multiple of 4). */
+ * gather: out[i] = in[idx[i]]; scatter: out[idx[i]] = in[i]; rows of row_bytes bytes (multiple of 4).  in and out must be 4-byte
+ * aligned (PA_EINVAL otherwise); rows move as 16-byte vectors when row_bytes, in and out are all multiples of 16, as 4-byte words
+ * otherwise.  idx[i] in [0, rows) is the caller's duty and is NOT checked; scatter: distinct idx (a repeated one leaves either row). */
 int pa_gather_rows(const void* in, const int32_t* idx, int n_idx, int64_t row_bytes, void* out, void* stream);
 int pa_scatter_rows(const void* in, const int32_t* idx, int n_idx, int64_t row_bytes, void* out, void* stream);
 /* Gradient of the last block's full-rows output: dx[M][D] = (add0 ? add0 : 0) + (add1 ? add1 : 0) + scatter(rows[n_idx][D] at
  * idx), f32, plus the copy dx_lp (dtype; optional) in the same pass.  idx: strictly ascending rows in [0, M); a row idx does not
- * name gets the addends only (zero when both are NULL).  Replaces pa_zero2d + pa_scatter_rows + an add. */
+ * name gets the addends only (exactly 0 when both are NULL).  Replaces pa_zero2d + pa_scatter_rows + an add.  D % 4 == 0
+ * (PA_EUNSUPPORTED); rows, add0, add1, dx and dx_lp must be 16-byte aligned where given (float4 columns; PA_EINVAL otherwise, nothing
+ * launched).  idx in range and ascending is the caller's duty and is not checked. */
 int pa_tail_inject(const float* rows, const int32_t* idx, int n_idx, const float* add0, const float* add1, float* dx,
                    void* dx_lp, int dtype, int M, int D, void* stream);
-/* zero `rows` rows of width_bytes at pitch_bytes */
+/* zero `rows` rows of width_bytes at pitch_bytes; the bytes of the pitch gap are not touched.  Any alignment: 16-byte stores when ptr,
+ * pitch and width are multiples of 16 and pitch != width, the runtime's memset (1-D when pitch == width, else 2-D) otherwise. */
 int pa_zero2d(void* ptr, int64_t pitch_bytes, int64_t width_bytes, int64_t rows, void* stream);
 /* out[i] = (accumulate ? out[i] : 0) + sum_z partial[z][i], i < n */
 int pa_reduce_partials(const float* partial, int splits, int64_t n, float* out, int accumulate,
@@ -562,15 +576,33 @@ int pa_attention_bwd_varlen(const void* qkv, int ldqkv, const void* o, const voi
  * Patch embedding + positional terms + Patchout: PatchEmbed.forward (models/passt.py:318-328) and
  * PaSST.forward_features :508-564 (K10-K14).  Gather-first: only the patches that survive
  * structured/unstructured Patchout are embedded.
+ *
+ * Argument checks of every entry of this section, in this order, and NOTHING is launched or written before all have passed:
+ *   1. NULL pointers and scalar ranges                                   PA_EINVAL
+ *   2. dtype (PA_F32 / PA_BF16)                                          PA_EINVAL
+ *   3. pointer alignment, where the entry states one                     PA_EINVAL
+ *   4. size limits (P * P > 1024, Np above the grid, int32 indexing)     PA_EUNSUPPORTED
+ * Index ranges.  Index arrays live in device memory and the host cannot see them.  UNCHECKED, the caller's duty -- an index out of
+ * range reads or writes out of bounds: patch_f[p] in [0, Fpe) / [0, Fg), patch_t[p] in [0, Tg) and toff + patch_t[p] < Tpe in
+ * pa_patch_gather, pa_patch_pos_table and pa_patch_bwd; cu_tok ascending with cu_tok[B] = M; toff[b] + column < Tpe for every
+ * named slot of pa_patch_bwd_rows.  TOLERATED by the kernels: pa_patch_gather_varlen reads 0 for a coordinate outside x (and for a
+ * row_clip outside [0, B)); pa_patch_input_bwd ignores (patch_f, patch_t) pairs outside the grid; the slot table of the two _rows
+ * entries may hold anything, an entry outside [0, M) counts as -1.  pa_patch_pos_table_varlen clamps row_t / row_f to the last
+ * embedding column: that is a memory-safety net, NOT a contract -- the table row of an out-of-range position is unspecified, and the
+ * backward entries do not mirror the clamp (they would drop such a row from d_time_pos / d_freq_pos).
+ * Alignment.  x, cols, the tables and every parameter gradient are accessed element by element: no requirement beyond the
+ * element's own.  The vector accesses and what they need are stated per entry below (pa_patch_bwd, the three folds).
  * ------------------------------------------------------------------------------------------ */
 /* im2col of the kept patches: x[B][1][F][T] f32 -> cols[B*Np][P*P] (dtype).
- * patch_f[Np], patch_t[Np]: grid coordinates (frequency row, time column) of kept patch p. */
+ * patch_f[Np], patch_t[Np]: grid coordinates (frequency row, time column) of kept patch p.
+ * PA_EINVAL: F < P, T < P, a non-positive stride, B, Np or P. */
 int pa_patch_gather(const float* x, int B, int F, int T, const int32_t* patch_f,
                     const int32_t* patch_t, int Np, int P, int fstride, int tstride, void* cols,
                     int dtype, void* stream);
 /* table[p][D] = bias + time_pos[:, toff + patch_t[p]] + freq_pos[:, patch_f[p]]   (f32)
  * time_pos is [D][Tpe], freq_pos is [D][Fpe] (the reference's (1,D,1,Tpe)/(1,D,Fpe,1) params).
- * Also writes the two prefix tokens: tok[b][0] = cls + npe[0], tok[b][1] = dist + npe[1]. */
+ * in f32 as (bias + time_pos) + freq_pos.  Also writes the two prefix tokens: tok[b][0] = cls + npe[0], tok[b][1] = dist + npe[1]
+ * (tok is [B][Ntok][D]; no other row of it is touched).  PA_EINVAL: non-positive Np, D, B, Tpe or Fpe, Ntok < 2. */
 int pa_patch_pos_table(const float* bias, const float* time_pos, int Tpe, const float* freq_pos,
                        int Fpe, const int32_t* patch_f, const int32_t* patch_t, int Np, int toff,
                        int D, float* table, const float* cls, const float* dist, const float* npe,
@@ -579,7 +611,9 @@ int pa_patch_pos_table(const float* bias, const float* time_pos, int Tpe, const 
  * d_cls, d_dist, d_npe[2][D], d_bias[D], d_time_pos[D][Tpe], d_freq_pos[D][Fpe] (all overwritten
  * or accumulated), and dcols_src: the patch rows of dtok compacted to [B*Np][D] (dtype) for the
  * weight-gradient GEMM.  gsum and the six parameter gradients all NULL: only dpatch is produced (frozen network, where dpatch
- * feeds the input-gradient GEMM of pa_patch_input_bwd). */
+ * feeds the input-gradient GEMM of pa_patch_input_bwd).  Deterministic (no atomics; the summation order is fixed but unspecified).
+ * PA_EINVAL: non-positive B, Np, D, Tpe or Fpe, Ntok < Np + 2, only some of the seven NULL, an unknown dtype -- refused before
+ * anything is launched -- and dtok, gsum or dpatch off 16-byte alignment (16-byte vectors of all three). */
 int pa_patch_bwd(const float* dtok, int B, int Ntok, int D, const int32_t* patch_f,
                  const int32_t* patch_t, int Np, int toff, int Tpe, int Fpe, float* gsum,
                  float* d_cls, float* d_dist, float* d_npe, float* d_bias, float* d_time_pos,
@@ -592,7 +626,9 @@ int pa_patch_bwd(const float* dtok, int B, int Ntok, int D, const int32_t* patch
  * output pixel adds its <= ceil(P/fstride) * ceil(P/tstride) patches in a fixed order (frequency row, then time column), no
  * atomics -- the result does not depend on the launch geometry.  grid_ws: int32 workspace of pa_patch_input_bwd_ws_ints() entries;
  * the call builds the grid -> slot table in it ([(F-P)/fstride+1][(T-P)/tstride+1], -1 = no kept patch there); (patch_f, patch_t)
- * pairs must be distinct, pairs outside the grid are ignored.  Spectrogram only: there is no gradient w.r.t. a waveform. */
+ * pairs must be distinct, pairs outside the grid are ignored.  Spectrogram only: there is no gradient w.r.t. a waveform.
+ * Alignment (this entry and its _varlen and _rows forms): dx 16-byte aligned (one 16-byte store per four elements of the flat dx),
+ * dcols 4-byte aligned (bf16 dcols are read in pairs where P and the offset into the patch row are even); PA_EINVAL otherwise. */
 int64_t pa_patch_input_bwd_ws_ints(int F, int T, int P, int fstride, int tstride);
 int pa_patch_input_bwd(const void* dcols, int dtype, int B, int Np, const int32_t* patch_f, const int32_t* patch_t, int P,
                        int fstride, int tstride, int F, int T, int32_t* grid_ws, float* dx, void* stream);

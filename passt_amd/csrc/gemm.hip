@@ -2183,8 +2183,11 @@ template <typename T>
 __global__ void convert_kernel(const float* __restrict__ in, T* __restrict__ out, int64_t n) {
     int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
+    const bool vec = ((uintptr_t)in & 15) == 0;      // an operand at an arbitrary offset of a flat buffer: scalar loads
     for (; i + 3 < n; i += stride) {
-        const float4 v = *(const float4*)(in + i);
+        float4 v;
+        if (vec) v = *(const float4*)(in + i);
+        else v = make_float4(in[i], in[i + 1], in[i + 2], in[i + 3]);
         out[i] = from_f32<T>(v.x); out[i + 1] = from_f32<T>(v.y);
         out[i + 2] = from_f32<T>(v.z); out[i + 3] = from_f32<T>(v.w);
     }
@@ -2246,7 +2249,8 @@ __global__ __launch_bounds__(256) void stage_weights_kernel(const pa_stage_desc*
     const int r0 = (t / tiles_c) * 64, c0 = (t % tiles_c) * 64;
     TO* dst = (TO*)d.dst;
     TO* dst_t = (TO*)d.dst_t;
-    if (((d.rows | d.cols) & 3) == 0 && ((uintptr_t)d.src & 15) == 0) {
+    // (dst / dst_t: 4-element stores, 8 bytes in bf16 and 16 in f32; NULL passes)
+    if (((d.rows | d.cols) & 3) == 0 && ((uintptr_t)d.src & 15) == 0 && (((uintptr_t)d.dst | (uintptr_t)d.dst_t) & (4 * sizeof(TO) - 1)) == 0) {
         // fast path (every PaSST weight): 16-byte loads, 4-element stores, 128+ contiguous bytes per 16 lanes
         const int lr = threadIdx.x >> 4, l4 = (threadIdx.x & 15) * 4;
 #pragma unroll
@@ -2352,7 +2356,7 @@ __global__ void gather_rows_kernel(const char* __restrict__ in, const int32_t* _
     const int i = blockIdx.x;
     const char* src = scatter ? in + (int64_t)i * row_bytes : in + (int64_t)idx[i] * row_bytes;
     char* dst = scatter ? out + (int64_t)idx[i] * row_bytes : out + (int64_t)i * row_bytes;
-    if ((row_bytes & 15) == 0) {
+    if ((row_bytes & 15) == 0 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0) {
         for (int64_t o = (int64_t)threadIdx.x * 16; o < row_bytes; o += (int64_t)blockDim.x * 16) *(uint4*)(dst + o) = *(const uint4*)(src + o);
     } else {
         for (int64_t o = (int64_t)threadIdx.x * 4; o < row_bytes; o += (int64_t)blockDim.x * 4) *(uint32_t*)(dst + o) = *(const uint32_t*)(src + o);
@@ -2544,6 +2548,8 @@ extern "C" int pa_convert_f32(const float* in, void* out, int64_t n, int dtype, 
 extern "C" int pa_convert_f32_rowscale(const float* in, const float* rowscale, void* out, int M, int D, int dtype, void* stream) {
     if (!rowscale) return (M < 0 || D < 0) ? PA_EINVAL : pa_convert_f32(in, out, (int64_t)M * D, dtype, stream);
     if (!in || !out || M < 0 || D <= 0) return PA_EINVAL;
+    if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
+    if ((((uintptr_t)in | (uintptr_t)out) & 15) != 0) return PA_EINVAL;     // four columns per access: 16-byte loads, 8- / 16-byte stores
     if (D % 4) return PA_EUNSUPPORTED;
     if (M == 0) return PA_OK;
     const int blocks = (int)std::min<int64_t>(cdiv((int64_t)M * (D / 4), 256), 4096);
@@ -2822,6 +2828,7 @@ extern "C" int pa_colsum(const void* in, int dtype, int R, int C, int ld, float*
 
 extern "C" int pa_gather_rows(const void* in, const int32_t* idx, int n_idx, int64_t row_bytes, void* out, void* stream) {
     if (!in || !idx || !out || n_idx <= 0 || row_bytes <= 0 || (row_bytes & 3)) return PA_EINVAL;
+    if ((((uintptr_t)in | (uintptr_t)out) & 3) != 0) return PA_EINVAL;      // 4-byte words; 16-byte vectors only where both are aligned
     hipLaunchKernelGGL(gather_rows_kernel, dim3(n_idx), dim3(row_bytes >= 2048 ? 128 : 64), 0, (hipStream_t)stream,
                        (const char*)in, idx, row_bytes, (char*)out, 0);
     return check_launch();
@@ -2829,6 +2836,7 @@ extern "C" int pa_gather_rows(const void* in, const int32_t* idx, int n_idx, int
 
 extern "C" int pa_scatter_rows(const void* in, const int32_t* idx, int n_idx, int64_t row_bytes, void* out, void* stream) {
     if (!in || !idx || !out || n_idx <= 0 || row_bytes <= 0 || (row_bytes & 3)) return PA_EINVAL;
+    if ((((uintptr_t)in | (uintptr_t)out) & 3) != 0) return PA_EINVAL;      // 4-byte words; 16-byte vectors only where both are aligned
     hipLaunchKernelGGL(gather_rows_kernel, dim3(n_idx), dim3(row_bytes >= 2048 ? 128 : 64), 0, (hipStream_t)stream,
                        (const char*)in, idx, row_bytes, (char*)out, 1);
     return check_launch();

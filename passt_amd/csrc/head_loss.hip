@@ -330,6 +330,8 @@ extern "C" int pa_tail_inject(const float* rows, const int32_t* idx, int n_idx, 
     if (!dx || M <= 0 || D <= 0 || n_idx < 0 || (n_idx > 0 && (!rows || !idx))) return PA_EINVAL;
     if (D % 4) return PA_EUNSUPPORTED;
     if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
+    // float4 columns of rows, add0, add1 and dx, four-element stores of dx_lp (NULL passes)
+    if ((((uintptr_t)rows | (uintptr_t)add0 | (uintptr_t)add1 | (uintptr_t)dx | (uintptr_t)dx_lp) & 15) != 0) return PA_EINVAL;
     const dim3 grid((unsigned)cdiv(M, 4));
     if (dtype == PA_BF16) hipLaunchKernelGGL(tail_inject_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, rows, idx, n_idx, add0, add1, dx, (bf16*)dx_lp, M, D);
     else hipLaunchKernelGGL(tail_inject_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, rows, idx, n_idx, add0, add1, dx, (float*)dx_lp, M, D);

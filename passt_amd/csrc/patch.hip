@@ -526,9 +526,14 @@ __global__ __launch_bounds__(256) void patch_param_grads_rows_kernel(const float
 
 using namespace pa;
 
+// Order of the argument checks of every patch entry (include/passt_amd.h): NULL pointers and scalars (PA_EINVAL), dtype (PA_EINVAL),
+// pointer alignment (PA_EINVAL), then the size limits (PA_EUNSUPPORTED).  Nothing is launched before all of them have passed.
+static inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
 extern "C" int pa_patch_gather(const float* x, int B, int F, int T, const int32_t* patch_f, const int32_t* patch_t,
                                int Np, int P, int fstride, int tstride, void* cols, int dtype, void* stream) {
-    if (!x || !patch_f || !patch_t || !cols || B <= 0 || Np <= 0 || P <= 0) return PA_EINVAL;
+    if (!x || !patch_f || !patch_t || !cols || B <= 0 || Np <= 0 || P <= 0 || fstride <= 0 || tstride <= 0 || F < P || T < P) return PA_EINVAL;
+    if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
     if (P * P > 1024) return PA_EUNSUPPORTED;
     dim3 grid((unsigned)Np, (unsigned)B);
     if (dtype == PA_BF16) hipLaunchKernelGGL(patch_gather_kernel<bf16>, grid, dim3(P * P), 0, (hipStream_t)stream, x, F, T, patch_f, patch_t, Np, P, fstride, tstride, (bf16*)cols);
@@ -542,6 +547,7 @@ extern "C" int pa_patch_pos_table(const float* bias, const float* time_pos, int 
                                   const float* cls, const float* dist, const float* npe, float* tok, int B, int Ntok,
                                   void* stream) {
     if (!bias || !time_pos || !freq_pos || !patch_f || !patch_t || !table || !cls || !dist || !npe || !tok) return PA_EINVAL;
+    if (Np <= 0 || D <= 0 || B <= 0 || Tpe <= 0 || Fpe <= 0 || Ntok < 2) return PA_EINVAL;
     const int64_t n = (int64_t)Np * D + (int64_t)B * 2 * D;
     hipLaunchKernelGGL(patch_pos_table_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, bias,
                        time_pos, Tpe, freq_pos, Fpe, patch_f, patch_t, Np, toff, D, table, cls, dist, npe, tok, B, Ntok);
@@ -552,6 +558,7 @@ extern "C" int pa_patch_gather_varlen(const float* x, int B, int F, int T_max, c
                                       const int32_t* row_t, int M, int P, int fstride, int tstride, void* cols, int dtype, void* stream) {
     if (!x || !row_clip || !row_f || !row_t || !cols || B <= 0 || F <= 0 || T_max <= 0 || M <= 0 || P <= 0 || fstride <= 0 || tstride <= 0)
         return PA_EINVAL;
+    if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
     if (P * P > 1024) return PA_EUNSUPPORTED;
     const dim3 grid((unsigned)M), block((unsigned)(P * P));
     if (dtype == PA_BF16)
@@ -581,8 +588,11 @@ extern "C" int pa_patch_bwd(const float* dtok, int B, int Ntok, int D, const int
                             void* stream) {
     // gsum and the six parameter gradients all NULL: only the compaction (frozen network: dpatch feeds the input-gradient GEMM)
     const bool rows_only = !gsum && !d_cls && !d_dist && !d_npe && !d_bias && !d_time_pos && !d_freq_pos;
-    if (!dtok || !patch_f || !patch_t || !dpatch || B <= 0 || Np <= 0 || D <= 0) return PA_EINVAL;
+    if (!dtok || !patch_f || !patch_t || !dpatch || B <= 0 || Np <= 0 || D <= 0 || Tpe <= 0 || Fpe <= 0 || Ntok < Np + 2) return PA_EINVAL;
     if (!rows_only && (!gsum || !d_cls || !d_dist || !d_npe || !d_bias || !d_time_pos || !d_freq_pos)) return PA_EINVAL;
+    if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
+    // batch_sum_kernel and patch_rows_kernel move 16-byte vectors of dtok, gsum and dpatch
+    if (misaligned(dtok, 16) || misaligned(gsum, 16) || misaligned(dpatch, 16)) return PA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     int rc = PA_OK;
     if (!rows_only) {
@@ -598,8 +608,7 @@ extern "C" int pa_patch_bwd(const float* dtok, int B, int Ntok, int D, const int
     const int64_t total = (int64_t)B * Np * D;
     const int blocks = (int)std::min<int64_t>(cdiv(total, 256), 8192);
     if (dtype == PA_BF16) hipLaunchKernelGGL(patch_rows_kernel<bf16>, dim3(blocks), dim3(256), 0, st, dtok, Ntok, D, Np, (bf16*)dpatch, total);
-    else if (dtype == PA_F32) hipLaunchKernelGGL(patch_rows_kernel<float>, dim3(blocks), dim3(256), 0, st, dtok, Ntok, D, Np, (float*)dpatch, total);
-    else return PA_EINVAL;
+    else hipLaunchKernelGGL(patch_rows_kernel<float>, dim3(blocks), dim3(256), 0, st, dtok, Ntok, D, Np, (float*)dpatch, total);
     return check_launch();
 }
 
@@ -613,6 +622,8 @@ extern "C" int pa_patch_input_bwd(const void* dcols, int dtype, int B, int Np, c
     if (!dcols || !patch_f || !patch_t || !grid_ws || !dx || B <= 0 || Np <= 0 || P <= 0 || fstride <= 0 || tstride <= 0 || F < P || T < P)
         return PA_EINVAL;
     if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
+    // the fold stores 16-byte vectors of dx and reads bf16 dcols in 4-byte pairs
+    if (misaligned(dx, 16) || misaligned(dcols, 4)) return PA_EINVAL;
     const int64_t cells = pa_patch_input_bwd_ws_ints(F, T, P, fstride, tstride);
     const int Fg = (F - P) / fstride + 1, Tg = (T - P) / tstride + 1;
     const int64_t n = (int64_t)B * F * T;
@@ -634,6 +645,8 @@ extern "C" int pa_patch_input_bwd_varlen(const void* dcols, int dtype, const int
                                          int T_max, float* dx, void* stream) {
     if (!dcols || !cu_tok || !dx || B <= 0 || P <= 0 || fstride <= 0 || tstride <= 0 || F < P || T_max < P) return PA_EINVAL;
     if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
+    // the fold stores 16-byte vectors of dx and reads bf16 dcols in 4-byte pairs
+    if (misaligned(dx, 16) || misaligned(dcols, 4)) return PA_EINVAL;
     const int Fg = (F - P) / fstride + 1;
     const int64_t n = (int64_t)B * F * T_max;
     if (cdiv(n, 1024) >= ((int64_t)1 << 31)) return PA_EUNSUPPORTED;
@@ -662,6 +675,8 @@ extern "C" int pa_patch_input_bwd_rows(const void* dcols, int dtype, int M, cons
                                        int F, int T_max, float* dx, void* stream) {
     if (!dcols || !slot || !dx || M <= 0 || B <= 0 || Tg <= 0 || P <= 0 || fstride <= 0 || tstride <= 0 || F < P || T_max < P) return PA_EINVAL;
     if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
+    // the fold stores 16-byte vectors of dx and reads bf16 dcols in 4-byte pairs
+    if (misaligned(dx, 16) || misaligned(dcols, 4)) return PA_EINVAL;
     const int Fg = (F - P) / fstride + 1;
     const int64_t n = (int64_t)B * F * T_max;
     // int32 indexing of the table and of the launch grid

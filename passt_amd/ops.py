@@ -162,6 +162,23 @@ def round_up(a, b):
     return (a + b - 1) // b * b
 
 
+def _aligned16(t):
+    """Entries that move 16-byte vectors refuse a base pointer off 16-byte alignment (include/passt_amd.h); an offset view gets a copy.
+    An aligned tensor -- every tensor torch allocated itself -- passes through: no launch is added."""
+    return t.clone() if t is not None and t.is_cuda and t.is_contiguous() and t.data_ptr() % 16 else t
+
+
+def _into_aligned16(out, make, fill):
+    """`fill(dst)` writes an entry's output; a caller's `out` off 16-byte alignment is filled through an aligned temporary"""
+    if out.is_cuda and out.data_ptr() % 16:
+        tmp = make()
+        fill(tmp)
+        out.copy_(tmp)
+    else:
+        fill(out)
+    return out
+
+
 # ---- front end -----------------------------------------------------------------------------
 def _mel_wave(wave):
     """The front end takes the alignment of its 16-byte and 8-byte loads from the element index, so the waveform's base pointer must be
@@ -302,6 +319,7 @@ def convert(x_f32, dtype, rowscale=None):
     if rowscale is not None:
         M, D = x_f32.shape
         out = torch.empty((M, D), device=x_f32.device, dtype=TORCH_DTYPE[dtype])
+        x_f32 = _aligned16(x_f32)
         check(_lib.load().pa_convert_f32_rowscale(_p(x_f32, torch.float32), _p(_rowscale(rowscale, M, "convert"), torch.float32), _p(out), M, D,
                                                   dtype, _stream()), "pa_convert_f32_rowscale")
         return out
@@ -1295,6 +1313,8 @@ def attention_bwd_varlen(qkv, o, d_o, lse, cu_tok, B, H, max_N, scale, nq=None, 
 def gather_rows(x, idx_i32):
     """out[i] = x[idx[i]] for a 2-D (or 1-D) contiguous tensor."""
     n = idx_i32.numel()
+    if x.is_cuda and x.is_contiguous() and x.data_ptr() % 4:          # rows move as 4-byte words: a 16-bit view at an odd element gets a copy
+        x = x.clone()
     out = torch.empty((n,) + tuple(x.shape[1:]), device=x.device, dtype=x.dtype)
     row_bytes = x.stride(0) * x.element_size()
     check(_lib.load().pa_gather_rows(_p(x), _p(idx_i32, torch.int32), n, row_bytes, _p(out), _stream()), "pa_gather_rows")
@@ -1305,6 +1325,8 @@ def scatter_rows_into_zeros(x_rows, idx_i32, n_rows):
     """zeros(n_rows, D) with out[idx[i]] = x_rows[i]"""
     out = torch.empty((n_rows,) + tuple(x_rows.shape[1:]), device=x_rows.device, dtype=x_rows.dtype)
     row_bytes = x_rows.stride(0) * x_rows.element_size()
+    if x_rows.is_cuda and x_rows.is_contiguous() and x_rows.data_ptr() % 4:
+        x_rows = x_rows.clone()
     lib = _lib.load()
     check(lib.pa_zero2d(_p(out), row_bytes, row_bytes, n_rows, _stream()), "pa_zero2d")
     check(lib.pa_scatter_rows(_p(x_rows), _p(idx_i32, torch.int32), idx_i32.numel(), row_bytes, _p(out), _stream()), "pa_scatter_rows")
@@ -1320,6 +1342,7 @@ def tail_inject(x_rows, idx_i32, n_rows, add0, add1, dtype):
     for a in (add0, add1):
         if a is not None and a.shape != (n_rows, D):
             raise _lib.PasstAmdError(f"tail_inject: an addend is {tuple(a.shape)}, expected {(n_rows, D)}")
+    x_rows, add0, add1 = _aligned16(x_rows), _aligned16(add0), _aligned16(add1)
     dx = torch.empty((n_rows, D), device=x_rows.device, dtype=torch.float32)
     dx_lp = torch.empty((n_rows, D), device=x_rows.device, dtype=TORCH_DTYPE[dtype]) if dtype != PA_F32 else None
     check(_lib.load().pa_tail_inject(_p(x_rows, torch.float32), _p(idx_i32, torch.int32), idx_i32.numel(), _p(add0, torch.float32),
@@ -1378,6 +1401,7 @@ def patch_bwd(dtok, patch_f, patch_t, toff, Tpe, Fpe, d_cls, d_dist, d_npe, d_bi
               accumulate=False):
     B, Ntok, D = dtok.shape
     Np = patch_f.numel()
+    dtok = _aligned16(dtok)
     gsum = torch.empty((Ntok, D), device=dtok.device, dtype=torch.float32) if d_cls is not None else None   # all d_* None: dpatch only
     dpatch = torch.empty((B * Np, D), device=dtok.device, dtype=TORCH_DTYPE[dtype])
     check(_lib.load().pa_patch_bwd(_p(dtok), B, Ntok, D, _p(patch_f), _p(patch_t), Np, toff, Tpe, Fpe, _p(gsum),
@@ -1398,9 +1422,10 @@ def patch_input_bwd(dcols, patch_f, patch_t, B, F, T, P, fstride, tstride, out=N
     if dx.shape != (B, 1, F, T):
         raise _lib.PasstAmdError(f"patch_input_bwd: out is {tuple(dx.shape)}, expected {(B, 1, F, T)}")
     grid = torch.empty(lib.pa_patch_input_bwd_ws_ints(F, T, P, fstride, tstride), device=dcols.device, dtype=torch.int32)
-    check(lib.pa_patch_input_bwd(_p(dcols), PA_DTYPE[dcols.dtype], B, Np, _p(patch_f, torch.int32), _p(patch_t, torch.int32), P, fstride, tstride,
-                                 F, T, _p(grid, torch.int32), _p(dx, torch.float32), _stream()), "pa_patch_input_bwd")
-    return dx
+    dcols = _aligned16(dcols)
+    return _into_aligned16(dx, lambda: torch.empty_like(dx), lambda o: check(
+        lib.pa_patch_input_bwd(_p(dcols), PA_DTYPE[dcols.dtype], B, Np, _p(patch_f, torch.int32), _p(patch_t, torch.int32), P, fstride, tstride,
+                               F, T, _p(grid, torch.int32), _p(o, torch.float32), _stream()), "pa_patch_input_bwd"))
 
 
 def patch_input_bwd_varlen(dcols, cu_tok, B, F, T_max, P, fstride, tstride, out=None):
@@ -1412,9 +1437,10 @@ def patch_input_bwd_varlen(dcols, cu_tok, B, F, T_max, P, fstride, tstride, out=
     dx = torch.empty((B, 1, F, T_max), device=dcols.device, dtype=torch.float32) if out is None else out
     if dx.shape != (B, 1, F, T_max):
         raise _lib.PasstAmdError(f"patch_input_bwd_varlen: out is {tuple(dx.shape)}, expected {(B, 1, F, T_max)}")
-    check(_lib.load().pa_patch_input_bwd_varlen(_p(dcols), PA_DTYPE[dcols.dtype], _p(cu_tok, torch.int32), B, P, fstride, tstride, F, T_max,
-                                                _p(dx, torch.float32), _stream()), "pa_patch_input_bwd_varlen")
-    return dx
+    dcols = _aligned16(dcols)
+    return _into_aligned16(dx, lambda: torch.empty_like(dx), lambda o: check(
+        _lib.load().pa_patch_input_bwd_varlen(_p(dcols), PA_DTYPE[dcols.dtype], _p(cu_tok, torch.int32), B, P, fstride, tstride, F, T_max,
+                                              _p(o, torch.float32), _stream()), "pa_patch_input_bwd_varlen"))
 
 
 def patch_bwd_varlen(dtok, cu_tok, B, Tpe, Fpe, d_cls, d_dist, d_npe, d_bias, d_tpos, d_fpos, accumulate=False):
@@ -1437,9 +1463,10 @@ def patch_input_bwd_rows(dcols, slot, F, T_max, P, fstride, tstride, out=None):
     dx = torch.empty((B, 1, F, T_max), device=dcols.device, dtype=torch.float32) if out is None else out
     if dx.shape != (B, 1, F, T_max):
         raise _lib.PasstAmdError(f"patch_input_bwd_rows: out is {tuple(dx.shape)}, expected {(B, 1, F, T_max)}")
-    check(_lib.load().pa_patch_input_bwd_rows(_p(dcols), PA_DTYPE[dcols.dtype], dcols.shape[0], _p(slot, torch.int32), B, Tg, P, fstride, tstride,
-                                              F, T_max, _p(dx, torch.float32), _stream()), "pa_patch_input_bwd_rows")
-    return dx
+    dcols = _aligned16(dcols)
+    return _into_aligned16(dx, lambda: torch.empty_like(dx), lambda o: check(
+        _lib.load().pa_patch_input_bwd_rows(_p(dcols), PA_DTYPE[dcols.dtype], dcols.shape[0], _p(slot, torch.int32), B, Tg, P, fstride, tstride,
+                                            F, T_max, _p(o, torch.float32), _stream()), "pa_patch_input_bwd_rows"))
 
 
 def patch_bwd_rows(dtok, slot, cu_tok, toff, Tpe, Fpe, d_cls, d_dist, d_npe, d_bias, d_tpos, d_fpos, accumulate=False):

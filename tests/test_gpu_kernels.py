@@ -1021,3 +1021,43 @@ def test_wgrad_tn_batched_matches_single_launches():
         ops.wgrad_tn(dY, X, single, dt, acc, db=db1)          # single launch, bias gradient from the same kernel
         assert rel_err(out, single.double().cpu()) < 1e-5     # same products, different split-K grouping
         assert rel_err(db1, dY.double().cpu().sum(0) + (0.5 if acc else 0.0)) < 1e-5
+
+
+def test_wrappers_copy_offset_views_before_entries_that_refuse_them():
+    """The entries that move 16-byte vectors refuse a base pointer off 16-byte alignment (include/passt_amd.h; the refusals themselves
+    are asserted without a device in tests/test_patch_cases_cpu.py).  The ops wrappers give such an entry a copy of an offset view,
+    so the caller sees the result of the aligned call, bit for bit; no misaligned pointer reaches a kernel here."""
+    def off(t):                                      # the same values one element behind a 16-byte boundary
+        buf = torch.empty(t.numel() + 1, device=DEV, dtype=t.dtype)
+        v = buf[1:].view(t.shape)
+        v.copy_(t)
+        assert v.data_ptr() % 16 and v.is_contiguous()
+        return v
+    M, D = 10, 260
+    rows, a0, a1 = rnd(2, D, seed=1).to(DEV), rnd(M, D, seed=2).to(DEV), rnd(M, D, seed=3).to(DEV)
+    idx = torch.tensor([0, 5], dtype=torch.int32, device=DEV)
+    want = ops.tail_inject(rows, idx, M, a0, a1, PA_BF16)
+    got = ops.tail_inject(off(rows), idx, M, off(a0), off(a1), PA_BF16)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    x = rnd(M, D, seed=4).to(DEV)
+    rs = torch.tensor([1.0, 0.5] * (M // 2), device=DEV)
+    assert torch.equal(ops.convert(off(x), PA_BF16, rowscale=rs), ops.convert(x, PA_BF16, rowscale=rs))
+    assert torch.equal(ops.convert(off(x), PA_BF16), ops.convert(x, PA_BF16))          # pa_convert_f32 reads an offset `in` itself
+    B, F, T, P, s = 2, 13, 18, 4, 3
+    Fg, Tg = (F - P) // s + 1, (T - P) // s + 1
+    pf = torch.arange(Fg, dtype=torch.int32).repeat_interleave(Tg).to(DEV)
+    pt = torch.arange(Tg, dtype=torch.int32).repeat(Fg).to(DEV)
+    dcols = rnd(B * Fg * Tg, P * P, seed=5).to(torch.bfloat16).to(DEV)
+    want = ops.patch_input_bwd(dcols, pf, pt, B, F, T, P, s, s)
+    out = off(torch.zeros(B, 1, F, T, device=DEV))
+    assert ops.patch_input_bwd(off(dcols), pf, pt, B, F, T, P, s, s, out=out) is out and torch.equal(out, want)
+    Np, Dm = Fg * Tg, 16
+    dtok = rnd(B, Np + 2, Dm, seed=6).to(DEV)
+    assert torch.equal(ops.patch_bwd(off(dtok), pf, pt, 0, Tg, Fg, None, None, None, None, None, None, PA_BF16),
+                       ops.patch_bwd(dtok, pf, pt, 0, Tg, Fg, None, None, None, None, None, None, PA_BF16))
+    xb = rnd(6, 8, seed=7).to(torch.bfloat16).to(DEV)
+    gi = torch.tensor([5, 0, 3], dtype=torch.int32, device=DEV)
+    assert torch.equal(ops.gather_rows(off(xb), gi), xb[gi.long()])                    # 2 bytes off: a copy; 4 bytes off: 4-byte words
+    xf = rnd(6, 8, seed=8).to(DEV)
+    assert torch.equal(ops.gather_rows(off(xf), gi), xf[gi.long()])
+    torch.cuda.synchronize()
