@@ -730,6 +730,37 @@ int pa_mixup(const float* x, const int32_t* perm, const float* lam, float* out, 
  * noise (< 1e-7 of the amplitude). */
 int pa_wave_augment(const float* x, int B, int64_t ldx, const int32_t* len, const float* amp, const int32_t* shift,
                     const int32_t* partner, const float* lam, float* ws, float* out, int64_t L, void* stream);
+/* Device-impulse-response augmentation, the first branch of pydub_augment (audioset/dataset.py:103-112, same body in esc50 /
+ * fsd50k / openmic): scipy.signal.convolve(waveform, ir, 'full') with one IR of a bank, then pad_or_truncate to L.  Causal, no
+ * delay compensation; the tail behind the clip is kept, up to L.  Overlap-save FFT tiles held in registers and LDS (ir_conv.hip);
+ * its output and len_out are the raw clips and lengths pa_wave_augment takes.  Additive to ABI 6.
+ *
+ * pa_ir_conv_plan: host only.  The transform geometry used for a bank whose longest IR has max_taps taps (1..PA_IR_MAX_TAPS):
+ *   *fft_n points per tile (4096 up to 1024 taps, 16384 above), *hop = new output samples per tile (fft_n - max_taps + 1 rounded
+ *   down to a multiple of 64).  Either pointer may be NULL.  PA_EINVAL outside the range.
+ * pa_ir_bank_floats: host only.  Size of `spectra` in floats (0 for arguments out of range).
+ * pa_ir_bank_prepare: once per bank and device.  irs [n_ir][ld_ir] f32, row i valid for ir_len[i] taps (NULL: ld_ir), the rest of
+ *   the row never read.  ld_ir IS the bank's max_taps (1..PA_IR_MAX_TAPS): it fixes the geometry, and the same value goes to
+ *   pa_wave_ir_convolve.  spectra (DEVICE memory, 8-byte aligned, pa_ir_bank_floats(n_ir, ld_ir) floats) is opaque: the
+ *   twiddle table of the transform followed by the IRs' spectra in the order the convolve kernel consumes them.  One host-to-
+ *   device copy of the table is enqueued on `stream` ahead of the launch, so this entry is not for a captured graph.
+ * pa_wave_ir_convolve:
+ *   out[b][t] = sum_k h_b[k] * x[b][t-k]   for 0 <= t < len_out[b] = min(len[b] + taps_b - 1, L);   out[b][t] = 0 for len_out[b] <= t < L
+ *   x [B][ldx] f32, len[b] valid samples (clamped to 0..ldx; NULL: ldx); x[b][len[b]:] is never read.  h_b = IR ir_idx[b] of the
+ *   bank, taps_b = ir_len[ir_idx[b]].  ir_idx[b] < 0 (or ir_idx == NULL): out[b][:min(len[b], L)] is a bit-exact copy of x, zeros
+ *   behind, len_out[b] = min(len[b], L).  ir_idx[b] >= n_ir or a tap count outside 1..max_taps in the DEVICE arrays never causes
+ *   an access outside the buffers: such a clip is a pass-through as well.  An empty clip (len[b] = 0) gives zeros, len_out[b] = 0.
+ *   out [B][ldo] f32, ldo >= L; only out[b][0:L) is written.  len_out [B] int32 may be NULL.  A row's result does not depend on
+ *   B or on the row's position in the batch.
+ *   PA_EINVAL (before any launch): x, out or spectra NULL; B, L, ldx or n_ir <= 0; B > 65535; L > 2^31 - 1; ldo < L; max_taps
+ *   outside 1..PA_IR_MAX_TAPS; ir_idx without ir_len; spectra not 8-byte aligned. */
+#define PA_IR_MAX_TAPS 8192
+int pa_ir_conv_plan(int max_taps, int* fft_n, int* hop);
+int64_t pa_ir_bank_floats(int n_ir, int max_taps);
+int pa_ir_bank_prepare(const float* irs, int n_ir, int ld_ir, const int32_t* ir_len, float* spectra, void* stream);
+int pa_wave_ir_convolve(const float* x, int B, int64_t ldx, const int32_t* len, const int32_t* ir_idx, const float* spectra,
+                        const int32_t* ir_len, int n_ir, int max_taps, float* out, int64_t ldo, int64_t L, int32_t* len_out,
+                        void* stream);
 /* torch.optim.AdamW (ex_audioset.py:104-109) on one flat f32 parameter buffer */
 int pa_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
              float beta2, float eps, float weight_decay, int step, void* stream);

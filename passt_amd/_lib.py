@@ -145,6 +145,10 @@ SIGNATURES = {
     "pa_sgd": (i32, [vp, vp, i64, f32, vp]),
     "pa_swa_update": (i32, [vp, vp, i64, i32, vp]),
     "pa_wave_augment": (i32, [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "pa_ir_conv_plan": (i32, [i32, C.POINTER(i32), C.POINTER(i32)]),
+    "pa_ir_bank_floats": (i64, [i32, i32]),
+    "pa_ir_bank_prepare": (i32, [vp, i32, i32, vp, vp, vp]),
+    "pa_wave_ir_convolve": (i32, [vp, i32, i64, vp, vp, vp, vp, i32, i32, vp, i64, i64, vp, vp]),
     "pa_eval_append": (i32, [vp, vp, vp, i32, i32, i64, i64, i32, vp, vp, vp]),
     "pa_eval_ws_bytes": (i64, [i32, i64]),
     "pa_eval_rank": (i32, [vp, vp, i32, i64, i64, vp, vp, vp, vp, vp, vp, vp]),

@@ -4,6 +4,7 @@ Every function takes CUDA(HIP) torch tensors, passes raw device pointers + the c
 libpasst_amd.so and returns the output tensors it allocated (torch is the allocator only).
 No fallback: a non-CUDA tensor or a missing library raises.
 """
+import collections
 import ctypes as C
 import functools
 import threading
@@ -1563,6 +1564,54 @@ def wave_augment(x, L, lengths=None, amp=None, shift=None, partner=None, lam=Non
     check(_lib.load().pa_wave_augment(_p(x, torch.float32, True), B, x.stride(0), _p(lengths, torch.int32), _p(amp, torch.float32), _p(shift, torch.int32), _p(partner, torch.int32), _p(lam, torch.float32), _p(ws),
                                       _p(out), L, _stream()), "pa_wave_augment")
     return out
+
+
+IR_MAX_TAPS = 8192            # PA_IR_MAX_TAPS
+IRSpectra = collections.namedtuple("IRSpectra", "spectra ir_len n_ir max_taps")      # what ir_bank_prepare returns
+
+
+def ir_conv_plan(max_taps):
+    """(fft_n, hop) of the overlap-save tiles used for a bank whose longest IR has ``max_taps`` taps (host only)."""
+    n, hop = C.c_int32(0), C.c_int32(0)
+    check(_lib.load().pa_ir_conv_plan(int(max_taps), C.byref(n), C.byref(hop)), "pa_ir_conv_plan")
+    return n.value, hop.value
+
+
+def ir_bank_prepare(irs, ir_len=None):
+    """irs [n_ir][max_taps] f32 (row i valid for ir_len[i] taps; the row length is the bank's max_taps) -> IRSpectra: the
+    opaque spectra buffer of pa_ir_bank_prepare together with ir_len (int32, on the device) and the bank's geometry."""
+    if irs.dim() != 2 or irs.shape[0] < 1 or not 1 <= irs.shape[1] <= IR_MAX_TAPS:
+        raise _lib.PasstAmdError(f"ir_bank_prepare: irs must be [n_ir >= 1][1..{IR_MAX_TAPS} taps], got {tuple(irs.shape)}")
+    n_ir, max_taps = irs.shape
+    if ir_len is None:
+        ir_len = torch.full((n_ir,), max_taps, device=irs.device, dtype=torch.int32)
+    if ir_len.numel() != n_ir:
+        raise _lib.PasstAmdError(f"ir_bank_prepare: ir_len holds {ir_len.numel()} entries for {n_ir} IRs")
+    lib = _lib.load()
+    spectra = torch.empty(lib.pa_ir_bank_floats(n_ir, max_taps), device=irs.device, dtype=torch.float32)
+    check(lib.pa_ir_bank_prepare(_p(irs, torch.float32), n_ir, max_taps, _p(ir_len, torch.int32), _p(spectra), _stream()), "pa_ir_bank_prepare")
+    return IRSpectra(spectra, ir_len, n_ir, max_taps)
+
+
+def wave_ir_convolve(x, L, lengths=None, ir_idx=None, bank=None, out=None):
+    """x [B][ldx] f32 raw clips -> (out [B][L], len_out int32 [B]): clip b convolved ('full') with IR ir_idx[b] of ``bank`` (an
+    IRSpectra), cut or zero padded to L; ir_idx[b] < 0 copies the clip (pa_wave_ir_convolve).  ``out``: an optional [B][L] f32
+    destination whose rows may be further apart than L."""
+    if bank is None:
+        raise _lib.PasstAmdError("wave_ir_convolve needs the IRSpectra of ir_bank_prepare")
+    B = x.shape[0]
+    if out is None:
+        out = torch.empty((B, L), device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (B, L):
+        raise _lib.PasstAmdError(f"wave_ir_convolve: out must be [{B}][{L}], got {tuple(out.shape)}")
+    if ir_idx is not None and ir_idx.numel() != B or lengths is not None and lengths.numel() != B:
+        raise _lib.PasstAmdError(f"wave_ir_convolve: lengths / ir_idx must hold {B} entries")
+    len_out = torch.empty(B, device=x.device, dtype=torch.int32)
+    check(_lib.load().pa_wave_ir_convolve(_p(x, torch.float32, True), B, max(x.stride(0), x.shape[1]), _p(lengths, torch.int32),
+                                          _p(ir_idx, torch.int32), _p(bank.spectra, torch.float32), _p(bank.ir_len, torch.int32),
+                                          bank.n_ir, bank.max_taps, _p(out, torch.float32, True), max(out.stride(0), L),
+                                          L, _p(len_out), _stream()), "pa_wave_ir_convolve")
+    return out, len_out
 
 
 def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step):
