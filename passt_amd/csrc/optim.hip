@@ -2,6 +2,7 @@
 // AdamW (ex_audioset.py:104-109) and plain SGD (model_speed_test, ex_audioset.py:392) on flat f32
 // buffers.  Pure HBM streaming kernels: float4 grid-stride loops.
 #include <algorithm>
+#include <cstring>
 
 #include "pa_common.h"
 
@@ -53,53 +54,68 @@ template <bool CLIP> __device__ __forceinline__ float clip_g(float g, float gs) 
     if constexpr (CLIP) return g * gs;
     else return g;
 }
-// 16-byte accesses (n4 = n / 4 when all four pointers are 16-byte aligned, else 0) + scalar tail
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, int64_t n4, int64_t n, float lr, float b1, float b2,
-                                                    float eps, float wd, float bc1, float bc2_sqrt) {
+// the hyper-parameters of one launch: [lr, beta1, beta2, eps, weight_decay, 1 - beta1^t, sqrt(1 - beta2^t)], the 7-float row of
+// pa_adamw_hyper
+struct AdamwHyper { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; };
+// adamw_one on one element / on four, the gradient through clip_g: every AdamW loop below is one of these two
+template <bool CLIP> __device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, const AdamwHyper& h, float gs) {
+    adamw_one(p, clip_g<CLIP>(g, gs), m, v, h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
+}
+template <bool CLIP>
+__device__ __forceinline__ void adamw_four(f32x4& pv, const f32x4& gv, f32x4& mv, f32x4& vv, const AdamwHyper& h, float gs) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float pe = pv[e], me = mv[e], ve = vv[e];
+        adamw_elem<CLIP>(pe, gv[e], me, ve, h, gs);
+        pv[e] = pe; mv[e] = me; vv[e] = ve;
+    }
+}
+// the hyper-parameters of one launch (by value, or the 7-float row in device memory: a launch whose arguments never change, i.e. one
+// that can sit in a captured hipGraph) for table entry ``entry``: with parameter groups (``scales``: one (lr_scale, wd_scale) pair per
+// descriptor) lr and weight decay are those of the launch times the entry's pair, so a captured launch follows the schedule through
+// the device row while every parameter keeps its own factor
+template <bool GROUPS>
+__device__ __forceinline__ AdamwHyper adamw_hyper_of(const AdamwHyper& hv, const float* __restrict__ hy_dev, const float2* __restrict__ scales,
+                                                     int entry) {
+    AdamwHyper h = hv;
+    if (hy_dev) { h.lr = hy_dev[0]; h.b1 = hy_dev[1]; h.b2 = hy_dev[2]; h.eps = hy_dev[3]; h.wd = hy_dev[4]; h.bc1 = hy_dev[5]; h.bc2_sqrt = hy_dev[6]; }
+    if constexpr (GROUPS) {
+        const float2 s = scales[entry];
+        h.lr *= s.x;
+        h.wd *= s.y;
+    }
+    return h;
+}
+// the clip factor of the step: one device float (pa_clip_coef writes it); a null pointer and CLIP = false mean 1
+template <bool CLIP> __device__ __forceinline__ float adamw_gscale(const float* __restrict__ gscale) {
+    if constexpr (CLIP) return gscale ? *gscale : 1.f;
+    else return 1.f;
+}
+
+// The flat form (pa_adamw, pa_adamw_dev: CLIP = false; pa_adamw_clip: CLIP = true): 16-byte accesses (n4 = n / 4 when all four pointers
+// are 16-byte aligned, else 0) + scalar tail
+template <bool CLIP>
+__global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, int64_t n4, int64_t n, AdamwHyper hv,
+                                                         const float* __restrict__ hy_dev, const float* __restrict__ gscale) {
+    const AdamwHyper h = adamw_hyper_of<false>(hv, hy_dev, nullptr, 0);
+    const float gs = adamw_gscale<CLIP>(gscale);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     for (int64_t i = t0; i < n4; i += stride) {
         f32x4 pv = ((f32x4*)p)[i], mv = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
-        const f32x4 gv = ((const f32x4*)g)[i];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float pe = pv[e], me = mv[e], ve = vv[e];
-            adamw_one(pe, gv[e], me, ve, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-            pv[e] = pe; mv[e] = me; vv[e] = ve;
-        }
+        adamw_four<CLIP>(pv, ((const f32x4*)g)[i], mv, vv, h, gs);
         ((f32x4*)p)[i] = pv; ((f32x4*)m)[i] = mv; ((f32x4*)v)[i] = vv;
     }
-    for (int64_t i = n4 * 4 + t0; i < n; i += stride) adamw_one(p[i], g[i], m[i], v[i], lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+    for (int64_t i = n4 * 4 + t0; i < n; i += stride) adamw_elem<CLIP>(p[i], g[i], m[i], v[i], h, gs);
 }
 
-// the same update with the hyper-parameters of the step read from device memory ([lr, beta1, beta2, eps, weight_decay,
-// 1 - beta1^t, sqrt(1 - beta2^t)]): a launch whose arguments never change, i.e. one that can sit in a captured hipGraph
-__global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, int64_t n4, int64_t n, const float* __restrict__ hy) {
-    const float lr = hy[0], b1 = hy[1], b2 = hy[2], eps = hy[3], wd = hy[4], bc1 = hy[5], bc2_sqrt = hy[6];
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (int64_t i = t0; i < n4; i += stride) {
-        f32x4 pv = ((f32x4*)p)[i], mv = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
-        const f32x4 gv = ((const f32x4*)g)[i];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float pe = pv[e], me = mv[e], ve = vv[e];
-            adamw_one(pe, gv[e], me, ve, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-            pv[e] = pe; mv[e] = me; vv[e] = ve;
-        }
-        ((f32x4*)p)[i] = pv; ((f32x4*)m)[i] = mv; ((f32x4*)v)[i] = vv;
-    }
-    for (int64_t i = n4 * 4 + t0; i < n; i += stride) adamw_one(p[i], g[i], m[i], v[i], lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-}
-
-// ---- AdamW + weight staging in ONE pass (round 6).  The step used to end with adamw_kernel writing every updated parameter and
+// ---- AdamW + weight staging in ONE pass (round 6).  The step used to end with adamw_flat_kernel writing every updated parameter and
 // the next forward beginning with stage_weights_kernel reading all of them back to make the GEMM-ready copies (bf16 W[out][in]
 // for the forward, bf16 W^T[in][out] for the input gradients): one extra 345 MB read + a launch per step.  Here the optimizer
 // launch of a bucket walks a descriptor table of the bucket's parameters: a matrix with copies is processed in 64 x 64 tiles
 // (256 B of each row per 16 lanes; the updated values go out as f32, as the straight cast, and -- through an LDS tile -- as the
-// transposed cast), everything else in runs of 4096 elements.  Same adamw_one() as adamw_kernel: parameters, moments and both
-// copies are bit-identical to adamw_kernel + stage_weights_kernel (tests/test_gpu_model.py).
-struct AdamwHyper { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; };
+// transposed cast), everything else in runs of 4096 elements.  Same adamw_one() as adamw_flat_kernel: parameters, moments and both
+// copies are bit-identical to adamw_flat_kernel + stage_weights_kernel (tests/test_gpu_model.py).
 // Parameters, moments and gradients of the matrix path are touched once per step: non-temporal (CP_NT_ADAMW, pa_common.h).  The
 // GEMM-ready copies leave as plain stores (non-temporal: +- 0, profiles/r06_cache_policy.txt).
 template <typename V> __device__ __forceinline__ V opt_ld(const V* p) {
@@ -128,71 +144,71 @@ __device__ __forceinline__ int adamw_find_entry(const pa_adamw_stage_desc* __res
     __syncthreads();
     return *s_entry;
 }
+// What one workgroup of a table launch works on: its table entry, the entry's hyper-parameters, the four buffers at the entry's offset,
+// its work item ``t`` there, and whether all four pointers are 16-byte aligned.  (The entry stays in the table: with a copy of the
+// descriptor in here the table kernels take other registers than before.)
+struct AdamwItem {
+    const pa_adamw_stage_desc* d;
+    AdamwHyper h;
+    float* pp; const float* gp; float* mp; float* vp;
+    int t;
+    bool aligned;
+};
+template <bool GROUPS>
+__device__ __forceinline__ AdamwItem adamw_item(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                float* __restrict__ v, const pa_adamw_stage_desc* __restrict__ descs, int n_desc,
+                                                const float* __restrict__ hy_dev, const AdamwHyper& hv, const float2* __restrict__ scales) {
+    __shared__ int s_entry;
+    const int bid = blockIdx.x;
+    const int entry = adamw_find_entry(descs, n_desc, bid, &s_entry);
+    const pa_adamw_stage_desc d = descs[entry];
+    AdamwItem w;
+    w.d = descs + entry;
+    w.h = adamw_hyper_of<GROUPS>(hv, hy_dev, scales, entry);
+    w.pp = p + d.offset;
+    w.gp = g + d.offset;
+    w.mp = m + d.offset;
+    w.vp = v + d.offset;
+    w.t = bid - d.tile_begin;
+    w.aligned = ((((uintptr_t)w.pp | (uintptr_t)w.gp | (uintptr_t)w.mp | (uintptr_t)w.vp) & 15) == 0);
+    return w;
+}
 // a parameter without copies (biases, LayerNorm, positional tables, the f32 head): work item t is a run of 4096 consecutive elements
-template <bool CLIP = false>
-__device__ __forceinline__ void adamw_run(float* pp, const float* gp, float* mp, float* vp, int64_t n, int t, bool aligned,
-                                          const AdamwHyper& h, float gs = 1.f) {
+template <bool CLIP> __device__ __forceinline__ void adamw_run(const AdamwItem& w, float gs) {
+    float* pp = w.pp; const float* gp = w.gp; float* mp = w.mp; float* vp = w.vp;
     const int tid = threadIdx.x;
-    const int64_t i0 = (int64_t)t * 4096, i1 = min(i0 + 4096, n);
-    if (aligned) {
+    const int64_t n = (int64_t)w.d->rows * w.d->cols, i0 = (int64_t)w.t * 4096, i1 = min(i0 + 4096, n);
+    if (w.aligned) {
         for (int64_t i = i0 + tid * 4; i < i1; i += 1024) {
             if (i + 4 <= i1) {
                 f32x4 pv = *(f32x4*)(pp + i), mv = *(f32x4*)(mp + i), vv = *(f32x4*)(vp + i);
-                const f32x4 gv = *(const f32x4*)(gp + i);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float pe = pv[e], me = mv[e], ve = vv[e];
-                    adamw_one(pe, clip_g<CLIP>(gv[e], gs), me, ve, h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
-                    pv[e] = pe; mv[e] = me; vv[e] = ve;
-                }
+                adamw_four<CLIP>(pv, *(const f32x4*)(gp + i), mv, vv, w.h, gs);
                 *(f32x4*)(pp + i) = pv; *(f32x4*)(mp + i) = mv; *(f32x4*)(vp + i) = vv;
             } else {
-                for (int64_t k = i; k < i1; ++k)
-                    adamw_one(pp[k], clip_g<CLIP>(gp[k], gs), mp[k], vp[k], h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
+                for (int64_t k = i; k < i1; ++k) adamw_elem<CLIP>(pp[k], gp[k], mp[k], vp[k], w.h, gs);
             }
         }
     } else {
-        for (int64_t i = i0 + tid; i < i1; i += 256)
-            adamw_one(pp[i], clip_g<CLIP>(gp[i], gs), mp[i], vp[i], h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
+        for (int64_t i = i0 + tid; i < i1; i += 256) adamw_elem<CLIP>(pp[i], gp[i], mp[i], vp[i], w.h, gs);
     }
-}
-// the hyper-parameters of one launch (by value, or the 7-float row in device memory) for table entry ``entry``: with parameter groups
-// (``scales``: one (lr_scale, wd_scale) pair per descriptor) lr and weight decay are those of the launch times the entry's pair, so a
-// captured launch follows the schedule through the device row while every parameter keeps its own factor
-template <bool GROUPS>
-__device__ __forceinline__ AdamwHyper adamw_hyper_of(const AdamwHyper& hv, const float* __restrict__ hy_dev, const float2* __restrict__ scales,
-                                                     int entry) {
-    AdamwHyper h = hv;
-    if (hy_dev) { h.lr = hy_dev[0]; h.b1 = hy_dev[1]; h.b2 = hy_dev[2]; h.eps = hy_dev[3]; h.wd = hy_dev[4]; h.bc1 = hy_dev[5]; h.bc2_sqrt = hy_dev[6]; }
-    if constexpr (GROUPS) {
-        const float2 s = scales[entry];
-        h.lr *= s.x;
-        h.wd *= s.y;
-    }
-    return h;
 }
 
-template <typename TO, bool GROUPS, bool CLIP = false>
+template <typename TO, bool GROUPS, bool CLIP>
 __device__ __forceinline__ void adamw_stage_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                  float* __restrict__ v, const pa_adamw_stage_desc* __restrict__ descs, int n_desc,
                                                  const float* __restrict__ hy_dev, const AdamwHyper& hv, const float2* __restrict__ scales,
-                                                 float gs = 1.f) {
+                                                 float gs) {
     __shared__ float tile[64][65];
-    __shared__ int s_entry;
-    const int bid = blockIdx.x, tid = threadIdx.x;
-    const int entry = adamw_find_entry(descs, n_desc, bid, &s_entry);
-    const pa_adamw_stage_desc d = descs[entry];
-    const AdamwHyper h = adamw_hyper_of<GROUPS>(hv, hy_dev, scales, entry);
-    float* pp = p + d.offset;
-    const float* gp = g + d.offset;
-    float* mp = m + d.offset;
-    float* vp = v + d.offset;
-    const int t = bid - d.tile_begin;
-    const bool aligned = ((((uintptr_t)pp | (uintptr_t)gp | (uintptr_t)mp | (uintptr_t)vp) & 15) == 0);
+    const AdamwItem w = adamw_item<GROUPS>(p, g, m, v, descs, n_desc, hy_dev, hv, scales);
+    const pa_adamw_stage_desc d = *w.d;
     if (!d.dst && !d.dst_t) {
-        adamw_run<CLIP>(pp, gp, mp, vp, (int64_t)d.rows * d.cols, t, aligned, h, gs);
+        adamw_run<CLIP>(w, gs);
         return;
     }
+    const AdamwHyper& h = w.h;
+    float* pp = w.pp; const float* gp = w.gp; float* mp = w.mp; float* vp = w.vp;
+    const int tid = threadIdx.x, t = w.t;
+    const bool aligned = w.aligned;
     const int tiles_c = (d.cols + 63) >> 6;
     const int r0 = (t / tiles_c) * 64, c0 = (t % tiles_c) * 64;
     TO* dst = (TO*)d.dst;
@@ -216,12 +232,7 @@ __device__ __forceinline__ void adamw_stage_body(float* __restrict__ p, const fl
             const int r = r0 + lr + 16 * i, c = c0 + l4;
             if (in[i]) {
                 const int64_t at = (int64_t)r * d.cols + c;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float pe = pv[i][e], me = mv[i][e], ve = vv[i][e];
-                    adamw_one(pe, clip_g<CLIP>(gv[i][e], gs), me, ve, h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
-                    pv[i][e] = pe; mv[i][e] = me; vv[i][e] = ve;
-                }
+                adamw_four<CLIP>(pv[i], gv[i], mv[i], vv[i], h, gs);
                 opt_st((f32x4*)(pp + at), pv[i]); opt_st((f32x4*)(mp + at), mv[i]); opt_st((f32x4*)(vp + at), vv[i]);
                 if (dst) {
                     if constexpr (sizeof(TO) == 2) st_bf16x4(dst + at, pv[i]);
@@ -253,7 +264,7 @@ __device__ __forceinline__ void adamw_stage_body(float* __restrict__ p, const fl
         float w = 0.f;
         if (ok) {
             const int64_t at = (int64_t)r * d.cols + c;
-            adamw_one(pp[at], clip_g<CLIP>(gp[at], gs), mp[at], vp[at], h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
+            adamw_elem<CLIP>(pp[at], gp[at], mp[at], vp[at], h, gs);
             w = pp[at];
             if (dst) dst[at] = from_f32<TO>(w);
         }
@@ -267,67 +278,21 @@ __device__ __forceinline__ void adamw_stage_body(float* __restrict__ p, const fl
     }
 }
 
-// parameter groups without staging: the same table (dst / dst_t are not looked at), every entry as runs of 4096 elements
+// The table form (pa_adamw_stage; GROUPS: pa_adamw_stage_groups; CLIP, with either: pa_adamw_stage_clip)
+template <typename TO, bool GROUPS, bool CLIP>
+__global__ __launch_bounds__(256) void adamw_table_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, const pa_adamw_stage_desc* __restrict__ descs,
+                                                          int n_desc, const float* __restrict__ hy_dev, AdamwHyper hv,
+                                                          const float2* __restrict__ scales, const float* __restrict__ gscale) {
+    adamw_stage_body<TO, GROUPS, CLIP>(p, g, m, v, descs, n_desc, hy_dev, hv, scales, adamw_gscale<CLIP>(gscale));
+}
+// parameter groups without staging (pa_adamw_groups): the same table (dst / dst_t are not looked at), every entry as runs of 4096
+// elements -- no tile in LDS
 __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, const pa_adamw_stage_desc* __restrict__ descs,
                                                            int n_desc, const float* __restrict__ hy_dev, AdamwHyper hv,
                                                            const float2* __restrict__ scales) {
-    __shared__ int s_entry;
-    const int bid = blockIdx.x;
-    const int entry = adamw_find_entry(descs, n_desc, bid, &s_entry);
-    const pa_adamw_stage_desc d = descs[entry];
-    const AdamwHyper h = adamw_hyper_of<true>(hv, hy_dev, scales, entry);
-    float* pp = p + d.offset;
-    const float* gp = g + d.offset;
-    float* mp = m + d.offset;
-    float* vp = v + d.offset;
-    const bool aligned = ((((uintptr_t)pp | (uintptr_t)gp | (uintptr_t)mp | (uintptr_t)vp) & 15) == 0);
-    adamw_run(pp, gp, mp, vp, (int64_t)d.rows * d.cols, bid - d.tile_begin, aligned, h);
-}
-
-template <typename TO>
-__global__ __launch_bounds__(256) void adamw_stage_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                          float* __restrict__ v, const pa_adamw_stage_desc* __restrict__ descs,
-                                                          int n_desc, const float* __restrict__ hy_dev, AdamwHyper hv) {
-    adamw_stage_body<TO, false>(p, g, m, v, descs, n_desc, hy_dev, hv, nullptr);
-}
-// ... with parameter groups (pa_adamw_stage_groups)
-template <typename TO>
-__global__ __launch_bounds__(256) void adamw_stage_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                                 float* __restrict__ v, const pa_adamw_stage_desc* __restrict__ descs,
-                                                                 int n_desc, const float* __restrict__ hy_dev, AdamwHyper hv,
-                                                                 const float2* __restrict__ scales) {
-    adamw_stage_body<TO, true>(p, g, m, v, descs, n_desc, hy_dev, hv, scales);
-}
-
-// ... with the clip factor of the step read from device memory (pa_adamw_stage_clip): the same body, g * factor entering adamw_one
-template <typename TO, bool GROUPS>
-__global__ __launch_bounds__(256) void adamw_stage_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                               float* __restrict__ v, const pa_adamw_stage_desc* __restrict__ descs,
-                                                               int n_desc, const float* __restrict__ hy_dev, AdamwHyper hv,
-                                                               const float2* __restrict__ scales, const float* __restrict__ gscale) {
-    adamw_stage_body<TO, GROUPS, true>(p, g, m, v, descs, n_desc, hy_dev, hv, scales, gscale ? *gscale : 1.f);
-}
-// the flat form (pa_adamw_clip): adamw_kernel / adamw_dev_kernel with the factor; scalars by value or from the device row
-__global__ __launch_bounds__(256) void adamw_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                         float* __restrict__ v, int64_t n4, int64_t n, AdamwHyper hv,
-                                                         const float* __restrict__ hy_dev, const float* __restrict__ gscale) {
-    const AdamwHyper h = adamw_hyper_of<false>(hv, hy_dev, nullptr, 0);
-    const float gs = gscale ? *gscale : 1.f;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (int64_t i = t0; i < n4; i += stride) {
-        f32x4 pv = ((f32x4*)p)[i], mv = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
-        const f32x4 gv = ((const f32x4*)g)[i];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float pe = pv[e], me = mv[e], ve = vv[e];
-            adamw_one(pe, clip_g<true>(gv[e], gs), me, ve, h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
-            pv[e] = pe; mv[e] = me; vv[e] = ve;
-        }
-        ((f32x4*)p)[i] = pv; ((f32x4*)m)[i] = mv; ((f32x4*)v)[i] = vv;
-    }
-    for (int64_t i = n4 * 4 + t0; i < n; i += stride)
-        adamw_one(p[i], clip_g<true>(g[i], gs), m[i], v[i], h.lr, h.b1, h.b2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
+    adamw_run<false>(adamw_item<true>(p, g, m, v, descs, n_desc, hy_dev, hv, scales), 1.f);
 }
 
 // ---- Global gradient norm + gradient accumulation: ONE streaming pass per span of the flat gradient buffer ---------------------
@@ -521,118 +486,102 @@ extern "C" int pa_mixup(const float* x, const int32_t* perm, const float* lam, f
     return check_launch();
 }
 
+// ---- AdamW, the host side: one builder of the launch's hyper-parameters, one launcher per kernel form.  The seven entries differ in
+// what they take and in the checks that are theirs alone.  With the device row (hyper_dev) the kernels take all seven floats from
+// there: the by-value ones, and ``step``, are ignored.
+static AdamwHyper adamw_hyper_host(float lr, float beta1, float beta2, float eps, float weight_decay, int step, const float* hyper_dev) {
+    if (hyper_dev) return AdamwHyper{lr, beta1, beta2, eps, weight_decay, 1.f, 1.f};
+    return AdamwHyper{lr, beta1, beta2, eps, weight_decay, 1.f - powf(beta1, (float)step), sqrtf(1.f - powf(beta2, (float)step))};
+}
+// blocks of 256 threads for a grid-stride loop over ``work`` items (float4s or elements)
+static int stream_blocks(int64_t work) { return (int)std::min<int64_t>(cdiv(std::max<int64_t>(work, 1), 256), 8192); }
+// n / 4 where every pointer OR-ed into ``ptrs`` is 16-byte aligned, else 0: the kernels' scalar loops take what is left
+static int64_t vec4_count(int64_t n, uintptr_t ptrs) { return (ptrs & 15) == 0 ? n / 4 : 0; }
+
+static int launch_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                       float weight_decay, int step, const float* hyper_dev, bool clip, const float* gscale_dev, void* stream) {
+    if (!p || !g || !m || !v || n <= 0 || (!hyper_dev && step < 1)) return PA_EINVAL;
+    const AdamwHyper h = adamw_hyper_host(lr, beta1, beta2, eps, weight_decay, step, hyper_dev);
+    const int64_t n4 = vec4_count(n, (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v);
+    const dim3 grid(stream_blocks(n4)), block(256);
+    if (clip) hipLaunchKernelGGL(adamw_flat_kernel<true>, grid, block, 0, (hipStream_t)stream, p, g, m, v, n4, n, h, hyper_dev, gscale_dev);
+    else hipLaunchKernelGGL(adamw_flat_kernel<false>, grid, block, 0, (hipStream_t)stream, p, g, m, v, n4, n, h, hyper_dev, gscale_dev);
+    return check_launch();
+}
+
+static bool table_args_ok(const float* p, const float* g, const float* m, const float* v, const pa_adamw_stage_desc* descs,
+                          const float* scales, int n_desc, int total_items, int step, const float* hyper_dev) {
+    return p && g && m && v && descs && !((uintptr_t)scales & 7) && n_desc >= 1 && total_items >= 1 && (hyper_dev || step >= 1);
+}
+// the table kernel of the copies' dtype, with groups where scales are given, with the clip factor where ``clip``
+static int launch_table(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, const float* scales, int n_desc,
+                        int total_items, int dtype, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                        const float* hyper_dev, bool clip, const float* gscale_dev, void* stream) {
+    if (!table_args_ok(p, g, m, v, descs, scales, n_desc, total_items, step, hyper_dev) || (dtype != PA_BF16 && dtype != PA_F32)) return PA_EINVAL;
+    const AdamwHyper h = adamw_hyper_host(lr, beta1, beta2, eps, weight_decay, step, hyper_dev);
+    const float2* sc = (const float2*)scales;
+    const dim3 grid(total_items), block(256);
+#define PA_ADAMW_TABLE(TO, GROUPS, CLIP) \
+    hipLaunchKernelGGL((adamw_table_kernel<TO, GROUPS, CLIP>), grid, block, 0, (hipStream_t)stream, p, g, m, v, descs, n_desc, hyper_dev, h, sc, gscale_dev)
+    switch ((dtype == PA_BF16 ? 4 : 0) | (sc ? 2 : 0) | (clip ? 1 : 0)) {
+        case 0: PA_ADAMW_TABLE(float, false, false); break;
+        case 1: PA_ADAMW_TABLE(float, false, true); break;
+        case 2: PA_ADAMW_TABLE(float, true, false); break;
+        case 3: PA_ADAMW_TABLE(float, true, true); break;
+        case 4: PA_ADAMW_TABLE(bf16, false, false); break;
+        case 5: PA_ADAMW_TABLE(bf16, false, true); break;
+        case 6: PA_ADAMW_TABLE(bf16, true, false); break;
+        default: PA_ADAMW_TABLE(bf16, true, true); break;
+    }
+#undef PA_ADAMW_TABLE
+    return check_launch();
+}
+
 extern "C" int pa_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                         float eps, float weight_decay, int step, void* stream) {
-    if (!p || !g || !m || !v || n <= 0 || step < 1) return PA_EINVAL;
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float bc2 = 1.f - powf(beta2, (float)step);
-    const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
-    const int64_t n4 = vec ? n / 4 : 0;
-    const int blocks = (int)std::min<int64_t>(cdiv(std::max<int64_t>(n4, 1), 256), 8192);
-    hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, n, lr, beta1, beta2, eps,
-                       weight_decay, bc1, sqrtf(bc2));
-    return check_launch();
+    return launch_flat(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, nullptr, false, nullptr, stream);
 }
 
 extern "C" int pa_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, void* stream) {
-    if (!p || !g || !m || !v || !hyper || n <= 0) return PA_EINVAL;
-    const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
-    const int64_t n4 = vec ? n / 4 : 0;
-    const int blocks = (int)std::min<int64_t>(cdiv(std::max<int64_t>(n4, 1), 256), 8192);
-    hipLaunchKernelGGL(adamw_dev_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, n, hyper);
-    return check_launch();
+    if (!hyper) return PA_EINVAL;
+    return launch_flat(p, g, m, v, n, 0.f, 0.f, 0.f, 0.f, 0.f, 0, hyper, false, nullptr, stream);
 }
 
-static int adamw_stage_launch(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, const float* scales,
-                              int n_desc, int total_items, int dtype, float lr, float beta1, float beta2, float eps, float weight_decay,
-                              int step, const float* hyper_dev, void* stream) {
-    if (!p || !g || !m || !v || !descs || n_desc < 1 || total_items < 1 || (!hyper_dev && step < 1)) return PA_EINVAL;
-    if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
-    AdamwHyper h{lr, beta1, beta2, eps, weight_decay, 1.f, 1.f};
-    if (!hyper_dev) {
-        h.bc1 = 1.f - powf(beta1, (float)step);
-        h.bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
-    }
-    const float2* sc = (const float2*)scales;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PA_BF16 && !sc)
-        hipLaunchKernelGGL(adamw_stage_kernel<bf16>, dim3(total_items), dim3(256), 0, st, p, g, m, v, descs, n_desc, hyper_dev, h);
-    else if (dtype == PA_BF16)
-        hipLaunchKernelGGL(adamw_stage_groups_kernel<bf16>, dim3(total_items), dim3(256), 0, st, p, g, m, v, descs, n_desc, hyper_dev, h, sc);
-    else if (!sc)
-        hipLaunchKernelGGL(adamw_stage_kernel<float>, dim3(total_items), dim3(256), 0, st, p, g, m, v, descs, n_desc, hyper_dev, h);
-    else
-        hipLaunchKernelGGL(adamw_stage_groups_kernel<float>, dim3(total_items), dim3(256), 0, st, p, g, m, v, descs, n_desc, hyper_dev, h, sc);
-    return check_launch();
+extern "C" int pa_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                             float weight_decay, int step, const float* hyper_dev, const float* gscale_dev, void* stream) {
+    return launch_flat(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, hyper_dev, true, gscale_dev, stream);
 }
 
 extern "C" int pa_adamw_stage(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, int n_desc,
                               int total_items, int dtype, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                               const float* hyper_dev, void* stream) {
-    return adamw_stage_launch(p, g, m, v, descs, nullptr, n_desc, total_items, dtype, lr, beta1, beta2, eps, weight_decay, step, hyper_dev,
-                              stream);
+    return launch_table(p, g, m, v, descs, nullptr, n_desc, total_items, dtype, lr, beta1, beta2, eps, weight_decay, step, hyper_dev, false,
+                        nullptr, stream);
 }
 
 extern "C" int pa_adamw_stage_groups(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, const float* scales,
                                      int n_desc, int total_items, int dtype, float lr, float beta1, float beta2, float eps,
                                      float weight_decay, int step, const float* hyper_dev, void* stream) {
-    if (!scales || ((uintptr_t)scales & 7)) return PA_EINVAL;
-    return adamw_stage_launch(p, g, m, v, descs, scales, n_desc, total_items, dtype, lr, beta1, beta2, eps, weight_decay, step, hyper_dev,
-                              stream);
+    if (!scales) return PA_EINVAL;
+    return launch_table(p, g, m, v, descs, scales, n_desc, total_items, dtype, lr, beta1, beta2, eps, weight_decay, step, hyper_dev, false,
+                        nullptr, stream);
 }
 
 extern "C" int pa_adamw_groups(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, const float* scales,
                                int n_desc, int total_items, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                                const float* hyper_dev, void* stream) {
-    if (!p || !g || !m || !v || !descs || !scales || ((uintptr_t)scales & 7) || n_desc < 1 || total_items < 1 || (!hyper_dev && step < 1))
-        return PA_EINVAL;
-    AdamwHyper h{lr, beta1, beta2, eps, weight_decay, 1.f, 1.f};
-    if (!hyper_dev) {
-        h.bc1 = 1.f - powf(beta1, (float)step);
-        h.bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
-    }
+    if (!scales || !table_args_ok(p, g, m, v, descs, scales, n_desc, total_items, step, hyper_dev)) return PA_EINVAL;
+    const AdamwHyper h = adamw_hyper_host(lr, beta1, beta2, eps, weight_decay, step, hyper_dev);
     hipLaunchKernelGGL(adamw_groups_kernel, dim3(total_items), dim3(256), 0, (hipStream_t)stream, p, g, m, v, descs, n_desc, hyper_dev, h,
                        (const float2*)scales);
-    return check_launch();
-}
-
-extern "C" int pa_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
-                             float weight_decay, int step, const float* hyper_dev, const float* gscale_dev, void* stream) {
-    if (!p || !g || !m || !v || n <= 0 || (!hyper_dev && step < 1)) return PA_EINVAL;
-    AdamwHyper h{lr, beta1, beta2, eps, weight_decay, 1.f, 1.f};
-    if (!hyper_dev) {
-        h.bc1 = 1.f - powf(beta1, (float)step);
-        h.bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
-    }
-    const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
-    const int64_t n4 = vec ? n / 4 : 0;
-    const int blocks = (int)std::min<int64_t>(cdiv(std::max<int64_t>(n4, 1), 256), 8192);
-    hipLaunchKernelGGL(adamw_clip_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, n, h, hyper_dev, gscale_dev);
     return check_launch();
 }
 
 extern "C" int pa_adamw_stage_clip(float* p, const float* g, float* m, float* v, const pa_adamw_stage_desc* descs, const float* scales,
                                    int n_desc, int total_items, int dtype, float lr, float beta1, float beta2, float eps,
                                    float weight_decay, int step, const float* hyper_dev, const float* gscale_dev, void* stream) {
-    if (!p || !g || !m || !v || !descs || n_desc < 1 || total_items < 1 || (!hyper_dev && step < 1)) return PA_EINVAL;
-    if ((dtype != PA_BF16 && dtype != PA_F32) || ((uintptr_t)scales & 7)) return PA_EINVAL;
-    AdamwHyper h{lr, beta1, beta2, eps, weight_decay, 1.f, 1.f};
-    if (!hyper_dev) {
-        h.bc1 = 1.f - powf(beta1, (float)step);
-        h.bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
-    }
-    const float2* sc = (const float2*)scales;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(total_items), block(256);
-    if (dtype == PA_BF16 && !sc)
-        hipLaunchKernelGGL((adamw_stage_clip_kernel<bf16, false>), grid, block, 0, st, p, g, m, v, descs, n_desc, hyper_dev, h, sc, gscale_dev);
-    else if (dtype == PA_BF16)
-        hipLaunchKernelGGL((adamw_stage_clip_kernel<bf16, true>), grid, block, 0, st, p, g, m, v, descs, n_desc, hyper_dev, h, sc, gscale_dev);
-    else if (!sc)
-        hipLaunchKernelGGL((adamw_stage_clip_kernel<float, false>), grid, block, 0, st, p, g, m, v, descs, n_desc, hyper_dev, h, sc, gscale_dev);
-    else
-        hipLaunchKernelGGL((adamw_stage_clip_kernel<float, true>), grid, block, 0, st, p, g, m, v, descs, n_desc, hyper_dev, h, sc, gscale_dev);
-    return check_launch();
+    return launch_table(p, g, m, v, descs, scales, n_desc, total_items, dtype, lr, beta1, beta2, eps, weight_decay, step, hyper_dev, true,
+                        gscale_dev, stream);
 }
 
 extern "C" int64_t pa_grad_norm_partials(int64_t n) { return n <= 0 ? 0 : cdiv(n, GN_CHUNK); }
@@ -652,9 +601,9 @@ extern "C" int pa_clip_coef(const float* partials, int n_partials, float max_nor
 }
 
 extern "C" void pa_adamw_hyper(float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* hyper7_host) {
-    hyper7_host[0] = lr; hyper7_host[1] = beta1; hyper7_host[2] = beta2; hyper7_host[3] = eps; hyper7_host[4] = weight_decay;
-    hyper7_host[5] = 1.f - powf(beta1, (float)step);
-    hyper7_host[6] = sqrtf(1.f - powf(beta2, (float)step));
+    const AdamwHyper h = adamw_hyper_host(lr, beta1, beta2, eps, weight_decay, step, nullptr);
+    static_assert(sizeof(h) == 7 * sizeof(float), "AdamwHyper is the 7-float row");
+    memcpy(hyper7_host, &h, sizeof(h));
 }
 
 extern "C" int pa_wave_augment(const float* x, int B, int64_t ldx, const int32_t* len, const float* amp, const int32_t* shift,
@@ -673,17 +622,14 @@ extern "C" int pa_wave_augment(const float* x, int B, int64_t ldx, const int32_t
 
 extern "C" int pa_swa_update(float* avg, const float* p, int64_t n, int num_averaged, void* stream) {
     if (!avg || !p || n <= 0 || num_averaged < 0) return PA_EINVAL;
-    const bool vec = (((uintptr_t)avg | (uintptr_t)p) & 15) == 0;
-    const int64_t n4 = vec ? n / 4 : 0;
-    const int blocks = (int)std::min<int64_t>(cdiv(std::max<int64_t>(n4, 1), 256), 8192);
+    const int64_t n4 = vec4_count(n, (uintptr_t)avg | (uintptr_t)p);
     // the reference divides by (n + 1); a reciprocal multiply differs by <= 1 ulp of the increment
-    hipLaunchKernelGGL(swa_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, avg, p, n4, n, 1.0f / (float)(num_averaged + 1));
+    hipLaunchKernelGGL(swa_kernel, dim3(stream_blocks(n4)), dim3(256), 0, (hipStream_t)stream, avg, p, n4, n, 1.0f / (float)(num_averaged + 1));
     return check_launch();
 }
 
 extern "C" int pa_sgd(float* p, const float* g, int64_t n, float lr, void* stream) {
     if (!p || !g || n <= 0) return PA_EINVAL;
-    const int blocks = (int)std::min<int64_t>(cdiv(n, 256), 8192);
-    hipLaunchKernelGGL(sgd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, n, lr);
+    hipLaunchKernelGGL(sgd_kernel, dim3(stream_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, n, lr);
     return check_launch();
 }

@@ -373,7 +373,7 @@ def make_stage_table(entries, device):
 
 def make_adamw_stage_table(entries, device):
     """entries: [(offset, rows, cols, dst or None, dst_t or None)] in flat-buffer order -> (device table, n, total work items) for
-    adamw_stage (pa_adamw_stage_desc; a parameter without copies is one run of 4096 elements per work item)."""
+    adamw_update (pa_adamw_stage_desc; a parameter without copies is one run of 4096 elements per work item)."""
     import numpy as np
     from ._lib import AdamwStageDesc
     arr = (AdamwStageDesc * len(entries))()
@@ -385,35 +385,50 @@ def make_adamw_stage_table(entries, device):
     return host.to(device), len(entries), items
 
 
-def adamw_stage(p, g, m, v, table, n, items, dtype, lr, beta1, beta2, eps, weight_decay, step, hyper_dev=None):
-    """AdamW over the parameters the table lists (offsets relative to p / g / m / v) + their GEMM-ready copies, one launch."""
-    check(_lib.load().pa_adamw_stage(_p(p, torch.float32), _p(g, torch.float32), _p(m, torch.float32), _p(v, torch.float32), _p(table), n, items,
-                                     dtype, float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
-                                     _p(hyper_dev), _stream()), "pa_adamw_stage")
-
-
 def make_adamw_scales(pairs, device):
-    """pairs: [(lr_scale, wd_scale)], one per table entry in table order -> the f32 [n][2] device array of adamw_stage_groups /
-    adamw_groups."""
+    """pairs: [(lr_scale, wd_scale)], one per table entry in table order -> the f32 [n][2] device array of adamw_update's ``scales``"""
     import numpy as np
     return torch.from_numpy(np.asarray(pairs, dtype=np.float32).reshape(-1, 2)).to(device)
 
 
-def adamw_stage_groups(p, g, m, v, table, scales, n, items, dtype, lr, beta1, beta2, eps, weight_decay, step, hyper_dev=None):
-    """adamw_stage with parameter groups: table entry i is updated with lr * scales[i, 0] and weight_decay * scales[i, 1]."""
-    assert scales.dtype == torch.float32 and scales.numel() == 2 * n and scales.is_contiguous()
-    check(_lib.load().pa_adamw_stage_groups(_p(p, torch.float32), _p(g, torch.float32), _p(m, torch.float32), _p(v, torch.float32), _p(table),
-                                            _p(scales), n, items, dtype, float(lr), float(beta1), float(beta2), float(eps),
-                                            float(weight_decay), int(step), _p(hyper_dev), _stream()), "pa_adamw_stage_groups")
+_ADAMW_FLAT = ("pa_adamw", "pa_adamw_dev", "pa_adamw_clip")
+_ADAMW_TABLE = ("pa_adamw_stage", "pa_adamw_stage_groups", "pa_adamw_groups", "pa_adamw_stage_clip")
 
 
-def adamw_groups(p, g, m, v, table, scales, n, items, lr, beta1, beta2, eps, weight_decay, step, hyper_dev=None):
-    """The plain form: AdamW with parameter groups over a table without copies (every entry in runs of 4096 elements); hyper_dev
-    (7 device floats, see adamw_hyper) in place of the by-value scalars makes the launch capturable."""
-    assert scales.dtype == torch.float32 and scales.numel() == 2 * n and scales.is_contiguous()
-    check(_lib.load().pa_adamw_groups(_p(p, torch.float32), _p(g, torch.float32), _p(m, torch.float32), _p(v, torch.float32), _p(table),
-                                      _p(scales), n, items, float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
-                                      int(step), _p(hyper_dev), _stream()), "pa_adamw_groups")
+def adamw_update(p, g, m, v, hyper, *, table=None, scales=None, dtype=None, gscale=None, entry=None):
+    """One AdamW launch on the flat f32 buffers p / g / m / v (g is read only), whichever C entry serves it.
+    hyper: the step's scalars by value, (lr, beta1, beta2, eps, weight_decay, step), or the 7-float device row of adamw_hyper (a launch
+    whose arguments never change: capturable in a hipGraph).
+    table: what make_adamw_stage_table / _Staged.adamw_table returned -- the parameters the launch covers (offsets relative to the
+    buffers) and their GEMM-ready copies of ``dtype``, written in the same pass; None: the whole of p as one flat span.
+    scales: make_adamw_scales' parameter groups -- table entry i is updated with lr * scales[i, 0] and weight_decay * scales[i, 1].
+    gscale: one device float, the clip factor: the update is that of g * gscale.
+    The entry is the one the combination names: flat pa_adamw / pa_adamw_dev (device row), pa_adamw_clip with gscale; table
+    pa_adamw_stage, pa_adamw_stage_groups with scales, pa_adamw_groups with scales and no dtype (a table without copies),
+    pa_adamw_stage_clip with gscale.  ``entry`` names another one that takes the same arguments (the parity tests drive all seven)."""
+    by_value = not torch.is_tensor(hyper)
+    if entry is None:
+        if table is None:
+            entry = "pa_adamw_clip" if gscale is not None else "pa_adamw" if by_value else "pa_adamw_dev"
+        else:
+            entry = ("pa_adamw_stage_clip" if gscale is not None else "pa_adamw_stage" if scales is None else
+                     "pa_adamw_groups" if dtype is None else "pa_adamw_stage_groups")
+    if entry not in (_ADAMW_FLAT if table is None else _ADAMW_TABLE):
+        raise _lib.PasstAmdError(f"adamw_update: {entry} is no AdamW entry {'without' if table is None else 'with'} a table")
+    lr, beta1, beta2, eps, wd, step = hyper if by_value else (0.0, 0.0, 0.0, 0.0, 0.0, 0)
+    bufs = (_p(p, torch.float32), _p(g, torch.float32), _p(m, torch.float32), _p(v, torch.float32))
+    scalars = (float(lr), float(beta1), float(beta2), float(eps), float(wd), int(step))
+    row, factor = _p(None if by_value else hyper, torch.float32), _p(gscale, torch.float32)
+    if table is None:
+        args = {"pa_adamw": scalars, "pa_adamw_dev": (row,), "pa_adamw_clip": scalars + (row, factor)}[entry]
+        args = (p.numel(),) + args
+    else:
+        tab, n, items = table[:3]
+        assert scales is None or (scales.dtype == torch.float32 and scales.numel() == 2 * n and scales.is_contiguous())
+        geo = (n, items) if entry == "pa_adamw_groups" else (n, items, dtype)
+        sc = () if entry == "pa_adamw_stage" else (_p(scales),)
+        args = (_p(tab),) + sc + geo + scalars + ((row, factor) if entry == "pa_adamw_stage_clip" else (row,))
+    check(getattr(_lib.load(), entry)(*bufs, *args, _stream()), entry)
 
 
 def stage_weights(table, n, tiles, dtype):
@@ -1614,17 +1629,6 @@ def wave_ir_convolve(x, L, lengths=None, ir_idx=None, bank=None, out=None):
     return out, len_out
 
 
-def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step):
-    check(_lib.load().pa_adamw(_p(p, torch.float32), _p(g, torch.float32), _p(m, torch.float32), _p(v, torch.float32), p.numel(), lr, beta1, beta2, eps, wd, step, _stream()),
-          "pa_adamw")
-
-
-def adamw_dev(p, g, m, v, hyper_dev):
-    """the same update with the step's scalars in device memory (7 floats, see adamw_hyper): capturable in a hipGraph"""
-    check(_lib.load().pa_adamw_dev(_p(p, torch.float32), _p(g, torch.float32), _p(m, torch.float32), _p(v, torch.float32), p.numel(),
-                                   _p(hyper_dev, torch.float32), _stream()), "pa_adamw_dev")
-
-
 def grad_norm_partials(n):
     """how many f32 partial sums pa_grad_accum_sumsq writes for a span of n elements (host only: a function of n alone)"""
     return int(_lib.load().pa_grad_norm_partials(int(n)))
@@ -1648,22 +1652,6 @@ def clip_coef(partials, max_norm, out):
         raise _lib.PasstAmdError("clip_coef: out holds 2 floats (norm, factor)")
     check(_lib.load().pa_clip_coef(_p(partials, torch.float32), partials.numel(), float(max_norm), _p(out, torch.float32), _stream()),
           "pa_clip_coef")
-
-
-def adamw_clip(p, g, m, v, lr, beta1, beta2, eps, wd, step, hyper_dev=None, gscale=None):
-    """adamw / adamw_dev (hyper_dev: 7 device floats) on g * gscale, gscale one device float (None: 1); g itself is not written"""
-    check(_lib.load().pa_adamw_clip(_p(p, torch.float32), _p(g, torch.float32), _p(m, torch.float32), _p(v, torch.float32), p.numel(),
-                                    float(lr), float(beta1), float(beta2), float(eps), float(wd), int(step), _p(hyper_dev, torch.float32),
-                                    _p(gscale, torch.float32), _stream()), "pa_adamw_clip")
-
-
-def adamw_stage_clip(p, g, m, v, table, scales, n, items, dtype, lr, beta1, beta2, eps, weight_decay, step, hyper_dev=None, gscale=None):
-    """adamw_stage / adamw_stage_groups / adamw_groups (scales may be None, table entries may omit their copies) on g * gscale"""
-    assert scales is None or (scales.dtype == torch.float32 and scales.numel() == 2 * n and scales.is_contiguous())
-    check(_lib.load().pa_adamw_stage_clip(_p(p, torch.float32), _p(g, torch.float32), _p(m, torch.float32), _p(v, torch.float32), _p(table),
-                                          _p(scales), n, items, dtype, float(lr), float(beta1), float(beta2), float(eps),
-                                          float(weight_decay), int(step), _p(hyper_dev), _p(gscale, torch.float32), _stream()),
-          "pa_adamw_stage_clip")
 
 
 def adamw_hyper(lr, beta1, beta2, eps, wd, step, out_host):

@@ -199,12 +199,12 @@ class AdamW(torch.optim.Optimizer):
         s, e = b["s"], b["e"]
         st = net._staged
         dt = net._last_dt if net._last_dt is not None else PA_BF16
-        tab, n, items, keys = st.adamw_table(("optim", id(self), s, e), [(ps[k], fl["offs"][k] - s) for k in range(i0, i1)], dt)
+        *table, keys = st.adamw_table(("optim", id(self), s, e), [(ps[k], fl["offs"][k] - s) for k in range(i0, i1)], dt)
+        args = (fl["flat_p"][s:e], b["flat_g"], fl["m"][s:e], fl["v"][s:e], (lr, b1, b2, eps, wd, t))
         if jobs is None:
-            ops.adamw_stage(fl["flat_p"][s:e], b["flat_g"], fl["m"][s:e], fl["v"][s:e], tab, n, items, dt, lr, b1, b2, eps, wd, t)
+            ops.adamw_update(*args, table=table, dtype=dt)
         else:       # clipping: launched behind the factor (_clip_and_launch), still inside this step()
-            jobs.append((b["flat_g"], lambda gs: ops.adamw_stage_clip(fl["flat_p"][s:e], b["flat_g"], fl["m"][s:e], fl["v"][s:e], tab, None,
-                                                                      n, items, dt, lr, b1, b2, eps, wd, t, gscale=gs)))
+            jobs.append((b["flat_g"], lambda gs: ops.adamw_update(*args, table=table, dtype=dt, gscale=gs)))
         b["step"].fill_(float(t))
         for k in range(i0, i1):
             fl["steps"][k] = t
@@ -213,7 +213,7 @@ class AdamW(torch.optim.Optimizer):
         return True
 
     def _launch(self, p, g, m, v, lr, b1, b2, eps, wd, step):
-        ops.adamw(p, g, m, v, lr, b1, b2, eps, wd, step)
+        ops.adamw_update(p, g, m, v, (lr, b1, b2, eps, wd, step))
 
     def _clip_and_launch(self, jobs):
         """jobs: [(flat gradients of a run, launch(gscale))] of the whole step.  Partial sums of squares per run, ONE factor over all
@@ -282,7 +282,7 @@ class AdamW(torch.optim.Optimizer):
                 if jobs is None:
                     self._launch(*args)
                 else:
-                    jobs.append((gflat, lambda gs, a=args: ops.adamw_clip(*a, gscale=gs)))
+                    jobs.append((gflat, lambda gs, a=args: ops.adamw_update(*a[:4], a[4:], gscale=gs)))
                 for k in range(i, j):
                     st = self.state[ps[k]]
                     if "exp_avg" not in st:

@@ -169,62 +169,32 @@ class TrainStep:
         else:
             ops.grad_accum_sumsq(self._gbuf[s:e], partials=self._partials[a:b])
 
-    def _optimizer_clip(self, s, e):
-        """_optimizer with the clip factor (device memory: self._clip_out[1]) on the gradients: the same launch per case"""
-        fp, g, m, v, gs = self.flat_p[s:e], self._gbuf[s:e], self.m[s:e], self.v[s:e], self._clip_out[1:]
-        hy = (self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self._t_now)
-        if self._g is not None and self._g.get("capturing"):
-            if self.groups is not None:
-                tab, n, items, scales = self._group_table(s, e)
-                return ops.adamw_stage_clip(fp, g, m, v, tab, scales, n, items, _precision(self.net), 0.0, 0.0, 0.0, 0.0, 0.0, 0,
-                                            hyper_dev=self._g["hyper"], gscale=gs)
-            return ops.adamw_clip(fp, g, m, v, 0.0, 0.0, 0.0, 0.0, 0.0, 0, hyper_dev=self._g["hyper"], gscale=gs)
-        if self.fused_stage:
-            st, dt = self.net._staged, _precision(self.net)
-            lo, hi = self._span_params(s, e)
-            tab, n, items, keys = st.adamw_table((s, e), [(self.named[i][1], self._offsets[i] - s) for i in range(lo, hi)], dt)
-            ops.adamw_stage_clip(fp, g, m, v, tab, None if self.groups is None else self._group_table(s, e)[3], n, items, dt, *hy, gscale=gs)
-            self._fresh += keys
-        elif self.groups is not None:
-            tab, n, items, scales = self._group_table(s, e)
-            ops.adamw_stage_clip(fp, g, m, v, tab, scales, n, items, _precision(self.net), *hy, gscale=gs)
-        else:
-            ops.adamw_clip(fp, g, m, v, *hy, gscale=gs)
-
     def _optimizer(self, s, e):
-        if self.clip is not None:
-            return self._optimizer_clip(s, e)
-        if self._g is not None and self._g.get("capturing"):
-            # inside the capture: the step's scalars come from device memory (launch arguments must not change between replays)
-            if self.optimizer != "adamw":
+        """the update of bucket [s, e): one launch"""
+        capturing = self._g is not None and self._g.get("capturing")
+        if self.optimizer != "adamw":
+            if capturing:
                 raise NotImplementedError("graph mode: AdamW only")
-            if self.groups is not None:
-                tab, n, items, scales = self._group_table(s, e)
-                return ops.adamw_groups(self.flat_p[s:e], self._gbuf[s:e], self.m[s:e], self.v[s:e], tab, scales, n, items, 0.0, 0.0, 0.0,
-                                        0.0, 0.0, 0, hyper_dev=self._g["hyper"])
-            return ops.adamw_dev(self.flat_p[s:e], self._gbuf[s:e], self.m[s:e], self.v[s:e], self._g["hyper"])
-        if self.optimizer == "adamw" and self.fused_stage:
-            # no kernel enqueued after this point reads this bucket's copies before the next forward: the bucket's own input-
-            # gradient GEMMs (the readers of W^T) are already on the stream, earlier blocks read their own weights
-            st, dt = self.net._staged, _precision(self.net)
+            return ops.sgd(self.flat_p[s:e], self._gbuf[s:e], self.lr)
+        # the step's scalars: inside the capture from device memory (launch arguments must not change between replays)
+        hyper = self._g["hyper"] if capturing else (self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self._t_now)
+        # the clip factor: device memory as well (pa_clip_coef wrote it behind the backward)
+        gs = None if self.clip is None else self._clip_out[1:]
+        table, scales, dt, keys = None, None, None, []
+        if self.fused_stage and not capturing:
+            # the bucket's parameters and their GEMM-ready copies.  No kernel enqueued after this point reads this bucket's copies
+            # before the next forward: the bucket's own input-gradient GEMMs (the readers of W^T) are already on the stream, earlier
+            # blocks read their own weights
+            dt = _precision(self.net)
             lo, hi = self._span_params(s, e)
-            tab, n, items, keys = st.adamw_table((s, e), [(self.named[i][1], self._offsets[i] - s) for i in range(lo, hi)], dt)
-            if self.groups is None:
-                ops.adamw_stage(self.flat_p[s:e], self._gbuf[s:e], self.m[s:e], self.v[s:e], tab, n, items, dt, self.lr, self.betas[0],
-                                self.betas[1], self.eps, self.wd, self._t_now)
-            else:
-                ops.adamw_stage_groups(self.flat_p[s:e], self._gbuf[s:e], self.m[s:e], self.v[s:e], tab, self._group_table(s, e)[3], n,
-                                       items, dt, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self._t_now)
-            self._fresh += keys
-        elif self.optimizer == "adamw" and self.groups is not None:
-            tab, n, items, scales = self._group_table(s, e)
-            ops.adamw_groups(self.flat_p[s:e], self._gbuf[s:e], self.m[s:e], self.v[s:e], tab, scales, n, items, self.lr, self.betas[0],
-                             self.betas[1], self.eps, self.wd, self._t_now)
-        elif self.optimizer == "adamw":
-            ops.adamw(self.flat_p[s:e], self._gbuf[s:e], self.m[s:e], self.v[s:e], self.lr, self.betas[0], self.betas[1],
-                      self.eps, self.wd, self._t_now)
-        else:
-            ops.sgd(self.flat_p[s:e], self._gbuf[s:e], self.lr)
+            *table, keys = self.net._staged.adamw_table((s, e), [(self.named[i][1], self._offsets[i] - s) for i in range(lo, hi)], dt)
+            scales = None if self.groups is None else self._group_table(s, e)[3]
+        elif self.groups is not None:
+            # one entry per parameter, no copies: no dtype either (pa_adamw_groups) -- pa_adamw_stage_clip takes one all the same
+            *table, scales = self._group_table(s, e)
+            dt = None if gs is None else _precision(self.net)
+        ops.adamw_update(self.flat_p[s:e], self._gbuf[s:e], self.m[s:e], self.v[s:e], hyper, table=table, scales=scales, dtype=dt, gscale=gs)
+        self._fresh += keys
 
     def _group_table(self, s, e):
         """(plain descriptor table, n, work items, scales) of flat span [s, e) for the launches with parameter groups: one entry per

@@ -22,6 +22,7 @@ from oracle import passt_oracle as O  # noqa: E402
 from passt_amd import _lib, ops  # noqa: E402
 from passt_amd import passt as P  # noqa: E402
 from passt_amd.train import TrainStep, group_scales  # noqa: E402
+from tests.adamw_cases import GUARD, HYPER, PARAMS, SCALES, SENT, group_case  # noqa: E402,F401
 from tests.golden import make_golden as G  # noqa: E402
 from tests.test_gpu_model import BF16_GRADS, build, rel  # noqa: E402
 
@@ -334,35 +335,9 @@ def test_train_step_layer_decay_and_no_weight_decay_vs_torch(graph):
         assert torch.equal(e.flat_p, g.flat_p) and torch.equal(e.m, g.m) and torch.equal(e.v, g.v)
 
 
-GUARD, SENT = 64, -1.5 * 2.0 ** 100
-SCALES = {"a": [(1.0, 1.0), (0.5, 0.0), (0.75 ** 2, 1.0), (0.0, 0.0), (1.0, 0.0)],
-          "b": [(0.0, 1.0), (0.75 ** 2, 0.0), (0.5, 1.0), (1.0, 0.0), (0.5, 1.0)],
-          "ones": [(1.0, 1.0)] * 5}
-# (rows, cols, copies, guard elements behind it): the 64-tile of the matrix has edges both ways; 4097 is one past a run; the 527
-# vector is followed directly by the 768 one, whose offset (and the later guard's) is then off 16-byte alignment
-PARAMS = [(100, 70, True, GUARD), (1, 4097, False, GUARD - 1), (1, 527, False, 0), (1, 768, False, GUARD), (1, 5, False, GUARD)]
-HYPER = dict(lr=1e-3, b1=0.9, b2=0.999, eps=1e-8, wd=1e-2, step=3)
-
-
 def _group_case(dtype):
-    """flat p / g / m / v with sentinel guards around every parameter, guarded copies, the descriptor table"""
-    gen = torch.Generator().manual_seed(17)
-    offs, n = [], GUARD
-    for rows, cols, _, guard in PARAMS:
-        offs.append(n)
-        n += rows * cols + guard
-    live = torch.zeros(n, dtype=torch.bool)
-    for off, (rows, cols, _, _) in zip(offs, PARAMS):
-        live[off:off + rows * cols] = True
-    p = torch.where(live, torch.randn(n, generator=gen) * 0.1, torch.tensor(SENT))
-    g = torch.where(live, torch.randn(n, generator=gen) * 0.01, torch.tensor(float("nan")))
-    m = torch.where(live, torch.randn(n, generator=gen) * 0.01, torch.tensor(SENT))
-    v = torch.where(live, torch.rand(n, generator=gen) * 1e-4, torch.tensor(SENT))
-    td = ops.TORCH_DTYPE[dtype]
-    rows, cols = PARAMS[0][:2]
-    copies = torch.full((2, GUARD + rows * cols + GUARD), SENT, dtype=td, device=DEV)
-    dst, dst_t = copies[0, GUARD:GUARD + rows * cols].view(rows, cols), copies[1, GUARD:GUARD + rows * cols].view(cols, rows)
-    return dict(p=p, g=g, m=m, v=v, live=live, offs=offs, copies=copies, dst=dst, dst_t=dst_t)
+    """flat p / g / m / v with sentinel guards around every parameter, guarded copies (tests/adamw_cases.py)"""
+    return group_case(dtype, DEV)
 
 
 def _group_tables(c, with_copies):
@@ -379,20 +354,13 @@ def _run_groups(dtype, entry, scales, hyper_dev=False):
     dev = {k: c[k].to(DEV) for k in "pgmv"}
     tab, n, items = _group_tables(c, entry != "groups")
     h = HYPER
-    hy = None
+    hyper = (h["lr"], h["b1"], h["b2"], h["eps"], h["wd"], h["step"])
     if hyper_dev:
         host = torch.empty(7, dtype=torch.float32)
-        ops.adamw_hyper(h["lr"], h["b1"], h["b2"], h["eps"], h["wd"], h["step"], host)
-        hy = host.to(DEV)
-    by_value = (0.0, 0.0, 0.0, 0.0, 0.0, 0) if hyper_dev else (h["lr"], h["b1"], h["b2"], h["eps"], h["wd"], h["step"])
-    if entry == "stage":
-        ops.adamw_stage(dev["p"], dev["g"], dev["m"], dev["v"], tab, n, items, dtype, *by_value, hyper_dev=hy)
-    else:
-        sc = ops.make_adamw_scales(scales, DEV)
-        if entry == "stage_groups":
-            ops.adamw_stage_groups(dev["p"], dev["g"], dev["m"], dev["v"], tab, sc, n, items, dtype, *by_value, hyper_dev=hy)
-        else:
-            ops.adamw_groups(dev["p"], dev["g"], dev["m"], dev["v"], tab, sc, n, items, *by_value, hyper_dev=hy)
+        ops.adamw_hyper(*hyper, host)
+        hyper = host.to(DEV)
+    sc = None if entry == "stage" else ops.make_adamw_scales(scales, DEV)
+    ops.adamw_update(dev["p"], dev["g"], dev["m"], dev["v"], hyper, table=(tab, n, items), scales=sc, dtype=dtype, entry="pa_adamw_" + entry)
     torch.cuda.synchronize()
     out = {k: dev[k].cpu() for k in "pmv"}
     out["copies"] = c["copies"].cpu()

@@ -145,34 +145,21 @@ def _adamw_launch(dtype, entry, which, hyper_dev, clip, factor):
     dev = dict(p=c["p"].to(DEV), g=g_in.to(DEV), m=c["m"].to(DEV), v=c["v"].to(DEV))
     g_before = dev["g"].clone()
     h = HYPER
-    hy = None
+    hyper = (h["lr"], h["b1"], h["b2"], h["eps"], h["wd"], h["step"])
     if hyper_dev:
         host = torch.empty(7, dtype=torch.float32)
-        ops.adamw_hyper(h["lr"], h["b1"], h["b2"], h["eps"], h["wd"], h["step"], host)
-        hy = host.to(DEV)
-    by_value = (0.0, 0.0, 0.0, 0.0, 0.0, 0) if hyper_dev else (h["lr"], h["b1"], h["b2"], h["eps"], h["wd"], h["step"])
+        ops.adamw_hyper(*hyper, host)
+        hyper = host.to(DEV)
     gs = torch.tensor([factor], dtype=torch.float32, device=DEV) if (clip and factor is not None) else None
     sc = ops.make_adamw_scales(SCALES[which], DEV) if entry in ("stage_groups", "groups") else None
     pgmv = (dev["p"], dev["g"], dev["m"], dev["v"])
     if entry == "flat":
+        name = "pa_adamw_clip" if clip else "pa_adamw_dev" if hyper_dev else "pa_adamw"
         for off, (rows, cols, _, _) in zip(c["offs"], PARAMS):          # every parameter as its own flat span (two are misaligned)
-            sl = tuple(t[off:off + rows * cols] for t in pgmv)
-            if clip:
-                ops.adamw_clip(*sl, *by_value, hyper_dev=hy, gscale=gs)
-            elif hyper_dev:
-                ops.adamw_dev(*sl, hy)
-            else:
-                ops.adamw(*sl, *by_value)
+            ops.adamw_update(*(t[off:off + rows * cols] for t in pgmv), hyper, gscale=gs, entry=name)
     else:
-        tab, n, items = _group_tables(c, entry != "groups")
-        if clip:
-            ops.adamw_stage_clip(*pgmv, tab, sc, n, items, dtype, *by_value, hyper_dev=hy, gscale=gs)
-        elif entry == "stage":
-            ops.adamw_stage(*pgmv, tab, n, items, dtype, *by_value, hyper_dev=hy)
-        elif entry == "stage_groups":
-            ops.adamw_stage_groups(*pgmv, tab, sc, n, items, dtype, *by_value, hyper_dev=hy)
-        else:
-            ops.adamw_groups(*pgmv, tab, sc, n, items, *by_value, hyper_dev=hy)
+        ops.adamw_update(*pgmv, hyper, table=_group_tables(c, entry != "groups"), scales=sc, dtype=dtype, gscale=gs,
+                         entry="pa_adamw_stage_clip" if clip else "pa_adamw_" + entry)
     torch.cuda.synchronize()
     assert torch.equal(_bits(dev["g"]), _bits(g_before))                # the gradient buffer is not written
     out = {k: dev[k].cpu() for k in "pmv"}

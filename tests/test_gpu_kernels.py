@@ -641,7 +641,7 @@ def test_mixup_and_optimizers():
     for step in (1, 2, 3):
         pr.grad = (g * step).double()
         opt.step()
-        ops.adamw(p, (g * step).to(DEV), m, v, 2e-3, 0.9, 0.999, 1e-8, 1e-2, step)
+        ops.adamw_update(p, (g * step).to(DEV), m, v, (2e-3, 0.9, 0.999, 1e-8, 1e-2, step), entry="pa_adamw")
     assert rel_err(p, pr.detach()) < 1e-5
     q = p0.clone().to(DEV)
     ops.sgd(q, g.to(DEV), 0.1)
@@ -751,7 +751,8 @@ def test_adamw_stage_equals_adamw_then_stage_weights(dt, hyper_on_device):
     hp = dict(lr=3e-3, b1=0.9, b2=0.999, eps=1e-8, wd=1e-2, step=7)
     # (a) separately
     pa, ma, va = P.clone(), Mo.clone(), Vo.clone()
-    ops.adamw(pa, G, ma, va, hp["lr"], hp["b1"], hp["b2"], hp["eps"], hp["wd"], hp["step"])
+    hyper = (hp["lr"], hp["b1"], hp["b2"], hp["eps"], hp["wd"], hp["step"])
+    ops.adamw_update(pa, G, ma, va, hyper, entry="pa_adamw")
     want = []
     for sh, o, c in zip(shapes, offs, copies):
         w = pa[o:o + int(np.prod(sh))].view(sh[0], -1) if c else None
@@ -766,15 +767,12 @@ def test_adamw_stage_equals_adamw_then_stage_weights(dt, hyper_on_device):
         dst_t = torch.full((cols, rows), 7.0, device=DEV, dtype=TD[dt]) if c in ("both", "t") else None
         entries.append((o, rows, cols, dst, dst_t))
         outs.append((dst, dst_t))
-    table, n, items = ops.make_adamw_stage_table(entries, DEV)
-    hy = None
+    table = ops.make_adamw_stage_table(entries, DEV)
     if hyper_on_device:
         host = torch.empty(7, dtype=torch.float32)
-        ops.adamw_hyper(hp["lr"], hp["b1"], hp["b2"], hp["eps"], hp["wd"], hp["step"], host)
-        hy = host.to(DEV)
-        ops.adamw_stage(pb, G, mb, vb, table, n, items, dt, 0.0, 0.0, 0.0, 0.0, 0.0, 0, hyper_dev=hy)
-    else:
-        ops.adamw_stage(pb, G, mb, vb, table, n, items, dt, hp["lr"], hp["b1"], hp["b2"], hp["eps"], hp["wd"], hp["step"])
+        ops.adamw_hyper(*hyper, host)
+        hyper = host.to(DEV)
+    ops.adamw_update(pb, G, mb, vb, hyper, table=table, dtype=dt, entry="pa_adamw_stage")
     torch.cuda.synchronize()
     assert torch.equal(pb, pa) and torch.equal(mb, ma) and torch.equal(vb, va)
     assert float((pb - P).abs().max()) > 1e-3

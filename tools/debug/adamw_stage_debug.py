@@ -19,7 +19,8 @@ for dt in (PA_BF16, PA_F32):
     Vo = (torch.rand(total, generator=g0) * 1e-4).to(DEV)
     hp = dict(lr=3e-3, b1=0.9, b2=0.999, eps=1e-8, wd=1e-2, step=7)
     pa, ma, va = P.clone(), Mo.clone(), Vo.clone()
-    ops.adamw(pa, G, ma, va, hp["lr"], hp["b1"], hp["b2"], hp["eps"], hp["wd"], hp["step"])
+    hyper = (hp["lr"], hp["b1"], hp["b2"], hp["eps"], hp["wd"], hp["step"])
+    ops.adamw_update(pa, G, ma, va, hyper)
     pb, mb, vb = P.clone(), Mo.clone(), Vo.clone()
     entries, outs = [], []
     for sh, o, c in zip(shapes, offs, copies):
@@ -30,7 +31,7 @@ for dt in (PA_BF16, PA_F32):
         entries.append((o, rows, cols, dst, dst_t)); outs.append((dst, dst_t))
     table, n, items = ops.make_adamw_stage_table(entries, DEV)
     print("dt", dt, "n", n, "items", items)
-    ops.adamw_stage(pb, G, mb, vb, table, n, items, dt, hp["lr"], hp["b1"], hp["b2"], hp["eps"], hp["wd"], hp["step"])
+    ops.adamw_update(pb, G, mb, vb, hyper, table=(table, n, items), dtype=dt)
     torch.cuda.synchronize()
     for sh, o, c, (d, t) in zip(shapes, offs, copies, outs):
         nn = int(np.prod(sh))
