@@ -718,6 +718,22 @@ int pa_ce_mixup_fwd_bwd(const float* logits, const int32_t* target, const int32_
 /* ex_audioset.py:175-177 / helpers/mixup.py: out[b] = x[b]*lam[b] + x[perm[b]]*(1-lam[b]) */
 int pa_mixup(const float* x, const int32_t* perm, const float* lam, float* out, int B,
              int64_t per_sample, void* stream);
+/* Spectrogram mixup of a ragged batch (additive to ABI 6).  x, out: [B][rows][ldt] f32, clip b valid in its first lens[b] columns
+ * of every row; lens (int32, clamped to [0, ldt] in the kernel), perm (int32, entries in [0, B)) and lam (f32) are device arrays of
+ * B entries.  The mixed clip keeps its own length; its partner j = perm[b] is cut to it, or continued with the constant ``pad``
+ * (the spectrogram of silence) when it is shorter -- pad_or_truncate at the spectrogram level:
+ *   t <  lens[b]:  out[b][r][t] = x[b][r][t] * lam[b] + (t < lens[j] ? x[j][r][t] : pad) * (1 - lam[b])
+ *   t >= lens[b]:  out[b][r][t] = 0.0f exactly
+ * One streaming pass: 16-byte accesses where ldt % 4 == 0 and x and out are 16-byte aligned -- and, beyond that, wherever a clip is a
+ * whole number of 16-byte groups (rows * ldt % 4 == 0, ldt >= 4: 128 mel rows of any frame count) -- a group that straddles lens[b],
+ * lens[j] or a row's end being resolved per lane; 4-byte accesses otherwise.  What x holds at or behind a clip's own length is never used: such a
+ * value is chosen away, not multiplied by zero, so a NaN or Inf there does not reach out.  Every element of out is written, nothing
+ * else.  The arithmetic is one multiplication and one fused multiply-add, fmaf(x[b], lam, c * (1 - lam)), the same as pa_mixup's
+ * 16-byte path: with every lens[b] == ldt and ldt % 4 == 0 the result equals pa_mixup(per_sample = rows * ldt) bit for bit.
+ * PA_EINVAL, nothing launched: a NULL pointer, B, rows or ldt < 1, rows * ldt >= 2^31, or out == x (the partner's row is read while
+ * other rows are written). */
+int pa_mixup_varlen(const float* x, const int32_t* lens, const int32_t* perm, const float* lam, float pad, float* out, int B,
+                    int rows, int ldt, void* stream);
 /* Waveform-side augmentation of one batch, ahead of the front end.  What the reference's data
  * pipeline does per clip on CPU workers, in its order: gain (audioset/dataset.py:102-112, amp = 10^(dB/20)),
  * pad_or_truncate to L samples (:73-78), roll (:315-329: out[t] = in[(t - shift) mod L]) and waveform mixup

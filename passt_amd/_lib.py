@@ -131,6 +131,7 @@ SIGNATURES = {
     "pa_bce_fwd_bwd": (i32, [vp, vp, i32, i32, f32, vp, vp, vp, vp]),
     "pa_ce_mixup_fwd_bwd": (i32, [vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp]),
     "pa_mixup": (i32, [vp, vp, vp, vp, i32, i64, vp]),
+    "pa_mixup_varlen": (i32, [vp, vp, vp, vp, f32, vp, i32, i32, i32, vp]),
     "pa_adamw": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp]),
     "pa_adamw_dev": (i32, [vp, vp, vp, vp, i64, vp, vp]),
     "pa_adamw_stage": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, i32, vp, vp]),

@@ -8,16 +8,65 @@
 
 namespace pa {
 
+// a * l + c * (1 - l) as ONE definite sequence of roundings: the product c * (1 - l), then one fused multiply-add.  It is what the
+// compiler's contraction made of mixup_kernel's expression; written out, pa_mixup's 16-byte path and pa_mixup_varlen cannot come to
+// differ by how a * b + c happens to be fused in each (the adamw_one story below).
+__device__ __forceinline__ float mix_one(float a, float l, float c, float oml) {
+#pragma clang fp contract(off)
+    const float cw = c * oml;
+    return __builtin_fmaf(l, a, cw);
+}
+
 __global__ void mixup_kernel(const float* __restrict__ x, const int32_t* __restrict__ perm, const float* __restrict__ lam,
                              float* __restrict__ out, int64_t per4) {
     const int b = blockIdx.y;
-    const float l = lam[b];
+    const float l = lam[b], oml = 1.f - l;
     const float4* xa = (const float4*)x + (int64_t)b * per4;
     const float4* xb = (const float4*)x + (int64_t)perm[b] * per4;
     float4* o = (float4*)out + (int64_t)b * per4;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per4; i += (int64_t)gridDim.x * blockDim.x) {
         const float4 a = xa[i], c = xb[i];
-        o[i] = make_float4(a.x * l + c.x * (1.f - l), a.y * l + c.y * (1.f - l), a.z * l + c.z * (1.f - l), a.w * l + c.w * (1.f - l));
+        o[i] = make_float4(mix_one(a.x, l, c.x, oml), mix_one(a.y, l, c.y, oml), mix_one(a.z, l, c.z, oml), mix_one(a.w, l, c.w, oml));
+    }
+}
+
+// Mixup of a ragged batch, [B][rows][ldt] with clip b valid in its first lens[b] columns: the mixed clip keeps its own length, the
+// partner is cut to it or continued with ``pad``, the cells behind it are 0.  One work item = W consecutive elements of one clip (W = 4:
+// a 16-byte group of the clip's rows * ldt floats, which is a multiple of 4; W = 1: the scalar path).  With ldt % 4 == 0 a group lies
+// in one row; otherwise it may run over a row's end into the next row's first columns (``wraps``; ldt >= W, so at most once).  A
+// group with no lane inside the clip is written without a load, one with no lane inside the partner's length loads only the clip's
+// own; any other group takes every lane's side by a select on the lane's own column, AFTER the loads -- a value behind a length is
+// chosen away, never multiplied by 0, so a NaN there stays there.
+template <int W> __global__ void mixup_varlen_kernel(const float* __restrict__ x, const int32_t* __restrict__ lens,
+                                                      const int32_t* __restrict__ perm, const float* __restrict__ lam, float pad,
+                                                      float* __restrict__ out, int ldt, uint32_t per) {
+    typedef float vec __attribute__((ext_vector_type(W)));
+    const int b = blockIdx.y, j = perm[b];
+    const float l = lam[b], oml = 1.f - l;
+    const int ni = min(max(lens[b], 0), ldt), nj = min(max(lens[j], 0), ldt);
+    const vec* xa = (const vec*)x + (int64_t)b * per;             // per = rows * ldt / W work items in one clip
+    const vec* xb = (const vec*)x + (int64_t)j * per;
+    vec* o = (vec*)out + (int64_t)b * per;
+    // the column of lane 0 is carried along the grid-stride loop: one division in front of it, an add and a compare inside
+    const uint32_t stride = gridDim.x * blockDim.x, i0 = blockIdx.x * blockDim.x + threadIdx.x;
+    const int dt = (int)(((uint64_t)stride * W) % (uint32_t)ldt);
+    int t0 = (int)(((uint64_t)i0 * W) % (uint32_t)ldt);
+    for (uint32_t i = i0; i < per; i += stride, t0 = t0 + dt < ldt ? t0 + dt : t0 + dt - ldt) {
+        const bool wraps = W > 1 && t0 + W > ldt;                  // the last lanes are columns 0.. of the next row
+        vec r = 0.f;
+        if (t0 < ni || (wraps && ni > 0)) {
+            const vec a = xa[i];
+            vec c = pad;
+            if (t0 < nj || (wraps && nj > 0)) c = xb[i];
+#pragma unroll
+            for (int e = 0; e < W; ++e) {
+                const int t = t0 + e < ldt ? t0 + e : t0 + e - ldt;
+                const float ce = t < nj ? c[e] : pad;
+                const float m = mix_one(a[e], l, ce, oml);
+                r[e] = t < ni ? m : 0.f;
+            }
+        }
+        o[i] = r;
     }
 }
 
@@ -483,6 +532,24 @@ extern "C" int pa_mixup(const float* x, const int32_t* perm, const float* lam, f
     const int64_t per4 = per_sample / 4;
     dim3 grid((unsigned)std::min<int64_t>(cdiv(per4, 256), 64), (unsigned)B);
     hipLaunchKernelGGL(mixup_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, perm, lam, out, per4);
+    return check_launch();
+}
+
+extern "C" int pa_mixup_varlen(const float* x, const int32_t* lens, const int32_t* perm, const float* lam, float pad, float* out, int B,
+                               int rows, int ldt, void* stream) {
+    if (!x || !lens || !perm || !lam || !out || B < 1 || rows < 1 || ldt < 1 || out == x) return PA_EINVAL;
+    if ((int64_t)rows * ldt >= ((int64_t)1 << 31)) return PA_EINVAL;       // the kernels index one clip with 32 bits
+    // pa_mixup's grid: up to 64 workgroups per clip, grid-stride over the rest.  16-byte groups where a clip is a whole number of them
+    // (always with ldt % 4 == 0; with 128 mel rows whatever the frame count) and both buffers are aligned
+    if (((int64_t)rows * ldt) % 4 == 0 && ldt >= 4 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0) {
+        const uint32_t per4 = (uint32_t)((int64_t)rows * ldt / 4);
+        dim3 grid((unsigned)std::min<int64_t>(cdiv((int64_t)per4, 256), 64), (unsigned)B);
+        hipLaunchKernelGGL(mixup_varlen_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, lens, perm, lam, pad, out, ldt, per4);
+    } else {
+        const uint32_t per = (uint32_t)((int64_t)rows * ldt);
+        dim3 grid((unsigned)std::min<int64_t>(cdiv((int64_t)per, 256), 64), (unsigned)B);
+        hipLaunchKernelGGL(mixup_varlen_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, lens, perm, lam, pad, out, ldt, per);
+    }
     return check_launch();
 }
 

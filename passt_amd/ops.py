@@ -1571,6 +1571,26 @@ def mixup(x, perm_i32, lam):
     return out
 
 
+def mixup_varlen(x, lens_dev, perm_i32, lam, pad, out=None):
+    """Spectrogram mixup of a ragged batch (pa_mixup_varlen).  x (B, 1, F, T) or (B, F, T) dense f32, clip b valid in its first
+    lens_dev[b] frames; lens_dev / perm_i32 int32 and lam f32 device tensors of B entries.  Returns a new tensor of x's shape: clip b
+    mixed with clip perm[b] cut to its length or continued with ``pad``, exactly 0 behind lens_dev[b].  ``out`` (a dense f32 tensor of
+    x's shape that is not x): written and returned instead of a new one."""
+    if x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[1] != 1):
+        raise _lib.PasstAmdError(f"mixup_varlen: expected a (B, 1, F, T) or (B, F, T) spectrogram batch, got shape {tuple(x.shape)}")
+    B, rows, ldt = x.shape[0], x.shape[-2], x.shape[-1]
+    for name, t in (("lens_dev", lens_dev), ("perm_i32", perm_i32), ("lam", lam)):
+        if t.numel() != B:
+            raise _lib.PasstAmdError(f"mixup_varlen: {name} has {t.numel()} entries for a batch of {B} clips")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape:
+        raise _lib.PasstAmdError(f"mixup_varlen: out has shape {tuple(out.shape)}, x {tuple(x.shape)}")
+    check(_lib.load().pa_mixup_varlen(_p(x, torch.float32), _p(lens_dev, torch.int32), _p(perm_i32, torch.int32), _p(lam, torch.float32),
+                                      float(pad), _p(out, torch.float32), B, rows, ldt, _stream()), "pa_mixup_varlen")
+    return out
+
+
 def wave_augment(x, L, lengths=None, amp=None, shift=None, partner=None, lam=None):
     """x [B][ldx] f32 raw clips -> [B][L]: gain, pad/truncate, roll, waveform mixup (pa_wave_augment)."""
     B, ldx = x.shape

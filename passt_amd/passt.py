@@ -838,13 +838,20 @@ def passt_forward(model, x, save, draws=None, hidden=None, attn=None, drop_path_
     return out if attn is None else out + (list(r.maps),)
 
 
-def _run_forward(model, x, lengths=None, save=False, draws=None, hidden=None, attn=None, rollout=None, drop_path_masks=None):
-    """The one way into the kernel sequence of a forward: the fixed path, or with ``lengths`` the packed one, under this model's GEMM
-    flags.  Returns the _Fwd."""
-    if lengths is not None and any(p > 0.0 for p in drop_path_rates(model)):
+def refuse_varlen_drop_path(model):
+    """The refusal of a ragged batch by a model with an active DropPath (training mode, rate > 0): net(x, lengths=) and
+    TrainStep.step(lengths=) raise the same NotImplementedError, the step before any of its draws."""
+    if any(p > 0.0 for p in drop_path_rates(model)):
         raise NotImplementedError("PaSST.forward(x, lengths=...) in training mode with drop_path_rate > 0 is not supported: the draw "
                                   "order that gives every clip the masks it would get alone at batch size 1 is not decided yet "
                                   "(train with equal-length batches, or with drop_path_rate = 0 on ragged ones)")
+
+
+def _run_forward(model, x, lengths=None, save=False, draws=None, hidden=None, attn=None, rollout=None, drop_path_masks=None):
+    """The one way into the kernel sequence of a forward: the fixed path, or with ``lengths`` the packed one, under this model's GEMM
+    flags.  Returns the _Fwd."""
+    if lengths is not None:
+        refuse_varlen_drop_path(model)
     with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
         if lengths is None:
             return _passt_forward(model, x, save, draws, hidden, attn, rollout, drop_path_masks)
@@ -968,6 +975,24 @@ def varlen_geometry_train(model, lengths, F_dim=None, T_max=None):
     longer than ``T_max``, or that cannot satisfy the configured counts: no more patch columns than s_patchout_t, no more frequency
     rows than s_patchout_f, no more patches left than u_patchout, or structured time Patchout on a clip with more patch columns than
     the time embedding (the reference indexes the cut grid with indices of the uncut one and fails, models/passt.py:536)."""
+    if F_dim is None:
+        F_dim = model.freq_new_pos_embed.shape[-2]
+    T_dims, cut = check_patchout_varlen(model, lengths, F_dim, T_max)
+    clips, T_eff = [], []
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                 # draw_patchout's "x will be cut", per clip: the caller warns once, from ``cut``
+        for T_dim in T_dims:
+            toff, Te, idx_t, idx_f, idx_u = draw_patchout(model, F_dim, T_dim)
+            clips.append(kept_patches(F_dim, Te, idx_t, idx_f, idx_u) + (toff,))
+            T_eff.append(Te)
+    return dict(_pack_clips(F_dim, T_eff, clips, slot=True), T_eff=T_eff, cut=cut)
+
+
+def check_patchout_varlen(model, lengths, F_dim=None, T_max=None):
+    """Every check varlen_geometry_train makes, and nothing else: no RNG call, no launch.  ``lengths``: valid frames per clip.  Returns
+    (patch columns per clip, the clips whose columns reach the time embedding's length); raises varlen_geometry_train's ValueErrors,
+    clip after clip.  A caller that has more to draw ahead of the Patchout draws (TrainStep.step(lengths=): the front end's, mixup's)
+    calls this first, so that a rejected batch consumes no random number."""
     P, ts = model.patch_embed.patch_size[0], model.patch_embed.stride[1]
     Tpe = model.time_new_pos_embed.shape[-1]
     if F_dim is None:
@@ -988,14 +1013,7 @@ def varlen_geometry_train(model, lengths, F_dim=None, T_max=None):
         if T_dim >= Tpe:
             cut.append(i)
         T_dims.append(T_dim)
-    clips, T_eff = [], []
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")                 # draw_patchout's "x will be cut", per clip: the caller warns once, from ``cut``
-        for T_dim in T_dims:
-            toff, Te, idx_t, idx_f, idx_u = draw_patchout(model, F_dim, T_dim)
-            clips.append(kept_patches(F_dim, Te, idx_t, idx_f, idx_u) + (toff,))
-            T_eff.append(Te)
-    return dict(_pack_clips(F_dim, T_eff, clips, slot=True), T_eff=T_eff, cut=cut)
+    return T_dims, cut
 
 
 def passt_forward_varlen(model, x, lengths, save=False):
@@ -1938,7 +1956,8 @@ class PaSST(nn.Module):
         gets ``x.grad``, exactly 0 behind lengths[i] and on pixels that only dropped patches cover; ``varlen_grad`` and ``input_grad``
         are not consulted -- and a plain forward with Patchout under ``torch.no_grad()``.  ``hidden`` / ``attn`` hand out the kept
         tokens per clip, as above.  Not covered: ``AugmentMelSTFT(..., lengths=)`` in training mode (pad, run the train-mode mel, then
-        ``net(spec, lengths=frames)``), a ragged TrainStep, mixup of clips of different lengths, EnsembelerModel.
+        ``net(spec, lengths=frames)``), EnsembelerModel.  The fused step takes ragged batches as ``TrainStep.step(x, y, lengths=)``,
+        with its own definition of mixup between clips of different lengths (passt_amd.train).
 
         ``torch.compile(net)`` (ex_audioset.py:135, model_speed_test :391): the whole forward is ONE opaque call to the
         compiler (``_lib.compile_opaque``: torch.compiler.disable's mechanism without the torch._dynamo import, installed at class

@@ -14,8 +14,14 @@ import torch
 
 from . import ops
 from .ddp import GradReducer
-from .passt import (_precision, drop_path_draws, drop_path_rates, param_stage, passt_backward, passt_forward, patchout_draws,
+from .passt import (_checked_input, _freq_rows, _precision, check_patchout_varlen, drop_path_draws, drop_path_rates, param_stage,
+                    passt_backward, passt_backward_varlen, passt_forward, passt_forward_varlen, patchout_draws, refuse_varlen_drop_path,
                     trainable_plan)
+from .preprocess import checked_lengths
+
+# What the front end writes for a silent cell, (ln(0 + 1e-5) + 4.5) / 5 (models/preprocess.py:78,84), as one float32: the value a
+# shorter mixup partner is continued with on a ragged batch (TrainStep.step(lengths=); TrainStep(mixup_pad=) overrides it)
+MIXUP_PAD = float(np.float32((np.log(1e-5) + 4.5) / 5.0))
 
 
 def group_scales(named_dims, depth, layer_decay=None, no_weight_decay=(), model_no_weight_decay=()):
@@ -43,7 +49,7 @@ def group_scales(named_dims, depth, layer_decay=None, no_weight_decay=(), model_
 class TrainStep:
     def __init__(self, net, mel=None, lr=2e-5, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, optimizer="adamw",
                  mixup_alpha=0.3, use_mixup=True, process_group=None, loss="bce", comm_dtype="fp32", transport="torch", graph=False,
-                 layer_decay=None, no_weight_decay=(), clip_grad_norm=None, accumulate=1):
+                 layer_decay=None, no_weight_decay=(), clip_grad_norm=None, accumulate=1, mixup_pad=None):
         """A partly frozen network (``requires_grad`` as it stands at construction) is trained as it is: the flat buffers, the moments
         and the all-reduce buckets span the trainable parameters only, the frozen ones keep their storage and are never written, the
         forward keeps nothing of the blocks below the lowest trainable stage and the backward ends behind it (passt.trainable_plan).
@@ -67,8 +73,11 @@ class TrainStep:
         loss gradient carries 1 / (world k); micro-steps 1 .. k - 1 fold their finished buckets into a second flat buffer
         (``flat_acc``) and touch nothing else -- no all-reduce (Lightning's no_sync), no optimizer launch, ``t`` stands still; the
         k-th folds, all-reduces, and updates from the accumulated buffer.  ``flush()`` applies a partial accumulation (the end
-        of an epoch whose batch count is no multiple of k)."""
+        of an epoch whose batch count is no multiple of k).
+        ``mixup_pad`` (None: MIXUP_PAD, the front end's value of a silent cell): what a shorter mixup partner is continued with in a
+        ragged step, see ``step(..., lengths=)``; not read by fixed-shape steps."""
         self.net, self.mel = net, mel
+        self.mixup_pad = MIXUP_PAD if mixup_pad is None else float(mixup_pad)
         self.lr, self.wd, self.betas, self.eps, self.optimizer = lr, weight_decay, betas, eps, optimizer
         self.mixup_alpha, self.use_mixup = mixup_alpha, use_mixup
         assert loss in ("bce", "ce")      # bce: ex_audioset.py:181-186 ; ce: ex_esc50.py:159-165 (class-index targets)
@@ -341,9 +350,45 @@ class TrainStep:
         self._apply()
         return loss
 
-    def step(self, wave_or_spec, target):
+    def step(self, wave_or_spec, target, lengths=None):
         """wave (B,1,L) / (B,L) when a mel module was given, else a spectrogram (B,1,F,T).
-        Returns the loss as a 1-element device tensor (no host sync)."""
+        Returns the loss as a 1-element device tensor (no host sync).
+
+        ``lengths`` (a sequence of ints or a 1-D integer tensor, one entry per clip): a batch of clips of DIFFERENT lengths,
+        left-aligned and padded to the longest -- with a mel module zero-padded waveforms (B, L_max) / (B, 1, L_max) and SAMPLES per
+        clip, without one a padded spectrogram (B, 1, F, T_max) and FRAMES per clip (what lies behind a clip's frames is never
+        used and may be anything).  The step then runs the packed kernel sequence over the clips' own tokens: ``mel(wave,
+        lengths=)``, the ragged mixup below, ``passt_forward_varlen``, today's loss kernels, ``passt_backward_varlen``, and the same
+        callbacks as the fixed step -- clipping, accumulation, parameter groups, frozen prefixes, the per-bucket optimizer and the
+        reducer are reached through them and have no second form.  ``lengths=None``: the launch sequence and the RNG consumption of
+        the fixed step, untouched.
+
+        Mixup on a ragged batch (``use_mixup``): partner j = perm[i] and lam_i are drawn exactly as on the fixed path (one
+        ``torch.randperm(B)``, one ``np.random.beta(alpha, alpha, B)``, lam = max(lam, 1 - lam)), whatever the lengths.  The mixed clip
+        KEEPS ITS OWN LENGTH n_i; the partner is brought to it the way the reference's loaders bring every clip to one length
+        (pad_or_truncate): cut if it is longer, continued with silence if it is shorter, silence at the spectrogram level being the
+        constant ``mixup_pad`` (default: what the front end writes for a silent cell, (ln(1e-5) + 4.5) / 5):
+            t <  n_i :  out[i, f, t] = x[i, f, t] * lam_i + (x[j, f, t] if t < n_j else pad) * (1 - lam_i)
+            t >= n_i :  out[i, f, t] = 0.0 exactly
+        (ops.mixup_varlen; with all n_i equal to the row pitch it is ops.mixup bit for bit).  Targets have no time axis and mix as on
+        the fixed path; for loss="ce" the partner's label rides in pa_ce_mixup_fwd_bwd.  One difference from a waveform-level pad is
+        deliberate: the last frames of a shorter partner are the STFT of a reflect-padded clip end, not of a clip continued with
+        zeros, so the seam is not what padding the waveform would give.
+
+        RNG order of a ragged step: all front-end draws of the batch, clip after clip (preprocess.varlen_clip_draws; a mel module in
+        eval mode: its two ``randint`` per call); then ``randperm`` and ``beta``; then the Patchout draws, clip after clip
+        (passt.varlen_geometry_train).
+
+        Every check runs before the first draw and the first launch, so a rejected step consumes no random number and changes no
+        buffer: NotImplementedError for a net in training mode without ``net.varlen_train = True``, for a mel module in training mode
+        without ``mel.varlen_train = True``, and for an active ``drop_path_rate`` (the refusal of ``net(x, lengths=)``); the checks of
+        ``lengths`` (preprocess.checked_lengths for samples, the packed forward's for frames); the Patchout feasibility of every
+        clip (passt.check_patchout_varlen, on frames = 1 + (n - 1) // hop when ``lengths`` are samples).
+
+        graph=True: a step with ``lengths`` always runs the eager sequence, as a batch of another shape does (_graph_fits); a
+        captured graph stays valid for later fixed-shape steps."""
+        if lengths is not None:
+            return self._step_varlen(wave_or_spec, target, lengths)
         net = self.net
         x = wave_or_spec
         if self.mel is not None:
@@ -367,12 +412,20 @@ class TrainStep:
         if self.graph and self.t >= self.graph_warmup and self._graph_fits(x):
             return self._graph_step(x, y, perm_d if self.use_mixup else None, lam_d if self.use_mixup else None)
         logits, feat, ctx = passt_forward(net, x, save=self.plan)
+        return self._loss_backward_update(logits, ctx, y, perm_d if self.use_mixup else None, lam_d if self.use_mixup else None,
+                                          passt_backward)
+
+    def _loss_backward_update(self, logits, ctx, y, perm_d, lam_d, backward):
+        """What follows the forward, fixed or packed (``backward``: passt_backward / passt_backward_varlen): the loss kernel, the
+        backward with the per-bucket callbacks, and on an updating micro-step the launches that end the update.  ``perm_d`` / ``lam_d``:
+        the step's mixup draws on the device, None without mixup."""
+        net = self.net
         gs = 1.0 / (self.reducer.world * self.accumulate)
         if self.loss == "bce":
             loss, dlogits = ops.bce_fwd_bwd(logits, y, grad_scale=gs)
         else:
             y32 = y.to(torch.int32)
-            if self.use_mixup:
+            if perm_d is not None:
                 loss, dlogits = ops.ce_mixup_fwd_bwd(logits, y32, y32[perm_d.long()].contiguous(), lam_d, grad_scale=gs)
             else:
                 loss, dlogits = ops.ce_mixup_fwd_bwd(logits, y32, grad_scale=gs)
@@ -383,7 +436,7 @@ class TrainStep:
         # touched before the backward has finished).
         self._t_now = self.t + 1
         self._last = self._micro + 1 >= self.accumulate         # does this micro-step end with the update?
-        passt_backward(net, ctx, dlogits, None, self.grads, on_block_done=self._block_done)
+        backward(net, ctx, dlogits, None, self.grads, on_block_done=self._block_done)
         self._micro += 1
         if not self._last:
             return loss             # parameters, moments, staged copies and t untouched
@@ -392,6 +445,61 @@ class TrainStep:
         self._micro = 0
         self._params_updated()
         return loss
+
+    def _checked_varlen(self, x, lengths):
+        """Every check of a ragged step, none of which draws or launches: returns (the front end's input or the spectrogram, samples
+        per clip or None, frames per clip)."""
+        net, mel = self.net, self.mel
+        if net.training and not getattr(net, "varlen_train", False):
+            raise NotImplementedError("TrainStep.step(..., lengths=): a network in training mode takes a ragged batch only with the "
+                                      "switch net.varlen_train = True (every clip then gets the Patchout it would get alone at batch size 1)")
+        if mel is not None and mel.training and not mel.varlen_train:
+            raise NotImplementedError("TrainStep.step(..., lengths=): a front end in train mode takes a ragged batch only with the "
+                                      "switch mel.varlen_train = True (every clip then gets its own fmin / fmax jitter and masks)")
+        refuse_varlen_drop_path(net)
+        if mel is not None:
+            if x.dim() == 3:
+                x = x.reshape(-1, x.shape[2])
+            if x.dim() != 2:
+                raise ValueError(f"TrainStep.step(..., lengths=): expected (B, L_max) or (B, 1, L_max) waveforms, got {tuple(x.shape)}")
+            samples = checked_lengths(mel, lengths, *x.shape)
+            frames = [1 + (n - 1) // mel.hopsize for n in samples]
+            F, T = mel.n_mels, max(frames)
+        else:
+            x, _ = _checked_input(net, x, True)
+            if torch.is_tensor(lengths):
+                if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+                    raise ValueError("lengths must be a sequence of ints or a 1-D integer tensor")
+                lengths = lengths.tolist()
+            samples, frames = None, [int(v) for v in lengths]
+            if len(frames) != x.shape[0]:
+                raise ValueError(f"lengths has {len(frames)} entries for a batch of {x.shape[0]} clips")
+            F, T = x.shape[2], x.shape[3]
+        check_patchout_varlen(net, frames, _freq_rows(net, F), T_max=T)
+        return x, samples, frames
+
+    def _step_varlen(self, x, target, lengths):
+        """step() on a ragged batch (see there): front end, ragged mixup, packed forward, loss, packed backward, update."""
+        net = self.net
+        x, samples, frames = self._checked_varlen(x, lengths)
+        if self.mel is not None:
+            spec, _ = self.mel(x.contiguous().float(), lengths=samples)     # the front-end draws of the batch, clip after clip
+            x = spec.unsqueeze(1)
+        y = target.contiguous() if self.loss == "ce" else target.to(torch.float32).contiguous()
+        perm_d = lam_d = None
+        if self.use_mixup:
+            B = x.shape[0]
+            perm = torch.randperm(B)                                            # helpers/mixup.py:6, as on the fixed path
+            lam = np.random.beta(self.mixup_alpha, self.mixup_alpha, B).astype(np.float32)
+            lam = np.maximum(lam, 1.0 - lam)
+            perm_d = ops.upload_small(perm.to(torch.int32), x.device)
+            lam_d = ops.upload_small(lam, x.device)
+            lens_d = ops.upload_small(torch.tensor(frames, dtype=torch.int32), x.device)
+            x = ops.mixup_varlen(x, lens_d, perm_d, lam_d, self.mixup_pad)
+            if self.loss == "bce":
+                y = ops.mixup(y, perm_d, lam_d)
+        logits, feat, ctx = passt_forward_varlen(net, x, frames, save=self.plan)      # the Patchout draws, clip after clip
+        return self._loss_backward_update(logits, ctx, y, perm_d, lam_d, passt_backward_varlen)
 
     def _graph_fits(self, x):
         """The captured graph replays ONE batch shape.  The reference's loaders never set drop_last, so the last batch of an epoch
