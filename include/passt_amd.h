@@ -746,6 +746,37 @@ int pa_mixup_varlen(const float* x, const int32_t* lens, const int32_t* perm, co
  * noise (< 1e-7 of the amplitude). */
 int pa_wave_augment(const float* x, int B, int64_t ldx, const int32_t* len, const float* amp, const int32_t* shift,
                     const int32_t* partner, const float* lam, float* ws, float* out, int64_t L, void* stream);
+/* The same augmentation of a ragged batch (additive to ABI 6): row b of out has n_b = olen[b] samples of its own, and every clip
+ * gets what it would get alone -- pa_wave_augment run with L = n_b on the pair (b, partner[b]).  "Clip c as row b sees it" is gain,
+ * pad_or_truncate(n_b), roll(shift[c]), in that order:
+ *   m            = min(len[c], n_b)
+ *   s(t)         = (t - shift[c]) mod n_b                       true modulo: any sign, |shift| may exceed n_b
+ *   item(c|b)[t] = s(t) < m ? x[c][s(t)] * amp[c] : 0           0 <= t < n_b
+ *   mean(c|b)    = (amp[c] / n_b) * sum_{s < m} x[c][s]
+ *   not mixed (partner[b] < 0, or partner == NULL):  out[b][t] = item(b|b)[t]
+ *   mixed, p = partner[b], l = max(lam[b], 1 - lam[b]):
+ *                out[b][t] = (item(b|b)[t] - mean(b|b)) * l + (item(p|b)[t] - mean(p|b)) * (1 - l)
+ *   n_b <= t < L:  out[b][t] = 0.0f exactly
+ * The partner is cut to n_b or continued with zeros, rolled by ITS shift modulo n_b and centred by ITS mean over n_b samples (on a
+ * ragged batch a partner's mean depends on who mixes it in, so a mixed row has two means of its own).  partner[b] == b is legal; a
+ * partner's item is always its unmixed item (out is never an input); n_b = 0 gives a zero row.  As in pa_wave_augment the
+ * reference's last `x - x.mean()` is omitted.
+ *   x [B][ldx] f32; len (NULL: ldx), olen, shift (NULL: 0), partner (NULL: nothing mixed) int32 and amp (NULL: 1), lam f32 are DEVICE
+ *   arrays of B entries.  len is clamped to [0, ldx] and olen to [0, L] in the kernel; a partner[b] >= B is taken as "not mixed".
+ *   x[c][s] with s >= len[c] or s >= n_b is never read: a value there is chosen away, not multiplied by zero.
+ *   out [B][ldo] f32, ldo >= L: exactly out[b][0:L) is written for every row.  ws: f32 workspace of 2 * B floats (the two means of
+ *   every mixed row; needed with partner only).
+ * Two launches with a partner array (means: one 1024-thread block per mixed row and operand, each summing in pa_wave_augment's
+ * order -- thread i takes samples i, i + 1024, ..., then two 64-lane butterflies; unmixed rows cost nothing), one without.  The
+ * mix pass resolves every wrap once per row (shift mod n_b), so a roll is two contiguous source runs and no sample pays a division;
+ * sample indices are 32-bit; 16-byte stores from each row's first 16-byte boundary on, 4-byte stores on the at most three elements
+ * in front and behind, decided per row, so any ldo and any out pointer are legal.  Arithmetic per mixed sample: x * amp, the two
+ * subtractions, (item(p|b) - mean) * (1 - l), then ONE fused multiply-add -- five roundings, none of them left to the compiler.
+ * PA_EINVAL, nothing launched: x, out or olen NULL; B, ldx or L < 1; B > 65535; L > 2^31 - 1; ldo < L; partner without lam and ws;
+ * out == x. */
+int pa_wave_augment_varlen(const float* x, int B, int64_t ldx, const int32_t* len, const int32_t* olen, const float* amp,
+                           const int32_t* shift, const int32_t* partner, const float* lam, float* ws, float* out, int64_t ldo,
+                           int64_t L, void* stream);
 /* Device-impulse-response augmentation, the first branch of pydub_augment (audioset/dataset.py:103-112, same body in esc50 /
  * fsd50k / openmic): scipy.signal.convolve(waveform, ir, 'full') with one IR of a bank, then pad_or_truncate to L.  Causal, no
  * delay compensation; the tail behind the clip is kept, up to L.  Overlap-save FFT tiles held in registers and LDS (ir_conv.hip);

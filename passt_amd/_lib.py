@@ -146,6 +146,7 @@ SIGNATURES = {
     "pa_sgd": (i32, [vp, vp, i64, f32, vp]),
     "pa_swa_update": (i32, [vp, vp, i64, i32, vp]),
     "pa_wave_augment": (i32, [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "pa_wave_augment_varlen": (i32, [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp]),
     "pa_ir_conv_plan": (i32, [i32, C.POINTER(i32), C.POINTER(i32)]),
     "pa_ir_bank_floats": (i64, [i32, i32]),
     "pa_ir_bank_prepare": (i32, [vp, i32, i32, vp, vp, vp]),

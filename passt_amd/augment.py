@@ -87,10 +87,18 @@ class WaveAugment:
             return gain_db, shift, partner, lam, ir_idx
         return gain_db, shift, partner, lam
 
-    def __call__(self, raw, target=None, lengths=None, params=None):
+    def __call__(self, raw, target=None, lengths=None, params=None, ragged=False):
         """raw (B, ldx) f32 on the GPU (zero padded rows; ``lengths`` int32 valid samples per row).  ``params``: what ``draw``
-        returns, with or without ir_idx.  Returns (wave (B,1,L), mixed target or None)."""
+        returns, with or without ir_idx.  Returns (wave (B,1,L), mixed target or None).
+
+        ``ragged=True``: nothing is padded.  Clip b keeps ``n_b = min(lengths[b], clip_samples)`` samples and gets what it would
+        get alone, the fixed path run with ``clip_samples = n_b``: its roll wraps at n_b, its partner is cut to n_b or continued
+        with zeros, rolled by its own shift modulo n_b and centred by its mean over n_b samples (``pa_wave_augment_varlen``).
+        Returns (wave (B, 1, max n_b), exactly 0 behind every n_b; mixed target or None; n, the list of the n_b): the arguments of
+        ``TrainStep.step(wave, target, lengths=n)`` and ``mel(wave.squeeze(1), lengths=n)``.  ``lengths`` is required and read on
+        the host (a sequence of ints, a CPU tensor, or a device tensor, synced once); the draws are ``draw(B)``, unchanged."""
         B = raw.shape[0]
+        host, n = self._ragged_lengths(raw, lengths) if ragged else (None, None)     # refusals come before any draw or launch
         params = params if params is not None else self.draw(B)
         gain_db, shift, partner, lam = params[:4]
         ir_idx = np.asarray(params[4], np.int32) if len(params) > 4 else None
@@ -99,18 +107,50 @@ class WaveAugment:
         sh = torch.from_numpy(np.asarray(shift, np.int32)).to(dev)
         pt = torch.from_numpy(np.asarray(partner, np.int32)).to(dev)
         lm = torch.from_numpy(np.asarray(lam, np.float32)).to(dev)
-        if lengths is not None:
+        if ragged:
+            lengths = torch.tensor(host, dtype=torch.int32).to(dev)
+        elif lengths is not None:
             lengths = lengths.to(device=dev, dtype=torch.int32)
         raw = raw.contiguous().float()
+        L = max(n) if ragged else self.L
         if ir_idx is not None and (ir_idx >= 0).any():                         # convolve(waveform, ir, 'full'), :107
             if self.ir_bank is None:
                 raise ValueError("WaveAugment: params carry IR indices but no ir_bank was given")
             if int(ir_idx.max()) >= len(self.ir_bank):
                 raise ValueError(f"WaveAugment: IR index {int(ir_idx.max())} outside the bank of {len(self.ir_bank)}")
-            raw, lengths = ops.wave_ir_convolve(raw, self.L, lengths, torch.from_numpy(ir_idx).to(dev), self.ir_bank.spectra(dev))
-        wave = ops.wave_augment(raw, self.L, lengths, amp, sh, pt, lm)
+            raw, lengths = ops.wave_ir_convolve(raw, L, lengths, torch.from_numpy(ir_idx).to(dev), self.ir_bank.spectra(dev))
+        if ragged:                                                             # an IR's tail is cut at n_b, as at L on the fixed path
+            wave = ops.wave_augment_varlen(raw, L, lengths, torch.tensor(n, dtype=torch.int32).to(dev), amp, sh, pt, lm)
+        else:
+            wave = ops.wave_augment(raw, L, lengths, amp, sh, pt, lm)
         if target is not None:                                                 # y = w y1 + (1 - w) y2, :137
             w = np.where(np.asarray(partner) >= 0, np.maximum(lam, 1.0 - np.asarray(lam)), 1.0).astype(np.float32)
             perm = np.where(np.asarray(partner) >= 0, partner, np.arange(B)).astype(np.int32)
             target = ops.mixup(target.contiguous().float(), torch.from_numpy(perm).to(dev), torch.from_numpy(w).to(dev))
+        if ragged:
+            return wave.unsqueeze(1), target, n
         return wave.unsqueeze(1), target
+
+    @staticmethod
+    def _host_lengths(lengths):
+        if torch.is_tensor(lengths):
+            return [int(v) for v in lengths.detach().reshape(-1).cpu().tolist()]       # a device tensor: the one sync
+        return [int(v) for v in np.asarray(lengths).reshape(-1).tolist()]
+
+    def _ragged_lengths(self, raw, lengths):
+        """(lengths on the host, the output lengths n_b) of a ragged call, or ValueError: nothing is drawn, launched or written
+        before this returns."""
+        if lengths is None:
+            raise ValueError("WaveAugment(ragged=True) needs lengths: the valid samples of every clip")
+        if raw.dim() != 2:
+            raise ValueError(f"WaveAugment(ragged=True): raw must be (B, samples), got shape {tuple(raw.shape)}")
+        B, ldx = raw.shape
+        host = self._host_lengths(lengths)
+        if len(host) != B:
+            raise ValueError(f"WaveAugment(ragged=True): lengths holds {len(host)} entries for a batch of {B} clips")
+        for b, v in enumerate(host):
+            if v < 1:
+                raise ValueError(f"WaveAugment(ragged=True): clip {b} has length {v}; every clip needs at least one sample")
+            if v > ldx:
+                raise ValueError(f"WaveAugment(ragged=True): clip {b} has length {v}, raw holds {ldx} samples per row")
+        return host, [min(v, self.L) for v in host]

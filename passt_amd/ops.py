@@ -1601,6 +1601,29 @@ def wave_augment(x, L, lengths=None, amp=None, shift=None, partner=None, lam=Non
     return out
 
 
+def wave_augment_varlen(x, L, lengths=None, out_lengths=None, amp=None, shift=None, partner=None, lam=None):
+    """x [B][ldx] f32 raw clips -> [B][L]: row b is clip b after gain, pad/truncate, roll and waveform mixup AT ITS OWN LENGTH
+    out_lengths[b] (<= L), exactly 0 behind it (pa_wave_augment_varlen).  lengths (valid samples per row of x; None: ldx),
+    out_lengths, shift, partner int32 and amp, lam f32 are device tensors of B entries."""
+    if x.dim() != 2:
+        raise _lib.PasstAmdError(f"wave_augment_varlen: expected raw clips [B][ldx], got shape {tuple(x.shape)}")
+    B = x.shape[0]
+    if out_lengths is None:
+        raise _lib.PasstAmdError("wave_augment_varlen needs out_lengths (int32, one per clip)")
+    for name, t in (("lengths", lengths), ("out_lengths", out_lengths), ("amp", amp), ("shift", shift), ("partner", partner), ("lam", lam)):
+        if t is not None and t.numel() != B:
+            raise _lib.PasstAmdError(f"wave_augment_varlen: {name} has {t.numel()} entries for a batch of {B} clips")
+    if partner is not None and lam is None:
+        raise _lib.PasstAmdError("wave_augment_varlen: partner needs lam")
+    out = torch.empty((B, L), device=x.device, dtype=torch.float32)
+    ws = torch.empty(2 * B, device=x.device, dtype=torch.float32) if partner is not None else None
+    check(_lib.load().pa_wave_augment_varlen(_p(x, torch.float32, True), B, max(x.stride(0), x.shape[1]), _p(lengths, torch.int32),
+                                             _p(out_lengths, torch.int32), _p(amp, torch.float32), _p(shift, torch.int32),
+                                             _p(partner, torch.int32), _p(lam, torch.float32), _p(ws), _p(out), L, L, _stream()),
+          "pa_wave_augment_varlen")
+    return out
+
+
 IR_MAX_TAPS = 8192            # PA_IR_MAX_TAPS
 IRSpectra = collections.namedtuple("IRSpectra", "spectra ir_len n_ir max_taps")      # what ir_bank_prepare returns
 
