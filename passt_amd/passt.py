@@ -33,6 +33,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from . import ops
 from ._lib import EPI_DGELU, EPI_RESID, EPI_STORE, PA_BF16, PA_F32, PasstAmdError, compile_opaque
@@ -1647,6 +1648,27 @@ _LIVE = weakref.WeakSet()            # live PaSST instances: how passt_amd.optim
 _RUNTIME_ATTRS = ("_staged", "_scratch", "_ddp", "_gemm_flags", "_flat", "_last_dt")
 
 
+def _after_fused_step(opt, args, kwargs):
+    """torch's fused optimizers (``fused=True``: torch._fused_adamw_ and its kin) rewrite the parameters in place WITHOUT bumping
+    ``_version`` (tests/test_module_state_cpu.py pins it), so the staged weight copies cannot see their step: every live model
+    that has a copy of one of the optimizer's parameters gets the epoch bump ``mark_params_updated`` gives.  Every other torch
+    optimizer bumps the versions itself and costs one dict lookup per group here."""
+    if not any(g.get("fused") for g in opt.param_groups):
+        return
+    ids = None
+    for net in list(_LIVE):
+        cache = net._staged.cache
+        if not cache:
+            continue
+        if ids is None:
+            ids = {id(p) for g in opt.param_groups for p in g["params"]}
+        if any(key[0] in ids for key in cache):
+            net.mark_params_updated()
+
+
+register_optimizer_step_post_hook(_after_fused_step)
+
+
 class PaSST(nn.Module):
     """Same constructor as the reference (models/passt.py:391-395)."""
 
@@ -1842,7 +1864,14 @@ class PaSST(nn.Module):
                                   "reference's forward_features holds before it pools is forward(x, hidden=(\"norm\",))")
 
     def mark_params_updated(self):
-        """Call after updating parameters through raw device pointers (passt_amd.optim does)."""
+        """Every staged weight copy (the bf16 casts, the transposes the backward reads) is stale: the next forward re-makes them.
+        A copy is current while its parameter's ``(_version, data_ptr())`` and this model's epoch are unchanged, so whatever bumps
+        the version counter or moves the storage is seen without this call: torch optimizers (the ``fused=True`` ones through a
+        step hook), ``load_state_dict``, in-place operations on the parameter under ``torch.no_grad()`` or on ``p.detach()``,
+        ``nn.init.*``, ``p.data = tensor``, a replaced sub-module.  Call it after a write that does neither: an in-place operation on
+        ``p.data`` (``p.data.mul_()``, ``p.data.copy_()``), a write through ``TrainStep.flat_p`` or the flat buffer of a
+        ``passt_amd.optim.AdamW`` (restoring a checkpoint of either), a kernel given the raw device pointer (passt_amd.optim
+        calls it itself)."""
         self._staged.epoch += 1
 
     @compile_opaque

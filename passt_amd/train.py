@@ -227,12 +227,14 @@ class TrainStep:
     def _params_updated(self):
         """End of a step: every parameter changed (epoch bump: all staged copies stale) -- except that the copies the fused
         optimizer launches of this step rewrote are current."""
-        self.net.mark_params_updated()
         st = self.net._staged
         if self._frozen_ids:
-            # ... and so are the copies of the frozen weights: nothing wrote those parameters (one stale copy would make the next
-            # forward refresh every copy, the frozen ones included)
-            self._fresh += [k for k in st.cache if k[0] in self._frozen_ids]
+            # ... and so are the copies of the frozen weights that were current before the bump: the step wrote none of those
+            # parameters (one stale copy would make the next forward refresh every copy, the frozen ones included).  One that was
+            # NOT current stays stale: the caller wrote the weight since its copy was made -- between a folding micro-step and
+            # flush(), or while the network ran in the other precision
+            self._fresh += [k for k, ent in st.cache.items() if k[0] in self._frozen_ids and ent[0] == st._version(ent[2])]
+        self.net.mark_params_updated()
         if self._fresh:
             st.mark_fresh(self._fresh)
             self._fresh = []
