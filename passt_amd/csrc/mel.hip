@@ -886,164 +886,150 @@ extern "C" int pa_mel_num_frames(int L, int hop) { return (L < 2 || hop <= 0) ? 
 // alignment from the element index (b * ldw + i0), i.e. relative to `wave`: the base itself has to be 16-byte aligned (include/passt_amd.h)
 static bool wave_misaligned(const float* wave) { return ((uintptr_t)wave & 15) != 0; }
 
-extern "C" int pa_mel_frontend_fwd(const float* wave, int B, int L, const float* window, const float* bin_mel,
-                                   const float* twiddle, float* out, const pa_mel_params* p, void* stream) {
-    if (!wave || !window || !bin_mel || !twiddle || !out || !p || B <= 0) return PA_EINVAL;
-    if (wave_misaligned(wave)) return PA_EINVAL;
+// ---- the host side: one description of a call, one set of checks, one launcher.  The six entries differ in what they take. ----
+// A fixed-length call is the packed one without lengths: every row holds `pitch` = L valid samples and the frame count is the row's own.
+enum MelForm { MEL_FIXED, MEL_PACKED, MEL_PACKED_AUG };
+struct MelCall {
+    MelForm form;
+    const float* wave;
+    int B, pitch;                         // rows, and floats from one row to the next
+    const int32_t* lens;                  // packed forms: valid samples per row
+    int T_max;                            // packed forms: columns of an output row (frames of the longest clip)
+    const pa_mel_clip_params* clip;       // aug form: the per-clip table
+    const float *window, *bin_mel, *twiddle;
+    const pa_mel_params* p;
+    hipStream_t stream;
+};
+
+// What every entry refuses, in the order the return codes come out.  io0 / io1: the forward's `out` (twice) or the backward's
+// `dout` and `dwave`.
+static int mel_check(const MelCall& c, const void* io0, const void* io1) {
+    const pa_mel_params* p = c.p;
+    if (!c.wave || !c.window || !c.bin_mel || !c.twiddle || !io0 || !io1 || !p || c.B <= 0) return PA_EINVAL;
+    if (c.form != MEL_FIXED && (!c.lens || c.T_max <= 0)) return PA_EINVAL;
+    if (c.form == MEL_PACKED_AUG && !c.clip) return PA_EINVAL;
+    if (wave_misaligned(c.wave)) return PA_EINVAL;
     if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
-    if (L - 1 <= NFFT / 2) return PA_EUNSUPPORTED;          // reflect padding needs L-1 > n_fft/2 (torch.stft rule)
-    if (p->n_frames != pa_mel_num_frames(L, p->hop)) return PA_EINVAL;
-    // 16 frames per workgroup (64-byte output rows, three workgroups per CU).  Measured and not adopted (round 5,
-    // profiles/r05_mel_probe.txt): 8 frames per workgroup -- 125 us against 90 at B = 64, and for grids that leave CUs without
-    // their three workgroups (ESC-50 at batch 12: 384 workgroups) 23-29 us against 19: the per-workgroup set-up (4 us of a 14 us
-    // life) is amortised over half the frames
-    hipStream_t st = (hipStream_t)stream;
+    // reflect padding needs L-1 > n_fft/2 (torch.stft rule); packed: no row can hold a clip long enough for it
+    if (c.pitch - 1 <= NFFT / 2) return PA_EUNSUPPORTED;
+    const int fit = pa_mel_num_frames(c.pitch, p->hop);
+    if (c.form == MEL_FIXED ? p->n_frames != fit : (p->n_frames != c.T_max || c.T_max > fit)) return PA_EINVAL;
+    return PA_OK;
+}
+
+template <auto Kernel> static bool mel_lds_attr() {
+    static signed char state[64] = {0};           // per kernel: the attribute belongs to a kernel and a device
+    return lds_attr_on_this_device((const void*)Kernel, 160 * 1024, state);
+}
+// All six kernels begin (wave, pitch, window, bin_mel, twiddle); `tail` is what follows.  A device that refuses the LDS attribute
+// fails the launch loudly.
+template <auto Kernel, typename... Tail> static int mel_launch(const MelCall& c, dim3 grid, size_t lds, Tail... tail) {
+    (void)mel_lds_attr<Kernel>();
+    hipLaunchKernelGGL(Kernel, grid, dim3(MEL_WAVES * 64), lds, c.stream, c.wave, c.pitch, c.window, c.bin_mel, (const float2*)c.twiddle, tail...);
+    return check_launch();
+}
+
+// dynamic LDS of the forward: the span buffer (PERSIST: two, in whole 1 KiB DMA pieces), the waves' scratch, and the output tile, which
+// holds the two per-bin tables first (mel_frontend_body)
+static size_t mel_fwd_lds(int fr, bool persist, const pa_mel_params& p) {
+    const size_t span = (size_t)(fr - 1) * p.hop + NFFT;
+    const size_t span_bytes = persist ? 2 * (((span + 4) * 4 + 1023) & ~(size_t)1023) : (span * 4 + 15) & ~(size_t)15;
+    return span_bytes + MEL_WAVES * WAVE_SCRATCH + std::max<size_t>((size_t)p.n_mels * (fr + 1) * 4, 2 * NC * 4);
+}
+
+static int mel_fwd(const MelCall& c, float* out, float fill) {
+    if (const int rc = mel_check(c, out, out)) return rc;
+    const pa_mel_params& p = *c.p;
     // Round 6, measured and NOT adopted (profiles/r06_mel_persistent.txt): the PERSISTENT form -- resident workgroups walk tiles of 8
     // frames, set-up once per workgroup, the next tile's span requested by LDS-DMA into a second buffer while this one is transformed
     // (mel_frontend_kernel<., true>; needs an even hop and room for two span buffers).  97-104 us against 89-92: and with NEITHER the
     // span requests NOR the output stores it still takes 87 us, as does the one-tile form without its stores -- the launch is bound by
     // the frames themselves at three waves per SIMD (~3 400 cycles per frame and SIMD for ~260 VALU + ~75 LDS instructions: dependent
     // butterfly chains and four LDS round trips per frame), not by the per-workgroup set-up the round-5 model blamed.  PA_MEL_PERSIST=1
-    // selects it (A/B, parity-tested).
+    // selects it for the fixed-length forward (A/B, parity-tested).
     static const int persist_env = [] { const char* e = getenv("PA_MEL_PERSIST"); return e ? atoi(e) : 0; }();
-    if (persist_env && p->hop % 2 == 0) {
-        constexpr int FRP = FR_PERSIST;
-        const int spanp = (FRP - 1) * p->hop + NFFT;
-        const size_t span_bytes = ((size_t)(spanp + 4) * 4 + 1023) & ~(size_t)1023;
-        const size_t ldsp = 2 * span_bytes + MEL_WAVES * WAVE_SCRATCH + std::max<size_t>((size_t)p->n_mels * (FRP + 1) * 4, 2 * NC * 4);
-        if (ldsp <= 160 * 1024) {
-            static signed char lds_attr_p[64] = {0};
-            static int cus[64] = {0};
-            int dev = 0;
-            if (lds_attr_on_this_device((const void*)mel_frontend_kernel<FRP, true, false>, 160 * 1024, lds_attr_p) && hipGetDevice(&dev) == hipSuccess &&
-                dev >= 0 && dev < 64) {
-                if (cus[dev] == 0) {
-                    int n = 0;
-                    cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-                }
-                const int tiles_per_clip = (int)cdiv(p->n_frames, FRP);
-                const int64_t n_tiles = (int64_t)tiles_per_clip * B;
-                const int per_cu = (int)std::max<size_t>(1, (160 * 1024) / ldsp);
-                if (n_tiles < ((int64_t)1 << 31)) {
-                    const int grid = (int)std::min<int64_t>(n_tiles, (int64_t)cus[dev] * per_cu);
-                    hipLaunchKernelGGL((mel_frontend_kernel<FRP, true, false>), dim3((unsigned)grid), dim3(MEL_WAVES * 64), ldsp, st, wave, L, window, bin_mel,
-                                       (const float2*)twiddle, out, *p, tiles_per_clip, (int)n_tiles, (const int32_t*)nullptr, 0.f);
-                    return check_launch();
-                }
+    if (c.form == MEL_FIXED && persist_env && p.hop % 2 == 0) {
+        constexpr auto kernel = mel_frontend_kernel<FR_PERSIST, true, false>;
+        const size_t ldsp = mel_fwd_lds(FR_PERSIST, true, p);
+        static int cus[64] = {0};
+        int dev = 0;
+        if (ldsp <= 160 * 1024 && mel_lds_attr<kernel>() && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
+            if (cus[dev] == 0) {
+                int n = 0;
+                cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
+            }
+            const int tiles_per_clip = (int)cdiv(p.n_frames, FR_PERSIST);
+            const int64_t n_tiles = (int64_t)tiles_per_clip * c.B;
+            const int per_cu = (int)std::max<size_t>(1, (160 * 1024) / ldsp);
+            if (n_tiles < ((int64_t)1 << 31)) {
+                const int grid = (int)std::min<int64_t>(n_tiles, (int64_t)cus[dev] * per_cu);
+                return mel_launch<kernel>(c, dim3((unsigned)grid), ldsp, out, p, tiles_per_clip, (int)n_tiles, c.lens, 0.f);
             }
         }
     }
-    const int fr = FR_DEFAULT;
-    const int span = (fr - 1) * p->hop + NFFT;
-    const size_t lds = ((span * 4 + 15) & ~15) + MEL_WAVES * WAVE_SCRATCH +
-                       std::max<size_t>((size_t)p->n_mels * (fr + 1) * 4, 2 * NC * 4);
+    // 16 frames per workgroup (64-byte output rows, three workgroups per CU).  Measured and not adopted (round 5,
+    // profiles/r05_mel_probe.txt): 8 frames per workgroup -- 125 us against 90 at B = 64, and for grids that leave CUs without
+    // their three workgroups (ESC-50 at batch 12: 384 workgroups) 23-29 us against 19: the per-workgroup set-up (4 us of a 14 us
+    // life) is amortised over half the frames
+    const size_t lds = mel_fwd_lds(FR_DEFAULT, false, p);
     if (lds > 160 * 1024) return PA_EUNSUPPORTED;
-    static signed char lds_attr[64] = {0};
-    (void)lds_attr_on_this_device((const void*)mel_frontend_kernel<FR_DEFAULT, false, false>, 160 * 1024, lds_attr);
-    dim3 grid((unsigned)cdiv(p->n_frames, fr), (unsigned)B);
-    hipLaunchKernelGGL((mel_frontend_kernel<FR_DEFAULT, false, false>), grid, dim3(MEL_WAVES * 64), lds, st, wave, L, window, bin_mel,
-                       (const float2*)twiddle, out, *p, (int)cdiv(p->n_frames, fr), (int)(cdiv(p->n_frames, fr) * B), (const int32_t*)nullptr, 0.f);
-    return check_launch();
-}
-
-extern "C" int pa_mel_frontend_fwd_varlen(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
-                                          const float* twiddle, float* out, int T_max, float fill, const pa_mel_params* p, void* stream) {
-    if (!wave || !lens || !window || !bin_mel || !twiddle || !out || !p || B <= 0 || T_max <= 0) return PA_EINVAL;
-    if (wave_misaligned(wave)) return PA_EINVAL;
-    if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
-    if (ldw - 1 <= NFFT / 2) return PA_EUNSUPPORTED;        // no row can hold a clip long enough for the reflect padding
-    if (p->n_frames != T_max || T_max > pa_mel_num_frames(ldw, p->hop)) return PA_EINVAL;
-    const int fr = FR_DEFAULT;
-    const int span = (fr - 1) * p->hop + NFFT;
-    const size_t lds = ((span * 4 + 15) & ~15) + MEL_WAVES * WAVE_SCRATCH + std::max<size_t>((size_t)p->n_mels * (fr + 1) * 4, 2 * NC * 4);
-    if (lds > 160 * 1024) return PA_EUNSUPPORTED;
-    static signed char lds_attr[64] = {0};
-    (void)lds_attr_on_this_device((const void*)mel_frontend_kernel<FR_DEFAULT, false, true>, 160 * 1024, lds_attr);
-    dim3 grid((unsigned)cdiv(T_max, fr), (unsigned)B);
-    hipLaunchKernelGGL((mel_frontend_kernel<FR_DEFAULT, false, true>), grid, dim3(MEL_WAVES * 64), lds, (hipStream_t)stream, wave, ldw, window, bin_mel,
-                       (const float2*)twiddle, out, *p, (int)cdiv(T_max, fr), (int)(cdiv(T_max, fr) * B), lens, fill);
-    return check_launch();
-}
-
-// the packed forward with every clip's own filterbank edges and mask bands (clip[b]; the six per-clip fields of *p are not read)
-extern "C" int pa_mel_frontend_fwd_varlen_aug(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
-                                              const float* twiddle, float* out, int T_max, float fill, const pa_mel_params* p,
-                                              const pa_mel_clip_params* clip, void* stream) {
-    if (!wave || !lens || !window || !bin_mel || !twiddle || !out || !p || !clip || B <= 0 || T_max <= 0) return PA_EINVAL;
-    if (wave_misaligned(wave)) return PA_EINVAL;
-    if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
-    if (ldw - 1 <= NFFT / 2) return PA_EUNSUPPORTED;
-    if (p->n_frames != T_max || T_max > pa_mel_num_frames(ldw, p->hop)) return PA_EINVAL;
-    const int fr = FR_DEFAULT;
-    const int span = (fr - 1) * p->hop + NFFT;
-    const size_t lds = ((span * 4 + 15) & ~15) + MEL_WAVES * WAVE_SCRATCH + std::max<size_t>((size_t)p->n_mels * (fr + 1) * 4, 2 * NC * 4);
-    if (lds > 160 * 1024) return PA_EUNSUPPORTED;
-    static signed char lds_attr[64] = {0};
-    (void)lds_attr_on_this_device((const void*)mel_frontend_aug_kernel, 160 * 1024, lds_attr);
-    dim3 grid((unsigned)cdiv(T_max, fr), (unsigned)B);
-    hipLaunchKernelGGL(mel_frontend_aug_kernel, grid, dim3(MEL_WAVES * 64), lds, (hipStream_t)stream, wave, ldw, window, bin_mel,
-                       (const float2*)twiddle, out, *p, (int)cdiv(T_max, fr), (int)(cdiv(T_max, fr) * B), lens, fill, clip);
-    return check_launch();
+    const int tiles_per_clip = (int)cdiv(p.n_frames, FR_DEFAULT), n_tiles = (int)((int64_t)tiles_per_clip * c.B);
+    const dim3 grid((unsigned)tiles_per_clip, (unsigned)c.B);
+    if (c.form == MEL_FIXED) return mel_launch<mel_frontend_kernel<FR_DEFAULT, false, false>>(c, grid, lds, out, p, tiles_per_clip, n_tiles, c.lens, 0.f);
+    if (c.form == MEL_PACKED) return mel_launch<mel_frontend_kernel<FR_DEFAULT, false, true>>(c, grid, lds, out, p, tiles_per_clip, n_tiles, c.lens, fill);
+    return mel_launch<mel_frontend_aug_kernel>(c, grid, lds, out, p, tiles_per_clip, n_tiles, c.lens, fill, c.clip);
 }
 
 // samples one workgroup of the backward owns: whole hops, at least 16 frames' worth and at least 2048 (the frames in front of the run
 // that are transformed again are then at most half of the work, whatever the hop)
 static int mel_bwd_rows(int hop) { return hop * (int)std::max<int64_t>(FR_DEFAULT, cdiv(2 * NFFT, hop)); }
 
-template <bool VL>
-static int mel_bwd_launch(const float* wave, int B, int Lp, const int32_t* lens, const float* window, const float* bin_mel, const float* twiddle,
-                          const float* dout, float* dwave, const pa_mel_params* p, void* stream) {
-    const int rows = mel_bwd_rows(p->hop);
+// The overlap-add happens inside the workgroups (see mel_frontend_bwd_body): the entries' `workspace` is not used and may be NULL.
+static int mel_bwd(const MelCall& c, const float* dout, float* dwave) {
+    if (const int rc = mel_check(c, dout, dwave)) return rc;
+    const pa_mel_params& p = *c.p;
+    const int rows = mel_bwd_rows(p.hop);
     const size_t lds = MEL_WAVES * WAVE_SCRATCH + (size_t)(rows + 2 * NFFT + 4) * 4;
     if (lds > 160 * 1024) return PA_EUNSUPPORTED;
-    static signed char lds_attr[64] = {0};
-    (void)lds_attr_on_this_device((const void*)mel_frontend_bwd_kernel<VL>, 160 * 1024, lds_attr);
-    dim3 grid((unsigned)cdiv(Lp, rows), (unsigned)B);
-    hipLaunchKernelGGL((mel_frontend_bwd_kernel<VL>), grid, dim3(MEL_WAVES * 64), lds, (hipStream_t)stream, wave, Lp, window, bin_mel,
-                       (const float2*)twiddle, dout, dwave, *p, rows, lens);
-    return check_launch();
+    const dim3 grid((unsigned)cdiv(c.pitch, rows), (unsigned)c.B);
+    if (c.form == MEL_FIXED) return mel_launch<mel_frontend_bwd_kernel<false>>(c, grid, lds, dout, dwave, p, rows, c.lens);
+    if (c.form == MEL_PACKED) return mel_launch<mel_frontend_bwd_kernel<true>>(c, grid, lds, dout, dwave, p, rows, c.lens);
+    return mel_launch<mel_frontend_aug_bwd_kernel>(c, grid, lds, dout, dwave, p, rows, c.lens, c.clip);
 }
 
-// The overlap-add happens inside the workgroups (see mel_frontend_bwd_kernel): no workspace is needed, `workspace` may be NULL.
+extern "C" int pa_mel_frontend_fwd(const float* wave, int B, int L, const float* window, const float* bin_mel,
+                                   const float* twiddle, float* out, const pa_mel_params* p, void* stream) {
+    return mel_fwd(MelCall{MEL_FIXED, wave, B, L, nullptr, 0, nullptr, window, bin_mel, twiddle, p, (hipStream_t)stream}, out, 0.f);
+}
+
+extern "C" int pa_mel_frontend_fwd_varlen(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
+                                          const float* twiddle, float* out, int T_max, float fill, const pa_mel_params* p, void* stream) {
+    return mel_fwd(MelCall{MEL_PACKED, wave, B, ldw, lens, T_max, nullptr, window, bin_mel, twiddle, p, (hipStream_t)stream}, out, fill);
+}
+
+// the packed forward with every clip's own filterbank edges and mask bands (clip[b]; the six per-clip fields of *p are not read)
+extern "C" int pa_mel_frontend_fwd_varlen_aug(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
+                                              const float* twiddle, float* out, int T_max, float fill, const pa_mel_params* p,
+                                              const pa_mel_clip_params* clip, void* stream) {
+    return mel_fwd(MelCall{MEL_PACKED_AUG, wave, B, ldw, lens, T_max, clip, window, bin_mel, twiddle, p, (hipStream_t)stream}, out, fill);
+}
+
 extern "C" int pa_mel_frontend_bwd(const float* wave, int B, int L, const float* window, const float* bin_mel, const float* twiddle,
                                    const float* dout, float* dwave, void* workspace, int64_t workspace_bytes, const pa_mel_params* p, void* stream) {
     (void)workspace; (void)workspace_bytes;
-    if (!wave || !window || !bin_mel || !twiddle || !dout || !dwave || !p || B <= 0) return PA_EINVAL;
-    if (wave_misaligned(wave)) return PA_EINVAL;
-    if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
-    if (L - 1 <= NFFT / 2) return PA_EUNSUPPORTED;
-    if (p->n_frames != pa_mel_num_frames(L, p->hop)) return PA_EINVAL;
-    return mel_bwd_launch<false>(wave, B, L, nullptr, window, bin_mel, twiddle, dout, dwave, p, stream);
+    return mel_bwd(MelCall{MEL_FIXED, wave, B, L, nullptr, 0, nullptr, window, bin_mel, twiddle, p, (hipStream_t)stream}, dout, dwave);
 }
 
 extern "C" int pa_mel_frontend_bwd_varlen(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
                                           const float* twiddle, const float* dout, int T_max, float* dwave, void* workspace,
                                           int64_t workspace_bytes, const pa_mel_params* p, void* stream) {
     (void)workspace; (void)workspace_bytes;
-    if (!wave || !lens || !window || !bin_mel || !twiddle || !dout || !dwave || !p || B <= 0 || T_max <= 0) return PA_EINVAL;
-    if (wave_misaligned(wave)) return PA_EINVAL;
-    if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
-    if (ldw - 1 <= NFFT / 2) return PA_EUNSUPPORTED;
-    if (p->n_frames != T_max || T_max > pa_mel_num_frames(ldw, p->hop)) return PA_EINVAL;
-    return mel_bwd_launch<true>(wave, B, ldw, lens, window, bin_mel, twiddle, dout, dwave, p, stream);
+    return mel_bwd(MelCall{MEL_PACKED, wave, B, ldw, lens, T_max, nullptr, window, bin_mel, twiddle, p, (hipStream_t)stream}, dout, dwave);
 }
 
 extern "C" int pa_mel_frontend_bwd_varlen_aug(const float* wave, int B, int ldw, const int32_t* lens, const float* window, const float* bin_mel,
                                               const float* twiddle, const float* dout, int T_max, float* dwave, void* workspace,
                                               int64_t workspace_bytes, const pa_mel_params* p, const pa_mel_clip_params* clip, void* stream) {
     (void)workspace; (void)workspace_bytes;
-    if (!wave || !lens || !window || !bin_mel || !twiddle || !dout || !dwave || !p || !clip || B <= 0 || T_max <= 0) return PA_EINVAL;
-    if (wave_misaligned(wave)) return PA_EINVAL;
-    if (p->n_fft != NFFT || p->n_mels < 4 || p->n_mels > 128 || p->hop <= 0 || p->hop > NFFT) return PA_EUNSUPPORTED;
-    if (ldw - 1 <= NFFT / 2) return PA_EUNSUPPORTED;
-    if (p->n_frames != T_max || T_max > pa_mel_num_frames(ldw, p->hop)) return PA_EINVAL;
-    const int rows = mel_bwd_rows(p->hop);
-    const size_t lds = MEL_WAVES * WAVE_SCRATCH + (size_t)(rows + 2 * NFFT + 4) * 4;
-    if (lds > 160 * 1024) return PA_EUNSUPPORTED;
-    static signed char lds_attr[64] = {0};
-    (void)lds_attr_on_this_device((const void*)mel_frontend_aug_bwd_kernel, 160 * 1024, lds_attr);
-    dim3 grid((unsigned)cdiv(ldw, rows), (unsigned)B);
-    hipLaunchKernelGGL(mel_frontend_aug_bwd_kernel, grid, dim3(MEL_WAVES * 64), lds, (hipStream_t)stream, wave, ldw, window, bin_mel,
-                       (const float2*)twiddle, dout, dwave, *p, rows, lens, clip);
-    return check_launch();
+    return mel_bwd(MelCall{MEL_PACKED_AUG, wave, B, ldw, lens, T_max, clip, window, bin_mel, twiddle, p, (hipStream_t)stream}, dout, dwave);
 }

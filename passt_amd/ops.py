@@ -187,67 +187,80 @@ def _mel_wave(wave):
     return wave.clone() if wave.is_cuda and wave.is_contiguous() and wave.data_ptr() % 16 else wave
 
 
-def mel_frontend(wave, window, bin_mel, twiddle, params: MelParams):
+def _mel_begin(what, wave, lens_dev, clip_dev):
+    """Where both directions start.  ``lens_dev`` selects the packed form, ``clip_dev`` (with it) the per-clip form; ``what`` is the
+    fixed-length function's name, the messages and the C entry carry the form's suffix.  Returns (what, suffix, aligned wave)."""
+    if clip_dev is not None and lens_dev is None:
+        raise _lib.PasstAmdError(f"{what}: the per-clip table belongs to the packed form, lens_dev is missing")
+    form = ("_varlen" if lens_dev is not None else "") + ("_aug" if clip_dev is not None else "")
+    what += form
     wave = _mel_wave(wave)
+    if lens_dev is not None and (wave.dim() != 2 or lens_dev.dim() != 1 or lens_dev.numel() != wave.shape[0]):
+        raise _lib.PasstAmdError(f"{what}: wave {tuple(wave.shape)} needs one length per row, got {tuple(lens_dev.shape)}")
     B, L = wave.shape
-    out = torch.empty((B, params.n_mels, params.n_frames), device=wave.device, dtype=torch.float32)
-    _timed("mel", 4.0 * (B * L + out.numel()),
-           lambda: check(_lib.load().pa_mel_frontend_fwd(_p(wave, torch.float32), B, L, _p(window, torch.float32), _p(bin_mel, torch.float32),
-                                                         _p(twiddle, torch.float32), _p(out), C.byref(params), _stream()),
-                         "pa_mel_frontend_fwd"))
+    if clip_dev is not None:
+        _mel_clip_table(clip_dev, B, what)
+    return what, form, wave
+
+
+def _mel_launch(kind, work, entry, wave, tables, params, lens_dev, clip_dev, mid):
+    """entry(wave, B, pitch, [lens,] window, bin_mel, twiddle, mid()..., params, [clip,] stream), filed under ``kind``"""
+    fn = getattr(_lib.load(), entry)
+    B, L = wave.shape
+    window, bin_mel, twiddle = tables
+
+    def call():               # the arguments in the entry's order: _p() checks them left to right, _stream() comes last
+        return check(fn(_p(wave, torch.float32), B, *((L,) if lens_dev is None else (wave.stride(0), _p(lens_dev, torch.int32))),
+                        _p(window, torch.float32), _p(bin_mel, torch.float32), _p(twiddle, torch.float32), *mid(), C.byref(params),
+                        *(() if clip_dev is None else (_p(clip_dev, torch.uint8),)), _stream()), entry)
+    _timed(kind, work, call)
+
+
+def mel_forward(wave, tables, params: MelParams, lens_dev=None, clip_dev=None, fill=0.0):
+    """mel_frontend, mel_frontend_varlen (with ``lens_dev``) or mel_frontend_varlen_aug (with ``clip_dev`` as well); ``tables`` is
+    (window, bin_mel, twiddle)."""
+    _, form, wave = _mel_begin("mel_frontend", wave, lens_dev, clip_dev)
+    out = torch.empty((wave.shape[0], params.n_mels, params.n_frames), device=wave.device, dtype=torch.float32)
+    packed = () if lens_dev is None else (params.n_frames, float(fill))
+    _mel_launch("mel", 4.0 * (wave.numel() + out.numel()), "pa_mel_frontend_fwd" + form, wave, tables, params, lens_dev, clip_dev,
+                lambda: (_p(out),) + packed)
     return out
+
+
+def mel_backward(wave, tables, params: MelParams, dout, lens_dev=None, clip_dev=None):
+    """mel_frontend_bwd, mel_frontend_bwd_varlen or mel_frontend_bwd_varlen_aug, chosen as in mel_forward."""
+    what, form, wave = _mel_begin("mel_frontend_bwd", wave, lens_dev, clip_dev)
+    B = wave.shape[0]
+    if tuple(dout.shape) != (B, params.n_mels, params.n_frames):
+        raise _lib.PasstAmdError(f"{what}: dout {tuple(dout.shape)} for a ({B}, {params.n_mels}, {params.n_frames}) output")
+    dwave = torch.empty_like(wave)
+    packed = () if lens_dev is None else (params.n_frames,)
+    _mel_launch("mel_bwd", 4.0 * (2 * wave.numel() + dout.numel()), "pa_mel_frontend_bwd" + form, wave, tables, params, lens_dev, clip_dev,
+                lambda: (_p(dout, torch.float32),) + packed + (_p(dwave), None, 0))
+    return dwave
+
+
+def mel_frontend(wave, window, bin_mel, twiddle, params: MelParams):
+    return mel_forward(wave, (window, bin_mel, twiddle), params)
 
 
 def mel_frontend_varlen(wave, lens_dev, window, bin_mel, twiddle, params: MelParams, fill=0.0):
     """Ragged batch: wave (B, L_max) f32 with clips left-aligned, lens_dev (B,) int32 on the device (valid samples per row; the
     caller has checked 1 + n_fft/2 < len <= L_max on the host).  Returns (B, n_mels, params.n_frames); the frames behind a clip's
     own end hold ``fill``."""
-    wave = _mel_wave(wave)
-    if wave.dim() != 2 or lens_dev.dim() != 1 or lens_dev.numel() != wave.shape[0]:
-        raise _lib.PasstAmdError(f"mel_frontend_varlen: wave {tuple(wave.shape)} needs one length per row, got {tuple(lens_dev.shape)}")
-    B, L = wave.shape
-    out = torch.empty((B, params.n_mels, params.n_frames), device=wave.device, dtype=torch.float32)
-    _timed("mel", 4.0 * (B * L + out.numel()),
-           lambda: check(_lib.load().pa_mel_frontend_fwd_varlen(_p(wave, torch.float32), B, wave.stride(0), _p(lens_dev, torch.int32),
-                                                                _p(window, torch.float32), _p(bin_mel, torch.float32), _p(twiddle, torch.float32),
-                                                                _p(out), params.n_frames, float(fill), C.byref(params), _stream()),
-                         "pa_mel_frontend_fwd_varlen"))
-    return out
+    return mel_forward(wave, (window, bin_mel, twiddle), params, lens_dev, fill=fill)
 
 
 def mel_frontend_bwd(wave, window, bin_mel, twiddle, params: MelParams, dout):
     """Gradient of mel_frontend w.r.t. ``wave`` (B, L) f32 for the upstream gradient ``dout`` (B, n_mels, n_frames) f32; ``params`` is
     the forward call's (mask ranges included).  Nothing was saved: the spectrum is recomputed from the wave.  Deterministic."""
-    wave = _mel_wave(wave)
-    B, L = wave.shape
-    if tuple(dout.shape) != (B, params.n_mels, params.n_frames):
-        raise _lib.PasstAmdError(f"mel_frontend_bwd: dout {tuple(dout.shape)} for a ({B}, {params.n_mels}, {params.n_frames}) output")
-    dwave = torch.empty_like(wave)
-    _timed("mel_bwd", 4.0 * (2 * B * L + dout.numel()),
-           lambda: check(_lib.load().pa_mel_frontend_bwd(_p(wave, torch.float32), B, L, _p(window, torch.float32), _p(bin_mel, torch.float32),
-                                                         _p(twiddle, torch.float32), _p(dout, torch.float32), _p(dwave), None, 0,
-                                                         C.byref(params), _stream()),
-                         "pa_mel_frontend_bwd"))
-    return dwave
+    return mel_backward(wave, (window, bin_mel, twiddle), params, dout)
 
 
 def mel_frontend_bwd_varlen(wave, lens_dev, window, bin_mel, twiddle, params: MelParams, dout):
     """Gradient of mel_frontend_varlen w.r.t. ``wave`` (B, L_max): row i equals the clip's own gradient in its first lens[i] samples and
     is exactly 0 behind them; ``dout`` behind a clip's frames is not used."""
-    wave = _mel_wave(wave)
-    if wave.dim() != 2 or lens_dev.dim() != 1 or lens_dev.numel() != wave.shape[0]:
-        raise _lib.PasstAmdError(f"mel_frontend_bwd_varlen: wave {tuple(wave.shape)} needs one length per row, got {tuple(lens_dev.shape)}")
-    B, L = wave.shape
-    if tuple(dout.shape) != (B, params.n_mels, params.n_frames):
-        raise _lib.PasstAmdError(f"mel_frontend_bwd_varlen: dout {tuple(dout.shape)} for a ({B}, {params.n_mels}, {params.n_frames}) output")
-    dwave = torch.empty_like(wave)
-    _timed("mel_bwd", 4.0 * (2 * B * L + dout.numel()),
-           lambda: check(_lib.load().pa_mel_frontend_bwd_varlen(_p(wave, torch.float32), B, wave.stride(0), _p(lens_dev, torch.int32),
-                                                                _p(window, torch.float32), _p(bin_mel, torch.float32), _p(twiddle, torch.float32),
-                                                                _p(dout, torch.float32), params.n_frames, _p(dwave), None, 0,
-                                                                C.byref(params), _stream()),
-                         "pa_mel_frontend_bwd_varlen"))
-    return dwave
+    return mel_backward(wave, (window, bin_mel, twiddle), params, dout, lens_dev)
 
 
 def upload_mel_clips(clips, device):
@@ -272,38 +285,12 @@ def mel_frontend_varlen_aug(wave, lens_dev, clip_dev, window, bin_mel, twiddle, 
     """mel_frontend_varlen with every clip's own filterbank edges and SpecAugment bands: ``clip_dev`` is ops.upload_mel_clips' table
     (its six values replace params.mel_low / inv_mel_delta / fmask_* / tmask_*, which are not read; the caller guarantees finite
     mel_low and inv_mel_delta > 0).  The frames behind a clip's own end hold ``fill``, never the mask constant."""
-    wave = _mel_wave(wave)
-    if wave.dim() != 2 or lens_dev.dim() != 1 or lens_dev.numel() != wave.shape[0]:
-        raise _lib.PasstAmdError(f"mel_frontend_varlen_aug: wave {tuple(wave.shape)} needs one length per row, got {tuple(lens_dev.shape)}")
-    B, L = wave.shape
-    _mel_clip_table(clip_dev, B, "mel_frontend_varlen_aug")
-    out = torch.empty((B, params.n_mels, params.n_frames), device=wave.device, dtype=torch.float32)
-    _timed("mel", 4.0 * (B * L + out.numel()),
-           lambda: check(_lib.load().pa_mel_frontend_fwd_varlen_aug(_p(wave, torch.float32), B, wave.stride(0), _p(lens_dev, torch.int32),
-                                                                    _p(window, torch.float32), _p(bin_mel, torch.float32),
-                                                                    _p(twiddle, torch.float32), _p(out), params.n_frames, float(fill),
-                                                                    C.byref(params), _p(clip_dev, torch.uint8), _stream()),
-                         "pa_mel_frontend_fwd_varlen_aug"))
-    return out
+    return mel_forward(wave, (window, bin_mel, twiddle), params, lens_dev, clip_dev, fill)
 
 
 def mel_frontend_bwd_varlen_aug(wave, lens_dev, clip_dev, window, bin_mel, twiddle, params: MelParams, dout):
     """Gradient of mel_frontend_varlen_aug w.r.t. ``wave``; ``clip_dev`` is the forward call's table."""
-    wave = _mel_wave(wave)
-    if wave.dim() != 2 or lens_dev.dim() != 1 or lens_dev.numel() != wave.shape[0]:
-        raise _lib.PasstAmdError(f"mel_frontend_bwd_varlen_aug: wave {tuple(wave.shape)} needs one length per row, got {tuple(lens_dev.shape)}")
-    B, L = wave.shape
-    _mel_clip_table(clip_dev, B, "mel_frontend_bwd_varlen_aug")
-    if tuple(dout.shape) != (B, params.n_mels, params.n_frames):
-        raise _lib.PasstAmdError(f"mel_frontend_bwd_varlen_aug: dout {tuple(dout.shape)} for a ({B}, {params.n_mels}, {params.n_frames}) output")
-    dwave = torch.empty_like(wave)
-    _timed("mel_bwd", 4.0 * (2 * B * L + dout.numel()),
-           lambda: check(_lib.load().pa_mel_frontend_bwd_varlen_aug(_p(wave, torch.float32), B, wave.stride(0), _p(lens_dev, torch.int32),
-                                                                    _p(window, torch.float32), _p(bin_mel, torch.float32),
-                                                                    _p(twiddle, torch.float32), _p(dout, torch.float32), params.n_frames,
-                                                                    _p(dwave), None, 0, C.byref(params), _p(clip_dev, torch.uint8), _stream()),
-                         "pa_mel_frontend_bwd_varlen_aug"))
-    return dwave
+    return mel_backward(wave, (window, bin_mel, twiddle), params, dout, lens_dev, clip_dev)
 
 
 # ---- staging ---------------------------------------------------------------------------------

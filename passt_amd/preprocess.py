@@ -25,11 +25,7 @@ class _MelWaveGrad(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, window, bin_mel, twiddle, p, lens_dev, clip_dev):
         ctx.c = (x, window, bin_mel, twiddle, p, lens_dev, clip_dev)
-        if lens_dev is None:
-            return ops.mel_frontend(x, window, bin_mel, twiddle, p)
-        if clip_dev is not None:
-            return ops.mel_frontend_varlen_aug(x, lens_dev, clip_dev, window, bin_mel, twiddle, p, fill=0.0)
-        return ops.mel_frontend_varlen(x, lens_dev, window, bin_mel, twiddle, p, fill=0.0)
+        return ops.mel_forward(x, (window, bin_mel, twiddle), p, lens_dev, clip_dev, fill=0.0)
 
     @staticmethod
     @torch.autograd.function.once_differentiable          # create_graph=True is not supported: the gradient is a plain tensor
@@ -39,13 +35,7 @@ class _MelWaveGrad(torch.autograd.Function):
             raise RuntimeError("passt_amd.AugmentMelSTFT: the saved waveform of this forward was already consumed by a backward "
                                "pass (retain_graph / double backward are not supported: run the forward again)")
         x, window, bin_mel, twiddle, p, lens_dev, clip_dev = c
-        g = g.contiguous().float()
-        if lens_dev is None:
-            dx = ops.mel_frontend_bwd(x, window, bin_mel, twiddle, p, g)
-        elif clip_dev is not None:
-            dx = ops.mel_frontend_bwd_varlen_aug(x, lens_dev, clip_dev, window, bin_mel, twiddle, p, g)
-        else:
-            dx = ops.mel_frontend_bwd_varlen(x, lens_dev, window, bin_mel, twiddle, p, g)
+        dx = ops.mel_backward(x, (window, bin_mel, twiddle), p, g.contiguous().float(), lens_dev, clip_dev)
         return dx, None, None, None, None, None, None
 
 
@@ -166,6 +156,19 @@ class AugmentMelSTFT(nn.Module):
         self.register_buffer("_twiddle", tw.float().contiguous(), persistent=False)
         self.varlen_train = False       # True: train mode accepts lengths= (every clip its own jitter and masks, see forward)
 
+    def _params(self, fmin, fmax, n_frames):
+        """The MelParams of one launch: the filterbank between ``fmin`` and ``fmax``, ``n_frames`` output columns, no mask bands."""
+        p = MelParams()
+        p.n_fft, p.hop, p.n_mels, p.n_frames = self.n_fft, self.hopsize, self.n_mels, n_frames
+        p.preemph = 0.97
+        mel_low = 1127.0 * math.log(1.0 + fmin / 700.0)
+        mel_high = 1127.0 * math.log(1.0 + fmax / 700.0)
+        p.mel_low = mel_low
+        p.inv_mel_delta = (self.n_mels + 1) / (mel_high - mel_low)
+        p.log_eps, p.out_add, p.out_scale = 0.00001, 4.5, 1.0 / 5.0
+        p.fmask_start = p.fmask_end = p.tmask_start = p.tmask_end = 0
+        return p
+
     @compile_opaque                 # ONE opaque eager call under torch.compile, like PaSST.forward
     def forward(self, x, lengths=None):
         """x: (B, L) waveforms -> (B, n_mels, 1 + (L-1)//hop).
@@ -199,16 +202,7 @@ class AugmentMelSTFT(nn.Module):
         fmax = self.fmax + self.fmax_aug_range // 2 - torch.randint(self.fmax_aug_range, (1,)).item()
         if not self.training:
             fmin, fmax = self.fmin, self.fmax
-        p = MelParams()
-        p.n_fft, p.hop, p.n_mels = self.n_fft, self.hopsize, self.n_mels
-        p.n_frames = 1 + (L - 1) // self.hopsize
-        p.preemph = 0.97
-        mel_low = 1127.0 * math.log(1.0 + fmin / 700.0)
-        mel_high = 1127.0 * math.log(1.0 + fmax / 700.0)
-        p.mel_low = mel_low
-        p.inv_mel_delta = (self.n_mels + 1) / (mel_high - mel_low)
-        p.log_eps, p.out_add, p.out_scale = 0.00001, 4.5, 1.0 / 5.0
-        p.fmask_start = p.fmask_end = p.tmask_start = p.tmask_end = 0
+        p = self._params(fmin, fmax, 1 + (L - 1) // self.hopsize)
         if self.training:
             if isinstance(self.freqm, _AxisMasking):
                 p.fmask_start, p.fmask_end = self.freqm.draw(self.n_mels)                 # :81
@@ -229,15 +223,6 @@ class AugmentMelSTFT(nn.Module):
             raise ValueError("expected (batch, samples)")
         lengths = checked_lengths(self, lengths, *x.shape)
         x = x.contiguous().float()
-        p = MelParams()
-        p.n_fft, p.hop, p.n_mels = self.n_fft, self.hopsize, self.n_mels
-        p.preemph = 0.97
-        mel_low = 1127.0 * math.log(1.0 + self.fmin / 700.0)
-        mel_high = 1127.0 * math.log(1.0 + self.fmax / 700.0)
-        p.mel_low = mel_low
-        p.inv_mel_delta = (self.n_mels + 1) / (mel_high - mel_low)
-        p.log_eps, p.out_add, p.out_scale = 0.00001, 4.5, 1.0 / 5.0
-        p.fmask_start = p.fmask_end = p.tmask_start = p.tmask_end = 0
         clip_dev = None
         if self.training:
             # every clip its own draws, in the order of the batch-1 loop; the kernel reads them from the table, not from p
@@ -249,14 +234,13 @@ class AugmentMelSTFT(nn.Module):
             torch.randint(self.fmin_aug_range, (1,))
             torch.randint(self.fmax_aug_range, (1,))
             frames = [1 + (n - 1) // self.hopsize for n in lengths]
-        p.n_frames = max(frames)
+        p = self._params(self.fmin, self.fmax, max(frames))
         lens_dev = ops.upload_small(torch.tensor(lengths, dtype=torch.int32), x.device)
+        tables = (self._window_padded, self._bin_mel, self._twiddle)
         if torch.is_grad_enabled() and x.requires_grad:
-            spec = _MelWaveGrad.apply(x, self._window_padded, self._bin_mel, self._twiddle, p, lens_dev, clip_dev)
-        elif clip_dev is not None:
-            spec = ops.mel_frontend_varlen_aug(x, lens_dev, clip_dev, self._window_padded, self._bin_mel, self._twiddle, p, fill=0.0)
+            spec = _MelWaveGrad.apply(x, *tables, p, lens_dev, clip_dev)
         else:
-            spec = ops.mel_frontend_varlen(x, lens_dev, self._window_padded, self._bin_mel, self._twiddle, p, fill=0.0)
+            spec = ops.mel_forward(x, tables, p, lens_dev, clip_dev, fill=0.0)
         return spec, torch.tensor(frames, dtype=torch.int64)
 
     def extra_repr(self):
