@@ -1107,6 +1107,24 @@ static int launch_gemm_v(const gemm_kargs<RS>& a, hipStream_t st) {
 // operands of the K = 2304 / 3072 input-gradient GEMMs do not survive in the 256 MB Infinity Cache between producer and
 // consumer), and one K-tile of lead (~1.1-1.4 us) is less than a loaded HBM round trip: those GEMMs ran 21-23 % slower in
 // the step than alone on cache-resident data (profiles/r02_instep_vs_isolated.json).  Needs TM <= 3 (LDS) and >= 2 K-tiles.
+// K loop of the bf16 instantiations (r07): v_mfma_f32_16x16x32_bf16, four per 32x32 block and 32-wide k-substep, on an LDS image
+// with a swizzle of its own (pa_mma.h: swz_nt128, perm16); the 16x16 results are shuffled ONCE per work item into the 32x32
+// accumulator layout (acc32_from_16), so every epilogue runs as it did.  -DPA_NT_MFMA32 (make EXTRA=-DPA_NT_MFMA32) builds the
+// 32x32x16 loop instead: the A/B library, no runtime knob.  f32 operands keep 32x32x2f32.
+#ifdef PA_NT_MFMA32
+template <typename T> constexpr bool NT_MFMA16 = false;
+#else
+template <typename T> constexpr bool NT_MFMA16 = sizeof(T) == 2;
+#endif
+// L / M phase pairs per K-tile of the 16x16x32 loop: 4 = one 32-wide substep of HALF the wave tile's token rows per pair, the weight
+// fragments kept across the two pairs of a substep ((TM + 4) fragments live).  2 = one substep of the whole wave tile per pair
+// ((2 TM + 4) fragments): half the barriers, but 21.15 ms against 20.81 in the step (profiles/nt_mfma16.txt)
+static constexpr int NT16_PHASES = 4;
+template <typename T> __device__ __forceinline__ int nt_swz(int row) {
+    if constexpr (NT_MFMA16<T>) return swz_nt128(row);
+    else return swz_f128(row);
+}
+
 template <int TM, bool A3> struct StaggerGeom {
     static constexpr int TBM = 64 * TM, TBN = 256;
     static constexpr int A_BYTES = TBM * KB, B_BYTES = TBN * KB, STAGE_BYTES = A_BYTES + B_BYTES;   // 48/56/64 KiB
@@ -1192,7 +1210,7 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const gemm_kargs<e
         for (int i = 0; i < A_PER; ++i) {
             const int q = (wave * A_PER + i) * 64 + lane;
             const int row = q >> 3;
-            const int c = (q & 7) ^ swz_f128(row);
+            const int c = (q & 7) ^ nt_swz<T>(row);
             voffA[i] = (uint32_t)min(row, a.M - 1 - m0) * (uint32_t)(a.lda * (int)sizeof(T)) + c * 16;
         }
     };
@@ -1204,7 +1222,7 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const gemm_kargs<e
         for (int i = 0; i < 4; ++i) {
             const int q = (wave * 4 + i) * 64 + lane;
             const int row = q >> 3;
-            const int c = (q & 7) ^ swz_f128(row);
+            const int c = (q & 7) ^ nt_swz<T>(row);
             voffB[i] = (uint32_t)min(row, a.N - 1 - n0) * (uint32_t)(a.ldb * (int)sizeof(T)) + c * 16;
         }
     };
@@ -1231,6 +1249,17 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const gemm_kargs<e
     const int offA = (wr * (TM * 32) + (lane & 31)) * 128;
     const int offB = (wc * 64 + (lane & 31)) * 128;
     const int half = lane >> 5;
+    // 16x16x32 loop: a lane reads row rX of every 16-row group of a tile, chunk 4s + (lane>>4) in substep s.  The tile that feeds
+    // the MFMA's ROW operand (A; with TR the weights, B) is read with perm16-permuted rows.  Group bases are multiples of 16 rows,
+    // which swz_nt128 does not see: one address per operand and substep, the groups are immediate offsets
+    constexpr bool M16 = NT_MFMA16<T>;
+    const int rA16 = TR ? (lane & 15) : perm16(lane & 15), rB16 = TR ? perm16(lane & 15) : (lane & 15);
+    int offA16[2], offB16[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        offA16[s] = (wr * (TM * 32) + rA16) * 128 + (((4 * s + (lane >> 4)) ^ swz_nt128(rA16)) << 4);
+        offB16[s] = (wc * 64 + rB16) * 128 + (((4 * s + (lane >> 4)) ^ swz_nt128(rB16)) << 4);
+    }
 
     int round = 0;
     int m0, n0, split;
@@ -1257,10 +1286,19 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const gemm_kargs<e
         // the accumulators are NOT cleared: the first k-substep of an item issues its MFMAs with C = 0 (mma32_first), which
         // saves TM x 32 v_mov per wave and item in the seam between two items
         f32x16 acc[TM][2];
+        // 16x16x32 loop: the epilogue's per-lane constants (slab addresses, row / column offsets, ~60 registers) are derived from an
+        // opaque copy of the lane id, so they are recomputed per item instead of being hoisted out of the item loop and kept (or
+        // spilled) across the K loop, whose fragments need the room
+        int lane_e = lane;
+        if constexpr (M16) asm volatile("" : "+v"(lane_e));
         constexpr int AUX_EPI = USE_V2 ? EPI : PA_EPI_STORE;
         std::conditional_t<TR, V3Aux<AUX_EPI, TM, RS>, V2Aux<AUX_EPI, TM, BLK, RS>> aux;
         constexpr int AUXN = decltype(aux)::N;
         static_assert(V3Aux<AUX_EPI, TM, RS>::N == V2Aux<AUX_EPI, TM, false, RS>::N, "both epilogues leave the same number of loads in flight");
+        // AUX_LATE (16x16x32 loop; the 256-row tile, where 128 accumulators + 32 fragment + 32 auxiliary registers do not fit the register
+        // file, and the LDS-free residual epilogue with row factors):
+        // the auxiliary rows are requested right behind the K loop, when the fragment registers are free, instead of in its last K-tile
+        constexpr bool AUX_LATE = NT_MFMA16<T> && USE_V2 && AUXN > 0 && (TM == 4 || (TR && RS));
         const int cur_m0 = m0, cur_n0 = n0, cur_split = split;
         if (wr == 1) __builtin_amdgcn_s_barrier();         // group 1 runs one barrier behind
         PA_PROBE_STAMP(round < 24, round * 16);
@@ -1282,37 +1320,54 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const gemm_kargs<e
             // loads this wave may leave in flight at the end of the tile (vmcnt retires in issue order, so the youngest
             // ones are named by their count): with A3 the A request of tile t+2, and in the item's last tile the
             // epilogue's auxiliary rows.  Issue order within the tile: B, then A, then aux.
-            const int tail = (A3 && fetchA ? A_PER : 0) + (USE_V2 && AUXN > 0 && last ? AUXN : 0);
+            const int tail = (A3 && fetchA ? A_PER : 0) + (USE_V2 && AUXN > 0 && !AUX_LATE && last ? AUXN : 0);
             auto wait_tile = [&]() {
                 if (tail == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 else if (tail == A_PER) wait_vmcnt<A_PER>();
                 else if (tail == AUXN) wait_vmcnt<(AUXN > 0 ? AUXN : 1)>();
                 else wait_vmcnt<A_PER + AUXN>();
             };
-            // one 16-wide k-substep per L / M segment pair: 8 barriers per K-tile (two substeps and 4 barriers: +2.7 % on the step,
-            // profiles/r03_gemm_variants_ab.txt)
-            constexpr int NPH = 4;
+            // 32x32 loop: one 16-wide k-substep per L / M segment pair, 8 barriers per K-tile (two substeps and 4 barriers: +2.7 % on
+            // the step, profiles/r03_gemm_variants_ab.txt).  16x16x32 loop: NPH pairs of one 32-wide substep each (whole wave tile,
+            // or half its token rows).  The requests keep their place in the tile: DMA in its first quarter(s), auxiliary rows at
+            // its middle, the drain in its last pair
+            constexpr int NPH = M16 ? NT16_PHASES : 4;
+            static_assert(NPH == 2 || NPH == 4, "phase pairs per K-tile");
+            constexpr int PH_DMA1 = NPH == 2 ? 0 : 1;       // second request (the first is made in pair 0)
+            constexpr int PPS = NPH / 2;                    // 16x16x32: pairs per substep, NG 16-row token groups in each
+            constexpr int NG = 2 * TM / PPS;
+            bf16x8 fa16[NG], fb16[4];
 #pragma unroll
             for (int ph = 0; ph < NPH; ++ph) {
                 // ---------------- L segment ----------------
                 typename Frag<T>::type fa[TM], fb[2];
-                const int coff = ((ph * 2 + half) ^ rsw) << 4;
+                if constexpr (M16) {
+                    const int s = ph / PPS, g0 = (ph % PPS) * NG;
 #pragma unroll
-                for (int i = 0; i < TM; ++i) fa[i] = *(const typename Frag<T>::type*)(sA + offA + i * 32 * 128 + coff);
+                    for (int x = 0; x < NG; ++x) fa16[x] = *(const bf16x8*)(sA + offA16[s] + (g0 + x) * 16 * 128);
+                    if (ph % PPS == 0) {
 #pragma unroll
-                for (int j = 0; j < 2; ++j) fb[j] = *(const typename Frag<T>::type*)(sB + offB + j * 32 * 128 + coff);
+                        for (int b = 0; b < 4; ++b) fb16[b] = *(const bf16x8*)(sB + offB16[s] + b * 16 * 128);
+                    }
+                } else {
+                    const int coff = ((ph * 2 + half) ^ rsw) << 4;
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) fa[i] = *(const typename Frag<T>::type*)(sA + offA + i * 32 * 128 + coff);
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) fb[j] = *(const typename Frag<T>::type*)(sB + offB + j * 32 * 128 + coff);
+                }
                 // the next K-tile(s) are requested at least one full segment pair before they are waited for
                 if constexpr (A3) {
                     if (ph == 0 && fetchB) dmaB(ib ^ 1, stepB);
-                    if (ph == 1 && fetchA) dmaA(slotA, stepA);
+                    if (ph == PH_DMA1 && fetchA) dmaA(slotA, stepA);
                 } else {
                     if (ph == 0 && fetchA) dmaA(slotA, stepA);
-                    if (ph == 1 && fetchB) dmaB(ib ^ 1, stepB);
+                    if (ph == PH_DMA1 && fetchB) dmaB(ib ^ 1, stepB);
                 }
                 // last K-tile of the item: request the first auxiliary rows of its epilogue now, AFTER this tile's LDS-DMA:
                 // they land under the remaining MFMAs
                 if constexpr (USE_V2 && AUXN > 0) {
-                    if (last && ph == NPH / 2) aux.issue(a, cur_m0, cur_n0, wr, wc, lane, rowscale_of<RS>(a));
+                    if (!AUX_LATE && last && ph == NPH / 2) aux.issue(a, cur_m0, cur_n0, wr, wc, lane_e, rowscale_of<RS>(a));
                 }
                 if (ph == NPH - 1 && wr == 1) wait_tile();
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1324,7 +1379,28 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const gemm_kargs<e
                 // resolution overlaps the tail of the M segment, is 3..7 % SLOWER -- the tail MFMAs then share the SIMD's matrix
                 // pipe with the other group's first ones: profiles/r02_kloop_experiments.json)
                 // TR: the weight fragment is the MFMA's A operand: the accumulator holds the transposed block (lane = token)
-                if (ph == 0 && t == 0) {              // uniform: first substep of the item starts the accumulation chains
+                if constexpr (M16) {
+                    // 16-row token group a = 2 i + pa against weight group b = 2 j + qb: register slice 2 p + q of acc[i][j], where
+                    // (p, q) = (pa, qb), or (qb, pa) with TR (the weights are the MFMA's row operand)
+                    const int g0 = (ph % PPS) * NG;
+                    if (ph < PPS && t == 0) {         // uniform: first substep of the item starts the accumulation chains
+#pragma unroll
+                        for (int x = 0; x < NG; ++x)
+#pragma unroll
+                            for (int b = 0; b < 4; ++b) {
+                                const int ga = g0 + x, pa = ga & 1, qb = b & 1;
+                                mma16_slice<true>(acc[ga >> 1][b >> 1], TR ? 2 * qb + pa : 2 * pa + qb, TR ? fb16[b] : fa16[x], TR ? fa16[x] : fb16[b]);
+                            }
+                    } else {
+#pragma unroll
+                        for (int x = 0; x < NG; ++x)
+#pragma unroll
+                            for (int b = 0; b < 4; ++b) {
+                                const int ga = g0 + x, pa = ga & 1, qb = b & 1;
+                                mma16_slice<false>(acc[ga >> 1][b >> 1], TR ? 2 * qb + pa : 2 * pa + qb, TR ? fb16[b] : fa16[x], TR ? fa16[x] : fb16[b]);
+                            }
+                    }
+                } else if (ph == 0 && t == 0) {       // uniform: first substep of the item starts the accumulation chains
 #pragma unroll
                     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1344,7 +1420,14 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const gemm_kargs<e
             ib ^= 1;
             PA_PROBE_STAMP(round < 24 && t < 13, round * 16 + 1 + t);
         }
+        if constexpr (AUX_LATE) aux.issue(a, cur_m0, cur_n0, wr, wc, lane_e, rowscale_of<RS>(a));
         if (wr == 0) __builtin_amdgcn_s_barrier();         // re-align the two groups: every fragment read is done
+        if constexpr (M16) {     // 8 v_permlane16_swap per 32x32 block, in place: the accumulators the epilogues know
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc32_from_16(acc[i][j]);
+        }
         // slabs go into the ring slots that were read last (ia / ib now name the ones holding the next item's tile 0)
         const int freeA = ia == 0 ? NA - 1 : ia - 1, freeB = ib ^ 1;
         char* slab_c;
@@ -1370,27 +1453,27 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(const gemm_kargs<e
             const float* brow = HAS_BIAS && a.bias ? (const float*)(smem + G::BIAS_OFF) : nullptr;
             if constexpr (TR) {
                 (void)slab;
-                if constexpr (EPI == PA_EPI_RESID) gemm_epilogue_v3_resid<TM, RS>(a, acc, brow, cur_m0, cur_n0, wr, wc, lane, aux);
-                else gemm_epilogue_v3_bf16<EPI, TM>(a, acc, brow, cur_m0, cur_n0, wr, wc, lane, aux);
-            } else if constexpr (EPI == PA_EPI_RESID) gemm_epilogue_v2_resid<TM, RS>(a, acc, (char*)slab, brow, cur_m0, cur_n0, wr, wc, lane, aux);
-            else gemm_epilogue_v2_bf16<EPI, TM, BLK>(a, acc, (char*)slab, brow, cur_m0, cur_n0, wr, wc, lane, (cur_m0 / TBM) * 2 + wr, aux);
+                if constexpr (EPI == PA_EPI_RESID) gemm_epilogue_v3_resid<TM, RS>(a, acc, brow, cur_m0, cur_n0, wr, wc, lane_e, aux);
+                else gemm_epilogue_v3_bf16<EPI, TM>(a, acc, brow, cur_m0, cur_n0, wr, wc, lane_e, aux);
+            } else if constexpr (EPI == PA_EPI_RESID) gemm_epilogue_v2_resid<TM, RS>(a, acc, (char*)slab, brow, cur_m0, cur_n0, wr, wc, lane_e, aux);
+            else gemm_epilogue_v2_bf16<EPI, TM, BLK>(a, acc, (char*)slab, brow, cur_m0, cur_n0, wr, wc, lane_e, (cur_m0 / TBM) * 2 + wr, aux);
         } else if constexpr (EPI == PA_EPI_RESID || EPI == PA_EPI_PARTIAL) {
             (void)slab;
             gemm_epilogue_f32_direct<EPI, TM>(a, acc, HAS_BIAS && a.bias ? (const float*)(smem + G::BIAS_OFF) : nullptr, cur_m0,
-                                              cur_n0, cur_split, wr, wc, lane);
+                                              cur_n0, cur_split, wr, wc, lane_e);
         } else {
             float bias8[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) bias8[e] = 0.f;
             if constexpr (HAS_BIAS) {
                 if (a.bias) {
-                    const float* brow = (const float*)(smem + G::BIAS_OFF) + wc * 64 + (lane & 7) * 8;
+                    const float* brow = (const float*)(smem + G::BIAS_OFF) + wc * 64 + (lane_e & 7) * 8;
                     const f32x4 lo = *(const f32x4*)brow, hi = *(const f32x4*)(brow + 4);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { bias8[e] = lo[e]; bias8[4 + e] = hi[e]; }
                 }
             }
-            gemm_epilogue<T, EPI, TM>(a, acc, slab, cur_m0, cur_n0, cur_split, wr, wc, lane, bias8, (cur_m0 / TBM) * 2 + wr);
+            gemm_epilogue<T, EPI, TM>(a, acc, slab, cur_m0, cur_n0, cur_split, wr, wc, lane_e, bias8, (cur_m0 / TBM) * 2 + wr);
         }
         PA_PROBE_STAMP(round < 24, round * 16 + 15);
 #ifdef PA_PROBE

@@ -63,6 +63,43 @@ __device__ __forceinline__ void mma32_c<float>(f32x16& acc, const f32x4& a, cons
 // row of accumulator register r for this lane
 __device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
+// ---- 16x16x32 bf16 MFMA under the 32x32 accumulator layout (the NT role-split K loop) -----------------------------
+// v_mfma_f32_16x16x32_bf16: lane l supplies A[row l&15][k = 8(l>>4)..+8] and B[k = 8(l>>4)..+8][col l&15]; the result
+// sits at col = l&15, row = 4(l>>4) + reg.  A 32x32 block is four such products D[p][q] (row half p, column half q).
+// The lane that feeds row slot x = l&15 of the ROW operand reads tile row 16p + perm16(x) (perm16 swaps bits 2 and 3),
+// the column operand reads tile row 16q + (l&15) plainly.  Then D[p][q] register r of lane l holds
+//     col = 16q + (l&15),   row = 16p + perm16(4(l>>4) + r) = 16p + r + 8((l>>4)&1) + 4(l>>5)
+// and ONE v_permlane16_swap per (p, r) -- it exchanges the odd 16-lane rows of D[p][0][r] with the even 16-lane rows of
+// D[p][1][r] -- leaves the pair as registers 8p + r and 8p + 4 + r of the 32x32 accumulator (col = l&31, acc_row()).
+__device__ __forceinline__ int perm16(int x) { return (x & 3) | ((x & 4) << 1) | ((x & 8) >> 1); }
+
+// The four 16x16 results of a block live IN the 32x32 accumulator's registers: D[p][q] in registers 8p + 4q .. + 3, so the swap
+// of registers 8p + r and 8p + 4 + r finishes the block in place (no second generation of accumulators).
+// acc[4k .. 4k+3] += a * b  (FIRST: = a * b, the C operand is the inline constant 0)
+template <bool FIRST>
+__device__ __forceinline__ void mma16_slice(f32x16& acc, int k, const bf16x8& a, const bf16x8& b) {
+    f32x4 c = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (!FIRST) c = f32x4{acc[4 * k], acc[4 * k + 1], acc[4 * k + 2], acc[4 * k + 3]};
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[4 * k + e] = c[e];
+}
+__device__ __forceinline__ void acc32_from_16(f32x16& acc) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float x = acc[8 * p + r], y = acc[8 * p + 4 + r];
+            const auto s = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, x), __builtin_bit_cast(unsigned, y), false, false);
+            acc[8 * p + r] = __builtin_bit_cast(float, (unsigned)s[0]);
+            acc[8 * p + 4 + r] = __builtin_bit_cast(float, (unsigned)s[1]);
+        }
+}
+// XOR term of the NT role-split kernels' 128-byte-row LDS image: chunk c of row `row` lives at physical chunk
+// c ^ swz_nt128(row).  Conflict-free for the ds_read_b128 of both 16x16x32 operand patterns (16 rows x 4 chunks, rows plain
+// or perm16-permuted) and for the 32-rows-at-one-chunk pattern of the 32x32 operands; tools/emulate_nt_mfma16.py checks it.
+__device__ __forceinline__ int swz_nt128(int row) { return (row >> 1) & 7; }
+
 // LDS tile layouts.  A tile is [rows][ROWBYTES] with ROWBYTES = 128 (8 x 16-byte chunks) or 256
 // (16 chunks); chunk c of row `row` lives at physical chunk c ^ f(row).  f is chosen so that BOTH
 // access patterns of the MFMA operands are bank-conflict free (guide sec. 2 lane groups, T2, T10):
