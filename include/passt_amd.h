@@ -919,6 +919,36 @@ int pa_eval_rank(const uint32_t* keys, const uint8_t* state, int C, int64_t n, i
                  int64_t* n_neg, int64_t* auc_num, double* ap, double* auc, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sliding-window inference over long recordings (PaSST.forward_windows).  A window is (recording, first frame, frames) of a
+ * recording longer than the time embedding; all windows of all recordings run as ONE packed batch, a window taking the place a
+ * clip has in the packed entries above.  Three int32 arrays of W entries IN DEVICE MEMORY describe the windows: win_src[w] (row of
+ * x), win_t0[w] (first frame, ANY value >= 0: no multiple of the stride, no alignment), win_len[w] (frames).
+ * pa_patch_gather_windows: x[B][1][F][T_pitch] f32 (recordings left-aligned; T_pitch may be odd, nothing is assumed aligned) ->
+ *   cols[M][P*P] (dtype): cols[r][i*P+j] = x[win_src[w]][row_f[r]*fstride+i][win_t0[w] + row_t[r]*tstride + j], w = row_win[r].
+ *   row_win plays row_clip's role (cu_tok and the prefix rows index windows); row_f / row_t mean what they mean in
+ *   pa_patch_gather_varlen, a prefix row (row_f < 0) is all zeros.  An element is read only if its frame lies in
+ *   [win_t0[w], win_t0[w] + win_len[w]) -- what lies behind a window, and so behind a recording's length, is never addressed; an
+ *   element outside it, outside x, or of a window / recording index outside its array reads as 0.  pa_patch_pos_table_varlen,
+ *   the patch GEMM, the packed attention and the tail then run unchanged on the M rows.
+ *   PA_EINVAL: NULL pointers, a size or stride < 1, an unknown dtype; PA_EUNSUPPORTED: P * P > 1024.
+ * pa_window_pool: in[W][C] f32 (per-window rows), offsets[B + 1] int32 IN DEVICE MEMORY (recording b owns rows offsets[b] ..
+ *   offsets[b + 1] - 1, ascending, offsets[0] = 0, offsets[B] = W) -> out[B][C] f32.  mode PA_POOL_MEAN: the rows are added in row
+ *   order in f32 and divided by the recording's own count; PA_POOL_MAX: the maximum, started from the first row.  act
+ *   PA_POOL_ACT_SIGMOID pools the f32 1 / (1 + exp(-z)) of pa_eval_append instead of the values.  No atomics, one thread per
+ *   output: equal inputs give equal bits.  A recording with one window gets that row's values exactly.
+ *   PA_EINVAL: NULL pointers, W, C or B < 1, an unknown mode or act, and B > W (some recording would be empty).  The offsets
+ *   themselves are the caller's duty (the host cannot see them): rows outside [0, W) are not read, and a recording that is empty
+ *   all the same gets NaN. */
+#define PA_POOL_MEAN 0
+#define PA_POOL_MAX 1
+#define PA_POOL_ACT_NONE 0
+#define PA_POOL_ACT_SIGMOID 1
+int pa_patch_gather_windows(const float* x, int B, int F, int T_pitch, const int32_t* win_src, const int32_t* win_t0,
+                            const int32_t* win_len, int W, const int32_t* row_win, const int32_t* row_f, const int32_t* row_t, int M,
+                            int P, int fstride, int tstride, void* cols, int dtype, void* stream);
+int pa_window_pool(const float* in, int W, int C, const int32_t* offsets, int B, int mode, int act, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Data-parallel exchange step: gradient all-reduce over RCCL / xGMI, one communicator per process (= per GPU).
  * Replaces Lightning's DDP plugin (ex_audioset.py:488-489 -> torch DDP: NCCL all-reduce of gradient buckets from
  * autograd hooks; mean of the per-rank gradients).  Here the caller owns the buckets: contiguous slices of its flat

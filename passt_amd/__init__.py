@@ -6,8 +6,9 @@ Public surface mirrors the reference's two model modules:
 plus the caller glue of ex_audioset.py's training step (passt_amd.train) and the data-parallel
 gradient reducer (passt_amd.ddp).  All compute goes through libpasst_amd.so (include/passt_amd.h).
 """
-from .passt import PaSST, get_model, get_model_passt, get_ensemble_model, EnsembelerModel  # noqa: F401
+from .passt import PaSST, get_model, get_model_passt, get_ensemble_model, EnsembelerModel, Windows, window_geometry  # noqa: F401
 from .preprocess import AugmentMelSTFT  # noqa: F401
 from . import metrics  # noqa: F401     (passt_amd.metrics.EvalAccumulator: validation mAP / ROC-AUC on the device)
+from . import windows  # noqa: F401     (passt_amd.windows.tag: waveform -> front end once -> PaSST.forward_windows)
 
 __version__ = "0.1.0"

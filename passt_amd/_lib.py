@@ -154,6 +154,8 @@ SIGNATURES = {
     "pa_eval_append": (i32, [vp, vp, vp, i32, i32, i64, i64, i32, vp, vp, vp]),
     "pa_eval_ws_bytes": (i64, [i32, i64]),
     "pa_eval_rank": (i32, [vp, vp, i32, i64, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "pa_patch_gather_windows": (i32, [vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp]),
+    "pa_window_pool": (i32, [vp, i32, i32, vp, i32, i32, i32, vp, vp]),
     "pa_comm_unique_id": (i32, [vp]),
     "pa_comm_init": (i32, [vp, i32, i32, C.POINTER(vp)]),
     "pa_allreduce_bucket": (i32, [vp, vp, i64, i32, vp]),
@@ -169,6 +171,8 @@ GEMM_EPILOGUE_V3 = 0x1000     # run a pa_gemm_nt call with the LDS-free epilogue
 COMM_ID_BYTES = 128
 EVAL_SIGMOID, EVAL_RAW = 0, 1       # pa_eval_append mode
 EVAL_EXCLUDED, EVAL_NEG, EVAL_POS, EVAL_NAN = 0, 1, 2, 3      # its one-byte sample state
+POOL_MEAN, POOL_MAX = 0, 1          # pa_window_pool mode
+POOL_ACT_NONE, POOL_ACT_SIGMOID = 0, 1      # its act
 
 _lib = None
 

@@ -1387,6 +1387,50 @@ def patch_gather_varlen(x, row_clip, row_f, row_t, P, fstride, tstride, dtype):
     return cols
 
 
+def patch_gather_windows(x, win_src, win_t0, win_len, row_win, row_f, row_t, P, fstride, tstride, dtype):
+    """cols [M][P*P] for the packed token rows of sliding windows over the recordings x (B, 1, F, T): row r is the patch (row_f, row_t)
+    of window row_win[r] = (recording win_src, first frame win_t0, win_len frames), read in place; prefix rows zero.  All index arrays:
+    int32 on the device, (W,) per window and (M,) per token row."""
+    B, _, F, T = x.shape
+    W, M = win_src.numel(), row_f.numel()
+    if win_t0.numel() != W or win_len.numel() != W or W < 1:
+        raise _lib.PasstAmdError("patch_gather_windows: win_src / win_t0 / win_len must have one entry per window")
+    if row_win.numel() != M or row_t.numel() != M or M < 1:
+        raise _lib.PasstAmdError("patch_gather_windows: row_win / row_f / row_t must have one entry per token row")
+    cols = torch.empty((M, P * P), device=x.device, dtype=TORCH_DTYPE[dtype])
+    check(_lib.load().pa_patch_gather_windows(_p(x, torch.float32), B, F, T, _p(win_src, torch.int32), _p(win_t0, torch.int32),
+                                              _p(win_len, torch.int32), W, _p(row_win, torch.int32), _p(row_f, torch.int32),
+                                              _p(row_t, torch.int32), M, P, fstride, tstride, _p(cols), dtype, _stream()),
+          "pa_patch_gather_windows")
+    return cols
+
+
+def window_pool(rows, offsets, mode="mean", act=None):
+    """(W, C) f32 per-window rows -> (B, C): recording b pools its own rows offsets[b]:offsets[b + 1] (pa_window_pool: rows added in
+    row order in f32, the mean divided by the recording's own count, the max started from its first row).  ``offsets``: B + 1 HOST
+    integers (sequence / numpy / CPU tensor), checked here -- they start at 0, end at W and leave no recording empty (ValueError,
+    nothing launched).  ``mode``: "mean" / "max"; ``act``: None or "sigmoid" (pool the sigmoid of the rows)."""
+    if mode not in ("mean", "max"):
+        raise ValueError(f"window_pool: mode must be 'mean' or 'max', got {mode!r}")
+    if act not in (None, "sigmoid"):
+        raise ValueError(f"window_pool: act must be None or 'sigmoid', got {act!r}")
+    if torch.is_tensor(offsets) and offsets.is_cuda:
+        raise ValueError("window_pool: offsets are host integers (they are checked before the launch)")
+    off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    if rows.dim() != 2:
+        raise ValueError(f"window_pool: expected (windows, columns) rows, got {tuple(rows.shape)}")
+    W, Cc = rows.shape
+    if off.size < 2 or off[0] != 0 or off[-1] != W or (np.diff(off) < 1).any():
+        raise ValueError(f"window_pool: offsets must rise from 0 to the {W} rows with at least one row per recording, got {off.tolist()}")
+    B = off.size - 1
+    out = torch.empty((B, Cc), device=rows.device, dtype=torch.float32)
+    off_dev = upload_small(off.astype(np.int32), rows.device)
+    check(_lib.load().pa_window_pool(_p(rows, torch.float32), W, Cc, _p(off_dev, torch.int32), B,
+                                     _lib.POOL_MAX if mode == "max" else _lib.POOL_MEAN,
+                                     _lib.POOL_ACT_SIGMOID if act == "sigmoid" else _lib.POOL_ACT_NONE, _p(out), _stream()), "pa_window_pool")
+    return out
+
+
 def patch_pos_table_varlen(bias, time_pos, freq_pos, row_f, row_t, cls, dist, npe):
     """table [M][D] f32: positional rows + conv bias under the patch rows, cls / dist + their position rows under the prefix rows."""
     M, D = row_f.numel(), bias.numel()

@@ -1077,6 +1077,186 @@ def _passt_forward_varlen(model, x, lengths, save=False, hidden=None, attn=None,
     return _forward_trunk(model, lay, xs, dt, save, patch, hidden, attn, rollout)._replace(tok_offsets=tok_offsets)
 
 
+# --------------------------------------------------------------------------------------------
+# sliding windows over recordings longer than the time embedding (PaSST.forward_windows)
+# --------------------------------------------------------------------------------------------
+class Windows(NamedTuple):
+    """What forward_windows reports per window.  ``logits`` (W, C) / ``features`` (W, D): window w's outputs; ``offsets``: int64 CPU
+    tensor of B + 1 entries, recording b owns windows offsets[b]:offsets[b + 1]; ``start`` / ``length``: int64 CPU tensors of W
+    entries (frames); ``dropped``: list of (recording, start, length) -- the tail="short" windows shorter than one patch."""
+    logits: torch.Tensor
+    features: torch.Tensor
+    offsets: torch.Tensor
+    start: torch.Tensor
+    length: torch.Tensor
+    dropped: list
+
+
+def check_window_rule(window, hop, tail, P):
+    """The window rule's own refusals (ValueError): ``window`` >= one patch, 1 <= ``hop`` <= ``window``, ``tail`` "align" or "short"."""
+    if tail not in ("align", "short"):
+        raise ValueError(f"tail must be 'align' or 'short', got {tail!r}")
+    if isinstance(window, bool) or isinstance(hop, bool) or int(window) != window or int(hop) != hop:
+        raise ValueError(f"window and hop are whole numbers of frames, got window={window!r}, hop={hop!r}")
+    if window < P:
+        raise ValueError(f"window={window} frames is shorter than one patch ({P} frames)")
+    if hop < 1 or hop > window:
+        raise ValueError(f"hop={hop} must lie in 1 .. window={window} (a larger hop would skip frames)")
+
+
+def window_spans(n, window, hop, tail, P):
+    """The windows of ONE recording of ``n`` >= P frames: ([(start, length)], [(start, length) dropped]).  n <= window: the one
+    window [0, n).  Otherwise K = ceil((n - window) / hop) + 1 windows; "align": starts k * hop for k < K - 1 and the last at
+    n - window (every window full, every frame covered); "short": starts k * hop, lengths min(window, n - start), a last window
+    shorter than one patch dropped."""
+    if n <= window:
+        return [(0, n)], []
+    K = -(-(n - window) // hop) + 1
+    if tail == "align":
+        return [(k * hop, window) for k in range(K - 1)] + [(n - window, window)], []
+    spans = [(k * hop, min(window, n - k * hop)) for k in range(K)]
+    if spans[-1][1] < P:
+        return spans[:-1], spans[-1:]
+    return spans, []
+
+
+def _pack_windows(F_dim, P, tstride, win_src, win_t0, win_len):
+    """_pack_clips over windows: every window is a sequence of its own (cls, dist, F_dim x ((len - P) // tstride + 1) patches, the time
+    embedding from offset 0); ``row_clip`` is the window index.  Adds ``win_src`` / ``win_t0`` / ``win_len`` (int32)."""
+    T_eff = [(int(n) - P) // tstride + 1 for n in win_len]
+    grids = {t: kept_patches(F_dim, t, None, None, None) + (0,) for t in set(T_eff)}
+    g = _pack_clips(F_dim, T_eff, [grids[t] for t in T_eff])
+    g.update(T_eff=T_eff, win_src=np.asarray(win_src, dtype=np.int32), win_t0=np.asarray(win_t0, dtype=np.int32),
+             win_len=np.asarray(win_len, dtype=np.int32))
+    return g
+
+
+def window_geometry(lengths, window, hop, tail, P, tstride, F_dim):
+    """Host geometry of forward_windows: the windows of every recording (window_spans), recording after recording, as ONE packed
+    batch.  ``lengths``: valid frames per recording.  Returns _pack_clips' dictionary over the windows (``row_clip`` = the window of
+    a token row, ``row_f`` / ``row_t`` / ``cu_tok`` / ``max_N`` / ...) plus, per window, ``win_src`` (recording), ``win_t0`` (first frame),
+    ``win_len`` (frames) as int32 arrays, ``T_eff`` (patch columns), ``offsets`` (int64, B + 1: recording b owns windows
+    offsets[b]:offsets[b + 1]) and ``dropped`` ([(recording, start, length)], tail="short" only).  ValueError for a bad window rule
+    (check_window_rule), an empty batch, and the first recording shorter than one patch."""
+    check_window_rule(window, hop, tail, P)
+    window, hop = int(window), int(hop)
+    lens = [int(v) for v in lengths]
+    if not lens:
+        raise ValueError("lengths is empty")
+    src, t0, ln, dropped, offsets = [], [], [], [], [0]
+    for b, n in enumerate(lens):
+        if n < P:
+            raise ValueError(f"recording {b}: {n} frames are shorter than one patch ({P} frames): no window")
+        spans, gone = window_spans(n, window, hop, tail, P)
+        src += [b] * len(spans)
+        t0 += [s for s, _ in spans]
+        ln += [m for _, m in spans]
+        dropped += [(b, s, m) for s, m in gone]
+        offsets.append(len(src))
+    g = _pack_windows(F_dim, P, tstride, src, t0, ln)
+    g.update(offsets=np.asarray(offsets, dtype=np.int64), dropped=dropped)
+    return g
+
+
+def window_chunks(ntok, max_tokens):
+    """Windows in order into chunks of at most ``max_tokens`` packed tokens (None: one chunk); a single larger window is a chunk of
+    its own.  ``ntok``: tokens per window.  Returns [(first window, one past the last)]."""
+    if max_tokens is None:
+        return [(0, len(ntok))]
+    chunks, lo, used = [], 0, 0
+    for w, n in enumerate(ntok):
+        if w > lo and used + n > max_tokens:
+            chunks.append((lo, w))
+            lo, used = w, 0
+        used += n
+    chunks.append((lo, len(ntok)))
+    return chunks
+
+
+def check_window_call(model, x, lengths, window, hop, tail, pool, pool_of, max_tokens):
+    """Every refusal of forward_windows, on the host, before anything is launched or uploaded.  Returns (lengths as ints, window,
+    hop) with the defaults filled in: window = the model's img_size[1], hop = window // 2."""
+    if model.training:
+        raise NotImplementedError("PaSST.forward_windows: eval mode only (sliding windows are an inference entry; call net.eval())")
+    if pool not in ("mean", "max", None):
+        raise ValueError(f"pool must be 'mean', 'max' or None, got {pool!r}")
+    if pool_of not in ("logits", "sigmoid"):
+        raise ValueError(f"pool_of must be 'logits' or 'sigmoid', got {pool_of!r}")
+    if max_tokens is not None and (isinstance(max_tokens, bool) or int(max_tokens) != max_tokens or max_tokens < 1):
+        raise ValueError(f"max_tokens must be a positive int or None, got {max_tokens!r}")
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 1:
+        raise ValueError(f"PaSST.forward_windows expects (B, 1, n_mels, frames) recordings, got {tuple(getattr(x, 'shape', ()))}")
+    B, _, F, T = x.shape
+    P, ts = model.patch_embed.patch_size[0], model.patch_embed.stride[1]
+    if window is None:
+        window = model.patch_embed.img_size[1]
+    if hop is None:
+        hop = window // 2
+    check_window_rule(window, hop, tail, P)
+    Tpe = model.time_new_pos_embed.shape[-1]
+    if (window - P) // ts + 1 > Tpe:
+        raise ValueError(f"window={window} frames has {(window - P) // ts + 1} patch columns, more than the time embedding's {Tpe}: "
+                         "windows are never cut")
+    if lengths is None:
+        lengths = [T] * B
+    elif torch.is_tensor(lengths):
+        if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+            raise ValueError("lengths must be a sequence of ints or a 1-D integer tensor")
+        lengths = lengths.tolist()
+    lengths = [int(v) for v in lengths]
+    if len(lengths) != B:
+        raise ValueError(f"lengths has {len(lengths)} entries for a batch of {B} recordings")
+    for b, n in enumerate(lengths):
+        if n > T:
+            raise ValueError(f"recording {b}: length {n} exceeds the input's {T} frames")
+    return lengths, int(window), int(hop)
+
+
+def pool_windows(logits, features, offsets, pool, pool_of):
+    """Per-window (W, C) logits and (W, D) features -> per-recording (B, C), (B, D): one pa_window_pool launch each.  ``pool_of`` =
+    "sigmoid" pools sigmoid(logits); the features are always pooled raw.  ``pool`` None: the per-window tensors themselves."""
+    if pool is None:
+        return logits, features
+    return (ops.window_pool(logits, offsets, pool, "sigmoid" if pool_of == "sigmoid" else None),
+            ops.window_pool(features, offsets, pool, None))
+
+
+def _passt_forward_windows(model, x, lengths, window, hop, tail, max_tokens):
+    """Kernel sequence of forward_windows behind check_window_call: per chunk one upload of the index arrays, the window gather, the
+    packed positional table, the patch GEMM and _forward_trunk on a _PackedLayout whose sequences are the windows.  Returns a
+    Windows with the per-window outputs."""
+    P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
+    F_dim = _freq_rows(model, x.shape[2])
+    g = window_geometry(lengths, window, hop, tail, P, ts, F_dim)
+    ntok = np.diff(g["cu_tok"].astype(np.int64))
+    chunks = window_chunks(ntok.tolist(), max_tokens)
+    x, dt = _checked_input(model, x, False)
+    lo_parts, fe_parts = [], []
+    with torch.no_grad(), ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
+        for lo, hi in chunks:
+            c = g if len(chunks) == 1 else _pack_windows(F_dim, P, ts, g["win_src"][lo:hi], g["win_t0"][lo:hi], g["win_len"][lo:hi].tolist())
+            cu, M = c["cu_tok"], c["row_f"].size
+            # one upload: [row_win | row_f | row_t | cu_tok | prefix rows | win_src | win_t0 | win_len]
+            parts = {k: c[k] for k in ("row_clip", "row_f", "row_t", "cu_tok")}
+            parts["pidx"] = (cu[:-1, None] + np.arange(2, dtype=np.int32)[None, :]).reshape(-1).astype(np.int32)
+            parts.update((k, c[k]) for k in ("win_src", "win_t0", "win_len"))
+            d = _upload_parts(parts, x.device)
+            # the packed path of _passt_forward_varlen from here on: only the gather knows that a sequence is a window
+            cols = ops.patch_gather_windows(x, d["win_src"], d["win_t0"], d["win_len"], d["row_clip"], d["row_f"], d["row_t"], P, fs, ts, dt)
+            table = ops.patch_pos_table_varlen(model.patch_embed.proj.bias, model.time_new_pos_embed, model.freq_new_pos_embed, d["row_f"],
+                                               d["row_t"], model.cls_token, model.dist_token, model.new_pos_embed)
+            xs = torch.empty((M, model.embed_dim), device=x.device, dtype=torch.float32)
+            ops.gemm_nt(cols, model._staged.get(model.patch_embed.proj.weight, dt, False), dt, EPI_RESID, resid=table, out_f32=xs)
+            lay = _PackedLayout(hi - lo, M, c["max_N"], d["cu_tok"], d["pidx"], ntok=ntok[lo:hi])
+            r = _forward_trunk(model, lay, xs, dt, False, None)
+            lo_parts.append(r.logits)
+            fe_parts.append(r.feat)
+    logits = lo_parts[0] if len(lo_parts) == 1 else torch.cat(lo_parts)
+    feat = fe_parts[0] if len(fe_parts) == 1 else torch.cat(fe_parts)
+    return Windows(logits, feat, torch.from_numpy(g["offsets"].copy()), torch.from_numpy(g["win_t0"].astype(np.int64)),
+                   torch.from_numpy(g["win_len"].astype(np.int64)), list(g["dropped"]))
+
+
 class _NoRowJobs(list):
     """``defer`` sink of the no-weight-gradients backward: deferred row reductions are dropped, nothing finishes them."""
 
@@ -2067,6 +2247,42 @@ class PaSST(nn.Module):
             roll.target = res[2 + (hid is not None) + (amap is not None)]
         return res
 
+    @compile_opaque                 # one opaque eager call under torch.compile, like forward
+    def forward_windows(self, x, lengths=None, *, window=None, hop=None, tail="align", pool="mean", pool_of="logits", max_tokens=None):
+        """Sliding-window inference over recordings longer than the time embedding: -> (logits, features, win).
+
+        ``x`` (B, 1, n_mels, T_max): B recordings, left-aligned; ``lengths``: frames per recording (sequence of ints or 1-D integer
+        tensor; None = all of them T_max).  What lies behind a recording's length is never read.  Eval mode only
+        (NotImplementedError in training mode); the outputs carry no grad_fn, like the default ragged forward; the precision is
+        ``forward``'s (``precision`` / autocast).
+
+        ``window`` (frames, default img_size[1]) and ``hop`` (default window // 2): a recording of n frames gets, for n <= window,
+        the one window [0, n); otherwise K = ceil((n - window) / hop) + 1 windows.  ``tail`` = "align": starts k * hop for
+        k < K - 1 and the last window at n - window -- every window is full and every frame is covered; "short": starts k * hop
+        with lengths min(window, n - start), a last window shorter than one patch is dropped and listed in ``win.dropped``.  The
+        hop is free: no multiple of the patch stride is asked for.  ValueError: window < one patch, hop < 1 or > window, a window
+        with more patch columns than the time embedding (windows are never cut and never warn), a recording shorter than one
+        patch or longer than T_max.  Every refusal comes before anything is launched.
+
+        Window w of recording b gets what ``net(x[b:b+1, :, :, s:e])`` returns alone at batch size 1 in eval mode (time embedding
+        from offset 0).  No unfolded copy is made: the patch gather reads every window in place (pa_patch_gather_windows), and all
+        windows of all recordings run as ONE packed sequence through the kernels of ``net(x, lengths=)``; for the same windows the
+        outputs equal ``net(unfolded, lengths=win.length)`` bit for bit.
+
+        ``win`` (Windows): ``logits`` (W, C), ``features`` (W, D) per window; ``offsets`` (int64 CPU, B + 1): recording b owns
+        windows offsets[b]:offsets[b + 1]; ``start`` / ``length`` (int64 CPU, W, frames); ``dropped``: [(recording, start, length)].
+
+        ``pool`` "mean" / "max": the returned logits (B, C) and features (B, D) are pooled over each recording's own windows on
+        the device (pa_window_pool: f32, rows in order, deterministic); ``pool_of`` = "sigmoid" pools sigmoid(logits) instead of
+        the logits, the features are always pooled raw.  ``pool`` None returns the per-window tensors in their place.
+
+        ``max_tokens``: None = one packed pass.  Otherwise the windows go, in order, into chunks of at most that many packed
+        tokens (a single larger window is its own chunk), one packed pass per chunk: the same ``win`` geometry, outputs equal to the
+        unchunked call within rounding (the GEMM plans depend on the row count), not bit for bit."""
+        lengths, window, hop = check_window_call(self, x, lengths, window, hop, tail, pool, pool_of, max_tokens)
+        win = _passt_forward_windows(self, x, lengths, window, hop, tail, max_tokens)
+        return pool_windows(win.logits, win.features, win.offsets, pool, pool_of) + (win,)
+
     def _outputs(self, r, hid, amap):
         """A forward's record in forward()'s shape: (logits, features[, [token outputs]][, [attention maps]][, tok_offsets]); a packed
         batch's maps (one flat buffer each) are cut into the clips' views here."""
@@ -2194,6 +2410,24 @@ class EnsembelerModel(nn.Module):
             all_out = out if all_out is None else out + all_out
         all_out = all_out / len(self.models)
         return all_out, all_out
+
+    def forward_windows(self, x, lengths=None, *, window=None, hop=None, tail="align", pool="mean", pool_of="logits", max_tokens=None):
+        """PaSST.forward_windows for the ensemble, mirroring ``forward``: the mean of the members' per-window logits, pooled
+        afterwards; as there, the second output repeats the first (``win.features`` is ``win.logits``).  ``window`` / ``hop``
+        default to the first member's; every member must accept the rule, all refusals come before the first launch."""
+        if window is None:
+            window = self.models[0].patch_embed.img_size[1]
+        if hop is None:
+            hop = window // 2
+        for m in self.models:
+            check_window_call(m, x, lengths, window, hop, tail, pool, pool_of, max_tokens)
+        all_out = win = None
+        for m in self.models:
+            _, _, win = m.forward_windows(x, lengths, window=window, hop=hop, tail=tail, pool=None, max_tokens=max_tokens)
+            all_out = win.logits if all_out is None else win.logits + all_out
+        all_out = all_out / len(self.models)
+        win = win._replace(logits=all_out, features=all_out)
+        return pool_windows(all_out, all_out, win.offsets, pool, pool_of) + (win,)
 
 
 def get_ensemble_model(arch_list=[], *, pretrained=True):
