@@ -556,6 +556,34 @@ int64_t pa_attention_bwd_ws_floats(int B, int H, int nq);
 int pa_attention_bwd(const void* qkv, int ldqkv, const void* o, const void* d_o, int ldo,
                      const float* lse, float* delta, void* dqkv, int lddqkv, int B, int H, int N, int nq,
                      float scale, int dtype, int flags, void* stream);
+/* ---- attention dropout (additive: the ABI version stays 6) ----
+ * Dropout on the attention probabilities (the reference's attn_drop, models/passt.py:343-361) inside the fused forward and backward.
+ * The mask is a pure function of a 64-bit seed and the element's position (csrc/pa_dropout.h).  t = round(256 p), 1 <= t <= 255: the
+ * rate actually applied is p_eff = t / 256, keep = 1 - p_eff, kept probabilities are scaled by 1 / keep.  Element (site, s = b*H + h,
+ * query q, key k), q and k the indices inside the sequence:
+ *     R    = philox4x32_10(counter = (k >> 2, q >> 2, s, site), key = (seed[0], seed[1]))   (multipliers D2511F53 / CD9E8D57,
+ *     byte = (R[q & 3] >> (8 * (k & 3))) & 0xff                                               key increments 9E3779B9 / BB67AE85)
+ *     kept <=> byte >= t
+ * site: the caller's name for the dropout site (the block index; values >= 65536 are reserved).
+ * pa_attention_fwd_dropout: pa_attention_fwd's arguments and layouts (nq < N included) plus seed (TWO words in DEVICE memory: no host
+ *   value enters the kernel, the launch can be captured in a graph), site and t.  lse and the row sum are those of the undropped
+ *   softmax, bit-identical to pa_attention_fwd on the same operands; a dropped probability is selected to zero in front of the P V
+ *   product and o = acc / (l * keep): a row whose keys are all dropped is exactly 0.
+ * pa_attention_bwd_dropout: pa_attention_bwd's arguments plus the same three; o and lse from pa_attention_fwd_dropout with the same
+ *   seed / site / t.  With D = kept / keep: dP = D (dO V^T), dS = P (dP - delta), delta = rowsum(dO o) from the stored o,
+ *   dV = (P D)^T dO, dQ / dK from dS (a dropped element has dS = -P delta, not 0).  Always the dQ + dK/dV kernel pair; the
+ *   PA_ATTN_BWD_* form flags are accepted and ignored, the result is bit-identical whichever are given.  Workspace and the Q third
+ *   of rows q >= nq as for pa_attention_bwd.
+ * PA_EINVAL before anything is launched: seed == NULL, t outside 1..255, and everything the plain entries refuse.  The packed
+ * (_varlen) entries have no dropout form.
+ * pa_attention_dropout_mask: HOST only, touches no device: keep_out[(s*nq + q)*N + k] = 1 (kept) or 0 for s < BH, q < nq, k < N,
+ *   from the same rule the kernels compile.  PA_EINVAL: keep_out == NULL, BH / nq / N <= 0, nq > N, t outside 1..255. */
+int pa_attention_fwd_dropout(const void* qkv, int ldqkv, void* o, int ldo, float* lse, int B, int H, int N, int nq, float scale, int dtype,
+                             int flags, const uint32_t* seed, uint32_t site, int t, void* stream);
+int pa_attention_bwd_dropout(const void* qkv, int ldqkv, const void* o, const void* d_o, int ldo, const float* lse, float* delta,
+                             void* dqkv, int lddqkv, int B, int H, int N, int nq, float scale, int dtype, int flags,
+                             const uint32_t* seed, uint32_t site, int t, void* stream);
+int pa_attention_dropout_mask(uint32_t seed0, uint32_t seed1, uint32_t site, int BH, int nq, int N, int t, uint8_t* keep_out);
 /* Backward over PACKED sequences of different lengths: the backward of pa_attention_fwd_varlen, same cu_tok / max_N / nq meaning, same
  * layouts.  nq >= max_N: o / d_o are packed like qkv's rows and lse is [H][cu_tok[B]]; nq < max_N (the last block's nq = 2): o / d_o /
  * lse are compact as in pa_attention_bwd, o[(b*nq + q)][H*64], lse[(b*H + h)*nq + q].  ws: f32 workspace of

@@ -15,6 +15,7 @@ PA_F32, PA_BF16 = 0, 1
 EPI_STORE, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_PARTIAL = 0, 1, 2, 3, 4
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+u32 = C.c_uint32
 
 
 class MelParams(C.Structure):
@@ -110,6 +111,9 @@ SIGNATURES = {
     "pa_attention_bwd": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp]),
     "pa_attention_bwd_varlen_ws_floats": (i64, [i64, i32, i32, i32]),
     "pa_attention_bwd_varlen": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, f32, i32, i32, vp]),
+    "pa_attention_fwd_dropout": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, f32, i32, i32, vp, u32, i32, vp]),
+    "pa_attention_bwd_dropout": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp, u32, i32, vp]),
+    "pa_attention_dropout_mask": (i32, [u32, u32, u32, i32, i32, i32, i32, vp]),
     "pa_gather_rows": (i32, [vp, vp, i32, i64, vp, vp]),
     "pa_scatter_rows": (i32, [vp, vp, i32, i64, vp, vp]),
     "pa_zero2d": (i32, [vp, i64, i64, i64, vp]),

@@ -15,11 +15,15 @@
 #include <type_traits>
 
 #include "pa_mma.h"
+#include "pa_dropout.h"
 
 namespace pa {
 
 // occupancy targets of the bf16 kernels (waves per SIMD)
 static constexpr int FWD_WAVES = 3, DQ_WAVES = 3, DKDV_WAVES = 2;
+// the dropout instances of the forward and of dQ: the Philox state next to the score block does not fit 168 registers (three
+// waves spill 20 / 40 bytes inside the tile loop), and their loops are VALU work a third wave does not speed up
+static constexpr int FWD_DROP_WAVES = 2, DQ_DROP_WAVES = 2;
 // Measured and not kept:
 //  * static wave priorities, distinct per hardware wave slot or per workgroup, against the observation that the co-resident
 //    waves of a SIMD pass through the matrix phase and the VALU phase of a tile together: no gain (fwd 71.4 -> 74.5 us,
@@ -330,10 +334,17 @@ static inline unsigned attn_grid(int nblk, int BH) { return (unsigned)(nblk * 8 
 // caller's nq there: nq == max N means "every query" (o and lse packed like qkv's rows, lse[h][total tokens]), otherwise o and
 // lse are compact as in the fixed-length form.  K / V rows staged for the tail tile are clamped to the sequence's own last row
 // (stage_last), so no row of a neighbour -- nor one behind the end of qkv -- is ever read.
-template <typename T, bool PRE, bool VL>
+//
+// DROP (pa_attention_fwd_dropout): dropout on the probabilities, mask rule of pa_dropout.h.  This lane's 16 scores of a key block
+// are four groups of four consecutive keys 8g + 4h + {0..3} of ONE query: one Philox call per group (the patch's word q & 3, one
+// byte per key).  The row sum l and lse are formed from the undropped p; a dropped p is SELECTED to zero in front of the P V
+// product and 1 / keep is folded into the final quotient: O = acc / (l keep).  The plain instances see none of it (if constexpr).
+template <typename T, bool PRE, bool VL, bool DROP = false>
 __device__ __forceinline__ void attn_fwd_body(const T* __restrict__ qkv, int ldqkv, T* __restrict__ o,
                                               int ldo, float* __restrict__ lse, int H, int N, int nq, float scale, int nblk, int BH,
-                                              const int32_t* __restrict__ cu_tok) {
+                                              const int32_t* __restrict__ cu_tok, const uint32_t* __restrict__ dseed = nullptr,
+                                              uint32_t dsite = 0, int dthr = 0) {
+    static_assert(!(VL && DROP), "the packed entries have no dropout form");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using F = typename Frag<T>::type;
     constexpr int NF = Tile<T>::NFRAG, NSB = AccSteps<T>::N, TB = Tile<T>::BYTES;
@@ -362,6 +373,9 @@ __device__ __forceinline__ void attn_fwd_body(const T* __restrict__ qkv, int ldq
     const int q0 = blk * 128 + wave * 32;
     const int qrow = min(q0 + (lane & 31), N - 1);
     const bool active = q0 < nq;                                // wave-uniform: this wave owns at least one stored query
+    uint32_t sd0 = 0, sd1 = 0;                                  // DROP: the seed (two scalar loads), this lane's query patch and word
+    if constexpr (DROP) { sd0 = dseed[0]; sd1 = dseed[1]; }
+    const uint32_t dqp = (uint32_t)(q0 + (lane & 31)) >> 2, dqw = (uint32_t)lane & 3u;
     const float sl2 = scale * LOG2E;
     const int ldb = ldqkv * (int)sizeof(T);
 
@@ -456,6 +470,21 @@ __device__ __forceinline__ void attn_fwd_body(const T* __restrict__ qkv, int ldq
             }
         }
         l_run += psum;
+        if constexpr (DROP) {
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+                if (kb == 1 && !both) break;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    // keys kt 64 + kb 32 + 8 g + 4 h + {0..3}: patch (kt 16 + kb 8 + 2 g + h)
+                    const Philox4 R = dropout_patch(sd0, sd1, dsite, (uint32_t)bh, dqp, (uint32_t)(kt * (TROWS / 4) + kb * 8 + 2 * g + (lane >> 5)));
+                    const uint32_t w = dqw == 0 ? R.w[0] : dqw == 1 ? R.w[1] : dqw == 2 ? R.w[2] : R.w[3];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (!dropout_kept(w, e, (uint32_t)dthr)) s[kb][4 * g + e] = 0.f;
+                }
+            }
+        }
         // O^T[d][q] += V^T[d][key] P^T[key][q]; the V column fragments of step i+1 are in flight under the MFMAs of step i
         constexpr int ns = both ? 2 * NSB : NSB;
         F vfr[2][2];
@@ -502,6 +531,7 @@ __device__ __forceinline__ void attn_fwd_body(const T* __restrict__ qkv, int ldq
         // only the first nq queries of every sequence are produced; o / lse are compact (nq rows per sequence)
         l_run += other_half(l_run);
         if (lane < 32 && q0 + lane < nq) lse_row[q0 + lane] = (m_run + __builtin_amdgcn_logf(l_run)) * LN2;   // natural log units
+        if constexpr (DROP) l_run *= (float)(256 - dthr) * (1.0f / 256.0f);      // behind lse: O = acc / (l keep), keep exact in f32
         if constexpr (sizeof(T) == 4) {
             // f32 rows get the quotient itself: v_rcp_f32 is good to 1 ulp and the product rounds once more, up to 1.5 ulp off
             // O / l (with q = 0 and integer v, where O and l are exact, 5 % of the elements were not a neighbour of the exact mean);
@@ -519,6 +549,13 @@ template <typename T, bool PRE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? FWD_WAVES : 2))) void attn_fwd_kernel(const T* __restrict__ qkv, int ldqkv, T* __restrict__ o,
                                                        int ldo, float* __restrict__ lse, int H, int N, int nq, float scale, int nblk, int BH) {
     attn_fwd_body<T, PRE, false>(qkv, ldqkv, o, ldo, lse, H, N, nq, scale, nblk, BH, nullptr);
+}
+// with dropout on the probabilities (see the note in front of attn_fwd_body); seed: two words in device memory
+template <typename T, bool PRE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? FWD_DROP_WAVES : 2))) void attn_fwd_dropout_kernel(
+    const T* __restrict__ qkv, int ldqkv, T* __restrict__ o, int ldo, float* __restrict__ lse, int H, int N, int nq, float scale, int nblk,
+    int BH, const uint32_t* __restrict__ seed, uint32_t site, int thr) {
+    attn_fwd_body<T, PRE, false, true>(qkv, ldqkv, o, ldo, lse, H, N, nq, scale, nblk, BH, nullptr, seed, site, thr);
 }
 // the packed form (see the note in front of attn_fwd_body): N = max N, nq == N: every query
 template <typename T, bool PRE>
@@ -538,10 +575,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 // planes [H][total tokens] like the forward's lse), otherwise d_o and the workspace are compact (nq rows per sequence) and this
 // kernel also zeroes the Q third of the rows it owns at or behind nq (the dQ kernel writes the rows in front), so that every row
 // of dqkv is written by the pair.  The Q / dO rows staged for the tail tile are clamped to the sequence's own last query.
-template <typename T, bool PRE, bool VL>
+//
+// DROP (pa_attention_bwd_dropout), D = kept / keep: dP = D (dO V^T), dS = P (dP - delta), dV = (P D)^T dO.  The dP chain starts from 0
+// (delta is added behind the mask: a dropped element has dS = -P delta), the dropped P is selected to zero for the dV product and
+// 1 / keep of dV is applied once when its rows are stored.  A lane owns a key here, and accumulator rows 4g .. 4g + 3 are four
+// consecutive queries: one Philox call per group, word = query inside the patch, this lane's byte (key & 3) of each.
+template <typename T, bool PRE, bool VL, bool DROP = false>
 __device__ __forceinline__ void attn_bwd_dkdv_body(const T* __restrict__ qkv, int ldqkv, const T* __restrict__ d_o, int ldo,
                                                    const float* __restrict__ ws, int64_t plane, T* __restrict__ dqkv, int lddqkv, int H, int N,
-                                                   int nq, float scale, int nblk, int BH, const int32_t* __restrict__ cu_tok) {
+                                                   int nq, float scale, int nblk, int BH, const int32_t* __restrict__ cu_tok,
+                                                   const uint32_t* __restrict__ dseed = nullptr, uint32_t dsite = 0, int dthr = 0) {
+    static_assert(!(VL && DROP), "the packed entries have no dropout form");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using F = typename Frag<T>::type;
     constexpr int NF = Tile<T>::NFRAG, NS = AccSteps<T>::N, TB = Tile<T>::BYTES;
@@ -579,6 +623,11 @@ __device__ __forceinline__ void attn_bwd_dkdv_body(const T* __restrict__ qkv, in
     const bool active = k0 < N;                                 // wave-uniform
     const float sl2 = scale * LOG2E;
     const int ldbq = ldqkv * (int)sizeof(T), ldbo = ldo * (int)sizeof(T);
+    uint32_t sd0 = 0, sd1 = 0;                                  // DROP: the seed (two scalar loads), this lane's key patch and byte
+    if constexpr (DROP) { sd0 = dseed[0]; sd1 = dseed[1]; }
+    const uint32_t dkp = (uint32_t)(k0 + (lane & 31)) >> 2;
+    const int dkb = lane & 3;
+    const float rkeep = DROP ? 256.0f / (float)(256 - dthr) : 1.0f;
 
     F kf[NF], vf[NF];
 #pragma unroll
@@ -628,16 +677,20 @@ __device__ __forceinline__ void attn_bwd_dkdv_body(const T* __restrict__ qkv, in
             for (int e = 0; e < 4; ++e) { nl[4 * g + e] = a[e]; dpa[4 * g + e] = d[e]; }
         }
         // S'[q][key] = (Q sl2) K^T - lse ; dP'[q][key] = dO V^T - delta   (A rows = q, B cols = key = lane)
+        f32x16 ndl;                                             // DROP: -delta, added behind the mask
+        if constexpr (DROP) ndl = dpa;
         if constexpr (PRE) {
             sa = nl;
 #pragma unroll
             for (int st = 0; st < NF; ++st) {
                 mma32<T>(sa, row_frag_off<T>(sQ, lo, qb * 32, st), kf[st]);
-                mma32<T>(dpa, row_frag_off<T>(sDO, lo, qb * 32, st), vf[st]);
+                if (DROP && st == 0) mma32_first<T>(dpa, row_frag_off<T>(sDO, lo, qb * 32, st), vf[st]);
+                else mma32<T>(dpa, row_frag_off<T>(sDO, lo, qb * 32, st), vf[st]);
             }
         } else {
             mma32_first<T>(sa, row_frag_off<T>(sQ, lo, qb * 32, 0), kf[0]);
-            mma32<T>(dpa, row_frag_off<T>(sDO, lo, qb * 32, 0), vf[0]);
+            if constexpr (DROP) mma32_first<T>(dpa, row_frag_off<T>(sDO, lo, qb * 32, 0), vf[0]);
+            else mma32<T>(dpa, row_frag_off<T>(sDO, lo, qb * 32, 0), vf[0]);
 #pragma unroll
             for (int st = 1; st < NF; ++st) {
                 mma32<T>(sa, row_frag_off<T>(sQ, lo, qb * 32, st), kf[st]);
@@ -646,11 +699,27 @@ __device__ __forceinline__ void attn_bwd_dkdv_body(const T* __restrict__ qkv, in
 #pragma unroll
             for (int r = 0; r < 16; ++r) sa[r] = fmaf(sa[r], sl2, nl[r]);
         }
+        if constexpr (DROP) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float p = __builtin_amdgcn_exp2f(sa[r]);
-            sa[r] = p;
-            dpa[r] *= p;                                        // dS / scale
+            for (int g = 0; g < 4; ++g) {
+                // queries qt 64 + qb 32 + 8 g + 4 h + {0..3}: patch (qt 16 + qb 8 + 2 g + h)
+                const Philox4 R = dropout_patch(sd0, sd1, dsite, (uint32_t)bh, (uint32_t)(qt * (TROWS / 4) + qb * 8 + 2 * g + (lane >> 5)), dkp);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int r = 4 * g + e;
+                    const float p = __builtin_amdgcn_exp2f(sa[r]);
+                    const bool kept = dropout_kept(R.w[e], dkb, (uint32_t)dthr);
+                    sa[r] = kept ? p : 0.f;
+                    dpa[r] = p * ((kept ? dpa[r] * rkeep : 0.f) + ndl[r]);     // dS / scale
+                }
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float p = __builtin_amdgcn_exp2f(sa[r]);
+                sa[r] = p;
+                dpa[r] *= p;                                    // dS / scale
+            }
         }
         // queries beyond nq exist only in the last tile; lanes whose own key is beyond N only produce their own,
         // never stored, outputs and need no mask
@@ -705,7 +774,7 @@ __device__ __forceinline__ void attn_bwd_dkdv_body(const T* __restrict__ qkv, in
         T* out = VL ? dqkv + tok0 * lddqkv + h * HD : dqkv + (int64_t)b * N * lddqkv + h * HD;
         // PRE: the Q rows in memory are Q * scale * log2(e): dK = dS^T Q * scale = acc * ln 2
         store_rows_direct<T>(dk, PRE ? LN2 : scale, out + D, lddqkv, k0, min(32, N - k0), lane);
-        store_rows_direct<T>(dv, 1.0f, out + 2 * D, lddqkv, k0, min(32, N - k0), lane);
+        store_rows_direct<T>(dv, DROP ? rkeep : 1.0f, out + 2 * D, lddqkv, k0, min(32, N - k0), lane);
         if constexpr (VL) {
             // compact form: the Q third of this wave's rows that carry no query gradient (two lanes per row, half a head row each)
             const int row = k0 + (lane & 31);
@@ -726,6 +795,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
                                                             T* __restrict__ dqkv, int lddqkv, int H, int N, int nq, float scale, int nblk, int BH) {
     attn_bwd_dkdv_body<T, PRE, false>(qkv, ldqkv, d_o, ldo, ws, plane, dqkv, lddqkv, H, N, nq, scale, nblk, BH, nullptr);
 }
+// with dropout on the probabilities (see the note in front of attn_bwd_dkdv_body)
+template <typename T, bool PRE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? DKDV_WAVES : 1))) void attn_bwd_dkdv_dropout_kernel(
+    const T* __restrict__ qkv, int ldqkv, const T* __restrict__ d_o, int ldo, const float* __restrict__ ws, int64_t plane, T* __restrict__ dqkv,
+    int lddqkv, int H, int N, int nq, float scale, int nblk, int BH, const uint32_t* __restrict__ seed, uint32_t site, int thr) {
+    attn_bwd_dkdv_body<T, PRE, false, true>(qkv, ldqkv, d_o, ldo, ws, plane, dqkv, lddqkv, H, N, nq, scale, nblk, BH, nullptr, seed, site, thr);
+}
 // the packed form (see the note in front of attn_bwd_dkdv_body): N = max N, nq == N: every query
 template <typename T, bool PRE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? DKDV_WAVES : 1))) void attn_bwd_dkdv_varlen_kernel(
@@ -741,10 +817,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 // attn_bwd_dkdv_body -- base rows and N from cu_tok; nq == max N: o / d_o packed like qkv's rows, lse and the two workspace planes
 // [H][total tokens]; otherwise compact.  The blocks a short sequence does not have return before their first memory access; K / V
 // rows of the tail tile are clamped to the sequence's own last row.
-template <typename T, bool PRE, bool VL>
+//
+// DROP: as in attn_bwd_dkdv_body, in the forward's orientation (a lane owns a query, accumulator rows 4g .. 4g + 3 are four
+// consecutive keys: the patch's word q & 3, one byte per key).  delta comes from the stored o, which already carries the mask.
+template <typename T, bool PRE, bool VL, bool DROP = false>
 __device__ __forceinline__ void attn_bwd_dq_body(const T* __restrict__ qkv, int ldqkv, const T* __restrict__ o, const T* __restrict__ d_o, int ldo,
                                                  const float* __restrict__ lse, float* __restrict__ delta, int64_t plane, T* __restrict__ dqkv,
-                                                 int lddqkv, int H, int N, int nq, float scale, int nblk, int BH, const int32_t* __restrict__ cu_tok) {
+                                                 int lddqkv, int H, int N, int nq, float scale, int nblk, int BH, const int32_t* __restrict__ cu_tok,
+                                                 const uint32_t* __restrict__ dseed = nullptr, uint32_t dsite = 0, int dthr = 0) {
+    static_assert(!(VL && DROP), "the packed entries have no dropout form");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using F = typename Frag<T>::type;
     constexpr int NF = Tile<T>::NFRAG, NS = AccSteps<T>::N, TB = Tile<T>::BYTES;
@@ -780,6 +861,10 @@ __device__ __forceinline__ void attn_bwd_dq_body(const T* __restrict__ qkv, int 
     const bool active = q0 < nq;                                // wave-uniform
     const float sl2 = scale * LOG2E;
     const int ldb = ldqkv * (int)sizeof(T);
+    uint32_t sd0 = 0, sd1 = 0;                                  // DROP: the seed (two scalar loads), this lane's query patch and word
+    if constexpr (DROP) { sd0 = dseed[0]; sd1 = dseed[1]; }
+    const uint32_t dqp = (uint32_t)q >> 2, dqw = (uint32_t)lane & 3u;
+    const float rkeep = DROP ? 256.0f / (float)(256 - dthr) : 1.0f;
 
     F qf[NF], dof[NF];
     float dlt = 0.f;
@@ -838,19 +923,37 @@ __device__ __forceinline__ void attn_bwd_dq_body(const T* __restrict__ qkv, int 
         // S'^T[key][q] = K (Q sl2)^T - lse ; dP'^T[key][q] = V dO^T - delta
         if constexpr (PRE) mma32_c<T>(sa, row_frag_off<T>(sK, lo, kb * 32, 0), qf[0], neglse);
         else mma32_first<T>(sa, row_frag_off<T>(sK, lo, kb * 32, 0), qf[0]);
-        {
-            float t = ndl;
-            asm volatile("" : "+v"(t));                         // keep the splat inside the loop (not 16 hoisted registers)
-            dpa = acc_splat(t);
+        if constexpr (DROP) {
+            mma32_first<T>(dpa, row_frag_off<T>(sV, lo, kb * 32, 0), dof[0]);      // -delta is added behind the mask
+        } else {
+            {
+                float t = ndl;
+                asm volatile("" : "+v"(t));                     // keep the splat inside the loop (not 16 hoisted registers)
+                dpa = acc_splat(t);
+            }
+            mma32<T>(dpa, row_frag_off<T>(sV, lo, kb * 32, 0), dof[0]);
         }
-        mma32<T>(dpa, row_frag_off<T>(sV, lo, kb * 32, 0), dof[0]);
 #pragma unroll
         for (int st = 1; st < NF; ++st) {
             mma32<T>(sa, row_frag_off<T>(sK, lo, kb * 32, st), qf[st]);
             mma32<T>(dpa, row_frag_off<T>(sV, lo, kb * 32, st), dof[st]);
         }
+        if constexpr (DROP) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) dpa[r] *= __builtin_amdgcn_exp2f(PRE ? sa[r] : fmaf(sa[r], sl2, -lse2));      // dS^T / scale
+            for (int g = 0; g < 4; ++g) {
+                const Philox4 R = dropout_patch(sd0, sd1, dsite, (uint32_t)bh, dqp, (uint32_t)(kt * (TROWS / 4) + kb * 8 + 2 * g + (lane >> 5)));
+                const uint32_t w = dqw == 0 ? R.w[0] : dqw == 1 ? R.w[1] : dqw == 2 ? R.w[2] : R.w[3];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int r = 4 * g + e;
+                    const float p = __builtin_amdgcn_exp2f(PRE ? sa[r] : fmaf(sa[r], sl2, -lse2));
+                    dpa[r] = p * ((dropout_kept(w, e, (uint32_t)dthr) ? dpa[r] * rkeep : 0.f) + ndl);     // dS^T / scale
+                }
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dpa[r] *= __builtin_amdgcn_exp2f(PRE ? sa[r] : fmaf(sa[r], sl2, -lse2));  // dS^T / scale
+        }
         if (LAST && (N & (TROWS - 1))) {                        // keys beyond N: last tile only
 #pragma unroll
             for (int r = 0; r < 16; ++r)
@@ -904,6 +1007,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
                                                           const float* __restrict__ lse, float* __restrict__ delta, int64_t plane,
                                                           T* __restrict__ dqkv, int lddqkv, int H, int N, int nq, float scale, int nblk, int BH) {
     attn_bwd_dq_body<T, PRE, false>(qkv, ldqkv, o, d_o, ldo, lse, delta, plane, dqkv, lddqkv, H, N, nq, scale, nblk, BH, nullptr);
+}
+// with dropout on the probabilities (see the note in front of attn_bwd_dq_body)
+template <typename T, bool PRE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? DQ_DROP_WAVES : 1))) void attn_bwd_dq_dropout_kernel(
+    const T* __restrict__ qkv, int ldqkv, const T* __restrict__ o, const T* __restrict__ d_o, int ldo, const float* __restrict__ lse,
+    float* __restrict__ delta, int64_t plane, T* __restrict__ dqkv, int lddqkv, int H, int N, int nq, float scale, int nblk, int BH,
+    const uint32_t* __restrict__ seed, uint32_t site, int thr) {
+    attn_bwd_dq_body<T, PRE, false, true>(qkv, ldqkv, o, d_o, ldo, lse, delta, plane, dqkv, lddqkv, H, N, nq, scale, nblk, BH, nullptr, seed, site, thr);
 }
 // the packed form (see the note in front of attn_bwd_dq_body): N = max N, nq == N: every query
 template <typename T, bool PRE>
@@ -1359,6 +1470,20 @@ static int attention_fwd_t(const void* qkv, int ldqkv, void* o, int ldo, float* 
     return check_launch();
 }
 
+template <typename T>
+static int attention_fwd_dropout_t(const void* qkv, int ldqkv, void* o, int ldo, float* lse, int B, int H, int N, int nq, float scale, int flags,
+                                   const uint32_t* seed, uint32_t site, int thr, hipStream_t st) {
+    const int nblk = (int)cdiv(nq, 128);
+    const dim3 grid(attn_grid(nblk, B * H)), block(256);
+    if (flags & PA_ATTN_Q_PRESCALED)
+        hipLaunchKernelGGL((attn_fwd_dropout_kernel<T, true>), grid, block, fwd_lds<T>(), st, (const T*)qkv, ldqkv, (T*)o, ldo, lse, H, N, nq, scale,
+                           nblk, B * H, seed, site, thr);
+    else
+        hipLaunchKernelGGL((attn_fwd_dropout_kernel<T, false>), grid, block, fwd_lds<T>(), st, (const T*)qkv, ldqkv, (T*)o, ldo, lse, H, N, nq, scale,
+                           nblk, B * H, seed, site, thr);
+    return check_launch();
+}
+
 // Work-item map of the packed form: cdiv(min(nq, max_N), 128) query blocks for EVERY (sequence, head), dealt by attn_item as in the
 // fixed-length launch, the surplus blocks of short sequences returning at once (an empty workgroup costs about a microsecond of one
 // CU slot; the AudioSet / FSD50K mix launches 960 workgroups of which 552 do work).  Chosen over a host-built (sequence, block)
@@ -1392,6 +1517,21 @@ static int attention_bwd_t(const void* qkv, int ldqkv, const void* o, const void
     if (rc) return rc;
     hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, PRE>), dim3(attn_grid(nblkk, B * H)), dim3(256), dkdv_lds<T>(), st, (const T*)qkv, ldqkv,
                        (const T*)d_o, ldo, delta, plane, (T*)dqkv, lddqkv, H, N, nq, scale, nblkk, B * H);
+    return check_launch();
+}
+
+// the kernel pair with the dropout mask; launches and workspace as in attention_bwd_t
+template <typename T, bool PRE>
+static int attention_bwd_dropout_t(const void* qkv, int ldqkv, const void* o, const void* d_o, int ldo, const float* lse, float* delta, void* dqkv,
+                                   int lddqkv, int B, int H, int N, int nq, float scale, const uint32_t* seed, uint32_t site, int thr, hipStream_t st) {
+    const int64_t plane = (int64_t)B * H * nq;
+    const int nblkq = (int)cdiv(nq, 128), nblkk = (int)cdiv(N, 128);
+    hipLaunchKernelGGL((attn_bwd_dq_dropout_kernel<T, PRE>), dim3(attn_grid(nblkq, B * H)), dim3(256), fwd_lds<T>(), st, (const T*)qkv, ldqkv,
+                       (const T*)o, (const T*)d_o, ldo, lse, delta, plane, (T*)dqkv, lddqkv, H, N, nq, scale, nblkq, B * H, seed, site, thr);
+    int rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL((attn_bwd_dkdv_dropout_kernel<T, PRE>), dim3(attn_grid(nblkk, B * H)), dim3(256), dkdv_lds<T>(), st, (const T*)qkv, ldqkv,
+                       (const T*)d_o, ldo, delta, plane, (T*)dqkv, lddqkv, H, N, nq, scale, nblkk, B * H, seed, site, thr);
     return check_launch();
 }
 
@@ -1492,6 +1632,53 @@ extern "C" int pa_attention_bwd(const void* qkv, int ldqkv, const void* o, const
         return pre ? attention_bwd_t<float, true>(qkv, ldqkv, o, d_o, ldo, lse, delta, dqkv, lddqkv, B, H, N, nq, scale, st)
                    : attention_bwd_t<float, false>(qkv, ldqkv, o, d_o, ldo, lse, delta, dqkv, lddqkv, B, H, N, nq, scale, st);
     return PA_EINVAL;
+}
+
+// ---- attention dropout (additive: the ABI version stays 6) ------------------------------------------------------------------
+extern "C" int pa_attention_fwd_dropout(const void* qkv, int ldqkv, void* o, int ldo, float* lse, int B, int H, int N, int nq, float scale,
+                                        int dtype, int flags, const uint32_t* seed, uint32_t site, int t, void* stream) {
+    if (!qkv || !o || !lse || !seed || B <= 0 || H <= 0 || N <= 0 || nq <= 0 || nq > N || t < 1 || t > 255 || (flags & ~PA_ATTN_Q_PRESCALED))
+        return PA_EINVAL;
+    if (!attn_args_ok(ldqkv, dtype) || !attn_args_ok(ldo, dtype)) return PA_EUNSUPPORTED;
+    if (ldqkv < 3 * H * HD || ldo < H * HD) return PA_EINVAL;      // a leading dimension below the row width
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PA_BF16) return attention_fwd_dropout_t<bf16>(qkv, ldqkv, o, ldo, lse, B, H, N, nq, scale, flags, seed, site, t, st);
+    if (dtype == PA_F32) return attention_fwd_dropout_t<float>(qkv, ldqkv, o, ldo, lse, B, H, N, nq, scale, flags, seed, site, t, st);
+    return PA_EINVAL;
+}
+
+extern "C" int pa_attention_bwd_dropout(const void* qkv, int ldqkv, const void* o, const void* d_o, int ldo, const float* lse, float* delta,
+                                        void* dqkv, int lddqkv, int B, int H, int N, int nq, float scale, int dtype, int flags,
+                                        const uint32_t* seed, uint32_t site, int t, void* stream) {
+    if (!qkv || !o || !d_o || !lse || !delta || !dqkv || !seed || B <= 0 || H <= 0 || N <= 0 || nq <= 0 || nq > N || t < 1 || t > 255 ||
+        (flags & ~(PA_ATTN_Q_PRESCALED | PA_ATTN_BWD_TWO_PASS | PA_ATTN_BWD_SINGLE_PASS | PA_ATTN_BWD_SINGLE_PASS_W16)))
+        return PA_EINVAL;
+    if (!attn_args_ok(ldqkv, dtype) || !attn_args_ok(ldo, dtype) || !attn_args_ok(lddqkv, dtype)) return PA_EUNSUPPORTED;
+    if (ldqkv < 3 * H * HD || lddqkv < 3 * H * HD || ldo < H * HD) return PA_EINVAL;      // a leading dimension below the row width
+    // always the dQ + dK/dV pair: the PA_ATTN_BWD_* form flags are accepted and ignored
+    const bool pre = flags & PA_ATTN_Q_PRESCALED;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PA_BF16)
+        return pre ? attention_bwd_dropout_t<bf16, true>(qkv, ldqkv, o, d_o, ldo, lse, delta, dqkv, lddqkv, B, H, N, nq, scale, seed, site, t, st)
+                   : attention_bwd_dropout_t<bf16, false>(qkv, ldqkv, o, d_o, ldo, lse, delta, dqkv, lddqkv, B, H, N, nq, scale, seed, site, t, st);
+    if (dtype == PA_F32)
+        return pre ? attention_bwd_dropout_t<float, true>(qkv, ldqkv, o, d_o, ldo, lse, delta, dqkv, lddqkv, B, H, N, nq, scale, seed, site, t, st)
+                   : attention_bwd_dropout_t<float, false>(qkv, ldqkv, o, d_o, ldo, lse, delta, dqkv, lddqkv, B, H, N, nq, scale, seed, site, t, st);
+    return PA_EINVAL;
+}
+
+// host only: the mask the two entries above apply, from the same rule (pa_dropout.h)
+extern "C" int pa_attention_dropout_mask(uint32_t seed0, uint32_t seed1, uint32_t site, int BH, int nq, int N, int t, uint8_t* keep_out) {
+    if (!keep_out || BH <= 0 || N <= 0 || nq <= 0 || nq > N || t < 1 || t > 255) return PA_EINVAL;
+    for (int s = 0; s < BH; ++s)
+        for (int qp = 0; qp < (nq + 3) / 4; ++qp)
+            for (int kp = 0; kp < (N + 3) / 4; ++kp) {
+                const Philox4 R = dropout_patch(seed0, seed1, site, (uint32_t)s, (uint32_t)qp, (uint32_t)kp);
+                for (int q = 4 * qp; q < std::min(4 * qp + 4, nq); ++q)
+                    for (int k = 4 * kp; k < std::min(4 * kp + 4, N); ++k)
+                        keep_out[((int64_t)s * nq + q) * N + k] = dropout_kept(R.w[q & 3], k & 3, (uint32_t)t) ? 1 : 0;
+            }
+    return PA_OK;
 }
 
 extern "C" int64_t pa_attention_bwd_varlen_ws_floats(int64_t total_tokens, int B, int H, int nq) {

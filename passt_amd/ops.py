@@ -7,6 +7,7 @@ No fallback: a non-CUDA tensor or a missing library raises.
 import collections
 import ctypes as C
 import functools
+import math
 import threading
 import os
 
@@ -1276,6 +1277,97 @@ def attention_bwd(qkv, o, d_o, lse, B, H, N, scale, nq=None, flags=0):
                                               o.stride(0), _p(lse, torch.float32), _p(delta), _p(dqkv), dqkv.stride(0), B, H, N, nq,
                                               scale, dtype, flags | _ATTN_BWD_FORCE, _stream()), "pa_attention_bwd"))
     return dqkv
+
+
+# ---- attention dropout: the mask is a pure function of (seed, site, sequence x head, query, key), include/passt_amd.h ----------
+def attn_drop_t(p):
+    """t = round(256 p) of a dropout rate: 0 = no dropout (the plain entries), 1..255 = active with the effective rate t / 256
+    (keep = 1 - t / 256; kept probabilities are scaled by 1 / keep, so the expectation is exact for the rate actually applied).
+    A rate so large that t > 255 is a ValueError."""
+    p = float(p)
+    if not (p >= 0.0):
+        raise ValueError(f"attention dropout rate {p!r} is negative or not a number")
+    t = int(math.floor(256.0 * p + 0.5))
+    if t > 255:
+        raise ValueError(f"attention dropout rate {p!r} rounds to {t}/256: the largest rate the fused attention applies is 255/256")
+    return t
+
+
+def attn_drop_keep(t):
+    return 1.0 - t / 256.0
+
+
+def _drop_seed(seed, device, what):
+    """two words in device memory (int32 storage, read as uint32)"""
+    if not torch.is_tensor(seed) or seed.numel() != 2 or seed.dtype not in (torch.int32, torch.uint32) or seed.device != device \
+            or not seed.is_contiguous():
+        raise _lib.PasstAmdError(f"{what}: seed must be a contiguous (2,) int32 tensor on {device}")
+    return seed
+
+
+def _drop_t(t, what):
+    if not isinstance(t, int) or not 1 <= t <= 255:
+        raise ValueError(f"{what}: t must be an int in 1..255 (attn_drop_t of the rate), got {t!r}")
+    return t
+
+
+def attention_fwd_dropout(qkv, B, H, N, scale, seed, site, t, nq=None, flags=0):
+    """attention_fwd with dropout on the probabilities: seed a (2,) int32 tensor on qkv's device, site the block index, t = attn_drop_t(p)
+    in 1..255.  lse is that of the undropped softmax."""
+    dtype = PA_DTYPE[qkv.dtype]
+    nq = N if nq is None else nq
+    _drop_seed(seed, qkv.device, "attention_fwd_dropout")
+    _drop_t(t, "attention_fwd_dropout")
+    o = torch.empty((B * nq, H * 64), device=qkv.device, dtype=qkv.dtype)
+    lse = torch.empty((B * H * nq,), device=qkv.device, dtype=torch.float32)
+    _timed("attn_fwd_drop", 4.0 * nq * N * 64 * B * H,
+           lambda: check(_lib.load().pa_attention_fwd_dropout(_p(qkv, None, True), qkv.stride(0), _p(o), o.stride(0), _p(lse), B, H, N, nq,
+                                                              scale, dtype, flags, _p(seed), int(site), t, _stream()), "pa_attention_fwd_dropout"))
+    return o, lse
+
+
+def attention_bwd_dropout(qkv, o, d_o, lse, B, H, N, scale, seed, site, t, nq=None, flags=0):
+    """attention_bwd for attention_fwd_dropout's o / lse under the same seed, site and t: always the dQ + dK/dV kernel pair."""
+    dtype = PA_DTYPE[qkv.dtype]
+    nq = N if nq is None else nq
+    _drop_seed(seed, qkv.device, "attention_bwd_dropout")
+    _drop_t(t, "attention_bwd_dropout")
+    dqkv = torch.empty_like(qkv)
+    lib = _lib.load()
+    delta = torch.empty(lib.pa_attention_bwd_ws_floats(B, H, nq), device=lse.device, dtype=torch.float32)
+    if nq < N:
+        es = qkv.element_size()
+        check(lib.pa_zero2d(_p(dqkv), dqkv.stride(0) * es, H * 64 * es, B * N, _stream()), "pa_zero2d")
+    _timed("attn_bwd_drop", 14.0 * nq * N * 64 * B * H,     # the kernel pair forms S and dP twice: seven N x N x 64 products
+           lambda: check(lib.pa_attention_bwd_dropout(_p(qkv, None, True), qkv.stride(0), _p(o, qkv.dtype, True), _p(d_o, qkv.dtype, True),
+                                                      o.stride(0), _p(lse, torch.float32), _p(delta), _p(dqkv), dqkv.stride(0), B, H, N, nq,
+                                                      scale, dtype, flags, _p(seed), int(site), t, _stream()), "pa_attention_bwd_dropout"))
+    return dqkv
+
+
+def attn_drop_seed_words(seed):
+    """(s0, s1) Python ints < 2^32 from two ints or a (2,) tensor (int32 storage is read as uint32)"""
+    if torch.is_tensor(seed):
+        if seed.numel() != 2:
+            raise ValueError(f"attention dropout seed: a (2,) tensor, got {tuple(seed.shape)}")
+        seed = [int(v) for v in seed.detach().cpu().reshape(2).tolist()]
+    s = tuple(int(v) & 0xFFFFFFFF if -2 ** 31 <= int(v) < 0 else int(v) for v in seed)
+    if len(s) != 2 or not all(0 <= v < 2 ** 32 for v in s):
+        raise ValueError(f"attention dropout seed: two ints in [0, 2^32), got {seed!r}")
+    return s
+
+
+def attn_drop_mask(seed, site, B, H, nq, N, p):
+    """The keep mask the fused attention applies at dropout site ``site`` (the block index) under ``seed`` (two ints < 2^32 or a (2,)
+    tensor) and the rate ``p`` (quantised: attn_drop_t): a CPU bool tensor (B, H, nq, N), True = kept.  Computed on the host from the
+    rule the kernels compile (pa_attention_dropout_mask); multiply the probabilities by mask / (1 - attn_drop_t(p) / 256) to replay."""
+    t = attn_drop_t(p)
+    if t == 0:
+        return torch.ones(B, H, nq, N, dtype=torch.bool)
+    s0, s1 = attn_drop_seed_words(seed)
+    out = torch.empty(B * H * nq * N, dtype=torch.uint8)
+    check(_lib.load().pa_attention_dropout_mask(s0, s1, int(site), B * H, nq, N, t, out.data_ptr()), "pa_attention_dropout_mask")
+    return out.view(B, H, nq, N).bool()
 
 
 def attention_bwd_varlen(qkv, o, d_o, lse, cu_tok, B, H, max_N, scale, nq=None, flags=0, ws=None, out=None):

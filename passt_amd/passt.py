@@ -338,10 +338,15 @@ class _FixedLayout:
     def hidden_view(self, h):
         return h.view(self.B, self.Ntok, -1)
 
-    def attention_fwd(self, qkv, H, scale, **kw):
+    def attention_fwd(self, qkv, H, scale, drop=None, **kw):
+        """``drop``: (seed, site, t) of a block with an active attention dropout -- the dropout entry; None: the plain one"""
+        if drop is not None:
+            return ops.attention_fwd_dropout(qkv, self.B, H, self.Ntok, scale, *drop, **kw)
         return ops.attention_fwd(qkv, self.B, H, self.Ntok, scale, **kw)
 
-    def attention_bwd(self, qkv, att, d_att, lse, H, scale, **kw):
+    def attention_bwd(self, qkv, att, d_att, lse, H, scale, drop=None, **kw):
+        if drop is not None:
+            return ops.attention_bwd_dropout(qkv, att, d_att, lse, self.B, H, self.Ntok, scale, *drop, **kw)
         return ops.attention_bwd(qkv, att, d_att, lse, self.B, H, self.Ntok, scale, **kw)
 
     def prefix_lse(self, lse, H):
@@ -677,6 +682,52 @@ def drop_path_scales(model, masks, B, device):
     return torch.where(active, m, torch.ones_like(m)) / keep
 
 
+def attn_drop_rates(model):
+    """Per block: t = round(256 p) of its ``attn.attn_drop.p`` (ops.attn_drop_t: the fused attention applies the rate t / 256) in
+    training mode; 0 in eval mode, for p == 0 and for a module without ``p`` (an Identity).  A p that rounds past 255 / 256 raises
+    ValueError."""
+    if not model.training:
+        return [0] * len(model.blocks)
+    out = []
+    for blk in model.blocks:
+        p = getattr(getattr(blk.attn, "attn_drop", None), "p", None)
+        out.append(ops.attn_drop_t(p) if p else 0)
+    return out
+
+
+class _AttnDrop:
+    """A forward's attention dropout: ``seed`` (2,) int32 on the device (read as two uint32 words), ``t`` per block (attn_drop_rates)."""
+
+    def __init__(self, seed, t):
+        self.seed, self.t = seed, t
+
+    def kw(self, i):
+        """the keyword goes only to the attention launches of a block with an active dropout; site = the block index"""
+        return dict(drop=(self.seed, i, self.t[i])) if self.t[i] else {}
+
+
+def attn_drop_seed_tensor(seed, device):
+    """``attn_drop_seed`` -- two Python ints < 2^32 or a (2,) tensor -- as the (2,) int32 device tensor the kernels read."""
+    if torch.is_tensor(seed) and seed.dtype == torch.int32 and tuple(seed.shape) == (2,):
+        return seed.to(device).contiguous()
+    s0, s1 = ops.attn_drop_seed_words(seed)
+    return torch.tensor([v - 2 ** 32 if v >= 2 ** 31 else v for v in (s0, s1)], dtype=torch.int32).to(device)
+
+
+def attn_drop_draw(device):
+    """The seed of one training forward: ONE (2,) int32 tensor from ``device``'s default generator (full 32-bit range per word)."""
+    return torch.randint(-2 ** 31, 2 ** 31, (2,), dtype=torch.int32, device=device)
+
+
+def refuse_varlen_attn_drop(model):
+    """The refusal of a ragged batch by a model with an active attention dropout (training mode, attn_drop.p > 0), before any draw:
+    the packed attention entries have no dropout form."""
+    if any(attn_drop_rates(model)):
+        raise NotImplementedError("PaSST.forward(x, lengths=...) in training mode with an active attention dropout "
+                                  "(blocks[i].attn.attn_drop.p > 0) is not supported: the packed attention kernels have no dropout "
+                                  "form (train with equal-length batches, or with attn_drop.p = 0 on ragged ones)")
+
+
 class _DropRows:
     """A forward's drop-path factors per ROW, expanded once: ``full`` (depth, 2, M) for launches over all token rows (``ntok`` rows per
     clip), ``tail`` (2, 2 B) for the last block on the compact prefix rows (2 per clip); ``active``: the blocks with a factor."""
@@ -701,7 +752,7 @@ def _drop_rows(model, lay, scales):
     return _DropRows(scales, rates, lay.Ntok)
 
 
-def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, rollout=None, drop=None):
+def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, rollout=None, drop=None, adrop=None):
     """Token matrix xs [M][D] f32 in layout ``lay`` -> blocks -> tail -> head.  Returns a _Fwd (tok_offsets left to the caller); ctx
     (``save`` only) is what _backward_trunk needs plus ``patch``, the entry path's own state for its patch-stage backward.
     ``hidden`` (parse_hidden's tuple or None): the token outputs to hand out, in that order -- a block's output is the f32
@@ -718,6 +769,9 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, roll
     chain rides with the backward (_backward_trunk).
     ``drop`` (a _DropRows or None): stochastic depth -- both residual GEMMs of a block with a factor add rowscale[m] * branch[m]; a
     block without one, and every block when ``drop`` is None, makes exactly the calls it always made.
+    ``adrop`` (an _AttnDrop or None): attention dropout -- the attention launch of a block with t > 0 is the dropout entry with site =
+    the block index; every other block, and every block when ``adrop`` is None, launches what it always launched.  Maps and the
+    "attn" rollout stay the undropped softmax (they are formed from qkv and lse, which carry no mask).
     ``save``: False, True (keep what a backward down to the patch stage needs) or a _Plan: the blocks below ``plan.stop`` launch what
     they always launch and keep nothing -- their entry of ``ctx["saved"]`` is None and their LayerNorms write no row statistics."""
     st = model._staged
@@ -741,8 +795,9 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, roll
         # straight from the matrix pipe (ATTN_Q_PRESCALED); every gradient stays the gradient of the unscaled Linear
         qkv = ops.linear(ln1, st.get(blk.attn.qkv.weight, dt, False), blk.attn.qkv.bias, dt,
                          colscale_n=D, colscale=scale * ops.LOG2E)
+        kw_d = {} if adrop is None else adrop.kw(bi)
         if not last or full_tail:
-            att, lse = lay.attention_fwd(qkv, H, scale, flags=aflags)
+            att, lse = lay.attention_fwd(qkv, H, scale, flags=aflags, **kw_d)
             x_res = xs
             if bi in amaps:
                 maps[bi] = lay.attention_probs(qkv, lay.prefix_lse(lse, H) if aprefix else lse, H, scale, 2 if aprefix else None,
@@ -753,7 +808,7 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, roll
             # 2 queries (keys/values still span every token), then proj / LN2 / MLP on [2B, D].  Exact, not an
             # approximation: the reference computes the other N-2 rows and discards them.
             pidx = lay.prefix_rows(xs.device)
-            att, lse = lay.attention_fwd(qkv, H, scale, nq=2, flags=aflags)
+            att, lse = lay.attention_fwd(qkv, H, scale, nq=2, flags=aflags, **kw_d)
             x_res = ops.gather_rows(xs, pidx)
             if bi in amaps:                 # aprefix: the two rows this launch produced
                 maps[bi] = lay.attention_probs(qkv, lse, H, scale, 2, amean, aflags)
@@ -798,6 +853,8 @@ def _forward_trunk(model, lay, xs, dt, save, patch, hidden=None, attn=None, roll
     ctx = dict(dt=dt, lay=lay, scale=scale, saved=saved, xl=xl, feat=feat, hn=hn, stats=stats, patch=patch, tail=tail) if save else None
     if save and drop is not None:
         ctx["drop"] = drop
+    if save and adrop is not None:
+        ctx["adrop"] = adrop
     if plan is not None:
         ctx["plan"] = plan
     return _Fwd(logits, feat, ctx, tuple(lay.hidden_view(outs[k]) for k in want), tuple(maps[k] for k in amaps), roll=roll)
@@ -824,15 +881,18 @@ def patchout_draws(model, x_shape):
     return dict(pf=pf_np, pt=pt_np, toff=toff, Np=pf_np.size)
 
 
-def passt_forward(model, x, save, draws=None, hidden=None, attn=None, drop_path_masks=None):
+def passt_forward(model, x, save, draws=None, hidden=None, attn=None, drop_path_masks=None, attn_drop_seed=None):
     """Kernel sequence of PaSST.forward (:576-595).  Returns (logits, features, ctx).  ``save``: False, True (everything a full
     backward needs) or a trainable_plan (what the backward of a partly frozen network needs, see _forward_trunk).  ``draws``: device-resident Patchout
     draws {pf, pt, pt_pos (= pt + time offset), Np} prepared by the caller (captured-graph mode) -- with an active DropPath also
     ``dp``, drop_path_draws' (depth, 2, B) factors; None = draw here.
     ``hidden`` (parse_hidden's tuple): returns (logits, features, ctx, hs), hs = the (B, Ntok, D) f32 token outputs asked for.
     ``attn`` (parse_attn's triple): returns (logits, features, ctx, hs, maps), maps = the attention maps asked for.
-    ``drop_path_masks`` ((depth, 2, B) keep flags): used in place of the stochastic-depth draws (PaSST.forward)."""
-    r = _run_forward(model, x, None, save, draws, hidden, attn, drop_path_masks=drop_path_masks)
+    ``drop_path_masks`` ((depth, 2, B) keep flags): used in place of the stochastic-depth draws (PaSST.forward).
+    ``attn_drop_seed`` (two ints < 2^32 or a (2,) tensor): used in place of the attention-dropout seed draw (PaSST.forward); with
+    ``draws``, an active attention dropout reads its seed from ``draws["ad"]``, a (2,) int32 device tensor."""
+    r = _run_forward(model, x, None, save, draws, hidden, attn, drop_path_masks=drop_path_masks,
+                     **({} if attn_drop_seed is None else dict(attn_drop_seed=attn_drop_seed)))
     out = (r.logits, r.feat, r.ctx)
     if hidden is not None or attn is not None:
         out += (list(r.hidden),)
@@ -848,18 +908,22 @@ def refuse_varlen_drop_path(model):
                                   "(train with equal-length batches, or with drop_path_rate = 0 on ragged ones)")
 
 
-def _run_forward(model, x, lengths=None, save=False, draws=None, hidden=None, attn=None, rollout=None, drop_path_masks=None):
+def _run_forward(model, x, lengths=None, save=False, draws=None, hidden=None, attn=None, rollout=None, drop_path_masks=None,
+                 attn_drop_seed=None):
     """The one way into the kernel sequence of a forward: the fixed path, or with ``lengths`` the packed one, under this model's GEMM
     flags.  Returns the _Fwd."""
     if lengths is not None:
         refuse_varlen_drop_path(model)
+        refuse_varlen_attn_drop(model)
     with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
         if lengths is None:
+            if attn_drop_seed is not None:
+                return _passt_forward(model, x, save, draws, hidden, attn, rollout, drop_path_masks, attn_drop_seed)
             return _passt_forward(model, x, save, draws, hidden, attn, rollout, drop_path_masks)
         return _passt_forward_varlen(model, x, lengths, save, hidden, attn, rollout)
 
 
-def _passt_forward(model, x, save, draws=None, hidden=None, attn=None, rollout=None, drop_path_masks=None):
+def _passt_forward(model, x, save, draws=None, hidden=None, attn=None, rollout=None, drop_path_masks=None, attn_drop_seed=None):
     x, dt = _checked_input(model, x, True)
     B, Cin, F, T = x.shape
     P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
@@ -880,6 +944,15 @@ def _passt_forward(model, x, save, draws=None, hidden=None, attn=None, rollout=N
             scales = draws["dp"]
         else:
             scales = drop_path_draws(model, B, x.device)
+    # attention dropout: one seed per forward, behind the Patchout and the drop-path draws
+    adrop, ad_t = None, attn_drop_rates(model)
+    if any(ad_t):
+        if attn_drop_seed is not None:
+            adrop = _AttnDrop(attn_drop_seed_tensor(attn_drop_seed, x.device), ad_t)
+        elif draws is not None and draws.get("ad") is not None:
+            adrop = _AttnDrop(draws["ad"], ad_t)
+        else:
+            adrop = _AttnDrop(attn_drop_draw(x.device), ad_t)
 
     # patch embedding: gather-first im2col GEMM, epilogue adds bias + time/freq positional rows and
     # scatters to token rows 2.. ; rows 0,1 = cls/dist + new_pos_embed                 (:323,:527-564)
@@ -893,9 +966,10 @@ def _passt_forward(model, x, save, draws=None, hidden=None, attn=None, rollout=N
     patch = dict(Np=Np, pf=pf, pt=pt_pos, pt_grid=pt, toff=toff, F=F, T=T, cols=cols) if _saves_patch(save) else None
     lay = _FixedLayout(model, B, Ntok)
     drop = _drop_rows(model, lay, scales)
+    kw = {} if adrop is None else dict(adrop=adrop)
     if drop is None:
-        return _forward_trunk(model, lay, tok.view(B * Ntok, D), dt, save, patch, hidden, attn, rollout)
-    return _forward_trunk(model, lay, tok.view(B * Ntok, D), dt, save, patch, hidden, attn, rollout, drop=drop)
+        return _forward_trunk(model, lay, tok.view(B * Ntok, D), dt, save, patch, hidden, attn, rollout, **kw)
+    return _forward_trunk(model, lay, tok.view(B * Ntok, D), dt, save, patch, hidden, attn, rollout, drop=drop, **kw)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1438,6 +1512,7 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
     the maps' gradients, the weight and bias gradients) sees the scaled gradient by construction."""
     dt, lay, st, scratch = ctx["dt"], ctx["lay"], model._staged, model._scratch
     drop = ctx.get("drop")
+    adrop = ctx.get("adrop")                # a forward with an active attention dropout: the same seed, site and t go to the backward
 
     def factor(i, branch, compact=False):       # the keyword goes only to a launch whose branch has a factor
         rows = None if drop is None else drop.rows(i, branch, compact)
@@ -1511,9 +1586,10 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
         wg.launch(dx_lp, att, g[pfx + "attn.proj.weight"], None)
         d_att = torch.empty_like(att)
         ops.gemm_nt(dx_lp, st.get(blk.attn.proj.weight, dt, True), dt, EPI_STORE, out_lp=d_att)
+        kw_d = {} if adrop is None else adrop.kw(i)
         want_map_grad = ag is not None and i in ag.triple[0]       # the map's gradient: right behind the attention backward, from what it read
         if not prefix_tail:
-            d_qkv = lay.attention_bwd(qkv, att, d_att, lse, H, ctx["scale"], flags=ops.ATTN_Q_PRESCALED)
+            d_qkv = lay.attention_bwd(qkv, att, d_att, lse, H, ctx["scale"], flags=ops.ATTN_Q_PRESCALED, **kw_d)
             if want_map_grad:
                 _map_grad(lay, ag, ag.triple[0].index(i), qkv, lse, d_att, H, ctx["scale"], False)
             if rr is not None and i >= rr.first:
@@ -1521,7 +1597,7 @@ def _backward_trunk(model, ctx, dlogits, dfeat, wg):
         else:
             # only 2 queries per sequence carry a gradient (the Q third of d_qkv is zero elsewhere); the residual gradient lives
             # on the prefix rows only
-            d_qkv = lay.attention_bwd(qkv, att, d_att, lse, H, ctx["scale"], nq=2, flags=ops.ATTN_Q_PRESCALED)
+            d_qkv = lay.attention_bwd(qkv, att, d_att, lse, H, ctx["scale"], nq=2, flags=ops.ATTN_Q_PRESCALED, **kw_d)
             if want_map_grad:
                 _map_grad(lay, ag, ag.triple[0].index(i), qkv, lse, d_att, H, ctx["scale"], True)
             if rr is not None and i >= rr.first:
@@ -1668,6 +1744,9 @@ def passt_backward_varlen(model, ctx, dlogits, dfeat, grads, on_block_done=None,
     return _backward(model, ctx, dlogits, dfeat, grads, on_block_done, want_dx, _patch_backward_varlen)
 
 
+_NLEAD = 7          # arguments of _PasstFunction.forward in front of x (none of them carries a gradient)
+
+
 class _PasstFunction(torch.autograd.Function):
     """One autograd node for the whole network: forward/backward are kernel sequences, torch only sees
     (x, *parameters) -> (logits, features).  ``lengths``: None = the fixed path, else the packed ragged-batch forward
@@ -1678,7 +1757,7 @@ class _PasstFunction(torch.autograd.Function):
     non-differentiable (on the packed path one flat buffer per map); the backward ignores their (None) gradients."""
 
     @staticmethod
-    def forward(ctx, model, lengths, hidden, attn, rollout, drop_path_masks, x, *params):
+    def forward(ctx, model, lengths, hidden, attn, rollout, drop_path_masks, attn_drop_seed, x, *params):
         req = attn if isinstance(attn, _AttnGradRequest) else None        # the maps' gradients were asked for as well
         named, total = model._graph_params(validate=False)            # the list forward() just handed to apply()
         flat = model._flat if (len(params) == 1 and model._flat is not None and params[0] is model._flat["token"]) else None
@@ -1690,10 +1769,10 @@ class _PasstFunction(torch.autograd.Function):
         # (under ddp.attach on several ranks the reducer's buckets are laid out over every parameter: all of them are produced)
         red = getattr(model, "_ddp", None)
         every = flat is not None or (red is not None and red.world > 1)
-        plan = trainable_plan(model, bool(ctx.needs_input_grad[6]), min(low) if low else None, named,
-                              (True,) * len(named) if every else tuple(ctx.needs_input_grad[7:]))
+        plan = trainable_plan(model, bool(ctx.needs_input_grad[_NLEAD]), min(low) if low else None, named,
+                              (True,) * len(named) if every else tuple(ctx.needs_input_grad[_NLEAD + 1:]))
         r = _run_forward(model, x, lengths, plan, hidden=hidden, attn=attn if req is None else req.triple, rollout=rollout,
-                         drop_path_masks=drop_path_masks)
+                         drop_path_masks=drop_path_masks, **({} if attn_drop_seed is None else dict(attn_drop_seed=attn_drop_seed)))
         # the integer row offsets of the packed path are non-differentiable as they are
         ctx.mark_non_differentiable(*r.maps, *(() if r.roll is None else (r.roll,)))
         ctx.rollout = rollout if isinstance(rollout, _RolloutRequest) else None   # "cam": the backward runs the chain
@@ -1701,8 +1780,8 @@ class _PasstFunction(torch.autograd.Function):
         ctx.attn_grad = req
         # the input spectrogram's gradient is computed only when asked for; a graph none of whose parameters requires a gradient
         # (a frozen loss network) runs the backward without any weight-gradient work
-        ctx.want_dx = bool(ctx.needs_input_grad[6])
-        ctx.frozen = not any(ctx.needs_input_grad[7:])
+        ctx.want_dx = bool(ctx.needs_input_grad[_NLEAD])
+        ctx.frozen = not any(ctx.needs_input_grad[_NLEAD + 1:])
         ctx.named, ctx.total, ctx.plan = named, total, plan
         # bound to a passt_amd.optim.AdamW (PaSST.bind_flat_grads): the only input is a token; the backward writes the gradients
         # straight into the optimizer's persistent flat buffer -- p.grad are views of it -- and hands autograd nothing
@@ -1717,8 +1796,9 @@ class _PasstFunction(torch.autograd.Function):
             raise RuntimeError("passt_amd.PaSST: the saved activations of this forward were already consumed by a backward "
                                "pass (retain_graph / double backward are not supported: run the forward again)")
         run_backward = passt_backward_varlen if ctx.varlen else passt_backward
-        # the model, the lengths, the hidden request, the attention-map request, the rollout request, the drop-path masks
-        lead = (None, None, None, None, None, None)
+        # the model, the lengths, the hidden request, the attention-map request, the rollout request, the drop-path masks, the
+        # attention-dropout seed
+        lead = (None,) * _NLEAD
         dev = c["feat"].device
         # gradients of the token outputs that fed the loss, as [M][D] rows (an unused one arrives as None and costs nothing)
         dhidden = {k: d.contiguous().view(c["lay"].M, -1) for k, d in zip(ctx.hidden or (), dhs) if d is not None}
@@ -1798,8 +1878,8 @@ class _PasstFunction(torch.autograd.Function):
             return lead + (dx, None)
         out = list(lead) + [dx] + [None] * len(named)      # the same list, in the same order, as PaSST.forward handed to apply()
         for i in plan.idx:
-            if ctx.needs_input_grad[7 + i]:
-                out[7 + i] = grads[named[i][0]]
+            if ctx.needs_input_grad[_NLEAD + 1 + i]:
+                out[_NLEAD + 1 + i] = grads[named[i][0]]
         return tuple(out)
 
 
@@ -1862,7 +1942,8 @@ class PaSST(nn.Module):
                                       "arch get_model() can return (models/passt.py:963-1008)")
         if in_chans != 1 or drop_rate or attn_drop_rate or mlp_ratio != 4. or not qkv_bias or representation_size:
             raise NotImplementedError("passt_amd hot path: in_chans=1, no dropout (drop_rate / attn_drop_rate; stochastic depth, "
-                                      "drop_path_rate, is covered), mlp_ratio=4, qkv_bias")
+                                      "drop_path_rate, is covered; attention dropout is set on the modules, as with the reference's "
+                                      "get_model(): net.blocks[i].attn.attn_drop.p = p), mlp_ratio=4, qkv_bias")
         if embed_dim % num_heads or embed_dim // num_heads != 64:
             raise NotImplementedError("attention kernels are built for head_dim 64 (768/12, 1024/16, 384/6 ...)")
         self.num_classes = num_classes
@@ -2056,7 +2137,7 @@ class PaSST(nn.Module):
 
     @compile_opaque
     def forward(self, x, lengths=None, hidden=None, attn=None, attn_rows="all", attn_heads="each", attn_grad=None, rollout=None,
-                rollout_from=0, drop_path_masks=None):
+                rollout_from=0, drop_path_masks=None, attn_drop_seed=None):
         """x: (B,1,F,T) -> (logits (B,C), features (B,D)); always a tuple (models/passt.py:588,595).  With the keywords below:
         ``(logits, features[, hidden][, attn][, roll][, tok_offsets])``, tok_offsets whenever ``lengths`` comes with ``hidden``, ``attn``
         or ``rollout``.
@@ -2131,7 +2212,22 @@ class PaSST(nn.Module):
         i, [i, 1] its MLP branch): used in place of the draws -- nothing is drawn; entries of blocks without an active ``DropPath``
         are ignored -- which is how a recorded run is replayed.  Ignored in eval mode, where, as at rate 0, the network launches
         exactly what it launches without stochastic depth.  With ``lengths`` in training mode an active ``DropPath`` raises
-        NotImplementedError.  ``drop_rate`` / ``attn_drop_rate`` (element-wise dropout) are not covered: the constructor raises.
+        NotImplementedError.
+
+        Attention dropout (the reference's ``nn.Dropout`` on the attention probabilities, set the reference's way:
+        ``for b in net.blocks: b.attn.attn_drop.p = 0.1``; the constructor still refuses ``attn_drop_rate``): in training mode a block
+        with ``attn_drop.p > 0`` runs the fused attention with dropout, forward and backward (``pa_attention_fwd_dropout`` /
+        ``_bwd_dropout``).  The rate is quantised to t = round(256 p) / 256 (``attn_drop_rates``; a p that rounds past 255 / 256 raises
+        ValueError) and kept probabilities are scaled by 1 / (1 - t / 256): exact in expectation for the rate applied.  The mask is
+        not the reference's (element-wise masks cannot be drawn reference-equal on the device) but a pure function of a 64-bit seed
+        and (block, clip x head, query, key): ``passt_amd.attn_drop_mask(seed, block, B, H, Nq, Ntok, p)`` restates it on the CPU.  A
+        training forward with at least one active block draws the seed once, ``torch.randint(-2**31, 2**31, (2,), dtype=torch.int32,
+        device=x.device)``, behind the Patchout and the drop-path draws; eval mode and all-zero rates draw nothing and launch exactly
+        what they launch without dropout.  ``attn_drop_seed`` (two ints < 2^32, or a (2,) tensor): used in place of the draw -- same
+        seed, same inputs: bit-identical outputs and gradients; ignored in eval mode.  ``attn=`` maps and ``rollout="attn"`` stay the
+        undropped softmax (the INPUT of ``attn_drop``).  NotImplementedError, before any draw: ``lengths`` in training mode with an
+        active attention dropout; ``attn_grad`` or ``rollout="cam"`` when a block they touch is active.  ``drop_rate`` (the other
+        element-wise dropout sites) is not covered: the constructor raises.
 
         An ``x`` that requires a gradient gets one (``x.grad`` / ``torch.autograd.grad``), as in the reference: PaSST as a
         differentiable loss network.  With every parameter frozen (``net.requires_grad_(False)``) this needs no switch and the backward
@@ -2185,6 +2281,15 @@ class PaSST(nn.Module):
             amap = parse_attn(attn, len(self.blocks), attn_rows, attn_heads)
         agrad = parse_attn_grad(attn_grad, attn, attn_heads)
         roll = parse_rollout(rollout, rollout_from, len(self.blocks))
+        ad_t = attn_drop_rates(self)
+        if any(ad_t):
+            if agrad is not None and any(ad_t[i] for i in amap[0]):
+                raise NotImplementedError("attn_grad on a block with an active attention dropout (attn_drop.p > 0 in training mode) is "
+                                          "not supported: the gradient with respect to the undropped map needs the mask in "
+                                          "pa_attention_probs_grad")
+            if roll is not None and roll[0] == "cam" and any(ad_t[roll[1]:]):
+                raise NotImplementedError("rollout=\"cam\" through a block with an active attention dropout (attn_drop.p > 0 in training "
+                                          "mode) is not supported: its gradient factor needs the mask in pa_attention_probs_grad")
         train_ragged = lengths is not None and self.training
         if train_ragged and not getattr(self, "varlen_train", False):
             raise NotImplementedError("PaSST.forward(x, lengths=...): training on ragged batches is not supported (eval mode only; "
@@ -2229,9 +2334,12 @@ class PaSST(nn.Module):
                 fl = None
             # bound (same validated parameter list as at bind time): the single token stands for every parameter
             params = (fl["token"],) if fl is not None else [p for _, p in named]
-            r = _Fwd.from_flat(_PasstFunction.apply(self, lengths, hid, amap if agrad is None else req, roll, drop_path_masks, x, *params), len(hid or ()),
+            r = _Fwd.from_flat(_PasstFunction.apply(self, lengths, hid, amap if agrad is None else req, roll, drop_path_masks,
+                                                    attn_drop_seed if any(ad_t) else None, x, *params), len(hid or ()),
                                len(amap[0]) if amap else 0, roll is not None)
         elif lengths is None and hid is None and amap is None and roll is None:
+            if attn_drop_seed is not None and any(ad_t):
+                return passt_forward(self, x, save=False, drop_path_masks=drop_path_masks, attn_drop_seed=attn_drop_seed)[:2]
             if drop_path_masks is not None:
                 return passt_forward(self, x, save=False, drop_path_masks=drop_path_masks)[:2]
             return passt_forward(self, x, save=False)[:2]       # the plain call stays on the public entry (callers stand in for it)
@@ -2239,7 +2347,8 @@ class PaSST(nn.Module):
             # the ragged forward records nothing unless asked to; the fixed one leaves that to the caller's own grad mode
             with torch.no_grad() if lengths is not None else contextlib.nullcontext():
                 r = _run_forward(self, x, lengths, hidden=hid, attn=amap, rollout=roll,
-                                 **({} if drop_path_masks is None else dict(drop_path_masks=drop_path_masks)))
+                                 **({} if drop_path_masks is None else dict(drop_path_masks=drop_path_masks)),
+                                 **({} if attn_drop_seed is None or not any(ad_t) else dict(attn_drop_seed=attn_drop_seed)))
         res = self._outputs(r, hid, amap)
         if agrad is not None:
             req.targets = list(res[2 if hid is None else 3])      # the tensors the caller holds: the backward fills their .grad

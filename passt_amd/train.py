@@ -14,7 +14,8 @@ import torch
 
 from . import ops
 from .ddp import GradReducer
-from .passt import (_checked_input, _freq_rows, _precision, check_patchout_varlen, drop_path_draws, drop_path_rates, param_stage,
+from .passt import (_checked_input, _freq_rows, _precision, attn_drop_draw, attn_drop_rates, check_patchout_varlen, drop_path_draws,
+                    drop_path_rates, param_stage, refuse_varlen_attn_drop,
                     passt_backward, passt_backward_varlen, passt_forward, passt_forward_varlen, patchout_draws, refuse_varlen_drop_path,
                     trainable_plan)
 from .preprocess import checked_lengths
@@ -62,6 +63,9 @@ class TrainStep:
         host: one replay instead of ~290 ctypes launches -- it matters where the step is short (ESC-50 at batch 12).
         Stochastic depth (a net built with drop_path_rate > 0): the step's factors are drawn on the device ahead of the replay
         (passt.drop_path_draws, where the eager forward draws them) into a buffer of fixed address next to the Patchout indices.
+        Attention dropout (net.blocks[i].attn.attn_drop.p > 0): the step's seed is drawn the same way (passt.attn_drop_draw, behind
+        the drop-path draws) into a (2,) buffer next to them; the dropout kernels read it from device memory, so the captured
+        launches replay with a new mask every step.
         ``clip_grad_norm`` = c (AdamW; Lightning's trainer.gradient_clip_val): the update uses g * min(1, c / (norm + 1e-6)), norm
         being the global L2 norm over the flat gradient buffer (the trainable parameters; torch.nn.utils.clip_grad_norm_'s
         arithmetic).  Every bucket's partial sums of squares go out from the backward (pa_grad_accum_sumsq), the factor is formed
@@ -334,6 +338,8 @@ class TrainStep:
         g["pt_pos"].copy_(ops.upload_small(d["pt"] + np.int32(d["toff"]), x.device))
         if g["dp"] is not None:
             g["dp"].copy_(d["dp"])          # stochastic depth: the step's factors, drawn on the device ahead of the replay
+        if g.get("ad") is not None:
+            g["ad"].copy_(d["ad"])          # attention dropout: the step's seed
         # (through the pinned ring like the index arrays: a fixed host buffer could be rewritten for step k + 1 before the
         # asynchronous copy of step k has read it)
         ops.adamw_hyper(self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self._t_now, g["hyper_host"])
@@ -459,6 +465,7 @@ class TrainStep:
             raise NotImplementedError("TrainStep.step(..., lengths=): a front end in train mode takes a ragged batch only with the "
                                       "switch mel.varlen_train = True (every clip then gets its own fmin / fmax jitter and masks)")
         refuse_varlen_drop_path(net)
+        refuse_varlen_attn_drop(net)
         if mel is not None:
             if x.dim() == 3:
                 x = x.reshape(-1, x.shape[2])
@@ -528,6 +535,8 @@ class TrainStep:
         d = patchout_draws(net, x.shape)                     # the Patchout draws of this step, where passt_forward would draw them
         if any(p > 0.0 for p in drop_path_rates(net)):       # ... and behind them the stochastic-depth draws, as passt_forward orders them
             d["dp"] = drop_path_draws(net, x.shape[0], x.device)
+        if any(attn_drop_rates(net)):                        # ... and behind those the attention-dropout seed
+            d["ad"] = attn_drop_draw(x.device)
         g = self._g
         if g is None or "graph" not in g:
             if g is None:
@@ -536,7 +545,7 @@ class TrainStep:
                          pt_pos=torch.empty(d["Np"], device=x.device, dtype=torch.int32), y=torch.empty_like(y),
                          y2=None if y2 is None else torch.empty_like(y2), lam=None if lam_d is None else torch.empty_like(lam_d),
                          hyper=torch.empty(7, device=x.device, dtype=torch.float32), hyper_host=torch.empty(7, dtype=torch.float32),
-                         dp=torch.empty_like(d["dp"]) if "dp" in d else None)
+                         dp=torch.empty_like(d["dp"]) if "dp" in d else None, ad=torch.empty_like(d["ad"]) if "ad" in d else None)
                 self._g = g
             self._graph_fill(g, d, x, y, y2, lam_d)
             net.mark_params_updated()                        # the staged weight copies are stale: their refresh launch is captured too
