@@ -575,7 +575,7 @@ int pa_attention_bwd(const void* qkv, int ldqkv, const void* o, const void* d_o,
  *   PA_ATTN_BWD_* form flags are accepted and ignored, the result is bit-identical whichever are given.  Workspace and the Q third
  *   of rows q >= nq as for pa_attention_bwd.
  * PA_EINVAL before anything is launched: seed == NULL, t outside 1..255, and everything the plain entries refuse.  The packed
- * (_varlen) entries have no dropout form.
+ * (_varlen) entries have their dropout form below (pa_attention_fwd_varlen_dropout / pa_attention_bwd_varlen_dropout).
  * pa_attention_dropout_mask: HOST only, touches no device: keep_out[(s*nq + q)*N + k] = 1 (kept) or 0 for s < BH, q < nq, k < N,
  *   from the same rule the kernels compile.  PA_EINVAL: keep_out == NULL, BH / nq / N <= 0, nq > N, t outside 1..255. */
 int pa_attention_fwd_dropout(const void* qkv, int ldqkv, void* o, int ldo, float* lse, int B, int H, int N, int nq, float scale, int dtype,
@@ -599,6 +599,25 @@ int64_t pa_attention_bwd_varlen_ws_floats(int64_t total_tokens, int B, int H, in
 int pa_attention_bwd_varlen(const void* qkv, int ldqkv, const void* o, const void* d_o, int ldo, const float* lse, float* ws,
                             void* dqkv, int lddqkv, const int32_t* cu_tok, int B, int H, int max_N, int nq, float scale, int dtype,
                             int flags, void* stream);
+/* ---- attention dropout on PACKED sequences (additive: the ABI version stays 6) ----
+ * pa_attention_fwd_varlen / pa_attention_bwd_varlen with the dropout of pa_attention_fwd_dropout / pa_attention_bwd_dropout: the packed
+ * entries' arguments, layouts (nq >= max_N: packed o / d_o and lse[H][cu_tok[B]]; nq < max_N: the compact form), workspace
+ * (pa_attention_bwd_varlen_ws_floats) and writes, plus seed (two words in device memory), site and t with the meaning above.  The mask
+ * rule is unchanged; for element (site, s, q, k) of packed sequence b, s = b*H + h with b the sequence's index in the batch, and q, k
+ * are the positions INSIDE the sequence (0 .. N_b - 1), not token rows of the packed buffer.  The rule does not depend on N, so
+ * sequence b gets bit for bit the mask -- and, the tile loop being the same, the o / lse / dqkv -- that pa_attention_fwd_dropout /
+ * pa_attention_bwd_dropout give sequence b of a batch of B >= b + 1 sequences of N_b tokens under the same seed / site / t;
+ * pa_attention_dropout_mask(seed0, seed1, site, (b + 1)*H, nq_b, N_b, t, .) restates it in its planes s = b*H .. b*H + H - 1.  lse is
+ * that of the undropped softmax, bit-identical to pa_attention_fwd_varlen's on the same operands.  The backward is always the dQ + dK/dV
+ * kernel pair (PA_ATTN_BWD_* form flags accepted and ignored).
+ * PA_EINVAL before anything is launched: seed == NULL, t outside 1..255, site >= 65536, and everything pa_attention_fwd_varlen /
+ * pa_attention_bwd_varlen refuse. */
+int pa_attention_fwd_varlen_dropout(const void* qkv, int ldqkv, void* o, int ldo, float* lse, const int32_t* cu_tok, int B, int H,
+                                    int max_N, int nq, float scale, int dtype, int flags, const uint32_t* seed, uint32_t site, int t,
+                                    void* stream);
+int pa_attention_bwd_varlen_dropout(const void* qkv, int ldqkv, const void* o, const void* d_o, int ldo, const float* lse, float* ws,
+                                    void* dqkv, int lddqkv, const int32_t* cu_tok, int B, int H, int max_N, int nq, float scale,
+                                    int dtype, int flags, const uint32_t* seed, uint32_t site, int t, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Patch embedding + positional terms + Patchout: PatchEmbed.forward (models/passt.py:318-328) and

@@ -114,6 +114,8 @@ SIGNATURES = {
     "pa_attention_fwd_dropout": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, f32, i32, i32, vp, u32, i32, vp]),
     "pa_attention_bwd_dropout": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp, u32, i32, vp]),
     "pa_attention_dropout_mask": (i32, [u32, u32, u32, i32, i32, i32, i32, vp]),
+    "pa_attention_fwd_varlen_dropout": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp, u32, i32, vp]),
+    "pa_attention_bwd_varlen_dropout": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, f32, i32, i32, vp, u32, i32, vp]),
     "pa_gather_rows": (i32, [vp, vp, i32, i64, vp, vp]),
     "pa_scatter_rows": (i32, [vp, vp, i32, i64, vp, vp]),
     "pa_zero2d": (i32, [vp, i64, i64, i64, vp]),

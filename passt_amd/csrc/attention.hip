@@ -339,12 +339,14 @@ static inline unsigned attn_grid(int nblk, int BH) { return (unsigned)(nblk * 8 
 // are four groups of four consecutive keys 8g + 4h + {0..3} of ONE query: one Philox call per group (the patch's word q & 3, one
 // byte per key).  The row sum l and lse are formed from the undropped p; a dropped p is SELECTED to zero in front of the P V
 // product and 1 / keep is folded into the final quotient: O = acc / (l keep).  The plain instances see none of it (if constexpr).
+// VL && DROP (pa_attention_fwd_varlen_dropout): bh is the global sequence x head and q0 / kt are local to the sequence, so the counters
+// below are those of the fixed-length launch: sequence b gets the mask -- and every bit of o and lse -- that the DROP instance gives
+// sequence b of a batch of N_b-token sequences.  The same holds for the two backward bodies.
 template <typename T, bool PRE, bool VL, bool DROP = false>
 __device__ __forceinline__ void attn_fwd_body(const T* __restrict__ qkv, int ldqkv, T* __restrict__ o,
                                               int ldo, float* __restrict__ lse, int H, int N, int nq, float scale, int nblk, int BH,
                                               const int32_t* __restrict__ cu_tok, const uint32_t* __restrict__ dseed = nullptr,
                                               uint32_t dsite = 0, int dthr = 0) {
-    static_assert(!(VL && DROP), "the packed entries have no dropout form");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using F = typename Frag<T>::type;
     constexpr int NF = Tile<T>::NFRAG, NSB = AccSteps<T>::N, TB = Tile<T>::BYTES;
@@ -410,6 +412,10 @@ __device__ __forceinline__ void attn_fwd_body(const T* __restrict__ qkv, int ldq
         const char* sK = smem + (kt & 1) * (2 * TB);
         const char* sV = sK + TB;
         f32x16 s[2];
+        // DROP without the pre-scaled q, full tiles: the scale and the reference are applied behind the row max (RAW below), so that the
+        // first of several key tiles can form score * sl2 - max with ONE rounding, as the plain instances do there (their first tile
+        // is peeled with m_run == 0 and the product contracts into the subtraction): lse is then the plain entry's in every bit.
+        constexpr bool RAW = DROP && !PRE && !LAST;
         // S'^T[key][q] = K (Q sl2)^T - m_run
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
@@ -418,7 +424,7 @@ __device__ __forceinline__ void attn_fwd_body(const T* __restrict__ qkv, int ldq
             else mma32_first<T>(s[kb], row_frag_off<T>(sK, lo, kb * 32, 0), qf[0]);
 #pragma unroll
             for (int st = 1; st < NF; ++st) mma32<T>(s[kb], row_frag_off<T>(sK, lo, kb * 32, st), qf[st]);
-            if constexpr (!PRE) {
+            if constexpr (!PRE && !RAW) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) s[kb][r] = fmaf(s[kb][r], sl2, -m_run);
             }
@@ -441,7 +447,24 @@ __device__ __forceinline__ void attn_fwd_body(const T* __restrict__ qkv, int ldq
             for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[1][r]);
         }
         mx = fmaxf(mx, other_half(mx));
-        if (kt == 0 || !__all(mx <= RESCALE_LOG2)) {
+        if constexpr (RAW) {
+            // s holds the raw scores.  x -> fma(x, sl2, -m_run) is monotone (sl2 > 0), so this is the max of the shifted scores
+            mx = fmaf(mx, sl2, -m_run);
+            const bool moved = kt != 0 && !__all(mx <= RESCALE_LOG2);       // the reference point moves in a later tile
+            const float ref = kt == 0 ? mx : m_run;             // first tile: m_run == 0 and the new reference goes into the fma itself
+            const float d = fmaxf(mx, 0.f);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { s[0][r] = fmaf(s[0][r], sl2, -ref); s[1][r] = fmaf(s[1][r], sl2, -ref); }
+            if (kt == 0) {
+                m_run = mx;
+            } else if (moved) {
+                const float alpha = __builtin_amdgcn_exp2f(-d);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { s[0][r] -= d; s[1][r] -= d; oacc[0][r] *= alpha; oacc[1][r] *= alpha; }
+                m_run += d;
+                l_run *= alpha;
+            }
+        } else if (kt == 0 || !__all(mx <= RESCALE_LOG2)) {
             // move the reference point: exactly to the row max on the first tile, up to it later
             const float d = kt == 0 ? mx : fmaxf(mx, 0.f);
 #pragma unroll
@@ -564,6 +587,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
                                                        int nblk, int BH, const int32_t* __restrict__ cu_tok) {
     attn_fwd_body<T, PRE, true>(qkv, ldqkv, o, ldo, lse, H, N, nq, scale, nblk, BH, cu_tok);
 }
+// the packed form with dropout: bh is the global sequence x head and q0 / kt are local to the sequence, so sequence b gets the mask
+// the fixed-length entry gives sequence b of a batch of any N
+template <typename T, bool PRE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? FWD_DROP_WAVES : 2))) void attn_fwd_varlen_dropout_kernel(
+    const T* __restrict__ qkv, int ldqkv, T* __restrict__ o, int ldo, float* __restrict__ lse, int H, int N, int nq, float scale, int nblk,
+    int BH, const int32_t* __restrict__ cu_tok, const uint32_t* __restrict__ seed, uint32_t site, int thr) {
+    attn_fwd_body<T, PRE, true, true>(qkv, ldqkv, o, ldo, lse, H, N, nq, scale, nblk, BH, cu_tok, seed, site, thr);
+}
 
 // ------------------------------------------------------------------------------------------------
 // backward, part 1: dK, dV.  Workgroup owns 128 keys (lane = key); queries stream through LDS.
@@ -585,7 +616,6 @@ __device__ __forceinline__ void attn_bwd_dkdv_body(const T* __restrict__ qkv, in
                                                    const float* __restrict__ ws, int64_t plane, T* __restrict__ dqkv, int lddqkv, int H, int N,
                                                    int nq, float scale, int nblk, int BH, const int32_t* __restrict__ cu_tok,
                                                    const uint32_t* __restrict__ dseed = nullptr, uint32_t dsite = 0, int dthr = 0) {
-    static_assert(!(VL && DROP), "the packed entries have no dropout form");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using F = typename Frag<T>::type;
     constexpr int NF = Tile<T>::NFRAG, NS = AccSteps<T>::N, TB = Tile<T>::BYTES;
@@ -809,6 +839,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
     int lddqkv, int H, int N, int nq, float scale, int nblk, int BH, const int32_t* __restrict__ cu_tok) {
     attn_bwd_dkdv_body<T, PRE, true>(qkv, ldqkv, d_o, ldo, ws, plane, dqkv, lddqkv, H, N, nq, scale, nblk, BH, cu_tok);
 }
+// the packed form with dropout (mask indices: see attn_fwd_varlen_dropout_kernel)
+template <typename T, bool PRE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? DKDV_WAVES : 1))) void attn_bwd_dkdv_varlen_dropout_kernel(
+    const T* __restrict__ qkv, int ldqkv, const T* __restrict__ d_o, int ldo, const float* __restrict__ ws, int64_t plane, T* __restrict__ dqkv,
+    int lddqkv, int H, int N, int nq, float scale, int nblk, int BH, const int32_t* __restrict__ cu_tok, const uint32_t* __restrict__ seed,
+    uint32_t site, int thr) {
+    attn_bwd_dkdv_body<T, PRE, true, true>(qkv, ldqkv, d_o, ldo, ws, plane, dqkv, lddqkv, H, N, nq, scale, nblk, BH, cu_tok, seed, site, thr);
+}
 
 // ------------------------------------------------------------------------------------------------
 // backward, part 2: dQ.  Workgroup owns 128 queries (lane = query); keys stream through LDS.
@@ -825,7 +863,6 @@ __device__ __forceinline__ void attn_bwd_dq_body(const T* __restrict__ qkv, int 
                                                  const float* __restrict__ lse, float* __restrict__ delta, int64_t plane, T* __restrict__ dqkv,
                                                  int lddqkv, int H, int N, int nq, float scale, int nblk, int BH, const int32_t* __restrict__ cu_tok,
                                                  const uint32_t* __restrict__ dseed = nullptr, uint32_t dsite = 0, int dthr = 0) {
-    static_assert(!(VL && DROP), "the packed entries have no dropout form");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using F = typename Frag<T>::type;
     constexpr int NF = Tile<T>::NFRAG, NS = AccSteps<T>::N, TB = Tile<T>::BYTES;
@@ -1023,6 +1060,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
     float* __restrict__ delta, int64_t plane, T* __restrict__ dqkv, int lddqkv, int H, int N, int nq, float scale, int nblk, int BH,
     const int32_t* __restrict__ cu_tok) {
     attn_bwd_dq_body<T, PRE, true>(qkv, ldqkv, o, d_o, ldo, lse, delta, plane, dqkv, lddqkv, H, N, nq, scale, nblk, BH, cu_tok);
+}
+// the packed form with dropout (mask indices: see attn_fwd_varlen_dropout_kernel)
+template <typename T, bool PRE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? DQ_DROP_WAVES : 1))) void attn_bwd_dq_varlen_dropout_kernel(
+    const T* __restrict__ qkv, int ldqkv, const T* __restrict__ o, const T* __restrict__ d_o, int ldo, const float* __restrict__ lse,
+    float* __restrict__ delta, int64_t plane, T* __restrict__ dqkv, int lddqkv, int H, int N, int nq, float scale, int nblk, int BH,
+    const int32_t* __restrict__ cu_tok, const uint32_t* __restrict__ seed, uint32_t site, int thr) {
+    attn_bwd_dq_body<T, PRE, true, true>(qkv, ldqkv, o, d_o, ldo, lse, delta, plane, dqkv, lddqkv, H, N, nq, scale, nblk, BH, cu_tok, seed, site,
+                                         thr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1553,6 +1599,38 @@ static int attention_bwd_varlen_t(const void* qkv, int ldqkv, const void* o, con
     return check_launch();
 }
 
+// the packed launches with the dropout mask: work items, layouts and workspace of attention_fwd_varlen_t / attention_bwd_varlen_t
+template <typename T>
+static int attention_fwd_varlen_dropout_t(const void* qkv, int ldqkv, void* o, int ldo, float* lse, const int32_t* cu_tok, int B, int H, int max_N,
+                                          int nq, float scale, int flags, const uint32_t* seed, uint32_t site, int thr, hipStream_t st) {
+    const int nqk = nq >= max_N ? max_N : nq;
+    const int nblk = (int)cdiv(nqk, 128);
+    const dim3 grid(attn_grid(nblk, B * H)), block(256);
+    if (flags & PA_ATTN_Q_PRESCALED)
+        hipLaunchKernelGGL((attn_fwd_varlen_dropout_kernel<T, true>), grid, block, fwd_lds<T>(), st, (const T*)qkv, ldqkv, (T*)o, ldo, lse, H, max_N, nqk,
+                           scale, nblk, B * H, cu_tok, seed, site, thr);
+    else
+        hipLaunchKernelGGL((attn_fwd_varlen_dropout_kernel<T, false>), grid, block, fwd_lds<T>(), st, (const T*)qkv, ldqkv, (T*)o, ldo, lse, H, max_N, nqk,
+                           scale, nblk, B * H, cu_tok, seed, site, thr);
+    return check_launch();
+}
+
+template <typename T, bool PRE>
+static int attention_bwd_varlen_dropout_t(const void* qkv, int ldqkv, const void* o, const void* d_o, int ldo, const float* lse, float* ws, void* dqkv,
+                                          int lddqkv, const int32_t* cu_tok, int B, int H, int max_N, int nq, float scale, const uint32_t* seed,
+                                          uint32_t site, int thr, hipStream_t st) {
+    const int nqk = nq >= max_N ? max_N : nq;
+    const int64_t plane = (int64_t)B * H * nqk;
+    const int nblkq = (int)cdiv(nqk, 128), nblkk = (int)cdiv(max_N, 128);
+    hipLaunchKernelGGL((attn_bwd_dq_varlen_dropout_kernel<T, PRE>), dim3(attn_grid(nblkq, B * H)), dim3(256), fwd_lds<T>(), st, (const T*)qkv, ldqkv,
+                       (const T*)o, (const T*)d_o, ldo, lse, ws, plane, (T*)dqkv, lddqkv, H, max_N, nqk, scale, nblkq, B * H, cu_tok, seed, site, thr);
+    int rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL((attn_bwd_dkdv_varlen_dropout_kernel<T, PRE>), dim3(attn_grid(nblkk, B * H)), dim3(256), dkdv_lds<T>(), st, (const T*)qkv,
+                       ldqkv, (const T*)d_o, ldo, ws, plane, (T*)dqkv, lddqkv, H, max_N, nqk, scale, nblkk, B * H, cu_tok, seed, site, thr);
+    return check_launch();
+}
+
 }  // namespace pa
 
 using namespace pa;
@@ -1703,4 +1781,37 @@ extern "C" int pa_attention_bwd_varlen(const void* qkv, int ldqkv, const void* o
                    : attention_bwd_varlen_t<bf16, false>(qkv, ldqkv, o, d_o, ldo, lse, ws, dqkv, lddqkv, cu_tok, B, H, max_N, nq, scale, st);
     return pre ? attention_bwd_varlen_t<float, true>(qkv, ldqkv, o, d_o, ldo, lse, ws, dqkv, lddqkv, cu_tok, B, H, max_N, nq, scale, st)
                : attention_bwd_varlen_t<float, false>(qkv, ldqkv, o, d_o, ldo, lse, ws, dqkv, lddqkv, cu_tok, B, H, max_N, nq, scale, st);
+}
+
+// ---- attention dropout on packed sequences (additive: the ABI version stays 6) -------------------------------------------------
+extern "C" int pa_attention_fwd_varlen_dropout(const void* qkv, int ldqkv, void* o, int ldo, float* lse, const int32_t* cu_tok, int B, int H,
+                                               int max_N, int nq, float scale, int dtype, int flags, const uint32_t* seed, uint32_t site, int t,
+                                               void* stream) {
+    if (!qkv || !o || !lse || !cu_tok || !seed || B <= 0 || H <= 0 || max_N <= 0 || nq <= 0 || t < 1 || t > 255 || site >= 65536u ||
+        (flags & ~PA_ATTN_Q_PRESCALED))
+        return PA_EINVAL;
+    if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
+    if (!attn_args_ok(ldqkv, dtype) || !attn_args_ok(ldo, dtype)) return PA_EUNSUPPORTED;
+    if (ldqkv < 3 * H * HD || ldo < H * HD) return PA_EINVAL;      // a leading dimension below the row width
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PA_BF16) return attention_fwd_varlen_dropout_t<bf16>(qkv, ldqkv, o, ldo, lse, cu_tok, B, H, max_N, nq, scale, flags, seed, site, t, st);
+    return attention_fwd_varlen_dropout_t<float>(qkv, ldqkv, o, ldo, lse, cu_tok, B, H, max_N, nq, scale, flags, seed, site, t, st);
+}
+
+extern "C" int pa_attention_bwd_varlen_dropout(const void* qkv, int ldqkv, const void* o, const void* d_o, int ldo, const float* lse, float* ws,
+                                               void* dqkv, int lddqkv, const int32_t* cu_tok, int B, int H, int max_N, int nq, float scale,
+                                               int dtype, int flags, const uint32_t* seed, uint32_t site, int t, void* stream) {
+    if (!qkv || !o || !d_o || !lse || !ws || !dqkv || !cu_tok || !seed || B <= 0 || H <= 0 || max_N <= 0 || nq <= 0 || t < 1 || t > 255 ||
+        site >= 65536u || (flags & ~(PA_ATTN_Q_PRESCALED | PA_ATTN_BWD_TWO_PASS | PA_ATTN_BWD_SINGLE_PASS | PA_ATTN_BWD_SINGLE_PASS_W16)))
+        return PA_EINVAL;
+    if (dtype != PA_BF16 && dtype != PA_F32) return PA_EINVAL;
+    if (!attn_args_ok(ldqkv, dtype) || !attn_args_ok(ldo, dtype) || !attn_args_ok(lddqkv, dtype)) return PA_EUNSUPPORTED;
+    if (ldqkv < 3 * H * HD || lddqkv < 3 * H * HD || ldo < H * HD) return PA_EINVAL;
+    const bool pre = flags & PA_ATTN_Q_PRESCALED;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PA_BF16)
+        return pre ? attention_bwd_varlen_dropout_t<bf16, true>(qkv, ldqkv, o, d_o, ldo, lse, ws, dqkv, lddqkv, cu_tok, B, H, max_N, nq, scale, seed, site, t, st)
+                   : attention_bwd_varlen_dropout_t<bf16, false>(qkv, ldqkv, o, d_o, ldo, lse, ws, dqkv, lddqkv, cu_tok, B, H, max_N, nq, scale, seed, site, t, st);
+    return pre ? attention_bwd_varlen_dropout_t<float, true>(qkv, ldqkv, o, d_o, ldo, lse, ws, dqkv, lddqkv, cu_tok, B, H, max_N, nq, scale, seed, site, t, st)
+               : attention_bwd_varlen_dropout_t<float, false>(qkv, ldqkv, o, d_o, ldo, lse, ws, dqkv, lddqkv, cu_tok, B, H, max_N, nq, scale, seed, site, t, st);
 }

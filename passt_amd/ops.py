@@ -1027,10 +1027,15 @@ def attention_fwd_varlen(qkv, cu_tok, B, H, max_N, scale, nq=None, flags=0):
     cu_tok[B] == qkv.shape[0]; max_N >= the longest sequence).  nq=None: every query -> o [total][H*64] packed like qkv,
     lse [H][total].  nq < max_N (the model's nq=2): compact o [(b*nq+q)][H*64], lse [(b*H+h)*nq+q]; rows of a sequence shorter
     than nq stay zero."""
+    return _attention_fwd_varlen("attention_fwd_varlen", qkv, cu_tok, B, H, max_N, scale, nq, flags, None)
+
+
+def _attention_fwd_varlen(name, qkv, cu_tok, B, H, max_N, scale, nq, flags, drop):
+    """the packed forward; ``drop``: None (pa_attention_fwd_varlen) or the checked (seed, site, t) of pa_attention_fwd_varlen_dropout"""
     dtype = PA_DTYPE[qkv.dtype]
     total, D = qkv.shape[0], H * 64
     if qkv.dim() != 2 or qkv.shape[1] != 3 * D or cu_tok.dim() != 1 or cu_tok.numel() != B + 1 or not 1 <= max_N <= total:
-        raise _lib.PasstAmdError(f"attention_fwd_varlen: qkv {tuple(qkv.shape)}, cu_tok {tuple(cu_tok.shape)}, B={B}, H={H}, max_N={max_N}")
+        raise _lib.PasstAmdError(f"{name}: qkv {tuple(qkv.shape)}, cu_tok {tuple(cu_tok.shape)}, B={B}, H={H}, max_N={max_N}")
     if nq is None or nq >= max_N:
         nq = max_N
         o = torch.empty((total, D), device=qkv.device, dtype=qkv.dtype)
@@ -1038,16 +1043,25 @@ def attention_fwd_varlen(qkv, cu_tok, B, H, max_N, scale, nq=None, flags=0):
         work = None
     else:
         if nq < 1:
-            raise _lib.PasstAmdError("attention_fwd_varlen: nq must be >= 1")
+            raise _lib.PasstAmdError(f"{name}: nq must be >= 1")
         o = torch.zeros((B * nq, D), device=qkv.device, dtype=qkv.dtype)
         lse = torch.zeros((B * H * nq,), device=qkv.device, dtype=torch.float32)
         work = 4.0 * nq * total * 64 * H
     # executed FLOPs of the all-queries form depend on the lengths, which live on the device: the per-launch profile files the
     # upper bound B * max_N^2 (bench_kernels.py reports the exact figure from its host copy of the lengths)
-    _timed("attn_fwd", work if work is not None else 4.0 * max_N * max_N * 64 * B * H,
-           lambda: check(_lib.load().pa_attention_fwd_varlen(_p(qkv, None, True), qkv.stride(0), _p(o), o.stride(0), _p(lse),
-                                                             _p(cu_tok, torch.int32), B, H, max_N, nq, scale, dtype, flags, _stream()),
-                         "pa_attention_fwd_varlen"))
+    work = work if work is not None else 4.0 * max_N * max_N * 64 * B * H
+    if drop is None:
+        _timed("attn_fwd", work,
+               lambda: check(_lib.load().pa_attention_fwd_varlen(_p(qkv, None, True), qkv.stride(0), _p(o), o.stride(0), _p(lse),
+                                                                 _p(cu_tok, torch.int32), B, H, max_N, nq, scale, dtype, flags, _stream()),
+                             "pa_attention_fwd_varlen"))
+    else:
+        seed, site, t = drop
+        _timed("attn_fwd_drop", work,
+               lambda: check(_lib.load().pa_attention_fwd_varlen_dropout(_p(qkv, None, True), qkv.stride(0), _p(o), o.stride(0), _p(lse),
+                                                                         _p(cu_tok, torch.int32), B, H, max_N, nq, scale, dtype, flags,
+                                                                         _p(seed), site, t, _stream()),
+                             "pa_attention_fwd_varlen_dropout"))
     return o, lse
 
 
@@ -1375,33 +1389,73 @@ def attention_bwd_varlen(qkv, o, d_o, lse, cu_tok, B, H, max_N, scale, nq=None, 
     max_N -> compact o / d_o [B*nq][D], lse [B*H*nq]).  Every row of dqkv is written: in the compact form the Q third is zero
     outside each sequence's first nq rows.  Always the dQ + dK/dV kernel pair.  ws / out: an f32 workspace / a [total][3D] tensor of
     qkv's dtype to use instead of fresh ones (tests put guard rows behind them)."""
+    return _attention_bwd_varlen("attention_bwd_varlen", qkv, o, d_o, lse, cu_tok, B, H, max_N, scale, nq, flags, ws, out, None)
+
+
+def _drop_site(site, what):
+    if not isinstance(site, int) or isinstance(site, bool) or not 0 <= site < 65536:
+        raise ValueError(f"{what}: site must be an int in 0..65535 (the block index), got {site!r}")
+    return site
+
+
+def attention_fwd_varlen_dropout(qkv, cu_tok, B, H, max_N, scale, seed, site, t, nq=None, flags=0):
+    """attention_fwd_varlen with dropout on the probabilities (attention_fwd_dropout's seed / site / t).  Sequence b gets the mask the
+    fixed entry gives sequence b of a batch: s = b*H + h, q and k the positions inside the sequence."""
+    _drop_seed(seed, qkv.device, "attention_fwd_varlen_dropout")
+    _drop_t(t, "attention_fwd_varlen_dropout")
+    _drop_site(site, "attention_fwd_varlen_dropout")
+    return _attention_fwd_varlen("attention_fwd_varlen_dropout", qkv, cu_tok, B, H, max_N, scale, nq, flags, (seed, site, t))
+
+
+def attention_bwd_varlen_dropout(qkv, o, d_o, lse, cu_tok, B, H, max_N, scale, seed, site, t, nq=None, flags=0, ws=None, out=None):
+    """attention_bwd_varlen for attention_fwd_varlen_dropout's o / lse under the same seed, site and t; same layouts, ws / out."""
+    _drop_seed(seed, qkv.device, "attention_bwd_varlen_dropout")
+    _drop_t(t, "attention_bwd_varlen_dropout")
+    _drop_site(site, "attention_bwd_varlen_dropout")
+    return _attention_bwd_varlen("attention_bwd_varlen_dropout", qkv, o, d_o, lse, cu_tok, B, H, max_N, scale, nq, flags, ws, out,
+                                 (seed, site, t))
+
+
+def _attention_bwd_varlen(name, qkv, o, d_o, lse, cu_tok, B, H, max_N, scale, nq, flags, ws, out, drop):
+    """the packed backward; ``drop``: None (pa_attention_bwd_varlen) or the checked (seed, site, t) of pa_attention_bwd_varlen_dropout"""
     dtype = PA_DTYPE[qkv.dtype]
     total, D = qkv.shape[0], H * 64
     if qkv.dim() != 2 or qkv.shape[1] != 3 * D or cu_tok.dim() != 1 or cu_tok.numel() != B + 1 or not 1 <= max_N <= total:
-        raise _lib.PasstAmdError(f"attention_bwd_varlen: qkv {tuple(qkv.shape)}, cu_tok {tuple(cu_tok.shape)}, B={B}, H={H}, max_N={max_N}")
+        raise _lib.PasstAmdError(f"{name}: qkv {tuple(qkv.shape)}, cu_tok {tuple(cu_tok.shape)}, B={B}, H={H}, max_N={max_N}")
     if nq is None or nq >= max_N:
         nq, rows, nlse = max_N, total, H * total
     else:
         if nq < 1:
-            raise _lib.PasstAmdError("attention_bwd_varlen: nq must be >= 1")
+            raise _lib.PasstAmdError(f"{name}: nq must be >= 1")
         rows, nlse = B * nq, B * H * nq
     if o.shape != (rows, D) or d_o.shape != (rows, D) or lse.numel() != nlse or o.stride(0) != d_o.stride(0):
-        raise _lib.PasstAmdError(f"attention_bwd_varlen: o {tuple(o.shape)} / d_o {tuple(d_o.shape)} / lse {tuple(lse.shape)} for {rows} query rows")
+        raise _lib.PasstAmdError(f"{name}: o {tuple(o.shape)} / d_o {tuple(d_o.shape)} / lse {tuple(lse.shape)} for {rows} query rows")
     lib = _lib.load()
     need = lib.pa_attention_bwd_varlen_ws_floats(total, B, H, nq)
     if ws is None:
         ws = torch.empty(need, device=lse.device, dtype=torch.float32)
     elif ws.numel() < need:
-        raise _lib.PasstAmdError(f"attention_bwd_varlen: workspace of {ws.numel()} floats, {need} needed")
+        raise _lib.PasstAmdError(f"{name}: workspace of {ws.numel()} floats, {need} needed")
     dqkv = torch.empty_like(qkv) if out is None else out
     if dqkv.shape != qkv.shape or dqkv.dtype != qkv.dtype:
-        raise _lib.PasstAmdError(f"attention_bwd_varlen: out is {tuple(dqkv.shape)} {dqkv.dtype}, expected {tuple(qkv.shape)} {qkv.dtype}")
+        raise _lib.PasstAmdError(f"{name}: out is {tuple(dqkv.shape)} {dqkv.dtype}, expected {tuple(qkv.shape)} {qkv.dtype}")
     # executed FLOPs depend on the lengths, which live on the device: the per-launch profile files the upper bound (see attention_fwd_varlen)
-    _timed("attn_bwd", 10.0 * nq * (max_N if rows == total else total / B) * 64 * B * H,
-           lambda: check(lib.pa_attention_bwd_varlen(_p(qkv, None, True), qkv.stride(0), _p(o, qkv.dtype, True), _p(d_o, qkv.dtype, True),
-                                                     o.stride(0), _p(lse, torch.float32), _p(ws, torch.float32), _p(dqkv, None, True), dqkv.stride(0),
-                                                     _p(cu_tok, torch.int32), B, H, max_N, nq, scale, dtype, flags, _stream()),
-                         "pa_attention_bwd_varlen"))
+    work = nq * (max_N if rows == total else total / B) * 64 * B * H
+    if drop is None:
+        _timed("attn_bwd", 10.0 * work,
+               lambda: check(lib.pa_attention_bwd_varlen(_p(qkv, None, True), qkv.stride(0), _p(o, qkv.dtype, True), _p(d_o, qkv.dtype, True),
+                                                         o.stride(0), _p(lse, torch.float32), _p(ws, torch.float32), _p(dqkv, None, True), dqkv.stride(0),
+                                                         _p(cu_tok, torch.int32), B, H, max_N, nq, scale, dtype, flags, _stream()),
+                             "pa_attention_bwd_varlen"))
+    else:
+        seed, site, t = drop
+        _timed("attn_bwd_drop", 14.0 * work,
+               lambda: check(lib.pa_attention_bwd_varlen_dropout(_p(qkv, None, True), qkv.stride(0), _p(o, qkv.dtype, True),
+                                                                 _p(d_o, qkv.dtype, True), o.stride(0), _p(lse, torch.float32),
+                                                                 _p(ws, torch.float32), _p(dqkv, None, True), dqkv.stride(0),
+                                                                 _p(cu_tok, torch.int32), B, H, max_N, nq, scale, dtype, flags, _p(seed), site, t,
+                                                                 _stream()),
+                             "pa_attention_bwd_varlen_dropout"))
     return dqkv
 
 

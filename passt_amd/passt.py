@@ -391,10 +391,15 @@ class _PackedLayout:
     def hidden_view(self, h):
         return h.view(self.M, -1)       # a view, not h itself: what the autograd node hands out must not be what its context keeps
 
-    def attention_fwd(self, qkv, H, scale, **kw):
+    def attention_fwd(self, qkv, H, scale, drop=None, **kw):
+        """``drop``: as in _FixedLayout.attention_fwd; clip b gets the mask of sequence b of a fixed batch (s = b*H + h, local q / k)"""
+        if drop is not None:
+            return ops.attention_fwd_varlen_dropout(qkv, self.cu_tok, self.B, H, self.max_N, scale, *drop, **kw)
         return ops.attention_fwd_varlen(qkv, self.cu_tok, self.B, H, self.max_N, scale, **kw)
 
-    def attention_bwd(self, qkv, att, d_att, lse, H, scale, **kw):
+    def attention_bwd(self, qkv, att, d_att, lse, H, scale, drop=None, **kw):
+        if drop is not None:
+            return ops.attention_bwd_varlen_dropout(qkv, att, d_att, lse, self.cu_tok, self.B, H, self.max_N, scale, *drop, **kw)
         return ops.attention_bwd_varlen(qkv, att, d_att, lse, self.cu_tok, self.B, H, self.max_N, scale, **kw)
 
     def prefix_lse(self, lse, H):
@@ -730,11 +735,16 @@ def refuse_varlen_attn_drop(model):
 
 class _DropRows:
     """A forward's drop-path factors per ROW, expanded once: ``full`` (depth, 2, M) for launches over all token rows (``ntok`` rows per
-    clip), ``tail`` (2, 2 B) for the last block on the compact prefix rows (2 per clip); ``active``: the blocks with a factor."""
+    clip), ``tail`` (2, 2 B) for the last block on the compact prefix rows (2 per clip); ``active``: the blocks with a factor.
+    ``ntok``: the clips' token counts -- one int (the fixed layout: every clip the same), or a (B,) integer tensor on the factors'
+    device with ``M``, their sum, known to the host (the packed layout: clip b's factor on all of its rows; no device read)."""
 
-    def __init__(self, scales, rates, ntok):
+    def __init__(self, scales, rates, ntok, M=None):
         self.active = [p > 0.0 for p in rates]
-        self.full = scales.repeat_interleave(ntok, dim=2).contiguous()
+        if torch.is_tensor(ntok):
+            self.full = scales.repeat_interleave(ntok, dim=2, output_size=M).contiguous()
+        else:
+            self.full = scales.repeat_interleave(ntok, dim=2).contiguous()
         self.tail = scales[-1].repeat_interleave(2, dim=1).contiguous()
 
     def rows(self, i, branch, compact=False):
@@ -899,6 +909,13 @@ def passt_forward(model, x, save, draws=None, hidden=None, attn=None, drop_path_
     return out if attn is None else out + (list(r.maps),)
 
 
+def varlen_regularized(model):
+    """Does a ragged batch of this model run with its regularisers (``net.varlen_regularize = True`` on a model in training mode with
+    an active DropPath or attention dropout)?  False: the packed path is the one without them and the two refusals below hold."""
+    return bool(getattr(model, "varlen_regularize", False)) and (any(p > 0.0 for p in drop_path_rates(model))
+                                                                   or any(attn_drop_rates(model)))
+
+
 def refuse_varlen_drop_path(model):
     """The refusal of a ragged batch by a model with an active DropPath (training mode, rate > 0): net(x, lengths=) and
     TrainStep.step(lengths=) raise the same NotImplementedError, the step before any of its draws."""
@@ -912,7 +929,8 @@ def _run_forward(model, x, lengths=None, save=False, draws=None, hidden=None, at
                  attn_drop_seed=None):
     """The one way into the kernel sequence of a forward: the fixed path, or with ``lengths`` the packed one, under this model's GEMM
     flags.  Returns the _Fwd."""
-    if lengths is not None:
+    reg = lengths is not None and varlen_regularized(model)
+    if lengths is not None and not reg:
         refuse_varlen_drop_path(model)
         refuse_varlen_attn_drop(model)
     with ops.gemm_flags(getattr(model, "_gemm_flags", 0)):
@@ -920,6 +938,8 @@ def _run_forward(model, x, lengths=None, save=False, draws=None, hidden=None, at
             if attn_drop_seed is not None:
                 return _passt_forward(model, x, save, draws, hidden, attn, rollout, drop_path_masks, attn_drop_seed)
             return _passt_forward(model, x, save, draws, hidden, attn, rollout, drop_path_masks)
+        if reg:
+            return _passt_forward_varlen(model, x, lengths, save, hidden, attn, rollout, drop_path_masks, attn_drop_seed, True)
         return _passt_forward_varlen(model, x, lengths, save, hidden, attn, rollout)
 
 
@@ -1095,8 +1115,17 @@ def passt_forward_varlen(model, x, lengths, save=False):
     """Kernel sequence of the packed forward: every clip gets what it would get alone at batch size 1.  Returns (logits, features);
     ``save=True``: (logits, features, ctx) with what passt_backward_varlen needs.  Without it nothing is kept and the launch sequence is
     the same.  Eval geometry (no Patchout) -- except for a model in training mode with ``varlen_train`` set: then every clip gets its own
-    Patchout draws (varlen_geometry_train) and the context carries the slot table the packed patch-stage backward walks."""
-    r = _run_forward(model, x, lengths, save)
+    Patchout draws (varlen_geometry_train) and the context carries the slot table the packed patch-stage backward walks.  A model with
+    ``varlen_regularize`` set and an active rate draws its stochastic-depth factors and its attention-dropout seed here
+    (passt_forward_varlen_replay takes them from the caller)."""
+    return passt_forward_varlen_replay(model, x, lengths, save)
+
+
+def passt_forward_varlen_replay(model, x, lengths, save=False, drop_path_masks=None, attn_drop_seed=None):
+    """passt_forward_varlen with passt_forward's two replay keywords, for a model with ``varlen_regularize`` set (PaSST.forward):
+    ``drop_path_masks`` ((depth, 2, B) keep flags) in place of the stochastic-depth draws, ``attn_drop_seed`` (two ints < 2^32 or a
+    (2,) tensor) in place of the seed draw; None: drawn.  Both are ignored without the switch or without an active rate."""
+    r = _run_forward(model, x, lengths, save, drop_path_masks=drop_path_masks, attn_drop_seed=attn_drop_seed)
     return (r.logits, r.feat, r.ctx) if save else (r.logits, r.feat)
 
 
@@ -1108,7 +1137,11 @@ def _upload_parts(parts, device):
     return {name: v.view(a.shape) for (name, a), v in zip(parts.items(), views)}
 
 
-def _passt_forward_varlen(model, x, lengths, save=False, hidden=None, attn=None, rollout=None):
+def _passt_forward_varlen(model, x, lengths, save=False, hidden=None, attn=None, rollout=None, drop_path_masks=None,
+                          attn_drop_seed=None, regularize=False):
+    """``regularize`` (_run_forward: the model's ``varlen_regularize`` with an active rate): stochastic depth and attention dropout as
+    the fixed path applies them to a batch of B clips -- the draws of _passt_forward in its order, behind the per-clip Patchout draws;
+    clip b's factor on all of its rows, clip b's attention mask that of sequence b.  False: neither is looked at."""
     x, dt = _checked_input(model, x, save)
     if torch.is_tensor(lengths):
         if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
@@ -1120,6 +1153,12 @@ def _passt_forward_varlen(model, x, lengths, save=False, hidden=None, attn=None,
         raise ValueError(f"lengths has {len(lengths)} entries for a batch of {B} clips")
     P, (fs, ts) = model.patch_embed.patch_size[0], model.patch_embed.stride
     train = model.training and getattr(model, "varlen_train", False)       # Patchout per clip (PaSST.forward lets no other training call in)
+    dp_rates = drop_path_rates(model) if regularize else ()
+    ad_t = attn_drop_rates(model) if regularize else ()
+    dp_on, ad_on = any(p > 0.0 for p in dp_rates), any(ad_t)
+    # what the caller handed over for a replay is checked before the first draw (the Patchout draws of the geometry below)
+    scales = drop_path_scales(model, drop_path_masks, B, x.device) if dp_on and drop_path_masks is not None else None
+    ad_seed = attn_drop_seed_tensor(attn_drop_seed, x.device) if ad_on and attn_drop_seed is not None else None
     if train:
         g = varlen_geometry_train(model, lengths, _freq_rows(model, F), T_max=T)
     else:
@@ -1133,7 +1172,15 @@ def _passt_forward_varlen(model, x, lengths, save=False, hidden=None, attn=None,
     parts["pidx"] = (cu[:-1, None] + np.arange(2, dtype=np.int32)[None, :]).reshape(-1).astype(np.int32)
     if train:
         parts.update((k, g[k]) for k in ("row_tpos", "toff", "slot"))
+    if dp_on:
+        parts["ntok"] = np.diff(cu).astype(np.int32)     # the clips' token counts: the drop-path factors are expanded on the device
     d = _upload_parts(parts, x.device)
+    # stochastic depth, then the attention-dropout seed: _passt_forward's draws in its order, behind the Patchout draws
+    if dp_on and scales is None:
+        scales = drop_path_draws(model, B, x.device)
+    adrop = None
+    if ad_on:
+        adrop = _AttnDrop(attn_drop_draw(x.device) if ad_seed is None else ad_seed, ad_t)
 
     # patch embedding: the packed im2col has a zero row under every prefix token and the table holds the token there, so the one
     # GEMM with the residual epilogue writes the whole token matrix (no scatter pass)
@@ -1148,7 +1195,10 @@ def _passt_forward_varlen(model, x, lengths, save=False, hidden=None, attn=None,
         patch.update(slot=d["slot"], toff=d["toff"])   # Patchout: the patch-stage backward finds a row's grid position through the table
     tok_offsets = torch.from_numpy(cu.astype(np.int64)) if (hidden is not None or attn is not None or rollout is not None) else None
     lay = _PackedLayout(B, M, g["max_N"], d["cu_tok"], d["pidx"], ntok=np.diff(cu))
-    return _forward_trunk(model, lay, xs, dt, save, patch, hidden, attn, rollout)._replace(tok_offsets=tok_offsets)
+    kw = {} if adrop is None else dict(adrop=adrop)
+    if dp_on:
+        kw["drop"] = _DropRows(scales, dp_rates, d["ntok"], M)
+    return _forward_trunk(model, lay, xs, dt, save, patch, hidden, attn, rollout, **kw)._replace(tok_offsets=tok_offsets)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1986,6 +2036,8 @@ class PaSST(nn.Module):
         # node under the fixed path's rule (grad enabled and anything requires a gradient; varlen_grad / input_grad are not looked at).
         # Off: such a call raises NotImplementedError, as it always did
         self.varlen_train = False
+        # ragged batches in training mode with stochastic depth / attention dropout active: refused unless asked for (forward's docstring)
+        self.varlen_regularize = False
         self.init_weights(weight_init)
         self._reset_runtime()
 
@@ -2226,7 +2278,7 @@ class PaSST(nn.Module):
         what they launch without dropout.  ``attn_drop_seed`` (two ints < 2^32, or a (2,) tensor): used in place of the draw -- same
         seed, same inputs: bit-identical outputs and gradients; ignored in eval mode.  ``attn=`` maps and ``rollout="attn"`` stay the
         undropped softmax (the INPUT of ``attn_drop``).  NotImplementedError, before any draw: ``lengths`` in training mode with an
-        active attention dropout; ``attn_grad`` or ``rollout="cam"`` when a block they touch is active.  ``drop_rate`` (the other
+        active attention dropout (unless ``net.varlen_regularize = True``, below); ``attn_grad`` or ``rollout="cam"`` when a block they touch is active.  ``drop_rate`` (the other
         element-wise dropout sites) is not covered: the constructor raises.
 
         An ``x`` that requires a gradient gets one (``x.grad`` / ``torch.autograd.grad``), as in the reference: PaSST as a
@@ -2263,6 +2315,21 @@ class PaSST(nn.Module):
         tokens per clip, as above.  Not covered: ``AugmentMelSTFT(..., lengths=)`` in training mode (pad, run the train-mode mel, then
         ``net(spec, lengths=frames)``), EnsembelerModel.  The fused step takes ragged batches as ``TrainStep.step(x, y, lengths=)``,
         with its own definition of mixup between clips of different lengths (passt_amd.train).
+        Stochastic depth and attention dropout on a ragged training batch are opt-in as well: by default (``net.varlen_regularize =
+        False``) a model with either active raises NotImplementedError before any draw.  With ``net.varlen_regularize = True`` A RAGGED
+        BATCH OF B CLIPS IS REGULARISED AS THE FIXED PATH REGULARISES A BATCH OF B CLIPS (not: each clip alone at batch size 1; Patchout
+        keeps its clip-after-clip CPU draws).  Draw order: the per-clip Patchout draws on the CPU generator; then
+        ``drop_path_draws(net, B, device)`` as it is -- one ``torch.rand((B, 1, 1))`` per active module call, blocks ascending,
+        attention branch then MLP branch; then ``attn_drop_draw(device)``, one seed.  After ``torch.manual_seed(s)`` a ragged forward
+        leaves the device generator where a fixed forward at the same B leaves it.  Clip b gets entry b of the (depth, 2, B) factors on
+        all of its token rows, however many it has (2 rows on the prefix-only tail); ``drop_path_masks`` has the fixed path's shape and
+        meaning.  The attention mask rule is unchanged: element (site = block, s = b*H + h, q, k) uses b, the clip's index in the
+        batch, and q, k, the positions inside the clip.  The rule does not depend on the token count, so clip b gets bit for bit the
+        mask the fixed path gives sequence b: ``passt_amd.attn_drop_mask(seed, block, b + 1, H, nq, N_b, p)[b]`` restates it on the
+        CPU, and ``attn_drop_seed`` replays it.  A shape error in either keyword raises ValueError before any draw.  With every rate 0,
+        and in eval mode, the switch changes nothing: the packed path launches what it launches without it.  Maps and
+        ``rollout="attn"`` stay the undropped softmax; ``attn_grad`` / ``rollout="cam"`` through an active block keep their refusal.
+        ``TrainStep.step(..., lengths=)`` reads the same switch on its net.
 
         ``torch.compile(net)`` (ex_audioset.py:135, model_speed_test :391): the whole forward is ONE opaque call to the
         compiler (``_lib.compile_opaque``: torch.compiler.disable's mechanism without the torch._dynamo import, installed at class

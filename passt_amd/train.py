@@ -17,6 +17,7 @@ from .ddp import GradReducer
 from .passt import (_checked_input, _freq_rows, _precision, attn_drop_draw, attn_drop_rates, check_patchout_varlen, drop_path_draws,
                     drop_path_rates, param_stage, refuse_varlen_attn_drop,
                     passt_backward, passt_backward_varlen, passt_forward, passt_forward_varlen, patchout_draws, refuse_varlen_drop_path,
+                    varlen_regularized,
                     trainable_plan)
 from .preprocess import checked_lengths
 
@@ -385,11 +386,13 @@ class TrainStep:
 
         RNG order of a ragged step: all front-end draws of the batch, clip after clip (preprocess.varlen_clip_draws; a mel module in
         eval mode: its two ``randint`` per call); then ``randperm`` and ``beta``; then the Patchout draws, clip after clip
-        (passt.varlen_geometry_train).
+        (passt.varlen_geometry_train); then, with ``net.varlen_regularize = True``, the stochastic-depth draws and the
+        attention-dropout seed on the device generator, as the fixed step draws them for a batch of B clips (PaSST.forward).
 
         Every check runs before the first draw and the first launch, so a rejected step consumes no random number and changes no
         buffer: NotImplementedError for a net in training mode without ``net.varlen_train = True``, for a mel module in training mode
-        without ``mel.varlen_train = True``, and for an active ``drop_path_rate`` (the refusal of ``net(x, lengths=)``); the checks of
+        without ``mel.varlen_train = True``, and -- unless ``net.varlen_regularize = True`` -- for an active ``drop_path_rate`` or
+        attention dropout (the refusals of ``net(x, lengths=)``, string for string); the checks of
         ``lengths`` (preprocess.checked_lengths for samples, the packed forward's for frames); the Patchout feasibility of every
         clip (passt.check_patchout_varlen, on frames = 1 + (n - 1) // hop when ``lengths`` are samples).
 
@@ -464,8 +467,9 @@ class TrainStep:
         if mel is not None and mel.training and not mel.varlen_train:
             raise NotImplementedError("TrainStep.step(..., lengths=): a front end in train mode takes a ragged batch only with the "
                                       "switch mel.varlen_train = True (every clip then gets its own fmin / fmax jitter and masks)")
-        refuse_varlen_drop_path(net)
-        refuse_varlen_attn_drop(net)
+        if not varlen_regularized(net):         # net.varlen_regularize with an active rate: the packed forward draws and applies them
+            refuse_varlen_drop_path(net)
+            refuse_varlen_attn_drop(net)
         if mel is not None:
             if x.dim() == 3:
                 x = x.reshape(-1, x.shape[2])
